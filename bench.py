@@ -17,10 +17,12 @@ There is no data-path collective inside a step: problems are independent and a p
 Usage (driver contract):  python bench.py --gpus N --steps K --warmup W
 N>1 is launched by torch.distributed.run (one rank per GPU).  Prints ONE JSON line on rank 0.
 
-Besides the timed region (K steps, `--inflight` independent pipelines) the N=1 run measures, outside the timed region:
-a single batch alone on the GPU (`roofline.solo`: no overlap between launches; `roofline.solo_two_wavefronts_per_simd`: the same with
-the kernel build a caller who waits for one batch selects, fh_sched.workgroups_per_cu <= 8), the PCIe-inclusive host-pointer path
-(`e2e_with_copies`), the FP64 flop rate against the measured FP64 FMA peak (`roofline.compute`) and the CPU baseline.
+A plain run sets up, warms up, times the K steps (`--inflight` independent pipelines), writes the results of the last timed step
+if `--dump-outputs DIR` is given, and prints the result line.  With `--full` the N=1 run also measures, outside the timed region:
+the roofline of the timed launches (`roofline`), a single batch alone on the GPU (`roofline.solo`: no overlap between launches;
+`roofline.solo_two_wavefronts_per_simd`: the same with the kernel build a caller who waits for one batch selects,
+fh_sched.workgroups_per_cu <= 8), the PCIe-inclusive host-pointer path (`e2e_with_copies`), the FP64 flop rate against the measured
+FP64 FMA peak (`roofline.compute`), the C5 and replan records and the CPU baseline.
 """
 import argparse
 import json
@@ -194,6 +196,30 @@ def dry_run(args, rank, world, local_rank):
         dist.destroy_process_group()
 
 
+DUMP_FIELDS = ("solved", "trials", "status", "factor", "dt", "cost")   # nodes / qp_iters / kflops count work, which work sharing may divide differently
+DUMP_MAX_PAIRS = 1 << 18     # pairs whose scalar fields are written (every pair of the default batch)
+DUMP_MAX_COEFF_PAIRS = 8192  # pairs whose coefficients and polytope assignment are written
+
+
+def dump_outputs(path, wres, sres, n_seg):
+    """--dump-outputs: the fh_result records of the last timed step (whole and safe solve of every pair), as float64 .npy files:
+    <whole|safe>_<field>.npy for the fields in DUMP_FIELDS, for the pairs in pair_index.npy; <whole|safe>_coeff.npy [k, n_seg, 12] and
+    <whole|safe>_assign.npy [k, n_seg] for the pairs in coeff_pair_index.npy.  The two index sets are a fixed sample (seed 0) of the
+    batch, all of it when it is small enough: at most 55 MB in all (20 MB at C4)."""
+    os.makedirs(path, exist_ok=True)
+    B = len(wres)
+    rng = np.random.default_rng(0)
+    rows = np.sort(rng.choice(B, size=min(B, DUMP_MAX_PAIRS), replace=False))
+    crows = np.sort(rng.choice(B, size=min(B, DUMP_MAX_COEFF_PAIRS), replace=False))
+    np.save(os.path.join(path, "pair_index.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "coeff_pair_index.npy"), crows.astype(np.float64))
+    for name, res in (("whole", wres), ("safe", sres)):
+        for f in DUMP_FIELDS:
+            np.save(os.path.join(path, "%s_%s.npy" % (name, f)), res[f][rows].astype(np.float64))
+        np.save(os.path.join(path, "%s_coeff.npy" % name), res["coeff"][crows, :n_seg].astype(np.float64))
+        np.save(os.path.join(path, "%s_assign.npy" % name), res["assign"][crows, :n_seg].astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -217,10 +243,15 @@ def main():
     ap.add_argument("--r-margin", type=float, default=0.05,
                     help="hand-off keeps R at least this far inside its safe corridor (FASTER decomposes the safe corridor around R); "
                          "negative: SURVEY.md 8(d) to the letter (R may fall outside the shrunk corridor)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies outside the timed region: roofline, solo launch, copies, flop rate, C5 and replan records, "
+                         "CPU baseline (default: the timed region only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step to DIR/<name>.npy (float64; rank 0's pairs), see dump_outputs()")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the legs outside the timed region (solo launch, copies, flop rate)")
-    ap.add_argument("--solo-only", action="store_true", help="of the legs outside the timed region run the solo launch only (A/B runs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the legs outside the timed region (solo launch, copies, flop rate)")
+    ap.add_argument("--solo-only", action="store_true", help="with --full: of the legs outside the timed region run the solo launch only (A/B runs)")
     ap.add_argument("--pipeline", choices=["fused", "split"], default="fused",
                     help="fused: one launch per step, each unit of work is a pair taken through whole solve, hand-off and safe solve; "
                          "split: whole launch -> hand-off launch -> safe launch (same results)")
@@ -437,7 +468,9 @@ def main():
     timed_launch_info, timed_kname = last.ctx.last_launch()   # (of a launch of the timed region: the untimed launches below run alone)
     wres = last.d_wres.cpu().numpy().view(abi.result_dtype)[:B]
     sres = last.d_sres.cpu().numpy().view(abi.result_dtype)[:B]
-    if args.pipeline == "fused" and not args.pair_outputs:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wres, sres, N)
+    if args.full and args.pipeline == "fused" and not args.pair_outputs:
         # the timed launches built the safe problems on chip; their records and rows (face counts for the algorithmic bytes, the pinned
         # re-solve of the compute leg) come from ONE more launch, untimed, with complete pair outputs — the same results bit for bit
         for pp in {id(last): last, id(pipes[0]): pipes[0]}.values():
@@ -447,22 +480,14 @@ def main():
             pp.ctx.set_sched(pair_outputs=0, **sched_kw)
         again = last.d_sres.cpu().numpy().view(abi.result_dtype)[:B]
         assert all(np.array_equal(again[f], sres[f]) for f in ("solved", "trials", "status", "factor", "dt", "cost")), "pair_outputs changed a result"
-    safe_h = last.d_safe.cpu().numpy().view(abi.problem_dtype)
-    sfaces_h = last.d_sfaces.cpu().numpy().view(abi.face_dtype)
+    if args.full:
+        safe_h = last.d_safe.cpu().numpy().view(abi.problem_dtype)
+        sfaces_h = last.d_sfaces.cpu().numpy().view(abi.face_dtype)
 
     if rank == 0:
         fused = args.pipeline == "fused"
-        launch_info, kname = timed_launch_info, timed_kname   # the instantiation and build that really ran, as rocprofv3 names it
         pairs_total = (total_pairs if strong else world * B) * args.steps
         value = pairs_total / elapsed
-        bytes_whole = algorithmic_bytes(whole, N)
-        active = safe_h["n_seg"] > 0
-        bytes_safe = algorithmic_bytes(safe_h[active], N) + 24 * int((~active).sum())
-        launches_per_step = 1 if fused else 2
-        bytes_per_launch = (bytes_whole + bytes_safe) / launches_per_step
-        avg_ms = float(np.mean(kernel_ms)) if len(kernel_ms) else float("nan")
-        achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9  # GB/s
-        traffic = measured_traffic(kname) or (None, None)
         out = {
             "metric": "trajectory solves/sec (whole+safe pairs) at N=%d, deg=3" % N,
             "value": value,
@@ -509,7 +534,18 @@ def main():
                    if args.workload == "c5" else {}),
                 "share_stats_last_launch": share_stats,
             },
-            "roofline": {
+        }
+        if args.full:
+            launch_info, kname = timed_launch_info, timed_kname   # the instantiation and build that really ran, as rocprofv3 names it
+            bytes_whole = algorithmic_bytes(whole, N)
+            active = safe_h["n_seg"] > 0
+            bytes_safe = algorithmic_bytes(safe_h[active], N) + 24 * int((~active).sum())
+            launches_per_step = 1 if fused else 2
+            bytes_per_launch = (bytes_whole + bytes_safe) / launches_per_step
+            avg_ms = float(np.mean(kernel_ms)) if len(kernel_ms) else float("nan")
+            achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9  # GB/s
+            traffic = measured_traffic(kname) or (None, None)
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": kname,
                 "mode": "timed region, %d launches in flight" % len(pipes),
@@ -532,9 +568,8 @@ def main():
                         "region, whose durations include time shared with the other launches in flight (not per-kernel evidence); "
                         "`aggregate_achieved`: all algorithmic bytes of the timed region over its wall time; `compute`: the FP64 flop "
                         "rate against the measured FP64 FMA peak",
-            },
-        }
-        if world == 1 and not args.no_extra:
+            }
+        if args.full and world == 1 and not args.no_extra:
             out["roofline"]["solo"], solo_res = solo_leg(torch, pipes[0], run_step, fused, B, bytes_per_launch, launches_per_step)
             # the headline figure is the launch ALONE (per-kernel evidence); the overlapped launches of the timed region are labelled
             rf, so = out["roofline"], out["roofline"]["solo"]
@@ -582,7 +617,7 @@ def main():
                 out["single_replan_latency_ms"] = latency_leg(whole, faces)
                 out["c5"] = c5_leg(torch, dev, local_rank, par, args.r_margin)
                 out["replan_faithful"] = replan_leg(torch, dev, local_rank, par)
-        if not args.no_cpu and world == 1:  # the CPU baseline is a property of the host: reported at N=1 only
+        if args.full and not args.no_cpu and world == 1:  # the CPU baseline is a property of the host: reported at N=1 only
             out["cpu_baseline"] = cpu_baseline(whole, faces, safe_h, sfaces_h, args.cpu_seconds)
         print(json.dumps(out))
     if world > 1:

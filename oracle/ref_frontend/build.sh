@@ -22,3 +22,12 @@ g++ -O2 -std=c++14 -fPIC -shared -w \
   "$HERE/ref_frontend.cpp" \
   -o "$OUT/libref_frontend.so"
 echo "built $OUT/libref_frontend.so"
+# SolverHip compiled against the reference's own types, run by tests/test_host_class.py where the reference is absent
+if [ -f "$REF/faster/include/faster_types.hpp" ] && [ -f "$ROOT/faster_amd/libfasterhip.so" ]; then
+  g++ -O1 -std=c++14 -w -DFASTER_HIP_USE_REFERENCE_TYPES \
+    -I "$HERE/shim" -I "$REF/faster/include" -I "$REF/thirdparty/DecompROS/DecompUtil/include" \
+    -I "$ROOT/include" -I "$ROOT/faster_amd/host" -I "$ROOT/tests/cpp" \
+    "$ROOT/tests/cpp/test_reference_types.cpp" "$ROOT/faster_amd/host/solver_hip.cpp" \
+    -o "$OUT/test_reference_types" -L "$ROOT/faster_amd" -lfasterhip -ldl -Wl,-rpath,'$ORIGIN/../../faster_amd'
+  echo "built $OUT/test_reference_types"
+fi

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $R/bench.py --no-cpu --no-extra --workload c5 --c5-rule reference --pairs 65536 --inflight 1 --steps 4 --warmup 1"
+BENCH="python $R/bench.py --full --no-cpu --no-extra --workload c5 --c5-rule reference --pairs 65536 --inflight 1 --steps 4 --warmup 1"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_solo -o s -- $BENCH > $OUT/stats_solo.log 2>&1
 i=0
 for C in "FETCH_SIZE" "WRITE_SIZE" \

@@ -10,7 +10,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $R/bench.py --no-cpu --no-extra"
+BENCH="python $R/bench.py --full --no-cpu --no-extra"
 # 1. the driver's configuration (several steps in flight) and 2. one batch at a time (per-launch durations without overlap)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $BENCH > $OUT/stats.log 2>&1
 tail -1 $OUT/stats.log | cut -c1-300

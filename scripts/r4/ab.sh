@@ -10,7 +10,7 @@ cd $R
 for v in "$@"; do
   so=$R/build/libfasterhip_$v.so
   [ "$v" = default ] && so=$R/faster_amd/libfasterhip.so
-  FASTERHIP_SO=$so timeout 300 python bench.py --no-cpu --solo-only --steps ${STEPS:-64} --warmup 8 ${BENCH_ARGS:-} > $OUT/bench_$v.json 2> $OUT/bench_$v.err
+  FASTERHIP_SO=$so timeout 300 python bench.py --full --no-cpu --solo-only --steps ${STEPS:-64} --warmup 8 ${BENCH_ARGS:-} > $OUT/bench_$v.json 2> $OUT/bench_$v.err
   python - "$v" $OUT/bench_$v.json <<'PY' | tee -a $OUT/ab.txt
 import json, sys
 try:

@@ -9,7 +9,7 @@ git rev-parse HEAD > $out/head.txt 2>/dev/null || true
 ( time timeout 1500 python -m pytest tests -m gpu -q -rs --durations=12 ) > $out/tests.txt 2>&1
 grep -v ASTAR $out/tests.txt | tail -25
 ( python __graft_entry__.py --smoke 2>&1 | grep -v ASTAR | tail -3 ) | tee $out/smoke.txt
-( time timeout 600 python bench.py ) > $out/bench.json 2> $out/bench.err
+( time timeout 600 python bench.py --full ) > $out/bench.json 2> $out/bench.err
 tail -2 $out/bench.err
 python - $out/bench.json <<'PY'
 import json, sys

@@ -8,7 +8,7 @@ for v in "$@"; do
   so=$R/build/libfasterhip_$v.so; [ "$v" = default ] && so=$R/faster_amd/libfasterhip.so
   for C in FETCH_SIZE WRITE_SIZE; do
     OUT=$R/gpurun_out/$TAG/$v/$C; mkdir -p $OUT
-    ( cd /tmp && FASTERHIP_SO=$so timeout 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT -o p -- python $R/bench.py --no-cpu --no-extra --inflight 1 --steps 8 --warmup 2 > $OUT/log.txt 2>&1 )
+    ( cd /tmp && FASTERHIP_SO=$so timeout 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT -o p -- python $R/bench.py --full --no-cpu --no-extra --inflight 1 --steps 8 --warmup 2 > $OUT/log.txt 2>&1 )
   done
   python - $R/gpurun_out/$TAG/$v $v <<'PY'
 import csv, glob, sys, collections

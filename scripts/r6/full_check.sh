@@ -9,6 +9,6 @@ git rev-parse HEAD > $out/head.txt 2>/dev/null || true
 ( time timeout 1700 python -m pytest tests -m gpu -q -rs --durations=12 ) > $out/tests.txt 2>&1
 grep -v "ASTAR\|amdgpu.ids" $out/tests.txt | tail -25
 ( python __graft_entry__.py --smoke 2>&1 | grep -v "ASTAR\|amdgpu.ids" | tail -3 ) | tee $out/smoke.txt
-( time timeout 700 python bench.py ) > $out/bench.json 2> $out/bench.err
+( time timeout 700 python bench.py --full ) > $out/bench.json 2> $out/bench.err
 tail -2 $out/bench.err
 python scripts/r6/bench_brief.py $out/bench.json

@@ -214,24 +214,19 @@ def test_jps_hip_equals_host_search(tmp_path):
 def test_reference_types_build_round_trip(tmp_path, oracle, fixture_corridor):
     """INTEGRATION.md §1 prescribes -DFASTER_HIP_USE_REFERENCE_TYPES: SolverHip against FASTER's own `state`
     (faster/include/faster_types.hpp:79-165) and DecompUtil's LinearConstraint3D (decomp_geometry/polyhedron.h:115-185), included where
-    they lie under /root/reference (Eigen through the test-only shim).  Compiles solver_hip.cpp that way and drives one replan's calls
-    — setX0 / setXf / setPolytopes / genNewTraj / fillX — with the C-ABI calls answered by the CPU oracle: known answer KA-1.
-    Skipped where /root/reference is absent (the GPU box)."""
-    ref = os.environ.get("FASTER_REFERENCE", "/root/reference")
-    inc_types = os.path.join(ref, "faster", "include")
-    inc_decomp = os.path.join(ref, "thirdparty", "DecompROS", "DecompUtil", "include")
-    if not (os.path.exists(os.path.join(inc_types, "faster_types.hpp")) and os.path.isdir(inc_decomp)):
-        pytest.skip("the reference sources are not present")
+    they lie in the reference tree (Eigen through the test-only shim).  oracle/ref_frontend/build.sh compiles solver_hip.cpp that way
+    into oracle/_ref/test_reference_types (build() runs it; here it is rebuilt where the reference is present, the built program is
+    used where it is not); the program drives one replan's calls — setX0 / setXf / setPolytopes / genNewTraj / fillX — with the C-ABI
+    calls answered by the CPU oracle: known answer KA-1."""
+    from faster_amd import build as fb
     from oracle import oracle as orc
+    from oracle.ref_frontend import ref as ref_frontend
 
-    exe = str(tmp_path / "test_reference_types")
-    host = os.path.join(ROOT, "faster_amd", "host")
-    subprocess.check_call(["g++", "-O1", "-std=c++14", "-w", "-DFASTER_HIP_USE_REFERENCE_TYPES",
-                           "-I", os.path.join(ROOT, "oracle", "ref_frontend", "shim"), "-I", inc_types, "-I", inc_decomp,
-                           "-I", os.path.join(ROOT, "include"), "-I", host, "-I", os.path.join(ROOT, "tests", "cpp"),
-                           os.path.join(ROOT, "tests", "cpp", "test_reference_types.cpp"), os.path.join(host, "solver_hip.cpp"),
-                           "-o", exe, "-L", os.path.join(ROOT, "faster_amd"), "-lfasterhip", "-ldl",
-                           "-Wl,-rpath," + os.path.join(ROOT, "faster_amd")])
+    fb.build_device()
+    ref_frontend.build()
+    exe = os.path.join(ROOT, "oracle", "_ref", "test_reference_types")
+    if not os.path.exists(exe):
+        pytest.skip("oracle/_ref/test_reference_types is not built and the reference sources are not present")
     fx = fixture_corridor
     sc = tmp_path / "fixture.txt"
     lines = [" ".join(repr(float(v)) for v in list(fx["x0"][:3]) + list(fx["xf"][:3])), str(len(fx["polytopes"]))]
