@@ -2794,7 +2794,8 @@ __device__ __forceinline__ int result_rows(const ShareArgs& sa) {
 // still being explored elsewhere (returns false: the worker that finishes the last part continues the problem).
 // staged: 0 the problem is staged from its record (x0, xf, the face rows); 1 the hand-off of a fused pair has staged it in LDS (the safe
 // problem: handoff_onchip) — `pr` is then the caller's TEMPLATE of the safe problem, of which only the scalars are read; 2 the pair has no
-// safe problem (its result says FH_ST_BAD_INPUT, as that of a record the staged hand-off marks with n_seg = 0).
+// safe problem (the caller writes its result: FH_ST_INTERRUPTED if the whole problem was interrupted, else FH_ST_BAD_INPUT, as that of a
+// record the staged hand-off marks with n_seg = 0).
 // defer_store: the result is left in the LDS table (Solver::emit_result) and the caller stores it (Solver::flush_result) — the fused pair
 // kernel runs the hand-off first, so that its loads are not queued behind the result's stores.
 template <int NSEG, class SV, class PR>
@@ -3461,9 +3462,14 @@ __global__ void __launch_bounds__(64, WPS) solve_kernel(const fh_problem* __rest
 #ifdef FH_PROFILE
           sv.glue_cycles = pinned_clock() - tglue__;
 #endif
-          if (staged == 2) {  // the pair has no safe problem: its safe result says FH_ST_BAD_INPUT, as that of a record the staged hand-off marks with n_seg = 0
+          if (staged == 2) {
+            // The pair has no safe problem.  Its safe result says FH_ST_INTERRUPTED if the whole problem was interrupted — at its draw or
+            // in its search, possibly by another workgroup that finished it: the status word of the whole result emit_result left in the
+            // table, which the hand-off has only read — and otherwise FH_ST_BAD_INPUT, as that of a record the staged hand-off marks with
+            // n_seg = 0 (whole problem bad input, infeasible or at a limit; no safe trajectory needed in rule modes 1 / 2).
+            const int whole_status = uniform_i32(reinterpret_cast<const int*>(sv.Q)[2]);
             sv.N = 0; sv.flops = 0ull;
-            sv.emit_result(false, 0, FH_ST_BAD_INPUT, 0, 0, 0.0, 0.0, 0.0, result_rows<NSEG>(sa));
+            sv.emit_result(false, 0, whole_status == FH_ST_INTERRUPTED ? FH_ST_INTERRUPTED : FH_ST_BAD_INPUT, 0, 0, 0.0, 0.0, 0.0, result_rows<NSEG>(sa));
             sv.flush_result(ka.sres[unit]);
             sv.unit_done(sa);
             break;

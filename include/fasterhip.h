@@ -201,7 +201,8 @@ typedef struct fh_sched {
                                  with 1: what a caller that streams batches wants (bench.py sets it).                                     */
   int32_t pair_outputs;       /* fh_solve_pairs_device / fh_pool_solve_pairs: 1: d_safe and d_safe_faces are OUTPUTS, complete for every
                                  pair, exactly as fh_pair_glue_device leaves them (x0 = R, n_poly, face_off, face_begin, the rows; n_seg = 0
-                                 marks a pair without a safe problem).  0 (default): they are scratch — the safe problem of a pair is built
+                                 marks a pair without a safe problem, an interrupted one included: its safe RESULT says FH_ST_INTERRUPTED,
+                                 see fh_solve_pairs_device).  0 (default): they are scratch — the safe problem of a pair is built
                                  in the LDS of the wavefront that solves it and is written to these buffers only when it is handed to
                                  another workgroup (a tree that several wavefronts explore; a few dozen of 32768 pairs): what is in them
                                  after the launch is unspecified, the TEMPLATE fields of d_safe (n_seg, bounds, dc, factor window,
@@ -452,7 +453,10 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
  * fh_pair_glue_device and fh_solve_batch_device back to back (the per-pair dependency of Faster::replan, faster.cpp:427 -> :475 ->
  * :521-536), so no safe solve waits for the slowest whole solve of the batch.  Arguments and results are those of the three calls
  * (d_safe holds the safe problem templates on entry, as for fh_pair_glue_device); results are bit-identical to them.  The safe
- * problems must fit the same max_seg / max_faces bounds as the whole ones. */
+ * problems must fit the same max_seg / max_faces bounds as the whole ones.  A pair without a safe problem reports its safe result
+ * FH_ST_BAD_INPUT, solved = 0, as the safe launch of the three calls does for a record marked n_seg = 0 — except a pair whose whole
+ * problem ended FH_ST_INTERRUPTED (fh_request_stop, fh_params.deadline_ms): its safe result is FH_ST_INTERRUPTED, solved = 0, trials 0,
+ * zero rows, so that a caller who retries interrupted problems retries the whole pair. */
 int fh_solve_pairs_device(fh_ctx* ctx, const fh_problem* d_whole, const fh_face* d_faces, int n, int max_seg, int max_faces,
                           double r_frac, double shrink, int max_safe_poly, fh_result* d_whole_results, fh_problem* d_safe,
                           fh_face* d_safe_faces, fh_result* d_safe_results);

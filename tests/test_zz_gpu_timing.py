@@ -151,6 +151,91 @@ def test_deadline():
         c.close()
 
 
+class _Pairs:
+    """Fused pair launches (fh_solve_pairs_device, N = 15 kernel) as `long_search` drives them: the call returns the whole results and
+    keeps the safe results of the same launch in `.safe`."""
+
+    def __init__(self):
+        self.safe = None
+
+    def __call__(self, c, pr, faces):
+        from test_gpu_pair_interrupts import launch_pairs
+
+        w, self.safe, _, _ = launch_pairs(c, pr, faces, corridor.safe_templates(pr), 15)
+        return w
+
+
+def _interrupted_pairs_are_interrupted(w, s):
+    """A pair whose whole problem was interrupted has no safe problem: its safe result is interrupted too, and unsolved."""
+    hit = w["status"] == abi.FH_ST_INTERRUPTED
+    assert np.all(w["solved"][hit] == 0)
+    assert np.all(s["status"][hit] == abi.FH_ST_INTERRUPTED), np.unique(s["status"][hit], return_counts=True)
+    assert np.all(s["solved"][s["status"] == abi.FH_ST_INTERRUPTED] == 0)
+    return hit
+
+
+def test_pairs_stop_request_from_another_thread():
+    """fh_request_stop() from another thread while a fused pair launch runs: at least one whole problem is interrupted, and every pair
+    whose whole problem was interrupted reports its safe result FH_ST_INTERRUPTED, unsolved."""
+    c = capi.Context(0, pair_outputs=False, compact_results=True)
+    pairs = _Pairs()
+    try:
+        easy, efaces, _ = corridor.whole_batch(64, seed=5)
+        pairs(c, easy, efaces)                            # (first launch: allocations)
+        pr, faces, rung, _ = long_search(c, pairs)
+        out = {}
+
+        def run():
+            out["w"] = pairs(c, pr, faces)
+            out["s"] = pairs.safe
+
+        th = threading.Thread(target=run)
+        th.start()
+        time.sleep(STOP_DELAY_S)                          # the launch is under way (it takes >= MIN_RUN_MS un-stopped: measured above)
+        c.request_stop()
+        th.join(timeout=60)
+        assert not th.is_alive()
+        hit = _interrupted_pairs_are_interrupted(out["w"], out["s"])
+        print("rung %s: %d of %d whole problems interrupted" % (rung, hit.sum(), len(hit)))
+        assert hit.sum() >= 1
+    finally:
+        c.clear_stop()
+        c.close()
+
+
+def test_pairs_deadline():
+    """fh_params.deadline_ms = 10 on easy + hard fused pairs: the easy pairs that are not interrupted give what they give without a
+    deadline (bit for bit, all fields but the work counters), more than 200 of the 256 finish, and a pair whose whole problem was
+    interrupted — easy or hard — reports its safe result FH_ST_INTERRUPTED, unsolved."""
+    from test_gpu_pair_interrupts import same_records
+
+    c = capi.Context(0, pair_outputs=False, compact_results=True)
+    pairs = _Pairs()
+    try:
+        easy, efaces, _ = corridor.whole_batch(256, seed=6)
+        pairs(c, easy, efaces)                            # (first launch: allocations)
+        pr, faces, rung, _ = long_search(c, pairs)
+        _configure(c, rung[1], rung[2], 0.0)
+        wref = pairs(c, easy, efaces)                     # the easy pairs without a deadline (no result depends on the batch around them)
+        sref = pairs.safe
+        allpr, allfaces = corridor.concat([(easy, efaces), (pr, faces)])
+        _configure(c, rung[1], rung[2], 10.0)
+        t = time.perf_counter()
+        w = pairs(c, allpr, allfaces)
+        dur = time.perf_counter() - t
+        s = pairs.safe
+        assert dur < 1e-3 * MIN_RUN_MS / 3, dur           # the 10 ms budget + copies, not the >= MIN_RUN_MS of the un-stopped search
+        hit = _interrupted_pairs_are_interrupted(w, s)
+        s_hit = s["status"] == abi.FH_ST_INTERRUPTED
+        done = ~hit[:256] & ~s_hit[:256]
+        assert done.sum() > 200, done.sum()               # the easy ones were done long before the deadline
+        assert same_records(w[:256][done], wref[done], 10).all() and same_records(s[:256][done], sref[done], 10).all()
+        assert hit[256:].sum() >= 1
+        print("rung %s: %d of 256 easy pairs finished, %d of %d hard whole problems interrupted" % (rung, done.sum(), hit[256:].sum(), len(pr)))
+    finally:
+        c.close()
+
+
 def test_speculative_search_ends_on_stop_and_deadline():
     """fh_solve_batch_speculative (what SolverHip::genNewTraj calls with setConcurrentFactors) with several factors in flight:
     FH_ST_INTERRUPTED is terminal — the search of a problem stops there, unsolved, instead of going on to later factor windows
