@@ -87,6 +87,32 @@ pair_rule_dtype = np.dtype([("mode", "<i4"), ("reserved", "<i4"), ("r_known", "<
                             ("delta_a", "<f8")])
 assert pair_rule_dtype.itemsize == 40
 
+# fh_vehicle / fh_fleet_params: steady-state replanning of a fleet (fh_fleet_*)
+FH_VEHICLE_TRAVELING, FH_VEHICLE_GOAL_SEEN, FH_VEHICLE_GOAL_REACHED = 0, 1, 2
+FH_FLEET_STAGE_NONE, FH_FLEET_STAGE_NO_PATH, FH_FLEET_STAGE_NO_WHOLE, FH_FLEET_STAGE_NO_SAFE = 0, 1, 2, 3
+FH_FLEET_STAGE_COMMITTED, FH_FLEET_STAGE_OVERFLOW = 5, 6
+vehicle_dtype = np.dtype([("g_term", "<f8", (3,)), ("state", state_dtype), ("status", "<i4"), ("plan_head", "<i4"), ("plan_size", "<i4"),
+                          ("active", "<i4"), ("whole_init", "<f8"), ("whole_final", "<f8"), ("whole_inc", "<f8"), ("safe_init", "<f8"),
+                          ("safe_final", "<f8"), ("safe_inc", "<f8"), ("safe_factor_worked", "<f8"), ("goal", "<f8", (3,)), ("ra", "<f8"),
+                          ("dist_to_goal", "<f8"), ("stage", "<i4"), ("needed_safe", "<i4"), ("k_end_whole", "<i4"), ("k_safe", "<i4"),
+                          ("index_h", "<i4"), ("n_whole", "<i4"), ("n_safe", "<i4"), ("reserved", "<i4"), ("whole_factor", "<f8"),
+                          ("safe_factor", "<f8")], align=True)
+assert vehicle_dtype.itemsize == 280, vehicle_dtype.itemsize
+fleet_params_dtype = np.dtype([("delta_t", "<i4"), ("reserved", "<i4"), ("goal_radius", "<f8"), ("wdx", "<f8"), ("wdy", "<f8"), ("wdz", "<f8"),
+                               ("ra", "<f8"), ("gamma_whole", "<f8"), ("gammap_whole", "<f8"), ("increment_whole", "<f8"), ("gamma_safe", "<f8"),
+                               ("gammap_safe", "<f8"), ("increment_safe", "<f8"), ("rule", pair_rule_dtype)], align=True)
+assert fleet_params_dtype.itemsize == 136, fleet_params_dtype.itemsize
+
+
+def default_fleet_params():
+    """fh_fleet_params with the values of faster/param/faster.yaml (deltaT of faster.hpp:131), unknown space as an input (rule mode 2)."""
+    p = np.zeros((), dtype=fleet_params_dtype)
+    p["delta_t"], p["goal_radius"], p["wdx"], p["wdy"], p["wdz"], p["ra"] = 10, 0.3, 20.0, 20.0, 4.0, 4.0
+    for k in ("whole", "safe"):
+        p["gamma_" + k], p["gammap_" + k], p["increment_" + k] = 20.0, 20.0, 1.0
+    p["rule"]["mode"], p["rule"]["drone_radius"], p["rule"]["delta_h"], p["rule"]["delta_a"] = 2, 0.42, 1.0, 0.5
+    return p
+
 
 def default_sched():
     s = np.zeros((), dtype=sched_dtype)

@@ -24,6 +24,7 @@ SYMBOLS = [
     "fh_map_dims", "fh_map_occupancy", "fh_map_plan_batch", "fh_map_plan_batch_device",
     "fh_sync", "fh_timing_reset", "fh_timing_read", "fh_last_kernel_ms", "fh_last_launch", "fh_version", "fh_abi_version",
     "fh_packed_result_size", "fh_pack_results_device", "fh_pack_results", "fh_unpack_results", "fh_control_points",
+    "fh_map_plan_batch_radius_device", "fh_fleet_init_device", "fh_fleet_begin_device", "fh_fleet_commit_device", "fh_fleet_next_goals_device",
 ]
 
 _LIB = None
@@ -209,6 +210,16 @@ def lib():
         L.fh_map_plan_batch.argtypes = [vp, vp, vp, i32, i32, f64, i32, vp, vp, vp]
         L.fh_map_plan_batch_device.restype = i32
         L.fh_map_plan_batch_device.argtypes = [vp, vp, vp, i32, i32, f64, i32, vp, vp, vp]
+        L.fh_map_plan_batch_radius_device.restype = i32
+        L.fh_map_plan_batch_radius_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, f64, i32, vp, vp, vp]
+        L.fh_fleet_init_device.restype = i32
+        L.fh_fleet_init_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+        L.fh_fleet_begin_device.restype = i32
+        L.fh_fleet_begin_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.fh_fleet_commit_device.restype = i32
+        L.fh_fleet_commit_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+        L.fh_fleet_next_goals_device.restype = i32
+        L.fh_fleet_next_goals_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
         L.fh_timing_reset.restype = i32
         L.fh_timing_reset.argtypes = [vp]
         L.fh_timing_read.restype = i32
@@ -402,6 +413,12 @@ class Map:
     def plan_batch_device(self, d_starts, d_goals, n, max_points, d_paths, d_n_points, d_expansions=None, max_vertex_dist=0.0, max_poly=0):
         self._check(lib().fh_map_plan_batch_device(self._h, d_starts, d_goals, n, max_points, float(max_vertex_dist), int(max_poly), d_paths,
                                                    d_n_points, d_expansions), "fh_map_plan_batch_device")
+
+    def plan_batch_radius_device(self, d_starts, d_goals, d_radius, d_active, n, max_points, d_paths, d_n_points, d_expansions=None,
+                                 max_vertex_dist=0.0, max_poly=0):
+        """fh_map_plan_batch_radius_device: every path clipped to the sphere of its own radius d_radius[i]; d_active (may be None): 0 = no search."""
+        self._check(lib().fh_map_plan_batch_radius_device(self._h, d_starts, d_goals, d_radius, d_active, n, max_points, float(max_vertex_dist),
+                                                          int(max_poly), d_paths, d_n_points, d_expansions), "fh_map_plan_batch_radius_device")
 
 
 class Context:
@@ -636,6 +653,25 @@ class Context:
     def next_goals_device(self, d_plans, d_counts, d_cursor, n, max_states, ticks, d_goals, d_ok=None):
         """fh_next_goals_device: Faster::getNextGoal (without yaw) for a batch of committed plans; `ticks` calls in a row."""
         self._check(lib().fh_next_goals_device(self._h, d_plans, d_counts, d_cursor, n, max_states, ticks, d_goals, d_ok), "fh_next_goals_device")
+
+    # ---- a fleet in steady state (fh_fleet_*): params is an abi.fleet_params_dtype record ----
+    def fleet_init_device(self, params, d_states, d_goals, n, max_states, d_vehicles, d_plans):
+        p = np.ascontiguousarray(params).reshape(1)
+        self._check(lib().fh_fleet_init_device(self._h, abi.ptr(p), d_states, d_goals, n, max_states, d_vehicles, d_plans), "fh_fleet_init_device")
+
+    def fleet_begin_device(self, params, d_vehicles, d_plans, n, max_states, d_whole, d_safe, d_starts, d_goals, d_radius, d_active):
+        p = np.ascontiguousarray(params).reshape(1)
+        self._check(lib().fh_fleet_begin_device(self._h, abi.ptr(p), d_vehicles, d_plans, n, max_states, d_whole, d_safe, d_starts, d_goals, d_radius,
+                                                d_active), "fh_fleet_begin_device")
+
+    def fleet_commit_device(self, params, d_vehicles, d_plans, n, max_states, d_n_points, d_whole, d_whole_results, d_safe, d_safe_results):
+        p = np.ascontiguousarray(params).reshape(1)
+        self._check(lib().fh_fleet_commit_device(self._h, abi.ptr(p), d_vehicles, d_plans, n, max_states, d_n_points, d_whole, d_whole_results, d_safe,
+                                                 d_safe_results), "fh_fleet_commit_device")
+
+    def fleet_next_goals_device(self, d_vehicles, d_plans, n, max_states, ticks, follow, d_goals):
+        self._check(lib().fh_fleet_next_goals_device(self._h, d_vehicles, d_plans, n, max_states, int(ticks), 1 if follow else 0, d_goals),
+                    "fh_fleet_next_goals_device")
 
     def pair_glue_device(self, d_whole, d_whole_results, d_faces, n, r_frac, shrink, max_safe_poly, d_safe, d_safe_faces):
         self._check(lib().fh_pair_glue_device(self._h, d_whole, d_whole_results, d_faces, n, r_frac, shrink, max_safe_poly,

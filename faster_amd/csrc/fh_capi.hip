@@ -21,6 +21,7 @@
 #include "fh_solve.hip.hpp"
 #include "fh_decomp.hip.hpp"
 #include "fh_safe.hip.hpp"  // (after fh_solve: it switches FP contraction off for what follows, like fh_decomp)
+#include "fh_fleet.hip.hpp"
 
 struct fh_ctx {
   int device = 0;
@@ -1225,6 +1226,68 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
                      (const fh_face*)ctx->d_buf[11], (const int32_t*)ctx->d_buf[12], faces_per_problem, d_safe_faces, w_off, w_npoly);
   hipLaunchKernelGGL(fh::safe_finalize_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, w_np, w_goal, d_goals, d_safe_faces, w_off, w_npoly, n,
                      faces_per_problem, n_seg_safe, d_safe);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// ---- steady-state replanning of a fleet (fh_fleet.hip.hpp): plans, status and factor windows carried across cycles ----
+static bool fleet_params_ok(const fh_fleet_params* p) {
+  return p && p->delta_t >= 1 && p->goal_radius >= 0 && p->wdx > 0 && p->wdy > 0 && p->wdz > 0 && p->ra > 0 && (p->rule.mode == 1 || p->rule.mode == 2);
+}
+
+int fh_fleet_init_device(fh_ctx* ctx, const fh_fleet_params* params, const fh_state* d_states, const double* d_goals, int n, int max_states,
+                         fh_vehicle* d_vehicles, fh_state* d_plans) {
+  if (!ctx || n < 0 || max_states < 1 || !fleet_params_ok(params)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx);
+  if (n == 0) return FH_OK;
+  if (!d_states || !d_goals || !d_vehicles || !d_plans) return FH_ERR_ARG;
+  hipLaunchKernelGGL(fh::fleet_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *params, d_states, d_goals, n, max_states,
+                     d_vehicles, d_plans);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_begin_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states,
+                          fh_problem* d_whole, fh_problem* d_safe, double* d_starts, double* d_goals, double* d_radius, int32_t* d_active) {
+  if (!ctx || n < 0 || max_states < 1 || !fleet_params_ok(params)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_whole || !d_safe || !d_starts || !d_goals || !d_radius || !d_active) return FH_ERR_ARG;
+  hipLaunchKernelGGL(fh::fleet_begin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *params, d_vehicles, d_plans, n, max_states,
+                     d_whole, d_safe, d_starts, d_goals, d_radius, d_active);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_commit_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicle* d_vehicles, fh_state* d_plans, int n, int max_states,
+                           const int32_t* d_n_points, const fh_problem* d_whole, const fh_result* d_whole_results, const fh_problem* d_safe,
+                           const fh_result* d_safe_results) {
+  if (!ctx || n < 0 || max_states < 1 || !fleet_params_ok(params)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_n_points || !d_whole || !d_whole_results || !d_safe || !d_safe_results) return FH_ERR_ARG;
+  if (params->rule.mode == 2 && !ctx->unknown.flags) {
+    ctx->err = "fh_pair_rule mode 2 needs the unknown voxels: fh_set_unknown_grid_device";
+    return FH_ERR_ARG;
+  }
+  hipLaunchKernelGGL(fh::fleet_commit_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, *params, d_vehicles, d_plans, n, max_states, d_n_points,
+                     d_whole, d_whole_results, d_safe, d_safe_results, ctx->unknown);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_next_goals_device(fh_ctx* ctx, fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states, int ticks, int follow,
+                               fh_state* d_goals) {
+  if (!ctx || n < 0 || max_states < 1 || ticks < 1) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_goals) return FH_ERR_ARG;
+  hipLaunchKernelGGL(fh::fleet_next_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_vehicles, d_plans, n, max_states, ticks,
+                     follow, d_goals);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }

@@ -1,0 +1,243 @@
+// fh_fleet.hip.hpp — steady-state replanning of a fleet on the device (gfx950, wave64): what Faster::replan carries from one period
+// to the next (/root/reference/faster/src/faster.cpp:296-595) — the committed plan, the start state A deltaT states into it, the
+// vehicle status and the two factor windows — kept per vehicle in caller-owned device memory (fh_vehicle, include/fasterhip.h).
+//
+// fleet_init_kernel   : setTerminalGoal + the first updateState (faster.cpp:139-155, :267-279).          One lane per vehicle.
+// fleet_begin_kernel  : G, dist_to_goal, GOAL_REACHED, k_end_whole, A, ra (faster.cpp:317-373).           One lane per vehicle.
+// fleet_commit_kernel : the outcome of the cycle, appendToPlan, GOAL_SEEN, the factor windows (:548-588, :606-648).
+//                       One wavefront per vehicle; the samples are written by sample_into, the sampler of fh_sample_batch.
+// fleet_next_kernel   : getNextGoal `ticks` times (faster.cpp:699-723, without yaw).                     One lane per vehicle.
+// The host restatement these kernels are checked against, cycle by cycle, is fhreplan::Planner (faster_amd/host/replan_stub.hpp),
+// compiled by g++ without contraction into fused multiply-adds: the geometry here is written with contraction off, in the same
+// operation order (a last-bit difference in G or ra changes a path, and a cycle later a factor window).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/fasterhip.h"
+#include "fh_sample.hip.hpp"
+
+namespace fh {
+
+__device__ __forceinline__ double fleet_norm3(double x, double y, double z) {
+#pragma clang fp contract(off)
+  return sqrt(x * x + y * y + z * z);  // V3::norm = sqrt(dot(*this)) (corridor_frontend.hpp)
+}
+
+// projectPointToBox (utils.cpp:1065-1115) as replan_stub.hpp's project_to_box restates it: the box of size w around c; p inside is
+// returned as it is, else the nearest crossing of the segment c -> p with a face plane
+__device__ inline void fleet_project_to_box(const double (&c)[3], const double (&p)[3], const double (&w)[3], double (&out)[3]) {
+#pragma clang fp contract(off)
+  double lo[3], hi[3];
+  for (int a = 0; a < 3; a++) { lo[a] = c[a] - w[a] / 2; hi[a] = c[a] + w[a] / 2; }
+  out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
+  if (p[0] < hi[0] && p[0] > lo[0] && p[1] < hi[1] && p[1] > lo[1] && p[2] < hi[2] && p[2] > lo[2]) return;
+  double best = INFINITY;
+  for (int ax = 0; ax < 3; ax++)
+    for (int side = 0; side < 2; side++) {
+      const double plane = side ? lo[ax] : hi[ax], den = p[ax] - c[ax];
+      if (den == 0) continue;
+      const double t = (plane - c[ax]) / den;
+      if (t < 0 || t > 1) continue;
+      double x[3];
+      for (int a = 0; a < 3; a++) x[a] = c[a] + (p[a] - c[a]) * t;
+      const double dist = fleet_norm3(x[0] - c[0], x[1] - c[1], x[2] - c[2]);
+      if (dist < best) { best = dist; out[0] = x[0]; out[1] = x[1]; out[2] = x[2]; }
+    }
+}
+
+__device__ __forceinline__ void fleet_clear_log(fh_vehicle& v) {
+  v.stage = FH_FLEET_STAGE_NONE;
+  v.needed_safe = 0; v.k_end_whole = 0; v.k_safe = 0; v.index_h = 0; v.n_whole = 0; v.n_safe = 0; v.reserved = 0;
+  v.whole_factor = 0; v.safe_factor = 0;
+}
+
+__global__ void __launch_bounds__(256) fleet_init_kernel(fh_fleet_params par, const fh_state* __restrict__ states, const double* __restrict__ goals,
+                                                         int n, int max_states, fh_vehicle* __restrict__ vehicles, fh_state* __restrict__ plans) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= n) return;
+  fh_vehicle v;
+  const fh_state s = states[i];
+  for (int a = 0; a < 3; a++) { v.g_term[a] = goals[3 * i + a]; v.goal[a] = v.g_term[a]; }
+  v.state = s;
+  v.status = FH_VEHICLE_TRAVELING;
+  v.plan_head = 0; v.plan_size = 1; v.active = 0;
+  v.whole_init = 1; v.whole_final = 10; v.whole_inc = par.increment_whole;  // faster.cpp:57
+  v.safe_init = 1; v.safe_final = 10; v.safe_inc = par.increment_safe;      // faster.cpp:68
+  v.safe_factor_worked = 0;                                                 // solverGurobi.hpp:135
+  v.ra = 0; v.dist_to_goal = 0;
+  fleet_clear_log(v);
+  vehicles[i] = v;
+  plans[(size_t)i * (size_t)max_states] = s;  // the first updateState seeds the plan (faster.cpp:146-152)
+}
+
+__global__ void __launch_bounds__(256) fleet_begin_kernel(fh_fleet_params par, fh_vehicle* __restrict__ vehicles, const fh_state* __restrict__ plans,
+                                                          int n, int max_states, fh_problem* __restrict__ whole, fh_problem* __restrict__ safe,
+                                                          double* __restrict__ starts, double* __restrict__ goals, double* __restrict__ radius,
+                                                          int32_t* __restrict__ active) {
+#pragma clang fp contract(off)
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= n) return;
+  fh_vehicle& v = vehicles[i];
+  const double here[3] = {v.state.pos[0], v.state.pos[1], v.state.pos[2]};
+  const double gterm[3] = {v.g_term[0], v.g_term[1], v.g_term[2]};
+  const double w[3] = {par.wdx, par.wdy, par.wdz};
+  double G[3];
+  fleet_project_to_box(here, gterm, w, G);                                                        // :317-319
+  const double dist = fleet_norm3(gterm[0] - here[0], gterm[1] - here[1], gterm[2] - here[2]);   // :331
+  int status = v.status;
+  if (dist < par.goal_radius) status = FH_VEHICLE_GOAL_REACHED;                                  // :332-335
+  const bool run = status != FH_VEHICLE_GOAL_REACHED && v.plan_size >= 1;                        // :337-343
+  int k_end = 0;
+  double ra = 0;
+  double x0[9] = {here[0], here[1], here[2], 0, 0, 0, 0, 0, 0};
+  if (run) {
+    k_end = v.plan_size - par.delta_t;                                                            // :351
+    k_end = k_end > 0 ? k_end : 0;
+    const fh_state& A = plans[(size_t)i * (size_t)max_states + v.plan_head + v.plan_size - 1 - k_end];  // :352
+    for (int a = 0; a < 3; a++) { x0[a] = A.pos[a]; x0[3 + a] = A.vel[a]; x0[6 + a] = A.accel[a]; }
+    const double r = dist - 0.001;
+    ra = par.ra < r ? par.ra : r;                                                                  // std::min(dist - 0.001, Ra), :373
+  }
+  v.status = status;
+  v.active = run ? 1 : 0;
+  for (int a = 0; a < 3; a++) v.goal[a] = G[a];
+  v.ra = ra;
+  v.dist_to_goal = dist;
+  fleet_clear_log(v);
+  v.k_end_whole = k_end;
+  fh_problem& pw = whole[i];
+  for (int j = 0; j < 9; j++) pw.x0[j] = x0[j];
+  pw.f_init = v.whole_init; pw.f_final = v.whole_final; pw.f_inc = v.whole_inc;
+  fh_problem& ps = safe[i];
+  ps.f_init = v.safe_init; ps.f_final = v.safe_final; ps.f_inc = v.safe_inc;
+  for (int a = 0; a < 3; a++) { starts[3 * i + a] = x0[a]; goals[3 * i + a] = G[a]; }
+  radius[i] = ra;
+  active[i] = run ? 1 : 0;
+}
+
+__device__ __forceinline__ bool fleet_problem_ok(const fh_problem& p, const fh_result& r) { return r.solved && p.n_seg >= 1 && p.n_seg <= FH_MAX_SEG; }
+
+__global__ void __launch_bounds__(64) fleet_commit_kernel(fh_fleet_params par, fh_vehicle* __restrict__ vehicles, fh_state* __restrict__ plans, int n,
+                                                          int max_states, const int32_t* __restrict__ n_points, const fh_problem* __restrict__ whole,
+                                                          const fh_result* __restrict__ wres, const fh_problem* __restrict__ safe,
+                                                          const fh_result* __restrict__ sres, UnknownGrid ug) {
+  __shared__ __attribute__((aligned(16))) double tile[64 * 12];
+  __shared__ double coef[FH_MAX_SEG * 12];
+  const int b = blockIdx.x;
+  if (b >= n) return;
+  const int lane = threadIdx.x;
+  fh_vehicle& v = vehicles[b];
+  if (!__builtin_amdgcn_readfirstlane(v.active)) return;  // the log was cleared by fleet_begin_kernel (a GOAL_REACHED vehicle: stage 0)
+  const fh_problem& pw = whole[b];
+  const fh_result& rw = wres[b];
+  const fh_problem& ps = safe[b];
+  const fh_result& rs = sres[b];
+  int stage = FH_FLEET_STAGE_NONE, need = 0, k = 0, iH = 0, size_w = 0, size_s = 0;
+  double wf = 0, sf = 0;
+  bool have_safe = false;
+  if (n_points[b] < 2) {
+    stage = FH_FLEET_STAGE_NO_PATH;                          // :361-367
+  } else if (!fleet_problem_ok(pw, rw)) {
+    stage = FH_FLEET_STAGE_NO_WHOLE;                         // :427-431 (a missing corridor marks the record n_seg = 0)
+  } else {
+    size_w = __builtin_amdgcn_readfirstlane(sample_count(pw, rw));
+    wf = rw.factor;
+    need = choose_r_index(pw, rw, 0.0, par.rule, lane, k, &ug, &iH) ? 1 : 0;  // findIndexH / findIndexR, :456-475
+    k = __builtin_amdgcn_readfirstlane(k);
+    iH = __builtin_amdgcn_readfirstlane(iH);
+    have_safe = need && fleet_problem_ok(ps, rs);
+    if (need && !have_safe) {
+      stage = FH_FLEET_STAGE_NO_SAFE;                        // :529-533
+    } else {
+      if (have_safe) {
+        size_s = __builtin_amdgcn_readfirstlane(sample_count(ps, rs));
+        sf = rs.factor;
+      }
+      const int kept = v.plan_size - v.k_end_whole - 1;      // appendToPlan: the last k_end_whole + 1 states go (:617-623)
+      const long long total = (long long)kept + (k + 1) + size_s;
+      stage = total > max_states ? FH_FLEET_STAGE_OVERFLOW : FH_FLEET_STAGE_COMMITTED;
+    }
+  }
+  stage = __builtin_amdgcn_readfirstlane(stage);
+  int new_size = 0, status = v.status;
+  if (stage == FH_FLEET_STAGE_COMMITTED) {
+    fh_state* base = plans + (size_t)b * (size_t)max_states;
+    const int head = __builtin_amdgcn_readfirstlane(v.plan_head);
+    const int kept = __builtin_amdgcn_readfirstlane(v.plan_size - v.k_end_whole - 1);
+    // the kept prefix [head, head + kept) to [0, kept): chunk c reads head + 64 c + lane and writes 64 c + lane, each state read into
+    // registers before it is written (a store of chunk c never touches what chunk c + 1 reads: head + 64 (c + 1) >= 64 c + 64)
+    if (head != 0)
+      for (int j0 = 0; j0 < kept; j0 += 64) {
+        const int j = j0 + lane;
+        fh_state s;
+        if (j < kept) s = base[head + j];
+        __syncthreads();
+        if (j < kept) base[j] = s;
+        __syncthreads();
+      }
+    __syncthreads();
+    sample_into(pw, rw, size_w, k + 1, base + kept, tile, coef, lane);            // whole samples 0 .. k_safe (:627-633)
+    int last = k;                                                                   // tile row of the last state written
+    if (size_s > 0) {
+      sample_into(ps, rs, size_s, size_s, base + kept + k + 1, tile, coef, lane);  // every safe sample (:635-640)
+      last = size_s - 1;
+    }
+    new_size = kept + k + 1 + size_s;
+    // plan_.back(): the last state written, still in the sampler's LDS tile (the same bits as in memory)
+    const double* lp = &tile[(last % 64) * 12];
+    {
+#pragma clang fp contract(off)
+      const double d = fleet_norm3(v.g_term[0] - lp[0], v.g_term[1] - lp[1], v.g_term[2] - lp[2]);
+      if (d < par.goal_radius) status = FH_VEHICLE_GOAL_SEEN;                     // :563-570
+    }
+  }
+  if (lane == 0) {
+    v.stage = stage;
+    if (stage >= FH_FLEET_STAGE_NO_SAFE) {  // (stages 3, 5, 6: the whole trajectory exists, findIndexH / findIndexR ran)
+      v.needed_safe = need;
+      v.index_h = iH;
+      v.k_safe = k;
+      v.n_whole = size_w;
+    }
+    if (stage >= FH_FLEET_STAGE_NO_SAFE) v.whole_factor = wf;
+    if (have_safe) {                       // sg_safe_.factor_that_worked_ changes with every successful safe solve (solver_hip.cpp:132)
+      v.safe_factor = sf;
+      v.n_safe = size_s;
+      v.safe_factor_worked = sf;
+    }
+    if (stage == FH_FLEET_STAGE_COMMITTED) {
+      v.plan_head = 0;
+      v.plan_size = new_size;
+      v.status = status;
+      // faster.cpp:578-584 — std::max(f - gamma, 1.0): 1.0 unless f - gamma is larger
+      const double wi = wf - par.gamma_whole, si = v.safe_factor_worked - par.gamma_safe;
+      v.whole_init = wi > 1.0 ? wi : 1.0;
+      v.whole_final = wf + par.gammap_whole;
+      v.whole_inc = par.increment_whole;
+      v.safe_init = si > 1.0 ? si : 1.0;
+      v.safe_final = v.safe_factor_worked + par.gammap_safe;
+      v.safe_inc = par.increment_safe;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) fleet_next_kernel(fh_vehicle* __restrict__ vehicles, const fh_state* __restrict__ plans, int n, int max_states,
+                                                         int ticks, int follow, fh_state* __restrict__ goals) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= n) return;
+  fh_vehicle& v = vehicles[i];
+  const int size = v.plan_size, head = v.plan_head;
+  fh_state g;
+  for (int a = 0; a < 3; a++) { g.pos[a] = 0; g.vel[a] = 0; g.accel[a] = 0; g.jerk[a] = 0; }
+  if (size > 0) {
+    const int last = head + (ticks - 1 < size - 1 ? ticks - 1 : size - 1);  // front() of the last of the `ticks` calls
+    g = plans[(size_t)i * (size_t)max_states + last];
+    const int pops = ticks < size - 1 ? ticks : size - 1;                    // pop_front() while more than one state is left
+    v.plan_head = head + pops;
+    v.plan_size = size - pops;
+    if (follow) v.state = g;
+  }
+  goals[i] = g;
+}
+
+}  // namespace fh

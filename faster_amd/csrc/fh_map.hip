@@ -370,9 +370,9 @@ int fh_map_occupancy(fh_map* m, int8_t* occ) {
   return FH_OK;
 }
 
-int fh_map_plan_batch_device(fh_map* m, const double* d_starts, const double* d_goals, int n, int max_points, double max_vertex_dist,
-                             int max_poly, double* d_paths, int32_t* d_n_points, int64_t* d_expansions) {
-  if (!m || !m->have_map || n < 0 || max_points < 2 || (n > 0 && (!d_starts || !d_goals || !d_paths || !d_n_points))) return FH_ERR_ARG;
+// d_radius / d_active: fh_map_plan_batch_radius_device (null: fh_map_plan_batch_device)
+static int plan_batch_device(fh_map* m, const double* d_starts, const double* d_goals, const double* d_radius, const int32_t* d_active, int n,
+                             int max_points, double max_vertex_dist, int max_poly, double* d_paths, int32_t* d_n_points, int64_t* d_expansions) {
   if (n == 0) return FH_OK;
   MapDeviceScope scope(m);
   int rc;
@@ -391,6 +391,8 @@ int fh_map_plan_batch_device(fh_map* m, const double* d_starts, const double* d_
   pa.max_vertex_dist = max_vertex_dist; pa.max_poly = max_poly;
   pa.jps_tables = m->d_jps_tables;
   pa.sphere_ra = m->sphere_ra;
+  pa.radius = d_radius;
+  pa.active = d_active;
   pa.profile_slot = -1;
 #ifdef FHP_PROFILE
   if (const char* e = std::getenv("FHP_PROFILE_SLOT")) pa.profile_slot = std::atoi(e);
@@ -442,6 +444,19 @@ int fh_map_plan_batch_device(fh_map* m, const double* d_starts, const double* d_
   else hipLaunchKernelGGL(fhp::plan_kernel<false>, dim3((unsigned)grid), dim3(64), 0, m->stream, mv, pa);
   FM_HIP(hipGetLastError());
   return FH_OK;
+}
+
+int fh_map_plan_batch_device(fh_map* m, const double* d_starts, const double* d_goals, int n, int max_points, double max_vertex_dist,
+                             int max_poly, double* d_paths, int32_t* d_n_points, int64_t* d_expansions) {
+  if (!m || !m->have_map || n < 0 || max_points < 2 || (n > 0 && (!d_starts || !d_goals || !d_paths || !d_n_points))) return FH_ERR_ARG;
+  return plan_batch_device(m, d_starts, d_goals, nullptr, nullptr, n, max_points, max_vertex_dist, max_poly, d_paths, d_n_points, d_expansions);
+}
+
+int fh_map_plan_batch_radius_device(fh_map* m, const double* d_starts, const double* d_goals, const double* d_radius, const int32_t* d_active,
+                                    int n, int max_points, double max_vertex_dist, int max_poly, double* d_paths, int32_t* d_n_points,
+                                    int64_t* d_expansions) {
+  if (!m || !m->have_map || n < 0 || max_points < 2 || (n > 0 && (!d_starts || !d_goals || !d_radius || !d_paths || !d_n_points))) return FH_ERR_ARG;
+  return plan_batch_device(m, d_starts, d_goals, d_radius, d_active, n, max_points, max_vertex_dist, max_poly, d_paths, d_n_points, d_expansions);
 }
 
 int fh_map_plan_batch(fh_map* m, const double* starts, const double* goals, int n, int max_points, double max_vertex_dist, int max_poly,

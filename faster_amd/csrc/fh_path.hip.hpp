@@ -70,6 +70,8 @@ struct PlanArgs {
   double max_vertex_dist;
   int max_poly;
   double sphere_ra;       // > 0: the path is clipped to JPS_in first (Faster::replan, faster.cpp:370-382), see clip in plan_kernel
+  const double* radius;   // [n] or null: the clip radius of every query as it is (fh_map_plan_batch_radius_device; sphere_ra is then unused)
+  const int* active;      // [n] or null: a query with active[q] == 0 searches nothing and returns 0 vertices
   const unsigned char* jps_tables;  // jump point search only: the neighbour tables, see Planner::init_jps
   const short* jps_entries;         // ... and the jump tables of this map [total][32], see jps_table_kernel
   int profile_slot;                 // FHP_PROFILE builds only (scripts/jps_phase_profile.py): which phase's cycles `expansions` receives
@@ -1398,7 +1400,8 @@ __global__ void __launch_bounds__(64, JPS ? 5 : 3) plan_kernel(MapView mv, PlanA
     pl.prof_acc = 0;
     const long long q_t0 = (long long)__builtin_readcyclecounter();
 #endif
-    if (!pl.outside(pl.s[0], pl.s[1], pl.s[2]) && !pl.outside(pl.t[0], pl.t[1], pl.t[2])) {
+    const bool live = !pa.active || rfl(pa.active[q]) != 0;
+    if (live && !pl.outside(pl.s[0], pl.s[1], pl.s[2]) && !pl.outside(pl.t[0], pl.t[1], pl.t[2])) {
       serial++;
       if (serial >= (JPS ? JPS_SERIAL_LIMIT : 0x7fffffffu)) {  // 2^31 (2^26) queries of this wavefront: its stamps start over, so its cell states are cleared first
         if (HASHED) for (int c = lane; c < pa.hslots; c += 64) pl.hk[c] = 0ull;
@@ -1439,8 +1442,8 @@ __global__ void __launch_bounds__(64, JPS ? 5 : 3) plan_kernel(MapView mv, PlanA
         int n_in = count;
         bool has_e = false;
         double E[3] = {0, 0, 0};
-        if (pa.sphere_ra > 0.0) {
-          const double ra = fmin(Planner::dist(gl, st) - 0.001, pa.sphere_ra);
+        if (pa.radius || pa.sphere_ra > 0.0) {
+          const double ra = pa.radius ? pa.radius[q] : fmin(Planner::dist(gl, st) - 0.001, pa.sphere_ra);
           for (int i = 1; i < count; i++) {
             double b[3];
             vertex(i, b);

@@ -209,7 +209,7 @@ __device__ __forceinline__ int wave_min_i32(int v) {
 // trajectory is needed (needToComputeSafePath == false, :462-466): k is then indexH = the last sample (:231).
 template <class PW, class RW>
 __device__ inline bool choose_r_index(const PW& pw, const RW& rw, double r_frac, const fh_pair_rule& rule, int lane, int& k,
-                                      const UnknownGrid* ug = nullptr) {
+                                      const UnknownGrid* ug = nullptr, int* index_h = nullptr) {  // index_h: findIndexH's indexH (modes 1, 2)
   const int N = pw.n_seg;
   const double DC = pw.dc;
   const int size = sample_count(pw, rw);
@@ -236,10 +236,12 @@ __device__ inline bool choose_r_index(const PW& pw, const RW& rw, double r_frac,
     }
     if (iH == 0x7fffffff) {  // needToComputeSafePath == false (:462-466): the pair ends with its whole trajectory
       k = size - 1;
+      if (index_h) *index_h = size - 1;
       return false;
     }
     int indexH = (int)(rule.delta_h * (double)iH);
     indexH = indexH > size - 1 ? size - 1 : (indexH < 0 ? 0 : indexH);
+    if (index_h) *index_h = indexH;
     fh_state sH;
     state_at(rw, N, DC, indexH, size, sH);
     // findIndexR (faster.cpp:173-216): first sample from which braking before H is no longer possible (x and y only)

@@ -1,0 +1,182 @@
+"""A fleet of vehicles replanning in steady state on the device (fh_fleet_*, include/fasterhip.h).
+
+Faster::replan (faster/src/faster.cpp:296-595) runs once per period and carries its plan, its status and its two factor windows from one
+call to the next.  `Fleet` keeps that state for N vehicles in device memory and runs one period of all of them as a fixed chain of batch
+launches on one stream, with no host round trip inside:
+
+    begin -> path search (sphere per vehicle) -> corridors -> corridor problems -> whole solve -> safe corridor -> safe solve -> commit
+
+All vehicles share one map and one grid of unknown voxels per cycle (set_map / set_unknown).  The host restatement every cycle is checked
+against is fhreplan::Planner (faster_amd/host/replan_stub.hpp); tests/test_gpu_fleet.py compares the two cycle by cycle.
+"""
+import numpy as np
+
+from . import abi, capi
+
+
+class Fleet:
+    """N vehicles, one map, one context.  Buffers are torch tensors on `device`; everything runs on the fleet's own stream."""
+
+    def __init__(self, n, params=None, device=0, n_seg=6, max_poly=3, max_points=32, faces_per_problem=192, max_states=1024, dc=0.01,
+                 v_max=5.0, a_max=5.0, j_max=8.0, decomp_radius=0.05, dist_max_vertexes=1.5, local_bbox=(2.0, 2.0, 1.0), z_ground=0.0,
+                 search="jps"):
+        import torch
+
+        self.torch = torch
+        self.n, self.N, self.max_poly, self.mp, self.fpp, self.max_states = int(n), int(n_seg), int(max_poly), int(max_points), int(faces_per_problem), int(max_states)
+        self.params = np.array(abi.default_fleet_params() if params is None else params, dtype=abi.fleet_params_dtype).reshape(())
+        self.decomp_radius, self.dist_max_vertexes, self.local_bbox, self.z_ground = float(decomp_radius), float(dist_max_vertexes), tuple(local_bbox), float(z_ground)
+        self.dev = torch.device("cuda", device)
+        self.stream = torch.cuda.Stream(device=self.dev)
+        self.ctx, self.map = capi.Context(device), capi.Map(device)
+        self.ctx.set_stream(self.stream.cuda_stream)
+        self.map.set_stream(self.stream.cuda_stream)
+        self.map.set_search(search)
+        rule = self.params["rule"]
+        self.ctx.set_pair_rule(mode=int(rule["mode"]), r_known=float(rule["r_known"]), drone_radius=float(rule["drone_radius"]),
+                               delta_h=float(rule["delta_h"]), delta_a=float(rule["delta_a"]))
+        B, u8, i32, f64 = self.n, torch.uint8, torch.int32, torch.float64
+        whole = abi.make_problems(B)
+        whole["n_seg"], whole["force_final_pos"], whole["dc"] = self.N, 1, dc
+        whole["v_max"], whole["a_max"], whole["j_max"] = v_max, a_max, j_max
+        safe = whole.copy()
+        safe["force_final_pos"] = 0
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.dev)  # noqa: E731
+        self.d_vehicles = z(B * abi.vehicle_dtype.itemsize, u8)
+        self.d_plans = z(B * self.max_states * abi.state_dtype.itemsize, u8)
+        self.d_whole = torch.from_numpy(whole.view(np.uint8).copy()).to(self.dev)
+        self.d_safe = torch.from_numpy(safe.view(np.uint8).copy()).to(self.dev)
+        self.d_starts, self.d_goals, self.d_radius, self.d_active = z((B, 3), f64), z((B, 3), f64), z(B, f64), z(B, i32)
+        self.d_paths, self.d_np, self.d_ex = z((B, self.mp, 3), f64), z(B, i32), z(B, torch.int64)
+        FB, RES = abi.face_dtype.itemsize, abi.result_dtype.itemsize
+        self.d_wf, self.d_sf = z(B * self.fpp * FB, u8), z(B * self.fpp * FB, u8)
+        self.d_off, self.d_npoly, self.d_last = z((B, 9), i32), z(B, i32), z((B, 3), f64)
+        self.d_wr, self.d_sr = z(B * RES, u8), z(B * RES, u8)
+        self.d_spaths, self.d_snp = z((B, self.max_poly + 1, 3), f64), z(B, i32)
+        self.d_next = z(B * abi.state_dtype.itemsize, u8)
+        self.cloud, self.n_cloud, self.grid = None, 0, None
+        torch.cuda.synchronize(self.dev)
+
+    def close(self):
+        if self.map is not None:
+            self.map.close()
+            self.ctx.close()
+            self.map = self.ctx = None
+
+    def _host_to_device(self, a, dtype):
+        t = self.torch
+        if isinstance(a, t.Tensor):
+            return a.to(self.dev, dtype=dtype).contiguous()
+        return t.from_numpy(np.ascontiguousarray(a)).to(self.dev, dtype=dtype)
+
+    def _follow_current(self):
+        self.stream.wait_stream(self.torch.cuda.current_stream(self.dev))
+
+    # ---- per-vehicle set-up and per-cycle inputs ----
+    def init(self, states, goals):
+        """setTerminalGoal(goals[i]) + the first updateState(states[i]) of every vehicle.  states: [n] abi.state_dtype or [n][3] positions."""
+        states = np.asarray(states)
+        if states.dtype != abi.state_dtype:
+            s = np.zeros(self.n, dtype=abi.state_dtype)
+            s["pos"] = np.asarray(states, dtype=np.float64).reshape(self.n, 3)
+            states = s
+        d_states = self._host_to_device(states.view(np.uint8).reshape(-1), self.torch.uint8)
+        d_goals = self._host_to_device(np.asarray(goals, dtype=np.float64).reshape(self.n, 3), self.torch.float64)
+        self._follow_current()
+        with self.torch.cuda.stream(self.stream):
+            self.ctx.fleet_init_device(self.params, d_states.data_ptr(), d_goals.data_ptr(), self.n, self.max_states, self.d_vehicles.data_ptr(),
+                                       self.d_plans.data_ptr())
+            d_states.record_stream(self.stream)
+            d_goals.record_stream(self.stream)
+
+    def set_map(self, cloud, cells, res, center, z_max, inflation):
+        """This cycle's occupied points (numpy or a device tensor [m][3]): the occupancy grid of the path search (MapUtil::readMap) and the
+        obstacles of both corridors."""
+        self.cloud = self._host_to_device(np.asarray(cloud, dtype=np.float64).reshape(-1, 3) if not isinstance(cloud, self.torch.Tensor) else cloud,
+                                          self.torch.float64)
+        self.n_cloud = int(self.cloud.shape[0])
+        self._follow_current()
+        self.cloud.record_stream(self.stream)  # (read by every later cycle's launches on the fleet's stream)
+        self.map.read_device(self.cloud.data_ptr(), self.n_cloud, cells, res, center, self.z_ground, z_max, inflation)
+
+    def set_unknown(self, flags, origin, res, dims):
+        """This cycle's unknown voxels: flags[(iz ny + iy) nx + ix] != 0 (numpy or a device tensor) on the lattice (origin, res, dims)."""
+        self.flags = self._host_to_device(np.asarray(flags, dtype=np.uint8).reshape(-1) if not isinstance(flags, self.torch.Tensor) else flags,
+                                          self.torch.uint8)
+        self.grid = (tuple(float(o) for o in origin), float(res), tuple(int(d) for d in dims))
+        self._follow_current()
+        self.flags.record_stream(self.stream)
+        self.ctx.set_unknown_grid_device(self.flags.data_ptr(), self.grid[0], self.grid[1], self.grid[2])
+
+    # ---- one period ----
+    def stages(self):
+        """The launches of one replan of every vehicle, in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        if self.cloud is None or self.grid is None:
+            raise capi.FasterHipError("Fleet.replan: set_map and set_unknown first")
+        B, P, c, m = self.n, self.params, self.ctx, self.map
+        p = lambda t: t.data_ptr()  # noqa: E731
+        origin, res, dims = self.grid
+        return [
+            ("begin", lambda: c.fleet_begin_device(P, p(self.d_vehicles), p(self.d_plans), B, self.max_states, p(self.d_whole), p(self.d_safe),
+                                                   p(self.d_starts), p(self.d_goals), p(self.d_radius), p(self.d_active))),
+            ("path_search", lambda: m.plan_batch_radius_device(p(self.d_starts), p(self.d_goals), p(self.d_radius), p(self.d_active), B, self.mp,
+                                                               p(self.d_paths), p(self.d_np), p(self.d_ex), self.dist_max_vertexes, 0)),
+            ("corridors", lambda: c.corridor_batch_device(p(self.cloud), self.n_cloud, p(self.d_paths), p(self.d_np), B, self.mp, self.max_poly, self.fpp,
+                                                          p(self.d_wf), p(self.d_off), p(self.d_npoly), p(self.d_last), self.decomp_radius,
+                                                          self.z_ground, self.local_bbox)),
+            ("corridor_problems", lambda: c.corridor_problems_device(p(self.d_np), p(self.d_last), p(self.d_goals), p(self.d_wf), p(self.d_off),
+                                                                     p(self.d_npoly), B, self.fpp, self.N, p(self.d_whole))),
+            ("whole_solve", lambda: c.solve_batch_device(p(self.d_whole), p(self.d_wf), B, self.N, self.fpp, p(self.d_wr))),
+            ("safe_corridor", lambda: c.safe_corridor_batch_device(p(self.d_whole), p(self.d_wr), p(self.d_paths), p(self.d_np), self.mp, p(self.d_goals),
+                                                                   p(self.cloud), self.n_cloud, origin, res, dims, B, 0.5, self.max_poly,
+                                                                   self.local_bbox, self.decomp_radius, self.z_ground, self.fpp, self.N,
+                                                                   p(self.d_safe), p(self.d_sf), p(self.d_spaths), p(self.d_snp))),
+            ("safe_solve", lambda: c.solve_batch_device(p(self.d_safe), p(self.d_sf), B, self.N, self.fpp, p(self.d_sr))),
+            ("commit", lambda: c.fleet_commit_device(P, p(self.d_vehicles), p(self.d_plans), B, self.max_states, p(self.d_np), p(self.d_whole),
+                                                     p(self.d_wr), p(self.d_safe), p(self.d_sr))),
+        ]
+
+    def replan(self):
+        """One replan of every vehicle (asynchronous: call sync() or read an accessor to wait)."""
+        self._follow_current()
+        for _, launch in self.stages():
+            launch()
+
+    def next_goals(self, ticks, follow=True):
+        """getNextGoal `ticks` times for every vehicle; returns the device buffer of the last goals ([n] fh_state as bytes).  follow: the
+        current state becomes that goal (updateState of a vehicle that tracks its plan perfectly)."""
+        self.ctx.fleet_next_goals_device(self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.n, self.max_states, int(ticks), follow,
+                                         self.d_next.data_ptr())
+        return self.d_next
+
+    def sync(self):
+        self.stream.synchronize()
+
+    # ---- accessors (synchronise) ----
+    def _host(self, t, dtype):
+        self.sync()
+        return t.cpu().numpy().view(dtype).copy()
+
+    def vehicles(self):
+        """[n] abi.vehicle_dtype: status, plan extent, windows, persisted safe factor and the log of the last replan."""
+        return self._host(self.d_vehicles, abi.vehicle_dtype)
+
+    def log(self):
+        v = self.vehicles()
+        return {k: v[k] for k in ("stage", "needed_safe", "k_end_whole", "k_safe", "index_h", "n_whole", "n_safe", "whole_factor", "safe_factor")}
+
+    def goals(self):
+        """[n] abi.state_dtype: what the last next_goals returned."""
+        return self._host(self.d_next, abi.state_dtype)
+
+    def plans(self):
+        """[n] lists of committed states (abi.state_dtype arrays), front first."""
+        v = self.vehicles()
+        raw = self._host(self.d_plans, abi.state_dtype).reshape(self.n, self.max_states)
+        return [raw[i, v["plan_head"][i]:v["plan_head"][i] + v["plan_size"][i]].copy() for i in range(self.n)]
+
+    def results(self):
+        """The whole and safe problems and results of the last cycle (diagnostics)."""
+        return {"whole": self._host(self.d_whole, abi.problem_dtype), "safe": self._host(self.d_safe, abi.problem_dtype),
+                "wres": self._host(self.d_wr, abi.result_dtype), "sres": self._host(self.d_sr, abi.result_dtype),
+                "n_points": self.d_np.cpu().numpy(), "paths": self.d_paths.cpu().numpy()}

@@ -559,6 +559,103 @@ int fh_map_plan_batch(fh_map* map, const double* starts, const double* goals, in
                       int max_poly, double* paths, int32_t* n_points, int64_t* expansions);
 int fh_map_plan_batch_device(fh_map* map, const double* d_starts, const double* d_goals, int n, int max_points, double max_vertex_dist,
                              int max_poly, double* d_paths, int32_t* d_n_points, int64_t* d_expansions);
+/* fh_map_plan_batch_device with the sphere of JPS_in given PER QUERY (a fleet in steady state: faster.cpp:373 cuts the path on the
+ * sphere of radius min(dist_to_goal - 0.001, Ra) around A, where dist_to_goal is measured from the vehicle's CURRENT state to the
+ * terminal goal, not from A to the projected goal that fh_map_set_sphere assumes).  d_radius [n]: the final radius of query i, used
+ * as it is (the clip of fh_map_set_sphere with that radius; every query is clipped whatever fh_map_set_sphere holds).  d_active [n]
+ * (may be NULL: every query is active): a query with d_active[i] == 0 searches nothing and returns n_points = 0.  Everything else as
+ * fh_map_plan_batch_device; that entry point is unchanged. */
+int fh_map_plan_batch_radius_device(fh_map* map, const double* d_starts, const double* d_goals, const double* d_radius, const int32_t* d_active,
+                                    int n, int max_points, double max_vertex_dist, int max_poly, double* d_paths, int32_t* d_n_points,
+                                    int64_t* d_expansions);
+
+/* ---- steady-state replanning of a fleet on the device: plans carried across cycles (Faster::replan every period) ----------------
+ * Faster::replan (faster/src/faster.cpp:296-595) runs every period and carries between two calls: the committed plan (a deque that
+ * getNextGoal pops at the front, :699-723, and appendToPlan cuts at the back, :606-648), the vehicle status (TRAVELING, GOAL_SEEN,
+ * GOAL_REACHED) and the two factor windows adapted from factor_that_worked_ after every committed replan (:582-588).  These entry
+ * points keep that state for N vehicles in caller-owned device memory, so that one cycle is a fixed chain of batch launches with no
+ * host round trip:
+ *   fh_fleet_begin_device -> fh_map_plan_batch_radius_device -> fh_corridor_batch_device -> fh_corridor_problems_device ->
+ *   fh_solve_batch_device (whole) -> fh_safe_corridor_batch_device -> fh_solve_batch_device (safe) -> fh_fleet_commit_device,
+ * then fh_fleet_next_goals_device for the ticks until the next cycle.  After every cycle each vehicle is where the host restatement
+ * faster_amd/host/replan_stub.hpp (Planner) would be.
+ * Supported: one shared map and one unknown-voxel grid per cycle (fh_map_read_device, fh_set_unknown_grid_device with rule mode 2), the
+ * staged faithful chain above.  Not supported: yaw (getDesiredYaw, the YAWING status), a map per vehicle, and the fused
+ * fh_solve_pairs_device as the committed path (its safe corridor is not FASTER's).
+ * Plan storage: plan of vehicle i = d_plans[i * max_states + plan_head .. + plan_size); a commit moves the kept prefix to index 0. */
+enum {
+  FH_VEHICLE_TRAVELING = 0,     /* faster.cpp: TRAVELING */
+  FH_VEHICLE_GOAL_SEEN = 1,     /* |G_term - plan.back()| < goal_radius after a commit (:563-570) */
+  FH_VEHICLE_GOAL_REACHED = 2   /* |G_term - state| < goal_radius (:326-339): no more replans */
+};
+/* fh_vehicle.stage: what the last replan did (fhreplan::ReplanLog::stage) */
+enum {
+  FH_FLEET_STAGE_NONE = 0,       /* not run (GOAL_REACHED)                                        */
+  FH_FLEET_STAGE_NO_PATH = 1,    /* no path (:361-367)                                             */
+  FH_FLEET_STAGE_NO_WHOLE = 2,   /* no whole corridor or no whole trajectory (:427-431)            */
+  FH_FLEET_STAGE_NO_SAFE = 3,    /* a safe trajectory was needed and not found (:529-533)          */
+  FH_FLEET_STAGE_COMMITTED = 5,  /* appended to the plan, status and windows updated (:548-588)    */
+  FH_FLEET_STAGE_OVERFLOW = 6    /* the new plan would exceed max_states: nothing committed (no reference counterpart) */
+};
+/* Per vehicle, in a caller-owned device array.  A failed replan (stages 1, 2, 3, 6) leaves plan, status and both windows untouched. */
+typedef struct fh_vehicle {
+  double g_term[3];                 /* setTerminalGoal (faster.cpp:267-279)                                    */
+  fh_state state;                   /* updateState: the current state (faster.cpp:139-155)                     */
+  int32_t status;                   /* FH_VEHICLE_*                                                            */
+  int32_t plan_head, plan_size;     /* the plan: d_plans[i * max_states + plan_head ..), plan_size states       */
+  int32_t active;                   /* set by fh_fleet_begin_device: this cycle's replan runs                  */
+  double whole_init, whole_final, whole_inc;  /* sg_whole_ factor window (setFactorInitialAndFinalAndIncrement) */
+  double safe_init, safe_final, safe_inc;     /* sg_safe_ factor window                                        */
+  double safe_factor_worked;        /* sg_safe_.factor_that_worked_: factor of the last SUCCESSFUL safe solve, 0 at first
+                                       (solverGurobi.hpp:135); the safe window after a commit is built from it (:586-588) */
+  double goal[3];                   /* this cycle's G = projectPointToBox(state, G_term, wdx, wdy, wdz) (:317-319) */
+  double ra;                        /* this cycle's sphere radius min(dist_to_goal - 0.001, Ra) (:373)          */
+  double dist_to_goal;              /* |G_term - state| (:331)                                                  */
+  /* the last replan (fhreplan::ReplanLog) */
+  int32_t stage;                    /* FH_FLEET_STAGE_*                                                         */
+  int32_t needed_safe;              /* findIndexH found unknown space near the whole trajectory (:462-466)      */
+  int32_t k_end_whole;              /* max(plan_size - deltaT, 0) (:351)                                        */
+  int32_t k_safe;                   /* sample of the whole trajectory that is R (findIndexR), or indexH         */
+  int32_t index_h;                  /* findIndexH                                                               */
+  int32_t n_whole, n_safe;          /* samples of the whole / safe trajectory (fillX)                           */
+  int32_t reserved;
+  double whole_factor, safe_factor; /* factor_that_worked_ of this replan's whole / safe solve (0: not solved)  */
+} fh_vehicle;
+/* The planner parameters of a fleet (faster/param/faster.yaml, faster.hpp:131) */
+typedef struct fh_fleet_params {
+  int32_t delta_t;                  /* deltaT: states between now and the start state A                         */
+  int32_t reserved;
+  double goal_radius;               /* goal_radius                                                               */
+  double wdx, wdy, wdz;             /* the box the goal is projected into, centred on the current state        */
+  double ra;                        /* Ra                                                                        */
+  double gamma_whole, gammap_whole, increment_whole;
+  double gamma_safe, gammap_safe, increment_safe;
+  fh_pair_rule rule;                /* findIndexH / findIndexR (mode 1 or 2; mode 2 needs fh_set_unknown_grid_device) */
+} fh_fleet_params;
+/* setTerminalGoal + the first updateState of every vehicle (faster.cpp:139-155, :267-279): state = d_states[i], G_term = d_goals[i]
+ * ([n][3]), plan = that one state, windows [1, 10] with the configured increments (faster.cpp:57, :68), safe factor 0, TRAVELING. */
+int fh_fleet_init_device(fh_ctx* ctx, const fh_fleet_params* params, const fh_state* d_states, const double* d_goals, int n, int max_states,
+                         fh_vehicle* d_vehicles, fh_state* d_plans);
+/* Steps 1-3 of a replan, one lane per vehicle (faster.cpp:317-373): G, dist_to_goal and GOAL_REACHED; k_end_whole and the start state A
+ * (the deltaT-th state of the plan once it is long enough); ra.  Writes x0 = A and the whole window into d_whole[i], the safe window
+ * into d_safe[i] (the templates of fh_safe_corridor_batch_device), and the path queries: d_starts[i] = A, d_goals[i] = G ([n][3]),
+ * d_radius[i] = ra, d_active[i] = 0 for a vehicle that does not replan.  Every other field of the problem records is left as the
+ * caller prepared it. */
+int fh_fleet_begin_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states,
+                          fh_problem* d_whole, fh_problem* d_safe, double* d_starts, double* d_goals, double* d_radius, int32_t* d_active);
+/* Steps 4-5, one wavefront per vehicle (appendToPlan, faster.cpp:606-648, and :555-588): classifies the cycle's outcome from the path
+ * counts (d_n_points of the path search), the whole problems and results and the safe problems and results of the staged chain as
+ * Planner::replan does; recomputes k_safe by the rule of params (the function fh_append_plans_device uses); erases the last
+ * k_end_whole + 1 states, appends whole samples 0 .. k_safe and every safe sample (the sampler of fh_sample_batch: the same bits);
+ * updates status, windows, the persisted safe factor and the log. */
+int fh_fleet_commit_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicle* d_vehicles, fh_state* d_plans, int n, int max_states,
+                           const int32_t* d_n_points, const fh_problem* d_whole, const fh_result* d_whole_results, const fh_problem* d_safe,
+                           const fh_result* d_safe_results);
+/* getNextGoal (faster.cpp:699-723, without yaw) `ticks` times in a row for every vehicle: d_goals[i] = the state the last call returns
+ * (front(), popped unless it is the last state of the plan).  follow != 0: the current state becomes that goal (a caller that tracks
+ * perfectly and calls updateState(goal)). */
+int fh_fleet_next_goals_device(fh_ctx* ctx, fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states, int ticks, int follow,
+                               fh_state* d_goals);
 
 /* Timing of the solve kernel, measured with HIP events recorded around every solve-kernel launch on
  * the context stream (the same stream the kernel runs on).  fh_timing_reset() forgets recorded launches;

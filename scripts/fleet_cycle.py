@@ -1,0 +1,109 @@
+"""One steady-state replan cycle of a fleet on the device (faster_amd/fleet.py), stage by stage: 65536 vehicles in the forest of
+frontend.forest_queries, unknown space as an input (rule mode 2), the stages of bench.py's `replan_faithful` plus the three fleet kernels
+(begin, commit, next goals).  Cycle 1 warms up; the vehicles then fly a few ticks, so that the timed cycles start from carried plans
+(k_end_whole > 0).  Prints one JSON line: per-stage milliseconds (median of the timed cycles, each stage fenced by events on the fleet's
+stream), the unfenced cycle time, the commit kernel's write rate and a device-to-device copy rate of the same device for scale.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles]"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from faster_amd import abi, capi, frontend  # noqa: E402
+from faster_amd.fleet import Fleet  # noqa: E402
+
+
+def main():
+    B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
+    cycles = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    res, infl, zmax = 0.2, 0.3, 3.0
+    cloud, cells, center, starts, goals, rng = frontend.forest_queries(B, 7, return_rng=True)
+    u = goals - starts
+    u /= np.maximum(np.linalg.norm(u, axis=1, keepdims=True), 1e-9)
+    states = np.zeros(B, dtype=abi.state_dtype)
+    states["pos"], states["vel"] = starts, u * rng.uniform(0, 1.5, size=(B, 1))
+    probe = capi.Map(0)
+    probe.read(cloud, cells, res, center, 0.0, zmax, infl)
+    dims, origin = probe.dims()
+    probe.close()
+    dims = [int(d) for d in dims]
+    iz, iy, ix = np.meshgrid(np.arange(dims[2]), np.arange(dims[1]), np.arange(dims[0]), indexing="ij")
+    centres = np.stack([(ix + 0.5) * res + origin[0], (iy + 0.5) * res + origin[1], (iz + 0.5) * res + origin[2]], axis=-1)
+    seen = np.zeros(iz.shape, dtype=bool)
+    for c, r in zip(rng.uniform([1, 1, 1.5], [19, 19, 1.5], size=(24, 3)), rng.uniform(2.0, 3.5, 24)):
+        seen |= np.linalg.norm(centres - c, axis=-1) < r
+    flags = (~seen).astype(np.uint8)
+    p = abi.default_fleet_params()
+    p["wdx"], p["wdy"], p["wdz"] = 8.0, 8.0, 4.0
+    p["rule"]["drone_radius"] = 0.3
+    fl = Fleet(B, p, max_states=1024)
+    out = {"vehicles": B, "unknown_fraction": float(flags.mean())}
+    try:
+        fl.set_map(cloud, cells, res, center, zmax, infl)
+        fl.set_unknown(flags, origin, res, dims)
+        fl.init(states, goals)
+        fl.replan()
+        fl.next_goals(5)
+        fl.sync()
+        names = [n for n, _ in fl.stages()] + ["next_goals"]
+        per = {n: [] for n in names}
+        commit_bytes, committed, kend = [], [], []
+        for _ in range(cycles):
+            before = fl.vehicles()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+            ev[0].record(fl.stream)
+            for j, (n, launch) in enumerate(fl.stages()):
+                launch()
+                ev[j + 1].record(fl.stream)
+            fl.next_goals(5)
+            ev[-1].record(fl.stream)
+            fl.sync()
+            after = fl.vehicles()
+            for j, n in enumerate(names):
+                per[n].append(ev[j].elapsed_time(ev[j + 1]))
+            ok = after["stage"] == abi.FH_FLEET_STAGE_COMMITTED
+            committed.append(int(ok.sum()))
+            kend.append(int((ok & (after["k_end_whole"] > 0)).sum()))
+            # what the commit kernel writes: the committed states (the moved prefix and the new samples) and the vehicle records
+            moved = np.where(before["plan_head"] != 0, before["plan_size"] - after["k_end_whole"] - 1, 0)
+            new = after["k_safe"] + 1 + after["n_safe"]
+            commit_bytes.append(int(abi.state_dtype.itemsize * (new[ok].sum() + moved[ok].sum()) + abi.vehicle_dtype.itemsize * B))
+        # the whole cycle without fences between the stages
+        t = []
+        for _ in range(cycles):
+            fl.sync()
+            t0 = time.perf_counter()
+            fl.replan()
+            fl.next_goals(5)
+            fl.sync()
+            t.append(1e3 * (time.perf_counter() - t0))
+        med = {n: float(np.median(v)) for n, v in per.items()}
+        fleet_ms = med["begin"] + med["commit"] + med["next_goals"]
+        # device-to-device copy of 2 GiB: read + write bytes per second
+        a = torch.empty(2 << 30, dtype=torch.uint8, device="cuda:0")
+        b = torch.empty_like(a)
+        b.copy_(a)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            b.copy_(a)
+        e1.record()
+        torch.cuda.synchronize()
+        copy_gbs = 5 * 2 * a.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        cb = float(np.median(commit_bytes))
+        out.update({"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "cycle_ms": float(np.median(t)),
+                    "fleet_kernels_ms": fleet_ms, "fleet_kernels_share": fleet_ms / float(sum(med.values())),
+                    "committed": committed, "committed_with_k_end_whole": kend, "commit_bytes": cb,
+                    "commit_write_gbs": cb / (med["commit"] * 1e-3) / 1e9, "hbm_copy_gbs": copy_gbs})
+    finally:
+        fl.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
