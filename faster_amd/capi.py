@@ -25,6 +25,7 @@ SYMBOLS = [
     "fh_sync", "fh_timing_reset", "fh_timing_read", "fh_last_kernel_ms", "fh_last_launch", "fh_version", "fh_abi_version",
     "fh_packed_result_size", "fh_pack_results_device", "fh_pack_results", "fh_unpack_results", "fh_control_points",
     "fh_map_plan_batch_radius_device", "fh_fleet_init_device", "fh_fleet_begin_device", "fh_fleet_commit_device", "fh_fleet_next_goals_device",
+    "fh_set_unknown_views_device", "fh_fleet_sense_device", "fh_set_sense_staging", "fh_map_occupancy_bits_device",
 ]
 
 _LIB = None
@@ -220,6 +221,14 @@ def lib():
         L.fh_fleet_commit_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
         L.fh_fleet_next_goals_device.restype = i32
         L.fh_fleet_next_goals_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+        L.fh_set_unknown_views_device.restype = i32
+        L.fh_set_unknown_views_device.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, i32]
+        L.fh_fleet_sense_device.restype = i32
+        L.fh_fleet_sense_device.argtypes = [vp, vp, ctypes.c_double, vp, vp, ctypes.c_size_t, vp, i32, vp, i32]
+        L.fh_set_sense_staging.restype = i32
+        L.fh_set_sense_staging.argtypes = [vp, i32]
+        L.fh_map_occupancy_bits_device.restype = i32
+        L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
         L.fh_timing_reset.argtypes = [vp]
         L.fh_timing_read.restype = i32
@@ -505,6 +514,31 @@ class Context:
         g["origin"], g["res"], g["dims"] = origin, res, dims
         g = np.ascontiguousarray(g).reshape(1)
         self._check(lib().fh_set_unknown_grid_device(self._h, abi.ptr(g), d_flags), "fh_set_unknown_grid_device")
+
+    def set_unknown_views_device(self, d_flags, view_stride=0, d_view_of=None, n_views=0, origin=None, res=None, dims=None):
+        """fh_set_unknown_views_device: one unknown-voxel view per query (rule mode 2): query i reads the flags at d_flags + view(i) *
+        view_stride, view(i) = d_view_of[i] (None: i); every view has the layout of set_unknown_grid_device.  d_flags = None: no views."""
+        if d_flags is None:
+            self._check(lib().fh_set_unknown_views_device(self._h, None, None, 0, None, 0), "fh_set_unknown_views_device")
+            return
+        g = np.zeros((), dtype=abi.voxel_grid_dtype)
+        g["origin"], g["res"], g["dims"] = origin, res, dims
+        g = np.ascontiguousarray(g).reshape(1)
+        self._check(lib().fh_set_unknown_views_device(self._h, abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views)),
+                    "fh_set_unknown_views_device")
+
+    def fleet_sense_device(self, vmap, r_sense, origin, res, dims, d_flags, view_stride, d_view_of, n_views, d_vehicles, n):
+        """fh_fleet_sense_device: every vehicle clears, in its view, the unknown flag of each voxel within r_sense that no occupied cell
+        of `vmap` (a Map) hides (the sensor model: include/fasterhip.h).  Asynchronous on the context's stream."""
+        g = np.zeros((), dtype=abi.voxel_grid_dtype)
+        g["origin"], g["res"], g["dims"] = origin, res, dims
+        g = np.ascontiguousarray(g).reshape(1)
+        self._check(lib().fh_fleet_sense_device(self._h, vmap._h, float(r_sense), abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views),
+                                                d_vehicles, int(n)), "fh_fleet_sense_device")
+
+    def set_sense_staging(self, on):
+        """fh_set_sense_staging (measurement only): whether fleet_sense_device copies the occupancy around a vehicle to LDS."""
+        self._check(lib().fh_set_sense_staging(self._h, 1 if on else 0), "fh_set_sense_staging")
 
     def pack_results_device(self, d_results, n, n_seg, d_packed):
         """fh_pack_results_device: n fh_result records -> n packed records of packed_result_size(n_seg) bytes (device pointers)."""

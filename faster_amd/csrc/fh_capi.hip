@@ -49,6 +49,8 @@ struct fh_ctx {
   double pair_margin = -1.0;                // fh_set_pair_margin
   fh_pair_rule pair_rule = {0, 0, 0.0, 0.0, 1.0, 0.5};  // fh_set_pair_rule
   fh::UnknownGrid unknown = {nullptr, 0.0, 0.0, 0.0, 1.0, 0, 0, 0, 0};  // fh_set_unknown_grid_device (rule mode 2); the flags belong to the caller
+  fh::UnknownViews views = {0, nullptr, 0, 0};  // fh_set_unknown_views_device: `unknown` is then view 0 and the lattice of every view (stride 0: one grid)
+  int sense_staging = 1;                        // fh_set_sense_staging
   bool ctl_ready = false;                   // the device-side control block is in its initial state (left so by the previous launch)
   bool launched = false;                    // a solve launch has been issued since the control block was last checked
   int last_grid = 0;
@@ -529,13 +531,32 @@ int fh_set_unknown_grid_device(fh_ctx* ctx, const fh_voxel_grid* grid, const uns
   if (!ctx) return FH_ERR_ARG;
   if (!d_flags) {  // none: rule mode 2 is refused until a grid is set again
     ctx->unknown.flags = nullptr;
+    ctx->views = fh::UnknownViews{0, nullptr, 0, 0};
     return FH_OK;
   }
   if (!grid || !(grid->res > 0) || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1) return FH_ERR_ARG;
   if ((long long)grid->dims[0] * grid->dims[1] * grid->dims[2] > (1ll << 30)) return FH_ERR_ARG;
+  ctx->views = fh::UnknownViews{0, nullptr, 0, 0};  // one grid replaces views
   ctx->unknown.flags = d_flags;
   ctx->unknown.ox = grid->origin[0]; ctx->unknown.oy = grid->origin[1]; ctx->unknown.oz = grid->origin[2]; ctx->unknown.res = grid->res;
   ctx->unknown.nx = grid->dims[0]; ctx->unknown.ny = grid->dims[1]; ctx->unknown.nz = grid->dims[2];
+  return FH_OK;
+}
+
+int fh_set_unknown_views_device(fh_ctx* ctx, const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of,
+                                int n_views) {
+  if (!ctx) return FH_ERR_ARG;
+  if (!d_flags) return fh_set_unknown_grid_device(ctx, nullptr, nullptr);
+  if (n_views < 1 || !grid || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1) return FH_ERR_ARG;
+  if (view_stride < (size_t)grid->dims[0] * (size_t)grid->dims[1] * (size_t)grid->dims[2]) {
+    ctx->err = "fh_set_unknown_views_device: view_stride is smaller than a view (dims[0] * dims[1] * dims[2] bytes)";
+    return FH_ERR_ARG;
+  }
+  const int rc = fh_set_unknown_grid_device(ctx, grid, d_flags);  // the lattice checks; view 0
+  if (rc != FH_OK) return rc;
+  ctx->views.stride = view_stride;
+  ctx->views.view_of = d_view_of;
+  ctx->views.n_views = n_views;
   return FH_OK;
 }
 
@@ -885,7 +906,7 @@ int fh_pair_glue_device(fh_ctx* ctx, const fh_problem* d_whole, const fh_result*
     return FH_ERR_ARG;
   }
   hipLaunchKernelGGL(fh::pair_glue_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_whole,
-                     d_whole_results, d_faces, n, r_frac, shrink, max_safe_poly, ctx->pair_margin, ctx->pair_rule, d_safe, d_safe_faces, ctx->unknown);
+                     d_whole_results, d_faces, n, r_frac, shrink, max_safe_poly, ctx->pair_margin, ctx->pair_rule, d_safe, d_safe_faces, ctx->unknown, ctx->views);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }
@@ -903,7 +924,7 @@ int fh_append_plans_device(fh_ctx* ctx, const fh_problem* d_whole, const fh_resu
     return FH_ERR_ARG;
   }
   hipLaunchKernelGGL(fh::plan_append_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_whole, d_whole_results, d_safe, d_safe_results, n,
-                     r_frac, ctx->pair_rule, max_states, d_plans, d_counts, d_k_safe, ctx->unknown);
+                     r_frac, ctx->pair_rule, max_states, d_plans, d_counts, d_k_safe, ctx->unknown, ctx->views);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }
@@ -932,6 +953,11 @@ int fh_solve_pairs_device(fh_ctx* ctx, const fh_problem* d_whole, const fh_face*
   if (max_safe_poly < 0 || max_safe_poly > FH_MAX_POLY || !(r_frac >= 0) || !(r_frac <= 1) || !(shrink >= 0)) return FH_ERR_ARG;
   if (ctx->pair_rule.mode == 2 && !ctx->unknown.flags) {
     ctx->err = "fh_pair_rule mode 2 needs the unknown voxels: fh_set_unknown_grid_device";
+    return FH_ERR_ARG;
+  }
+  if (ctx->views.stride) {
+    ctx->err = "fh_solve_pairs_device does not support unknown-voxel views (fh_set_unknown_views_device): use the staged chain, or one grid "
+               "(fh_set_unknown_grid_device)";
     return FH_ERR_ARG;
   }
   if (max_seg <= 0 || max_seg > FH_MAX_SEG) max_seg = FH_MAX_SEG;
@@ -978,7 +1004,8 @@ int fh_timing_read(fh_ctx* ctx, double* ms, int cap) {
 
 static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, const double* d_segments, int n_segments,
                             const double local_bbox[3], double drone_radius, double z_ground, int max_faces, fh_face* d_faces, int32_t* d_counts,
-                            const fh::UnknownLattice& lat, const double* d_seg_spheres);
+                            const fh::UnknownLattice& lat, const double* d_seg_spheres, const fh::UnknownViews& views = fh::UnknownViews{0, nullptr, 0, 0},
+                            int segs_per_query = 1);
 
 int fh_decompose_batch_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, const double* d_segments, int n_segments,
                               const double local_bbox[3], double drone_radius, double z_ground, int max_faces, fh_face* d_faces,
@@ -993,7 +1020,7 @@ int fh_decompose_batch_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_clou
 // decomposition as well, listed before the cloud (fh_safe.hip.hpp)
 static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, const double* d_segments, int n_segments,
                             const double local_bbox[3], double drone_radius, double z_ground, int max_faces, fh_face* d_faces, int32_t* d_counts,
-                            const fh::UnknownLattice& lat, const double* d_seg_spheres) {
+                            const fh::UnknownLattice& lat, const double* d_seg_spheres, const fh::UnknownViews& views, int segs_per_query) {
   if (!ctx || n_cloud < 0 || n_segments < 0 || max_faces < 8 || !local_bbox) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
   DeviceScope device_scope(ctx);
@@ -1023,7 +1050,7 @@ static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud,
 #endif
   hipLaunchKernelGGL(fh::decomp_kernel, dim3((unsigned)grid), dim3(64), 0, ctx->stream, d_cloud_xyz, n_cloud, d_segments, n_segments,
                      local_bbox[0], local_bbox[1], local_bbox[2], drone_radius, z_ground, max_faces, (double*)ctx->d_buf[7], d_faces,
-                     d_counts, d_blocks, lat, lat.on ? d_seg_spheres : nullptr, (int*)ctx->d_buf[18]);
+                     d_counts, d_blocks, lat, lat.on ? d_seg_spheres : nullptr, (int*)ctx->d_buf[18], views, segs_per_query > 0 ? segs_per_query : 1);
   FH_HIP(hipGetLastError());
 #ifdef FHD_EXPERIMENT
   if (std::getenv("FHD_HIST")) {  // (diagnostic: how long the lists of this launch were)
@@ -1199,7 +1226,7 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
   int32_t* w_npoly = (int32_t*)(base + o_np);
   int32_t* w_np = d_safe_n_points ? d_safe_n_points : (int32_t*)(base + o_cnt);
   hipLaunchKernelGGL(fh::safe_path_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_whole, d_whole_results, d_paths, d_n_points, n, max_points,
-                     r_frac, ctx->pair_rule, max_poly_safe, d_safe, w_paths, w_np, w_sph, ctx->unknown);
+                     r_frac, ctx->pair_rule, max_poly_safe, d_safe, w_paths, w_np, w_sph, ctx->unknown, ctx->views);
   hipLaunchKernelGGL(fh::safe_spheres_kernel, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, ctx->stream, w_sph, n, max_poly_safe,
                      (double*)ctx->d_buf[17]);
   FH_HIP(hipGetLastError());
@@ -1220,7 +1247,8 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
     lat.flags = ctx->unknown.flags;
   }
   if ((rc = decompose_device(ctx, d_cloud_xyz, n_cloud, (const double*)ctx->d_buf[10], (int)nseg, local_bbox, drone_radius, z_ground, seg_cap,
-                             (fh_face*)ctx->d_buf[11], (int32_t*)ctx->d_buf[12], lat, (const double*)ctx->d_buf[17])) != FH_OK)
+                             (fh_face*)ctx->d_buf[11], (int32_t*)ctx->d_buf[12], lat, (const double*)ctx->d_buf[17],
+                             ctx->pair_rule.mode == 2 ? ctx->views : fh::UnknownViews{0, nullptr, 0, 0}, max_poly_safe)) != FH_OK)
     return rc;
   hipLaunchKernelGGL(corridor_assemble_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, w_np, n, max_poly_safe, seg_cap,
                      (const fh_face*)ctx->d_buf[11], (const int32_t*)ctx->d_buf[12], faces_per_problem, d_safe_faces, w_off, w_npoly);
@@ -1274,7 +1302,7 @@ int fh_fleet_commit_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicl
     return FH_ERR_ARG;
   }
   hipLaunchKernelGGL(fh::fleet_commit_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, *params, d_vehicles, d_plans, n, max_states, d_n_points,
-                     d_whole, d_whole_results, d_safe, d_safe_results, ctx->unknown);
+                     d_whole, d_whole_results, d_safe, d_safe_results, ctx->unknown, ctx->views);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }
@@ -1288,6 +1316,49 @@ int fh_fleet_next_goals_device(fh_ctx* ctx, fh_vehicle* d_vehicles, const fh_sta
   if (!d_vehicles || !d_plans || !d_goals) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::fleet_next_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_vehicles, d_plans, n, max_states, ticks,
                      follow, d_goals);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_set_sense_staging(fh_ctx* ctx, int on) {
+  if (!ctx || (on != 0 && on != 1)) return FH_ERR_ARG;
+  ctx->sense_staging = on;
+  return FH_OK;
+}
+
+int fh_fleet_sense_device(fh_ctx* ctx, fh_map* map, double r_sense, const fh_voxel_grid* grid, unsigned char* d_flags, size_t view_stride,
+                          const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n) {
+  if (!ctx || !map || n < 0 || n_views < 1 || !grid || !(r_sense > 0) || !(r_sense < 1e300)) return FH_ERR_ARG;
+  if (!(grid->res > 0) || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1) return FH_ERR_ARG;
+  const long long cells = (long long)grid->dims[0] * grid->dims[1] * grid->dims[2];
+  if (cells > (1ll << 30) || view_stride < (size_t)cells) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  fh::SenseArgs a;
+  std::memset(&a, 0, sizeof(a));
+  int32_t mdims[3];
+  double morigin[3], mres = 0;
+  const unsigned* d_occ = nullptr;
+  if (fh_map_dims(map, mdims, morigin) != FH_OK || fh_map_occupancy_bits_device(map, &d_occ, &mres) != FH_OK) {
+    ctx->err = "fh_fleet_sense_device: the map holds no grid (fh_map_read_device first)";
+    return FH_ERR_ARG;
+  }
+  if (!(r_sense / mres <= 4096.0)) {  // (a ray has ceil(|q - p| / (0.5 res_map)) - 1 sample points)
+    ctx->err = "fh_fleet_sense_device: r_sense is more than 4096 cells of the map";
+    return FH_ERR_ARG;
+  }
+  DeviceScope device_scope(ctx);
+  if (n == 0) return FH_OK;
+  if (!d_flags || !d_vehicles) return FH_ERR_ARG;
+  a.r_sense = r_sense;
+  a.ox = grid->origin[0]; a.oy = grid->origin[1]; a.oz = grid->origin[2]; a.res = grid->res;
+  a.nx = grid->dims[0]; a.ny = grid->dims[1]; a.nz = grid->dims[2]; a.n = n;
+  a.flags = d_flags;
+  a.views.stride = view_stride; a.views.view_of = d_view_of; a.views.n_views = n_views;
+  a.occ = d_occ;
+  a.mox = morigin[0]; a.moy = morigin[1]; a.moz = morigin[2]; a.mres = mres;
+  a.mx = mdims[0]; a.my = mdims[1]; a.mz = mdims[2]; a.stage = ctx->sense_staging;
+  a.vehicles = d_vehicles;
+  hipLaunchKernelGGL(fh::fleet_sense_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, a);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }

@@ -381,7 +381,8 @@ __global__ void __launch_bounds__(64, 3) decomp_kernel(const double* __restrict_
                                                     int n_segments, double bx, double by, double bz, double inflate, double z_ground,
                                                     int max_faces, double* __restrict__ workspace, fh_face* __restrict__ faces,
                                                     int32_t* __restrict__ counts, const double* __restrict__ blocks, UnknownLattice lat,
-                                                    const double* __restrict__ spheres, int* __restrict__ ticket) {
+                                                    const double* __restrict__ spheres, int* __restrict__ ticket, UnknownViews views,
+                                                    int segs_per_query) {
   // the segment's list of box points: 256 inflated points (3 x 256 doubles + 256 flag bytes) or, in the same bytes, 1536 ids + flag bytes.
   // flags: bit0 first (inside the initial sphere), bit1 inside (current loop), bit2 remain
   static_assert(FH_DECOMP_CAP_IDS % 64 == 0 && FH_DECOMP_CAP <= FH_DECOMP_CAP_IDS, "the id list aliases the coordinate list; blocks of 64 do not straddle its end");
@@ -493,7 +494,11 @@ __global__ void __launch_bounds__(64, 3) decomp_kernel(const double* __restrict_
         cnt += __popcll(m);
       }
     };
-    if (lat.flags) {
+    // the segment's own flags: with views (fh_set_unknown_views_device) those of its query, segment / segs_per_query
+    const unsigned char* sflags = view_flags(lat.flags, views, views.stride ? seg / segs_per_query : 0);
+    if (lat.flags && !sflags) {
+      // (a view number out of range: no unknown voxels)
+    } else if (lat.flags) {
       // [r6] the caller's unknown voxels: a cell's flag is a byte in memory, and a trip of 64 cells that waits for its own load is a memory
       // round trip per trip.  Four trips' flags are requested together; the cells are then noted in the same order as before (the list —
       // and with it every tie rule — is unchanged).  (Measured: 8.9 -> 8.5 ms for the safe corridors of the replan workload.)
@@ -508,7 +513,7 @@ __global__ void __launch_bounds__(64, 3) decomp_kernel(const double* __restrict_
           const int ic = live ? idx : 0;
           const int iz = fhu::div(ic, cxy, lrange.inv_cxy), rem = ic - iz * cxy, iy = fhu::div(rem, lrange.cx, lrange.inv_cx), ix = rem - iy * lrange.cx;
           packed[u] = live ? ((iz << 20) | (iy << 10) | ix) : -1;
-          fl[u] = lat.flags[((size_t)(lrange.z0 + iz) * lat.ny + (lrange.y0 + iy)) * lat.nx + (lrange.x0 + ix)];
+          fl[u] = sflags[((size_t)(lrange.z0 + iz) * lat.ny + (lrange.y0 + iy)) * lat.nx + (lrange.x0 + ix)];
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {

@@ -7,6 +7,8 @@
 // fleet_commit_kernel : the outcome of the cycle, appendToPlan, GOAL_SEEN, the factor windows (:548-588, :606-648).
 //                       One wavefront per vehicle; the samples are written by sample_into, the sampler of fh_sample_batch.
 // fleet_next_kernel   : getNextGoal `ticks` times (faster.cpp:699-723, without yaw).                     One lane per vehicle.
+// fleet_sense_kernel  : every vehicle clears, in its own unknown-voxel view, what it can see (no reference counterpart: the sensor
+//                       model of include/fasterhip.h, checked against a numpy restatement).             One workgroup per vehicle.
 // The host restatement these kernels are checked against, cycle by cycle, is fhreplan::Planner (faster_amd/host/replan_stub.hpp),
 // compiled by g++ without contraction into fused multiply-adds: the geometry here is written with contraction off, in the same
 // operation order (a last-bit difference in G or ra changes a path, and a cycle later a factor window).
@@ -120,11 +122,12 @@ __device__ __forceinline__ bool fleet_problem_ok(const fh_problem& p, const fh_r
 __global__ void __launch_bounds__(64) fleet_commit_kernel(fh_fleet_params par, fh_vehicle* __restrict__ vehicles, fh_state* __restrict__ plans, int n,
                                                           int max_states, const int32_t* __restrict__ n_points, const fh_problem* __restrict__ whole,
                                                           const fh_result* __restrict__ wres, const fh_problem* __restrict__ safe,
-                                                          const fh_result* __restrict__ sres, UnknownGrid ug) {
+                                                          const fh_result* __restrict__ sres, UnknownGrid ug, UnknownViews vw) {
   __shared__ __attribute__((aligned(16))) double tile[64 * 12];
   __shared__ double coef[FH_MAX_SEG * 12];
   const int b = blockIdx.x;
   if (b >= n) return;
+  ug.flags = view_flags(ug.flags, vw, b);
   const int lane = threadIdx.x;
   fh_vehicle& v = vehicles[b];
   if (!__builtin_amdgcn_readfirstlane(v.active)) return;  // the log was cleared by fleet_begin_kernel (a GOAL_REACHED vehicle: stage 0)
@@ -238,6 +241,158 @@ __global__ void __launch_bounds__(256) fleet_next_kernel(fh_vehicle* __restrict_
     if (follow) v.state = g;
   }
   goals[i] = g;
+}
+
+// ---- sensing: every vehicle clears, in ITS view, the unknown flag of each voxel it can see (fh_fleet_sense_device) ----
+// The model (include/fasterhip.h states it; tests restate it in numpy and compare every byte): voxel centre q = ((i + 0.5) res + origin) is
+// in range of p when sqrt(dx dx + dy dy + dz dz) < r_sense, and visible when none of the points p + (q - p) (j / K), j = 1 .. K - 1,
+// K = max(1, ceil(|q - p| / (0.5 res_map))), lies in an occupied cell of the map other than the cell q itself lies in (a point outside
+// the map is free).  All in double, no contraction, in this order.  Only zeros are ever stored: vehicles that share a view clear the union, in any order.
+//
+// One workgroup of four wavefronts per vehicle.  Scan: a wavefront takes rows (iz, iy) of the lattice cells inside the bounding box of the
+// sphere, lanes along x, and reads the flag bytes; a cell that is already known costs nothing more (steady state: nearly all of them).
+// The cells that are unknown and in range are compacted into an LDS queue, so that the rays — 40 samples each at r_sense = 4 m, res 0.2 —
+// are cast by full wavefronts and not by the few lanes of a row that need one.  The occupancy bits a ray can touch (the bounding box of
+// the sphere in map cells, rows padded to 32 bits) are copied to LDS when the first queue is drained, and not at all by a vehicle whose
+// surroundings are known already.
+#define FH_SENSE_QUEUE 2048      // cells waiting for their ray (LDS, 8 KB)
+#define FH_SENSE_OCC_WORDS 6144  // staged occupancy (LDS, 24 KB: 54 x 54 rows of two words); a larger box is read from memory
+struct SenseArgs {
+  double r_sense;
+  double ox, oy, oz, res;      // the lattice of the views
+  int nx, ny, nz, n;
+  unsigned char* flags;
+  UnknownViews views;
+  const unsigned* occ;         // the map: one bit per cell, cell (x, y, z) = bit (z my + y) mx + x
+  double mox, moy, moz, mres;
+  int mx, my, mz, stage;
+  const fh_vehicle* vehicles;
+};
+
+__device__ __forceinline__ int sense_clamp_cell(double v, int lo, int hi) {  // floor(v) clamped to [lo, hi], safe for any v
+  const double f = floor(v);
+  return !(f > (double)lo) ? lo : (f > (double)hi ? hi : (int)f);
+}
+
+__global__ void __launch_bounds__(256) fleet_sense_kernel(SenseArgs a) {
+#pragma clang fp contract(off)
+  __shared__ int queue[FH_SENSE_QUEUE];
+  __shared__ unsigned occ_lds[FH_SENSE_OCC_WORDS];
+  __shared__ int q_count;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (b >= a.n) return;
+  const int view = a.views.view_of ? a.views.view_of[b] : b;
+  if (view < 0 || view >= a.views.n_views) return;
+  unsigned char* flags = a.flags + (size_t)view * a.views.stride;
+  const double px = a.vehicles[b].state.pos[0], py = a.vehicles[b].state.pos[1], pz = a.vehicles[b].state.pos[2];
+  if (!(fabs(px) < 1e300) || !(fabs(py) < 1e300) || !(fabs(pz) < 1e300)) return;  // (NaN or infinite: sees nothing)
+  const double r = a.r_sense;
+  // lattice cells whose centre can be in range: one cell of slack on each side of the sphere's bounding box
+  const int x0 = sense_clamp_cell((px - r - a.ox) / a.res - 1.0, 0, a.nx), x1 = sense_clamp_cell((px + r - a.ox) / a.res + 1.0, -1, a.nx - 1);
+  const int y0 = sense_clamp_cell((py - r - a.oy) / a.res - 1.0, 0, a.ny), y1 = sense_clamp_cell((py + r - a.oy) / a.res + 1.0, -1, a.ny - 1);
+  const int z0 = sense_clamp_cell((pz - r - a.oz) / a.res - 1.0, 0, a.nz), z1 = sense_clamp_cell((pz + r - a.oz) / a.res + 1.0, -1, a.nz - 1);
+  const int cx = x1 - x0 + 1, cy = y1 - y0 + 1, cz = z1 - z0 + 1;
+  if (cx <= 0 || cy <= 0 || cz <= 0) return;  // the sphere misses the lattice
+  // the map cells a sample point can fall into: the same box in the map's cells
+  const int bx0 = sense_clamp_cell((px - r - a.mox) / a.mres - 1.0, 0, a.mx), bx1 = sense_clamp_cell((px + r - a.mox) / a.mres + 1.0, -1, a.mx - 1);
+  const int by0 = sense_clamp_cell((py - r - a.moy) / a.mres - 1.0, 0, a.my), by1 = sense_clamp_cell((py + r - a.moy) / a.mres + 1.0, -1, a.my - 1);
+  const int bz0 = sense_clamp_cell((pz - r - a.moz) / a.mres - 1.0, 0, a.mz), bz1 = sense_clamp_cell((pz + r - a.moz) / a.mres + 1.0, -1, a.mz - 1);
+  const int bcx = bx1 - bx0 + 1, bcy = by1 - by0 + 1, bcz = bz1 - bz0 + 1;
+  const int row_words = (bcx + 31) >> 5;
+  const bool box_ok = bcx > 0 && bcy > 0 && bcz > 0;
+  const bool can_stage = a.stage && box_ok && (long long)row_words * bcy * bcz <= FH_SENSE_OCC_WORDS;
+  bool staged = false;
+  if (tid == 0) q_count = 0;
+  __syncthreads();
+
+  const int chunks = (cx + 63) >> 6;        // 64 cells of a row at a time
+  const int units = cy * cz * chunks;       // (row, chunk) pairs (at most the cells of the lattice, <= 2^30)
+  for (int u0 = 0; u0 < units; u0 += 8) {
+    // scan: two units per wavefront and trip, both flag loads in flight together
+    int cell[2];
+    unsigned char fl[2];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      const int u = u0 + 2 * wave + k;
+      cell[k] = -1;
+      fl[k] = 0;
+      if (u < units) {
+        const int row = chunks == 1 ? u : u / chunks, ix = (u - row * chunks) * 64 + lane;
+        const int iz = row / cy, iy = row - iz * cy;
+        if (ix < cx) {
+          cell[k] = ((z0 + iz) * a.ny + (y0 + iy)) * a.nx + (x0 + ix);
+          fl[k] = flags[cell[k]];
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      bool cand = false;
+      if (cell[k] >= 0 && fl[k] != 0) {
+        const int ix = cell[k] % a.nx, t = cell[k] / a.nx, iy = t % a.ny, iz = t / a.ny;
+        const double dx = ((double)ix + 0.5) * a.res + a.ox - px, dy = ((double)iy + 0.5) * a.res + a.oy - py,
+                     dz = ((double)iz + 0.5) * a.res + a.oz - pz;
+        cand = sqrt(dx * dx + dy * dy + dz * dz) < r;
+      }
+      const unsigned long long m = __ballot(cand);
+      if (m) {
+        int base = 0;
+        if (lane == 0) base = atomicAdd(&q_count, __popcll(m));
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (cand) queue[base + __popcll(m & ((1ull << lane) - 1ull))] = cell[k];  // (drained below before it can overflow: 512 a trip)
+      }
+    }
+    __syncthreads();
+    const int waiting = q_count;
+    __syncthreads();  // (every wavefront has read the count before the next trip adds to it)
+    if (waiting == 0 || (waiting <= FH_SENSE_QUEUE - 512 && u0 + 8 < units)) continue;
+    if (can_stage && !staged) {
+      // local word w of local row (lz, ly) = the 32 bits of the map from cell (bx0 + 32 w, by0 + ly, bz0 + lz) on: two words of the map
+      const int total_words = row_words * bcy * bcz;
+      const long long map_bits = (long long)a.mx * a.my * a.mz;
+      for (int w = tid; w < total_words; w += 256) {
+        const int lrow = w / row_words, lw = w - lrow * row_words, lz = lrow / bcy, ly = lrow - lz * bcy;
+        const long long bit = ((long long)(bz0 + lz) * a.my + (by0 + ly)) * a.mx + bx0 + 32 * lw;
+        const long long wi = bit >> 5;
+        const int sh = (int)(bit & 31);
+        const unsigned lo = a.occ[wi];
+        const unsigned hi = sh && (wi + 1) * 32 < map_bits ? a.occ[wi + 1] : 0u;  // (the word after the map's last is not the map's)
+        occ_lds[w] = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;  // (bits past the row's end belong to other rows and are never looked at)
+      }
+      staged = true;
+      __syncthreads();
+    }
+    for (int e = tid; e < waiting; e += 256) {
+      const int c = queue[e];
+      const int ix = c % a.nx, t = c / a.nx, iy = t % a.ny, iz = t / a.ny;
+      const double qx = ((double)ix + 0.5) * a.res + a.ox, qy = ((double)iy + 0.5) * a.res + a.oy, qz = ((double)iz + 0.5) * a.res + a.oz;
+      const double dx = qx - px, dy = qy - py, dz = qz - pz;
+      const double d = sqrt(dx * dx + dy * dy + dz * dz);
+      const double qfx = floor((qx - a.mox) / a.mres), qfy = floor((qy - a.moy) / a.mres), qfz = floor((qz - a.moz) / a.mres);  // q's own map cell
+      const double kf = ceil(d / (0.5 * a.mres));
+      const int K = kf > 1.0 ? (int)kf : 1;  // (r_sense / res_map is bounded by fh_fleet_sense_device)
+      bool blocked = false;
+      for (int j = 1; j < K && !blocked; j++) {
+        const double tt = (double)j / (double)K;
+        const double fx = floor((px + dx * tt - a.mox) / a.mres), fy = floor((py + dy * tt - a.moy) / a.mres),
+                     fz = floor((pz + dz * tt - a.moz) / a.mres);
+        if (fx == qfx && fy == qfy && fz == qfz) continue;  // the map cell of q itself is not tested: an occupied cell is seen, not what is behind it
+        if (!(fx >= 0.0 && fx < (double)a.mx && fy >= 0.0 && fy < (double)a.my && fz >= 0.0 && fz < (double)a.mz)) continue;  // outside the map: free
+        const int sx = (int)fx, sy = (int)fy, sz = (int)fz;
+        const int lx = sx - bx0, ly = sy - by0, lz = sz - bz0;
+        if (staged && lx >= 0 && lx < bcx && ly >= 0 && ly < bcy && lz >= 0 && lz < bcz) {
+          blocked = (occ_lds[(lz * bcy + ly) * row_words + (lx >> 5)] >> (lx & 31)) & 1u;
+        } else {
+          const long long id = ((long long)sz * a.my + sy) * a.mx + sx;
+          blocked = (a.occ[id >> 5] >> (id & 31)) & 1u;
+        }
+      }
+      if (!blocked) flags[c] = 0;
+    }
+    __syncthreads();
+    if (tid == 0) q_count = 0;
+    __syncthreads();
+  }
 }
 
 }  // namespace fh

@@ -358,6 +358,14 @@ int fh_map_dims(const fh_map* m, int32_t dims[3], double origin[3]) {
   return FH_OK;
 }
 
+// the grid where it lives: one bit per cell in device memory (valid until the next fh_map_read* or fh_map_destroy)
+int fh_map_occupancy_bits_device(const fh_map* m, const unsigned** d_bits, double* res) {
+  if (!m || !m->have_map || !d_bits) return FH_ERR_ARG;
+  *d_bits = m->d_bits;
+  if (res) *res = m->res;
+  return FH_OK;
+}
+
 // occupancy as the reference stores it: one int8 per cell, 0 free / 100 occupied (x fastest)
 int fh_map_occupancy(fh_map* m, int8_t* occ) {
   if (!m || !m->have_map || !occ) return FH_ERR_ARG;

@@ -135,10 +135,12 @@ __global__ void __launch_bounds__(64) safe_path_kernel(const fh_problem* __restr
                                                        const double* __restrict__ paths, const int32_t* __restrict__ n_points, int n,
                                                        int max_points, double r_frac, fh_pair_rule rule, int max_poly_safe,
                                                        fh_problem* __restrict__ safe, double* __restrict__ safe_paths,
-                                                       int32_t* __restrict__ safe_np, double* __restrict__ spheres, UnknownGrid ug) {
+                                                       int32_t* __restrict__ safe_np, double* __restrict__ spheres, UnknownGrid ug,
+                                                       UnknownViews vw) {
   __shared__ P3 s_orig[SAFE_PATH_CAP + 2], s_cur[SAFE_PATH_CAP + 2];  // (LDS, not per-lane arrays: those would be 2 KB of scratch per lane)
   const int b = blockIdx.x, lane = threadIdx.x;
   if (b >= n) return;
+  ug.flags = view_flags(ug.flags, vw, b);
   const fh_problem& pw = whole[b];
   const fh_result& rw = wres[b];
   const int mp = max_poly_safe + 1;

@@ -138,6 +138,20 @@ struct UnknownGrid {
   double ox, oy, oz, res;
   int nx, ny, nz, pad;
 };
+// One unknown-voxel view per query (fh_set_unknown_views_device): query i reads the flags at base + view(i) * stride, view(i) =
+// view_of ? view_of[i] : i; every view has the lattice and the byte layout of the UnknownGrid it replaces.  stride == 0: no views (the
+// one grid of fh_set_unknown_grid_device).  A view number outside [0, n_views) is the caller's error: such a query has no unknown voxels.
+// (Kept OUT of UnknownGrid: that struct is an argument of solve_kernel, whose register allocation does not take changes lightly.)
+struct UnknownViews {
+  size_t stride;
+  const int32_t* view_of;
+  int n_views, pad;
+};
+__device__ __forceinline__ const unsigned char* view_flags(const unsigned char* base, const UnknownViews& vw, int query) {
+  if (!vw.stride || !base) return base;
+  const int view = vw.view_of ? vw.view_of[query] : query;
+  return view >= 0 && view < vw.n_views ? base + (size_t)view * vw.stride : nullptr;
+}
 // Is an unknown voxel centre closer than `radius` to p?  What `kdtree_unk_.nearestKSearch(p, 1, ...)` followed by `sqrt(d2) < radius`
 // decides in findIndexH (faster.cpp:236-240) — evaluated in DOUBLE precision against double voxel centres.  The reference searches a
 // pcl::PointXYZ cloud: its query point, its voxel centres and d2 are single precision (faster.cpp:233-238); for a sample within float
@@ -424,9 +438,10 @@ __device__ inline void pair_glue_one(const PW& pw, const RW& rw, const fh_face* 
 __global__ void __launch_bounds__(64) pair_glue_kernel(const fh_problem* __restrict__ whole, const fh_result* __restrict__ wres,
                                                        const fh_face* __restrict__ wfaces, int n, double r_frac, double shrink,
                                                        int max_safe_poly, double r_margin, fh_pair_rule rule, fh_problem* __restrict__ safe,
-                                                       fh_face* __restrict__ sfaces, UnknownGrid ug) {
+                                                       fh_face* __restrict__ sfaces, UnknownGrid ug, UnknownViews vw) {
   const int b = blockIdx.x;
   if (b >= n) return;
+  ug.flags = view_flags(ug.flags, vw, b);
   pair_glue_one<false>(whole[b], wres[b], wfaces, r_frac, shrink, max_safe_poly, r_margin, rule, safe[b], sfaces, threadIdx.x, nullptr, &ug);
 }
 
@@ -438,11 +453,13 @@ __global__ void __launch_bounds__(64) pair_glue_kernel(const fh_problem* __restr
 __global__ void __launch_bounds__(64) plan_append_kernel(const fh_problem* __restrict__ whole, const fh_result* __restrict__ wres,
                                                          const fh_problem* __restrict__ safe, const fh_result* __restrict__ sres, int n,
                                                          double r_frac, fh_pair_rule rule, int max_states, fh_state* __restrict__ plans,
-                                                         int32_t* __restrict__ counts, int32_t* __restrict__ k_safe_out, UnknownGrid ug) {
+                                                         int32_t* __restrict__ counts, int32_t* __restrict__ k_safe_out, UnknownGrid ug,
+                                                         UnknownViews vw) {
   __shared__ __attribute__((aligned(16))) double tile[64 * 12];
   __shared__ double coef[FH_MAX_SEG * 12];
   const int b = blockIdx.x;
   if (b >= n) return;
+  ug.flags = view_flags(ug.flags, vw, b);
   const int lane = threadIdx.x;
   const fh_problem& pw = whole[b];
   const fh_result& rw = wres[b];

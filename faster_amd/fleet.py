@@ -6,8 +6,13 @@ launches on one stream, with no host round trip inside:
 
     begin -> path search (sphere per vehicle) -> corridors -> corridor problems -> whole solve -> safe corridor -> safe solve -> commit
 
-All vehicles share one map and one grid of unknown voxels per cycle (set_map / set_unknown).  The host restatement every cycle is checked
-against is fhreplan::Planner (faster_amd/host/replan_stub.hpp); tests/test_gpu_fleet.py compares the two cycle by cycle.
+All vehicles share one map of occupied space per cycle (set_map).  Unknown space is either one grid for the whole fleet (set_unknown) or a
+view per vehicle or team (set_unknown_views) that the vehicles grow on the device by looking around (sense): a closed-loop period is then
+
+    sense -> replan -> next_goals
+
+with no host data in it.  The host restatement every cycle is checked against is fhreplan::Planner (faster_amd/host/replan_stub.hpp);
+tests/test_gpu_fleet.py and tests/test_gpu_fleet_views.py compare the two cycle by cycle.
 """
 import numpy as np
 
@@ -55,6 +60,8 @@ class Fleet:
         self.d_spaths, self.d_snp = z((B, self.max_poly + 1, 3), f64), z(B, i32)
         self.d_next = z(B * abi.state_dtype.itemsize, u8)
         self.cloud, self.n_cloud, self.grid = None, 0, None
+        self.flags = self.view_flags = self.view_of = None
+        self.n_views = 0
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -107,12 +114,67 @@ class Fleet:
         self._follow_current()
         self.flags.record_stream(self.stream)
         self.ctx.set_unknown_grid_device(self.flags.data_ptr(), self.grid[0], self.grid[1], self.grid[2])
+        self.view_flags = self.view_of = None  # (one grid replaces views)
+        self.n_views = 0
+
+    def set_unknown_views(self, flags=None, view_of=None, n_views=None, *, origin, res, dims):
+        """Unknown voxels per vehicle: vehicle i reads and senses view view_of[i] (None: view i, n_views = n) of a [n_views][cells] uint8
+        device tensor, cells = dims[0] dims[1] dims[2], each view laid out like set_unknown's grid.  flags = None allocates the views, all
+        ones: everything unknown; a tensor is adopted as it is (not copied when it is already on the device: sense() writes into it).
+        Memory: n_views x cells bytes.  Where a view per vehicle does not fit, view_of lets vehicles share views (a team with one map)."""
+        t = self.torch
+        dims = tuple(int(d) for d in dims)
+        cells = dims[0] * dims[1] * dims[2]
+        if view_of is not None:
+            self.view_of = self._host_to_device(np.asarray(view_of, dtype=np.int32).reshape(-1) if not isinstance(view_of, t.Tensor) else view_of, t.int32)
+            if self.view_of.numel() != self.n:
+                raise capi.FasterHipError("Fleet.set_unknown_views: view_of needs one entry per vehicle")
+        else:
+            self.view_of = None
+        if flags is None:
+            n_views = int(n_views) if n_views is not None else self.n
+            self.view_flags = t.ones((n_views, cells), dtype=t.uint8, device=self.dev)
+        else:
+            f = flags if isinstance(flags, t.Tensor) else np.asarray(flags, dtype=np.uint8)
+            self.view_flags = self._host_to_device(f, t.uint8).reshape(-1, cells)
+            if n_views is not None and int(n_views) != self.view_flags.shape[0]:
+                raise capi.FasterHipError("Fleet.set_unknown_views: flags hold %d views, n_views = %d" % (self.view_flags.shape[0], int(n_views)))
+        self.n_views = int(self.view_flags.shape[0])
+        if self.view_of is None and self.n_views < self.n:
+            raise capi.FasterHipError("Fleet.set_unknown_views: %d views for %d vehicles need view_of" % (self.n_views, self.n))
+        if self.view_of is not None and (int(self.view_of.min()) < 0 or int(self.view_of.max()) >= self.n_views):
+            raise capi.FasterHipError("Fleet.set_unknown_views: view_of names a view outside [0, %d)" % self.n_views)
+        self.grid = (tuple(float(o) for o in origin), float(res), dims)
+        self.flags = None
+        self._follow_current()
+        self.view_flags.record_stream(self.stream)
+        if self.view_of is not None:
+            self.view_of.record_stream(self.stream)
+        self.ctx.set_unknown_views_device(self.view_flags.data_ptr(), cells, None if self.view_of is None else self.view_of.data_ptr(), self.n_views,
+                                          self.grid[0], self.grid[1], self.grid[2])
+
+    def sense(self, r_sense):
+        """Every vehicle looks around from its current position and clears, in its view, the unknown flag of each voxel within r_sense
+        that the occupied cells of the map do not hide (fh_fleet_sense_device: the sensor model is stated in include/fasterhip.h).  One
+        launch on the fleet's stream."""
+        if self.view_flags is None or self.cloud is None:
+            raise capi.FasterHipError("Fleet.sense: set_map and set_unknown_views first")
+        self._follow_current()
+        origin, res, dims = self.grid
+        self.ctx.fleet_sense_device(self.map, r_sense, origin, res, dims, self.view_flags.data_ptr(), self.view_flags.shape[1],
+                                    None if self.view_of is None else self.view_of.data_ptr(), self.n_views, self.d_vehicles.data_ptr(), self.n)
+
+    def views(self):
+        """[n_views][nz][ny][nx] uint8 on the host: the unknown flags of every view (synchronises)."""
+        _, _, dims = self.grid
+        self.sync()
+        return self.view_flags.cpu().numpy().reshape(self.n_views, dims[2], dims[1], dims[0])
 
     # ---- one period ----
     def stages(self):
         """The launches of one replan of every vehicle, in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
         if self.cloud is None or self.grid is None:
-            raise capi.FasterHipError("Fleet.replan: set_map and set_unknown first")
+            raise capi.FasterHipError("Fleet.replan: set_map and set_unknown (or set_unknown_views) first")
         B, P, c, m = self.n, self.params, self.ctx, self.map
         p = lambda t: t.data_ptr()  # noqa: E731
         origin, res, dims = self.grid

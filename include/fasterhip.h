@@ -358,6 +358,20 @@ int fh_set_pair_rule(fh_ctx* ctx, const fh_pair_rule* rule);
  * launches like any other input; it need not be the lattice of an fh_map).  d_flags = NULL: no unknown grid (mode 2 is refused). */
 struct fh_voxel_grid;
 int fh_set_unknown_grid_device(fh_ctx* ctx, const struct fh_voxel_grid* grid, const unsigned char* d_flags);
+/* Rule mode 2 with one unknown-voxel VIEW per query (what THIS vehicle has seen): query i reads its flags at
+ * d_flags + (size_t)view(i) * view_stride, view(i) = d_view_of ? d_view_of[i] : i.  Every view has the lattice `grid` and the byte layout
+ * of fh_set_unknown_grid_device; view_stride >= dims[0] * dims[1] * dims[2].  Several queries may name the same view (a team that shares
+ * its map).  d_flags and d_view_of are device pointers owned by the caller and read by every later launch; n_views is the number of views
+ * behind d_flags.  A view number outside [0, n_views) is the caller's error: that query is treated as having no unknown voxels.
+ * Views replace a grid set with fh_set_unknown_grid_device and the other way round; d_flags = NULL: neither.
+ * While views are set, every STAGED entry point that asks the unknown voxels in rule mode 2 asks the view of its query:
+ * fh_pair_glue_device, fh_append_plans_device, fh_fleet_commit_device (findIndexH / findIndexR), fh_safe_corridor_batch_device (the march
+ * towards unknown space, and the decomposition: the segments of pair i list the unknown voxels of view(i)).  With no views set these
+ * entry points compute bit for bit what they computed before views existed.
+ * NOT supported with views: the fused pair kernel.  fh_solve_pairs_device returns FH_ERR_ARG (fh_last_error names views) until
+ * fh_set_unknown_grid_device is called again; fh_pool_* has no call that sets views (a pool takes one grid per device). */
+int fh_set_unknown_views_device(fh_ctx* ctx, const struct fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride,
+                                const int32_t* d_view_of, int n_views);
 int fh_pair_glue_device(fh_ctx* ctx, const fh_problem* d_whole, const fh_result* d_whole_results,
                         const fh_face* d_faces, int n, double r_frac, double shrink, int max_safe_poly,
                         fh_problem* d_safe, fh_face* d_safe_faces);
@@ -555,6 +569,9 @@ int fh_map_read_device(fh_map* map, const double* d_cloud_xyz, int n_cloud, cons
                        double z_ground, double z_max, double inflation);
 int fh_map_dims(const fh_map* map, int32_t dims[3], double origin[3]);
 int fh_map_occupancy(fh_map* map, int8_t* occ); /* [nz][ny][nx], 0 free / 100 occupied, as MapUtil stores it */
+/* The same grid where it lives: *d_bits = device pointer to one bit per cell, cell (x, y, z) = bit ((z ny + y) nx + x) & 31 of word
+ * ((z ny + y) nx + x) >> 5; *res (may be NULL) = the cell size.  Valid until the next fh_map_read* or fh_map_destroy of the map. */
+int fh_map_occupancy_bits_device(const fh_map* map, const unsigned** d_bits, double* res);
 int fh_map_plan_batch(fh_map* map, const double* starts, const double* goals, int n, int max_points, double max_vertex_dist,
                       int max_poly, double* paths, int32_t* n_points, int64_t* expansions);
 int fh_map_plan_batch_device(fh_map* map, const double* d_starts, const double* d_goals, int n, int max_points, double max_vertex_dist,
@@ -579,9 +596,11 @@ int fh_map_plan_batch_radius_device(fh_map* map, const double* d_starts, const d
  *   fh_solve_batch_device (whole) -> fh_safe_corridor_batch_device -> fh_solve_batch_device (safe) -> fh_fleet_commit_device,
  * then fh_fleet_next_goals_device for the ticks until the next cycle.  After every cycle each vehicle is where the host restatement
  * faster_amd/host/replan_stub.hpp (Planner) would be.
- * Supported: one shared map and one unknown-voxel grid per cycle (fh_map_read_device, fh_set_unknown_grid_device with rule mode 2), the
- * staged faithful chain above.  Not supported: yaw (getDesiredYaw, the YAWING status), a map per vehicle, and the fused
- * fh_solve_pairs_device as the committed path (its safe corridor is not FASTER's).
+ * Supported: one shared map of occupied space per cycle (fh_map_read_device); unknown space in rule mode 2 either as one grid for the
+ * whole fleet (fh_set_unknown_grid_device) or as a view per vehicle or team (fh_set_unknown_views_device), which the vehicles grow on
+ * the device by sensing (fh_fleet_sense_device): a closed-loop period is sense -> the chain above -> next goals with no host data in it;
+ * the staged faithful chain above.  Not supported: yaw (getDesiredYaw, the YAWING status), a map of occupied space per vehicle, and
+ * the fused fh_solve_pairs_device as the committed path (its safe corridor is not FASTER's, and it takes no views).
  * Plan storage: plan of vehicle i = d_plans[i * max_states + plan_head .. + plan_size); a commit moves the kept prefix to index 0. */
 enum {
   FH_VEHICLE_TRAVELING = 0,     /* faster.cpp: TRAVELING */
@@ -656,6 +675,31 @@ int fh_fleet_commit_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicl
  * perfectly and calls updateState(goal)). */
 int fh_fleet_next_goals_device(fh_ctx* ctx, fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states, int ticks, int follow,
                                fh_state* d_goals);
+
+/* Sensing: every vehicle i looks around from d_vehicles[i].state.pos and clears, in ITS view (d_flags + view(i) * view_stride, view(i) =
+ * d_view_of ? d_view_of[i] : i, as fh_set_unknown_views_device), the unknown flag of every voxel it can see.  FASTER's mapper is a
+ * package of its own and not part of the planner; this is the project's own sensor model, and it is exact — tests compare every byte
+ * with a numpy restatement.  With p the vehicle's position and q = ((i + 0.5) res + origin), per axis, the centre of a voxel of `grid`:
+ *   in range: |q - p| < r_sense, where |q - p| = sqrt(dx dx + dy dy + dz dz), d = q - p, in double, summed x, y, z, no fused
+ *     multiply-add;
+ *   visible:  none of the sample points p + (q - p) (j / K), j = 1 .. K - 1, K = max(1, ceil(|q - p| / (0.5 res_map))), lies in an
+ *     occupied cell of `map` (the grid fh_map_occupancy returns: MapUtil's inflated occupancy).  Cell of a point: floor((x - origin_map) /
+ *     res_map) per axis; a point outside the map is free.  The end point q is not tested, and neither is a sample point that lies in
+ *     the map cell of q itself (the last samples are closer than half a cell to q, so they would always fall into it): the first
+ *     occupied cell along a ray becomes known, what lies behind it stays unknown;
+ *   in range and visible: flags_view[(iz ny + iy) nx + ix] = 0.
+ * Nothing is ever set to non-zero: knowledge only grows.  Every vehicle senses, whatever its status.  Vehicles that share a view
+ * clear the union of what they see; because only zeros are stored the result does not depend on scheduling.  A vehicle with a view
+ * number outside [0, n_views) or a position that is not finite senses nothing.  The sensor is omnidirectional (the fleet has no yaw),
+ * has no noise and no minimum range, and sees through nothing: limits of the model, not of the implementation.
+ * r_sense > 0, at most 4096 res_map.  Asynchronous on the stream of `ctx`; `map` is only read, and must have been filled on the same
+ * stream (faster_amd.fleet.Fleet sets both to one stream).  A voxel that is already known costs one byte read and no ray, so a fleet
+ * in steady state pays for the shell it moved into. */
+int fh_fleet_sense_device(fh_ctx* ctx, fh_map* map, double r_sense, const struct fh_voxel_grid* grid, unsigned char* d_flags, size_t view_stride,
+                          const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n);
+/* Measurement only (results do not depend on it): 1 (default) a vehicle that has rays to cast copies the occupancy bits of the bounding
+ * box of its sphere to LDS first; 0 every sample point reads the map in memory. */
+int fh_set_sense_staging(fh_ctx* ctx, int on);
 
 /* Timing of the solve kernel, measured with HIP events recorded around every solve-kernel launch on
  * the context stream (the same stream the kernel runs on).  fh_timing_reset() forgets recorded launches;

@@ -3,7 +3,16 @@ frontend.forest_queries, unknown space as an input (rule mode 2), the stages of 
 (begin, commit, next goals).  Cycle 1 warms up; the vehicles then fly a few ticks, so that the timed cycles start from carried plans
 (k_end_whole > 0).  Prints one JSON line: per-stage milliseconds (median of the timed cycles, each stage fenced by events on the fleet's
 stream), the unfenced cycle time, the commit kernel's write rate and a device-to-device copy rate of the same device for scale.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles]"""
+
+--views adds, to the same JSON line, the cycle with one unknown-voxel view per vehicle (Fleet.set_unknown_views), twice:
+  "views_same_flags": every view a copy of the shared grid and no sensing — the same work as the shared-grid cycle, so any difference is
+      the price of the per-vehicle flags pointer;
+  "views_sensing": every view starts all unknown, the vehicles sense (Fleet.sense, --r-sense metres, default 3) before every replan: the
+      first sense, when every voxel in range still needs its ray ("sense_first_ms"), then the closed loop sense -> replan -> 5 ticks in
+      steady state, sensing as a stage of its own.  --no-staging: sensing reads the occupancy in memory instead of staging it in LDS.
+Memory of the views: vehicles x nx ny nz bytes (printed; 65536 vehicles in this forest: 12.6 GB).  A fleet that does not fit lets vehicles
+share views (view_of).
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--r-sense R] [--no-staging]"""
 import json
 import os
 import sys
@@ -17,9 +26,86 @@ from faster_amd import abi, capi, frontend  # noqa: E402
 from faster_amd.fleet import Fleet  # noqa: E402
 
 
+def timed_cycles(fl, cycles, r_sense=None):
+    """`cycles` cycles, every stage fenced by events: {stage: [ms]} (with r_sense: sensing first, as a stage of its own)."""
+    names = (["sense"] if r_sense else []) + [n for n, _ in fl.stages()] + ["next_goals"]
+    per = {n: [] for n in names}
+    for _ in range(cycles):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        ev[0].record(fl.stream)
+        k = 0
+        if r_sense:
+            fl.sense(r_sense)
+            k = 1
+            ev[1].record(fl.stream)
+        for j, (n, launch) in enumerate(fl.stages()):
+            launch()
+            ev[k + j + 1].record(fl.stream)
+        fl.next_goals(5)
+        ev[-1].record(fl.stream)
+        fl.sync()
+        for j, n in enumerate(names):
+            per[n].append(ev[j].elapsed_time(ev[j + 1]))
+    return {n: float(np.median(v)) for n, v in per.items()}
+
+
+def views_cycles(B, cycles, p, world, r_sense, staging):
+    """The cycle with a view per vehicle: see the module docstring."""
+    cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims = world
+    n_cells = dims[0] * dims[1] * dims[2]
+    out = {"views_bytes": B * n_cells, "r_sense": r_sense, "sense_staging": bool(staging)}
+    print("views: %d x %d bytes = %.2f GB" % (B, n_cells, B * n_cells / 1e9), file=sys.stderr)
+    fl = Fleet(B, p, max_states=1024)
+    try:
+        fl.ctx.set_sense_staging(staging)
+        fl.set_map(cloud, cells, res, center, zmax, infl)
+        views = torch.from_numpy(flags.reshape(1, -1)).to(fl.dev).repeat(B, 1)
+        fl.set_unknown_views(views, origin=origin, res=res, dims=dims)
+        fl.init(states, goals)
+        fl.replan()
+        fl.next_goals(5)
+        fl.sync()
+        med = timed_cycles(fl, cycles)
+        out["views_same_flags"] = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values()))}
+        # the closed loop: everything unknown at first, the vehicles back at their starts
+        views.fill_(1)
+        fl.init(states, goals)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(fl.stream)
+        fl.sense(r_sense)
+        e1.record(fl.stream)
+        fl.sync()
+        out["sense_first_ms"] = e0.elapsed_time(e1)
+        fl.replan()
+        fl.next_goals(5)
+        fl.sync()
+        med = timed_cycles(fl, cycles, r_sense)
+        t = []
+        for _ in range(cycles):
+            fl.sync()
+            t0 = time.perf_counter()
+            fl.sense(r_sense)
+            fl.replan()
+            fl.next_goals(5)
+            fl.sync()
+            t.append(1e3 * (time.perf_counter() - t0))
+        v = fl.vehicles()
+        out["views_sensing"] = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "cycle_ms": float(np.median(t)),
+                                "committed_last": int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum()),
+                                "unknown_fraction_end": float(views.float().mean().item())}
+    finally:
+        fl.close()
+    return out
+
+
 def main():
-    B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
-    cycles = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    r_sense = 3.0
+    if "--r-sense" in sys.argv:
+        r_sense = float(sys.argv[sys.argv.index("--r-sense") + 1])
+        args.remove(sys.argv[sys.argv.index("--r-sense") + 1])
+    B = int(args[0]) if len(args) > 0 else 65536
+    cycles = int(args[1]) if len(args) > 1 else 3
     res, infl, zmax = 0.2, 0.3, 3.0
     cloud, cells, center, starts, goals, rng = frontend.forest_queries(B, 7, return_rng=True)
     u = goals - starts
@@ -102,6 +188,9 @@ def main():
                     "commit_write_gbs": cb / (med["commit"] * 1e-3) / 1e9, "hbm_copy_gbs": copy_gbs})
     finally:
         fl.close()
+    if "--views" in sys.argv:
+        world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
+        out.update(views_cycles(B, cycles, p, world, r_sense, "--no-staging" not in sys.argv))
     print(json.dumps(out))
 
 
