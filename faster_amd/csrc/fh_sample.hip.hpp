@@ -505,9 +505,10 @@ __global__ void __launch_bounds__(256) next_goal_kernel(const fh_state* __restri
   int c = cursor[i];
   if (cnt > 0) {
     c = c < 0 ? 0 : (c > cnt - 1 ? cnt - 1 : c);
-    const int last_read = c + (ticks - 1) < cnt - 1 ? c + (ticks - 1) : cnt - 1;  // front() of the last of the `ticks` calls
+    const int room = cnt - 1 - c;  // states behind the cursor, >= 0: `ticks` is compared with it, never added first (any ticks >= 1, no wrap)
+    const int last_read = ticks - 1 < room ? c + (ticks - 1) : cnt - 1;  // front() of the last of the `ticks` calls
     g = plans[(size_t)i * (size_t)max_states + last_read];
-    c = c + ticks < cnt - 1 ? c + ticks : cnt - 1;                                // pop_front() while more than one state is left
+    c = ticks < room ? c + ticks : cnt - 1;                              // pop_front() while more than one state is left
     cursor[i] = c;
   }
   goals[i] = g;
