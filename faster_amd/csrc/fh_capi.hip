@@ -675,9 +675,9 @@ int fh_solve_batch(fh_ctx* ctx, const fh_problem* problems, const fh_face* faces
     if (p.n_seg >= 1 && p.n_seg <= FH_MAX_SEG) max_seg = std::max(max_seg, (int)p.n_seg);
     if (p.n_poly >= 1 && p.n_poly <= FH_MAX_POLY) {
       const int nf = p.face_off[p.n_poly];
-      if (nf >= 0 && nf <= FH_MAX_FACES) {
+      if (nf >= 0 && nf <= FH_MAX_FACES && p.face_begin >= 0) {  // (face_begin < 0: the kernel reports FH_ST_BAD_INPUT before it reads a row)
         // the kernel cannot see n_faces: reject corridors that point outside the face array here
-        if (p.face_begin < 0 || (int64_t)p.face_begin + nf > n_faces) {
+        if ((int64_t)p.face_begin + nf > n_faces) {
           ctx->err = "fh_solve_batch: problem " + std::to_string(i) + " addresses faces outside [0, n_faces)";
           return FH_ERR_ARG;
         }

@@ -105,8 +105,8 @@ void run_shard(fh_pool* pool, int g, const Job& job) {
     if (p.n_seg >= 1 && p.n_seg <= FH_MAX_SEG) max_seg = std::max(max_seg, (int)p.n_seg);
     if (p.n_poly < 1 || p.n_poly > FH_MAX_POLY) continue;
     const int nf = p.face_off[p.n_poly];
-    if (nf < 0 || nf > FH_MAX_FACES) continue;  // the kernel reports FH_ST_BAD_INPUT
-    if (p.face_begin < 0 || (int64_t)p.face_begin + nf > job.n_faces) {
+    if (nf < 0 || nf > FH_MAX_FACES || p.face_begin < 0) continue;  // the kernel reports FH_ST_BAD_INPUT (before it reads a row)
+    if ((int64_t)p.face_begin + nf > job.n_faces) {
       d.err = "fh_pool: a problem addresses faces outside [0, n_faces)";
       d.rc = FH_ERR_ARG;
       return;

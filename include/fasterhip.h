@@ -289,8 +289,12 @@ int fh_solve_batch_speculative(fh_ctx* ctx, const fh_problem* problems, const fh
 /* Same, with every pointer already resident in device memory (HBM). Asynchronous on the
  * context's stream; call fh_sync() before reading results.  max_seg / max_faces are upper bounds on
  * n_seg and on the per-problem face count of the batch (they select the kernel instantiation and its
- * LDS carve; pass 0 for the library maxima FH_MAX_SEG / FH_MAX_FACES).  A problem exceeding them is
- * reported with FH_ST_BAD_INPUT. */
+ * LDS carve; pass 0 for the library maxima FH_MAX_SEG / FH_MAX_FACES).  A problem is reported with
+ * FH_ST_BAD_INPUT when it exceeds the KERNEL BUILD these bounds select — the smallest of 6, 10, 15 and 16
+ * segments that holds max_seg, and max_faces rounded up to a multiple of 8 rows — not when it exceeds the
+ * caller's numbers themselves: with max_seg = 7 a problem of 10 segments is solved and one of 11 is not,
+ * with max_faces = 9 a problem of 16 rows is solved and one of 17 is not (tests/test_gpu_solve_edges.py;
+ * fh_solve_batch and fh_pool_* pass the maxima of the records they are given). */
 int fh_solve_batch_device(fh_ctx* ctx, const fh_problem* d_problems, const fh_face* d_faces, int n, int max_seg,
                           int max_faces, fh_result* d_results);
 
