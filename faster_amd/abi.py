@@ -89,6 +89,7 @@ assert pair_rule_dtype.itemsize == 40
 
 # fh_vehicle / fh_fleet_params: steady-state replanning of a fleet (fh_fleet_*)
 FH_VEHICLE_TRAVELING, FH_VEHICLE_GOAL_SEEN, FH_VEHICLE_GOAL_REACHED = 0, 1, 2
+FH_VEHICLE_YAWING = 3
 FH_FLEET_STAGE_NONE, FH_FLEET_STAGE_NO_PATH, FH_FLEET_STAGE_NO_WHOLE, FH_FLEET_STAGE_NO_SAFE = 0, 1, 2, 3
 FH_FLEET_STAGE_COMMITTED, FH_FLEET_STAGE_OVERFLOW = 5, 6
 vehicle_dtype = np.dtype([("g_term", "<f8", (3,)), ("state", state_dtype), ("status", "<i4"), ("plan_head", "<i4"), ("plan_size", "<i4"),
@@ -102,6 +103,19 @@ fleet_params_dtype = np.dtype([("delta_t", "<i4"), ("reserved", "<i4"), ("goal_r
                                ("ra", "<f8"), ("gamma_whole", "<f8"), ("gammap_whole", "<f8"), ("increment_whole", "<f8"), ("gamma_safe", "<f8"),
                                ("gammap_safe", "<f8"), ("increment_safe", "<f8"), ("rule", pair_rule_dtype)], align=True)
 assert fleet_params_dtype.itemsize == 136, fleet_params_dtype.itemsize
+# fh_heading / fh_yaw_params: yaw, the YAWING status and the forward sensor (fh_fleet_*_yaw_*, fh_fleet_sense_fov_device)
+heading_dtype = np.dtype([("yaw", "<f8"), ("previous_yaw", "<f8"), ("dyaw_filtered", "<f8"), ("goal_yaw", "<f8"), ("goal_dyaw", "<f8"),
+                          ("look_at", "<f8", (3,)), ("dir", "<f8", (2,)), ("reserved", "<f8", (2,))], align=True)
+assert heading_dtype.itemsize == 96, heading_dtype.itemsize
+yaw_params_dtype = np.dtype([("w_max", "<f8"), ("alpha_filter_dyaw", "<f8"), ("dc", "<f8")], align=True)
+assert yaw_params_dtype.itemsize == 24, yaw_params_dtype.itemsize
+
+
+def default_yaw_params(dc=0.01):
+    """fh_yaw_params with the values of faster/param/faster.yaml: w_max 4.0, alpha_filter_dyaw 0."""
+    p = np.zeros((), dtype=yaw_params_dtype)
+    p["w_max"], p["alpha_filter_dyaw"], p["dc"] = 4.0, 0.0, dc
+    return p
 
 
 def default_fleet_params():

@@ -26,6 +26,8 @@ SYMBOLS = [
     "fh_packed_result_size", "fh_pack_results_device", "fh_pack_results", "fh_unpack_results", "fh_control_points",
     "fh_map_plan_batch_radius_device", "fh_fleet_init_device", "fh_fleet_begin_device", "fh_fleet_commit_device", "fh_fleet_next_goals_device",
     "fh_set_unknown_views_device", "fh_fleet_sense_device", "fh_set_sense_staging", "fh_map_occupancy_bits_device",
+    "fh_fleet_heading_init_device", "fh_fleet_set_headings_device", "fh_fleet_set_goals_device", "fh_fleet_next_goals_yaw_device",
+    "fh_fleet_sense_fov_device",
 ]
 
 _LIB = None
@@ -227,6 +229,17 @@ def lib():
         L.fh_fleet_sense_device.argtypes = [vp, vp, ctypes.c_double, vp, vp, ctypes.c_size_t, vp, i32, vp, i32]
         L.fh_set_sense_staging.restype = i32
         L.fh_set_sense_staging.argtypes = [vp, i32]
+        L.fh_fleet_heading_init_device.restype = i32
+        L.fh_fleet_heading_init_device.argtypes = [vp, vp, i32, vp]
+        L.fh_fleet_set_headings_device.restype = i32
+        L.fh_fleet_set_headings_device.argtypes = [vp, vp, i32]
+        L.fh_fleet_set_goals_device.restype = i32
+        L.fh_fleet_set_goals_device.argtypes = [vp, vp, vp, vp, vp, i32]
+        L.fh_fleet_next_goals_yaw_device.restype = i32
+        L.fh_fleet_next_goals_yaw_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+        L.fh_fleet_sense_fov_device.restype = i32
+        L.fh_fleet_sense_fov_device.argtypes = [vp, vp, ctypes.c_double, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, ctypes.c_double,
+                                                ctypes.c_double]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -536,6 +549,16 @@ class Context:
         self._check(lib().fh_fleet_sense_device(self._h, vmap._h, float(r_sense), abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views),
                                                 d_vehicles, int(n)), "fh_fleet_sense_device")
 
+    def fleet_sense_fov_device(self, vmap, r_sense, origin, res, dims, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_headings,
+                               tan_half_h, tan_half_v):
+        """fh_fleet_sense_fov_device: fleet_sense_device through a field of view along fh_heading.dir, given by the tangents of its half
+        angles."""
+        g = np.zeros((), dtype=abi.voxel_grid_dtype)
+        g["origin"], g["res"], g["dims"] = origin, res, dims
+        self._check(lib().fh_fleet_sense_fov_device(self._h, vmap._h, float(r_sense), abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views),
+                                                    d_vehicles, int(n), d_headings, float(tan_half_h), float(tan_half_v)),
+                    "fh_fleet_sense_fov_device")
+
     def set_sense_staging(self, on):
         """fh_set_sense_staging (measurement only): whether fleet_sense_device copies the occupancy around a vehicle to LDS."""
         self._check(lib().fh_set_sense_staging(self._h, 1 if on else 0), "fh_set_sense_staging")
@@ -702,6 +725,23 @@ class Context:
         p = np.ascontiguousarray(params).reshape(1)
         self._check(lib().fh_fleet_commit_device(self._h, abi.ptr(p), d_vehicles, d_plans, n, max_states, d_n_points, d_whole, d_whole_results, d_safe,
                                                  d_safe_results), "fh_fleet_commit_device")
+
+    # ---- heading: yaw, new terminal goals (yaw_params is an abi.yaw_params_dtype record) ----
+    def fleet_heading_init_device(self, d_yaw0, n, d_headings):
+        self._check(lib().fh_fleet_heading_init_device(self._h, d_yaw0, int(n), d_headings), "fh_fleet_heading_init_device")
+
+    def fleet_set_headings_device(self, d_headings, n):
+        """fh_fleet_set_headings_device: the safe-corridor stage writes look_at into these records (None: detach)."""
+        self._check(lib().fh_fleet_set_headings_device(self._h, d_headings, int(n)), "fh_fleet_set_headings_device")
+
+    def fleet_set_goals_device(self, params, d_vehicles, d_new_goals, d_mask, n):
+        p = np.ascontiguousarray(params, dtype=abi.fleet_params_dtype)
+        self._check(lib().fh_fleet_set_goals_device(self._h, abi.ptr(p), d_vehicles, d_new_goals, d_mask, int(n)), "fh_fleet_set_goals_device")
+
+    def fleet_next_goals_yaw_device(self, yaw_params, d_vehicles, d_plans, d_headings, n, max_states, ticks, follow, d_goals, d_goal_yaw):
+        p = np.ascontiguousarray(yaw_params, dtype=abi.yaw_params_dtype)
+        self._check(lib().fh_fleet_next_goals_yaw_device(self._h, abi.ptr(p), d_vehicles, d_plans, d_headings, int(n), int(max_states), int(ticks),
+                                                         1 if follow else 0, d_goals, d_goal_yaw), "fh_fleet_next_goals_yaw_device")
 
     def fleet_next_goals_device(self, d_vehicles, d_plans, n, max_states, ticks, follow, d_goals):
         self._check(lib().fh_fleet_next_goals_device(self._h, d_vehicles, d_plans, n, max_states, int(ticks), 1 if follow else 0, d_goals),

@@ -51,6 +51,8 @@ struct fh_ctx {
   fh::UnknownGrid unknown = {nullptr, 0.0, 0.0, 0.0, 1.0, 0, 0, 0, 0};  // fh_set_unknown_grid_device (rule mode 2); the flags belong to the caller
   fh::UnknownViews views = {0, nullptr, 0, 0};  // fh_set_unknown_views_device: `unknown` is then view 0 and the lattice of every view (stride 0: one grid)
   int sense_staging = 1;                        // fh_set_sense_staging
+  fh_heading* headings = nullptr;               // fh_fleet_set_headings_device: the caller's records (look_at is written by the safe-corridor stage)
+  int n_headings = 0;
   bool ctl_ready = false;                   // the device-side control block is in its initial state (left so by the previous launch)
   bool launched = false;                    // a solve launch has been issued since the control block was last checked
   int last_grid = 0;
@@ -1185,7 +1187,7 @@ int fh_corridor_problems_device(fh_ctx* ctx, const int32_t* d_n_points, const do
   if (!d_n_points || !d_last_vertex || !d_goals || !d_faces || !d_face_off || !d_n_poly || !d_problems) return FH_ERR_ARG;
   if ((size_t)n * (size_t)faces_per_problem > (size_t)0x7fffffff) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::safe_finalize_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_n_points, d_last_vertex, d_goals, d_faces, d_face_off,
-                     d_n_poly, n, faces_per_problem, n_seg, d_problems);
+                     d_n_poly, n, faces_per_problem, n_seg, d_problems, (fh_heading*)nullptr);  // (the whole problem's xf is not M_)
   FH_HIP(hipGetLastError());
   return FH_OK;
 }
@@ -1209,6 +1211,10 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
     return FH_ERR_ARG;
   }
   if ((size_t)n * (size_t)faces_per_problem > (size_t)0x7fffffff) return FH_ERR_ARG;
+  if (ctx->headings && n > ctx->n_headings) {
+    ctx->err = "fh_safe_corridor_batch_device: more queries than heading records attached (fh_fleet_set_headings_device)";
+    return FH_ERR_ARG;
+  }
   const int mp = max_poly_safe + 1;
   const size_t nseg = (size_t)n * max_poly_safe;
   // one buffer: safe paths [n][mp][3] | spheres [n][4] | goal M [n][3] | face_off [n][9] | n_poly [n] | np [n]
@@ -1226,7 +1232,7 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
   int32_t* w_npoly = (int32_t*)(base + o_np);
   int32_t* w_np = d_safe_n_points ? d_safe_n_points : (int32_t*)(base + o_cnt);
   hipLaunchKernelGGL(fh::safe_path_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_whole, d_whole_results, d_paths, d_n_points, n, max_points,
-                     r_frac, ctx->pair_rule, max_poly_safe, d_safe, w_paths, w_np, w_sph, ctx->unknown, ctx->views);
+                     r_frac, ctx->pair_rule, max_poly_safe, d_safe, w_paths, w_np, w_sph, ctx->unknown, ctx->views, ctx->headings);
   hipLaunchKernelGGL(fh::safe_spheres_kernel, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, ctx->stream, w_sph, n, max_poly_safe,
                      (double*)ctx->d_buf[17]);
   FH_HIP(hipGetLastError());
@@ -1253,7 +1259,7 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
   hipLaunchKernelGGL(corridor_assemble_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, w_np, n, max_poly_safe, seg_cap,
                      (const fh_face*)ctx->d_buf[11], (const int32_t*)ctx->d_buf[12], faces_per_problem, d_safe_faces, w_off, w_npoly);
   hipLaunchKernelGGL(fh::safe_finalize_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, w_np, w_goal, d_goals, d_safe_faces, w_off, w_npoly, n,
-                     faces_per_problem, n_seg_safe, d_safe);
+                     faces_per_problem, n_seg_safe, d_safe, ctx->headings);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }
@@ -1326,8 +1332,9 @@ int fh_set_sense_staging(fh_ctx* ctx, int on) {
   return FH_OK;
 }
 
-int fh_fleet_sense_device(fh_ctx* ctx, fh_map* map, double r_sense, const fh_voxel_grid* grid, unsigned char* d_flags, size_t view_stride,
-                          const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n) {
+static int fleet_sense(fh_ctx* ctx, fh_map* map, double r_sense, const fh_voxel_grid* grid, unsigned char* d_flags, size_t view_stride,
+                       const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n, const fh_heading* d_headings, double th, double tv,
+                       const char* who) {
   if (!ctx || !map || n < 0 || n_views < 1 || !grid || !(r_sense > 0) || !(r_sense < 1e300)) return FH_ERR_ARG;
   if (!(grid->res > 0) || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1) return FH_ERR_ARG;
   const long long cells = (long long)grid->dims[0] * grid->dims[1] * grid->dims[2];
@@ -1339,11 +1346,11 @@ int fh_fleet_sense_device(fh_ctx* ctx, fh_map* map, double r_sense, const fh_vox
   double morigin[3], mres = 0;
   const unsigned* d_occ = nullptr;
   if (fh_map_dims(map, mdims, morigin) != FH_OK || fh_map_occupancy_bits_device(map, &d_occ, &mres) != FH_OK) {
-    ctx->err = "fh_fleet_sense_device: the map holds no grid (fh_map_read_device first)";
+    ctx->err = std::string(who) + ": the map holds no grid (fh_map_read_device first)";
     return FH_ERR_ARG;
   }
   if (!(r_sense / mres <= 4096.0)) {  // (a ray has ceil(|q - p| / (0.5 res_map)) - 1 sample points)
-    ctx->err = "fh_fleet_sense_device: r_sense is more than 4096 cells of the map";
+    ctx->err = std::string(who) + ": r_sense is more than 4096 cells of the map";
     return FH_ERR_ARG;
   }
   DeviceScope device_scope(ctx);
@@ -1358,7 +1365,73 @@ int fh_fleet_sense_device(fh_ctx* ctx, fh_map* map, double r_sense, const fh_vox
   a.mox = morigin[0]; a.moy = morigin[1]; a.moz = morigin[2]; a.mres = mres;
   a.mx = mdims[0]; a.my = mdims[1]; a.mz = mdims[2]; a.stage = ctx->sense_staging;
   a.vehicles = d_vehicles;
-  hipLaunchKernelGGL(fh::fleet_sense_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, a);
+  a.headings = d_headings; a.th = th; a.tv = tv;
+  if (d_headings)
+    hipLaunchKernelGGL(fh::fleet_sense_kernel<true>, dim3((unsigned)n), dim3(256), 0, ctx->stream, a);
+  else
+    hipLaunchKernelGGL(fh::fleet_sense_kernel<false>, dim3((unsigned)n), dim3(256), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_sense_device(fh_ctx* ctx, fh_map* map, double r_sense, const fh_voxel_grid* grid, unsigned char* d_flags, size_t view_stride,
+                          const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n) {
+  return fleet_sense(ctx, map, r_sense, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, nullptr, 0.0, 0.0, "fh_fleet_sense_device");
+}
+
+int fh_fleet_sense_fov_device(fh_ctx* ctx, fh_map* map, double r_sense, const fh_voxel_grid* grid, unsigned char* d_flags, size_t view_stride,
+                              const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n, const fh_heading* d_headings,
+                              double tan_half_h, double tan_half_v) {
+  if (!(tan_half_h > 0) || !(tan_half_h < 1e300) || !(tan_half_v > 0) || !(tan_half_v < 1e300)) return FH_ERR_ARG;
+  if (n > 0 && !d_headings) return FH_ERR_ARG;
+  return fleet_sense(ctx, map, r_sense, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_headings, tan_half_h, tan_half_v,
+                     "fh_fleet_sense_fov_device");
+}
+
+// ---- heading (fh_fleet.hip.hpp): yaw, new terminal goals ----
+int fh_fleet_heading_init_device(fh_ctx* ctx, const double* d_yaw0, int n, fh_heading* d_headings) {
+  if (!ctx || n < 0) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx);
+  if (n == 0) return FH_OK;
+  if (!d_headings) return FH_ERR_ARG;
+  hipLaunchKernelGGL(fh::fleet_heading_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_yaw0, n, d_headings);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_set_headings_device(fh_ctx* ctx, fh_heading* d_headings, int n) {
+  if (!ctx || (d_headings && n < 1)) return FH_ERR_ARG;
+  ctx->headings = d_headings;
+  ctx->n_headings = d_headings ? n : 0;
+  return FH_OK;
+}
+
+int fh_fleet_set_goals_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicle* d_vehicles, const double* d_new_goals, const int32_t* d_mask,
+                              int n) {
+  if (!ctx || n < 0 || !fleet_params_ok(params)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_new_goals) return FH_ERR_ARG;
+  hipLaunchKernelGGL(fh::fleet_set_goals_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *params, d_vehicles, d_new_goals, d_mask,
+                     n);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_next_goals_yaw_device(fh_ctx* ctx, const fh_yaw_params* yaw_params, fh_vehicle* d_vehicles, const fh_state* d_plans,
+                                   fh_heading* d_headings, int n, int max_states, int ticks, int follow, fh_state* d_goals, double* d_goal_yaw) {
+  if (!ctx || n < 0 || max_states < 1 || ticks < 1 || ticks > 65536 || !yaw_params) return FH_ERR_ARG;
+  if (!(yaw_params->w_max >= 0) || !(yaw_params->w_max < 1e300) || !(yaw_params->alpha_filter_dyaw >= 0) || !(yaw_params->alpha_filter_dyaw <= 1) ||
+      !(yaw_params->dc > 0) || !(yaw_params->dc < 1e300))
+    return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_headings || !d_goals || !d_goal_yaw) return FH_ERR_ARG;
+  hipLaunchKernelGGL(fh::fleet_next_yaw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *yaw_params, d_vehicles, d_plans,
+                     d_headings, n, max_states, ticks, follow, d_goals, d_goal_yaw);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }

@@ -7,6 +7,8 @@
 // fleet_commit_kernel : the outcome of the cycle, appendToPlan, GOAL_SEEN, the factor windows (:548-588, :606-648).
 //                       One wavefront per vehicle; the samples are written by sample_into, the sampler of fh_sample_batch.
 // fleet_next_kernel   : getNextGoal `ticks` times (faster.cpp:699-723, without yaw).                     One lane per vehicle.
+// fleet_set_goals_kernel : setTerminalGoal for a running fleet (:139-159: GOAL_REACHED becomes YAWING).  One lane per vehicle.
+// fleet_next_yaw_kernel  : getNextGoal with getDesiredYaw and yaw, `ticks` times (:650-723).                One lane per vehicle.
 // fleet_sense_kernel  : every vehicle clears, in its own unknown-voxel view, what it can see (no reference counterpart: the sensor
 //                       model of include/fasterhip.h, checked against a numpy restatement).             One workgroup per vehicle.
 // The host restatement these kernels are checked against, cycle by cycle, is fhreplan::Planner (faster_amd/host/replan_stub.hpp),
@@ -88,7 +90,7 @@ __global__ void __launch_bounds__(256) fleet_begin_kernel(fh_fleet_params par, f
   const double dist = fleet_norm3(gterm[0] - here[0], gterm[1] - here[1], gterm[2] - here[2]);   // :331
   int status = v.status;
   if (dist < par.goal_radius) status = FH_VEHICLE_GOAL_REACHED;                                  // :332-335
-  const bool run = status != FH_VEHICLE_GOAL_REACHED && v.plan_size >= 1;                        // :337-343
+  const bool run = status != FH_VEHICLE_GOAL_REACHED && status != FH_VEHICLE_YAWING && v.plan_size >= 1;  // :337-343 (:334: nor while YAWING)
   int k_end = 0;
   double ra = 0;
   double x0[9] = {here[0], here[1], here[2], 0, 0, 0, 0, 0, 0};
@@ -243,6 +245,93 @@ __global__ void __launch_bounds__(256) fleet_next_kernel(fh_vehicle* __restrict_
   goals[i] = g;
 }
 
+// setTerminalGoal (faster.cpp:139-159) for the vehicles the mask selects
+__global__ void __launch_bounds__(256) fleet_set_goals_kernel(fh_fleet_params par, fh_vehicle* __restrict__ vehicles, const double* __restrict__ new_goals,
+                                                              const int32_t* __restrict__ mask, int n) {
+#pragma clang fp contract(off)
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= n) return;
+  if (mask && !mask[i]) return;
+  fh_vehicle& v = vehicles[i];
+  const double here[3] = {v.state.pos[0], v.state.pos[1], v.state.pos[2]};
+  const double gterm[3] = {new_goals[3 * i], new_goals[3 * i + 1], new_goals[3 * i + 2]};
+  const double w[3] = {par.wdx, par.wdy, par.wdz};
+  double G[3];
+  fleet_project_to_box(here, gterm, w, G);                                  // :148
+  for (int a = 0; a < 3; a++) { v.g_term[a] = gterm[a]; v.goal[a] = G[a]; }
+  if (v.status == FH_VEHICLE_GOAL_REACHED) v.status = FH_VEHICLE_YAWING;    // :149-152 (not done in any other status)
+}
+
+__global__ void __launch_bounds__(256) fleet_heading_init_kernel(const double* __restrict__ yaw0, int n, fh_heading* __restrict__ headings) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= n) return;
+  fh_heading h;
+  const double y = yaw0 ? yaw0[i] : 0.0;
+  h.yaw = y; h.previous_yaw = y; h.dyaw_filtered = 0; h.goal_yaw = 0; h.goal_dyaw = 0;
+  h.look_at[0] = 0; h.look_at[1] = 0; h.look_at[2] = 0;
+  h.dir[0] = cos(y); h.dir[1] = sin(y);
+  h.reserved[0] = 0; h.reserved[1] = 0;
+  headings[i] = h;
+}
+
+// getNextGoal + getDesiredYaw + yaw (faster.cpp:650-723) `ticks` times: the plan cursor moves as in fleet_next_kernel; the yaw needs the
+// goal position of every tick, so this one walks them.  Restated by fhreplan::Planner::getNextGoalYaw and tests/heading_model.py.
+__global__ void __launch_bounds__(256) fleet_next_yaw_kernel(fh_yaw_params yp, fh_vehicle* __restrict__ vehicles, const fh_state* __restrict__ plans,
+                                                             fh_heading* __restrict__ headings, int n, int max_states, int ticks, int follow,
+                                                             fh_state* __restrict__ goals, double* __restrict__ goal_yaw) {
+#pragma clang fp contract(off)
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= n) return;
+  fh_vehicle& v = vehicles[i];
+  const int size = v.plan_size, head = v.plan_head;
+  fh_state g;
+  for (int a = 0; a < 3; a++) { g.pos[a] = 0; g.vel[a] = 0; g.accel[a] = 0; g.jerk[a] = 0; }
+  double out_yaw = 0, out_dyaw = 0;
+  if (size > 0) {
+    const fh_state* plan = plans + (size_t)i * (size_t)max_states + head;
+    fh_heading h = headings[i];
+    int status = v.status;
+    const double gt[2] = {v.g_term[0], v.g_term[1]};
+    const double pi = 3.14159265358979323846;  // M_PI
+    for (int t = 0; t < ticks; t++) {
+      const int at = t < size - 1 ? t : size - 1;  // front() of call t: popped while more than one state is left
+      const double gx = plan[at].pos[0], gy = plan[at].pos[1];
+      double yaw, dyaw;
+      if (status == FH_VEHICLE_GOAL_REACHED) {     // :683-686
+        dyaw = 0.0;
+        yaw = h.previous_yaw;
+      } else {
+        const double tx = status == FH_VEHICLE_YAWING ? gt[0] : h.look_at[0], ty = status == FH_VEHICLE_YAWING ? gt[1] : h.look_at[1];
+        const double desired = atan2(ty - gy, tx - gx);                                            // :674, :680
+        double diff = desired - h.yaw;
+        diff = fmod(diff + pi, 2 * pi);                                                            // angle_wrap, utils.cpp:496-502
+        if (diff < 0) diff += 2 * pi;
+        diff -= pi;
+        if (fabs(diff) < 0.04 && status == FH_VEHICLE_YAWING) status = FH_VEHICLE_TRAVELING;       // :690-693
+        const double not_filtered = copysign(1.0, diff) * yp.w_max;                                // :655
+        h.dyaw_filtered = (1 - yp.alpha_filter_dyaw) * not_filtered + yp.alpha_filter_dyaw * h.dyaw_filtered;  // :657
+        dyaw = h.dyaw_filtered;
+        yaw = h.previous_yaw + h.dyaw_filtered * yp.dc;                                            // :662
+      }
+      h.previous_yaw = yaw;                                                                        // :718
+      h.goal_yaw = yaw; h.goal_dyaw = dyaw;
+      if (follow) h.yaw = yaw;
+    }
+    h.dir[0] = cos(h.previous_yaw); h.dir[1] = sin(h.previous_yaw);
+    out_yaw = h.goal_yaw; out_dyaw = h.goal_dyaw;
+    headings[i] = h;
+    v.status = status;
+    const int last = ticks - 1 < size - 1 ? ticks - 1 : size - 1;
+    g = plan[last];
+    const int pops = ticks < size - 1 ? ticks : size - 1;
+    v.plan_head = head + pops;
+    v.plan_size = size - pops;
+    if (follow) v.state = g;
+  }
+  goals[i] = g;
+  goal_yaw[2 * i] = out_yaw; goal_yaw[2 * i + 1] = out_dyaw;
+}
+
 // ---- sensing: every vehicle clears, in ITS view, the unknown flag of each voxel it can see (fh_fleet_sense_device) ----
 // The model (include/fasterhip.h states it; tests restate it in numpy and compare every byte): voxel centre q = ((i + 0.5) res + origin) is
 // in range of p when sqrt(dx dx + dy dy + dz dz) < r_sense, and visible when none of the points p + (q - p) (j / K), j = 1 .. K - 1,
@@ -255,6 +344,12 @@ __global__ void __launch_bounds__(256) fleet_next_kernel(fh_vehicle* __restrict_
 // are cast by full wavefronts and not by the few lanes of a row that need one.  The occupancy bits a ray can touch (the bounding box of
 // the sphere in map cells, rows padded to 32 bits) are copied to LDS when the first queue is drained, and not at all by a vehicle whose
 // surroundings are known already.
+//
+// FOV = true (fh_fleet_sense_fov_device): the sensor looks along (c, s) = fh_heading.dir and a voxel must also be in view: f = c dx + s dy > 0,
+// |c dy - s dx| <= f tan_half_h, |dz| <= f tan_half_v.  The per-voxel predicate alone decides; what the field of view saves is the scan: the
+// box scanned (and, in map cells, staged) is not the sphere's but one that holds the frustum cut at r_sense — every point of it is f (c, s) +
+// l (-s, c) with 0 < f < r, |l| <= f th, so x - px lies in [min(0, r (c - |s| th)), max(0, r (c + |s| th))], y alike, |z - pz| <= r tv —
+// intersected with the sphere's box, with the same cell of slack.  It contains p, so it holds every ray too.
 #define FH_SENSE_QUEUE 2048      // cells waiting for their ray (LDS, 8 KB)
 #define FH_SENSE_OCC_WORDS 6144  // staged occupancy (LDS, 24 KB: 54 x 54 rows of two words); a larger box is read from memory
 struct SenseArgs {
@@ -267,6 +362,8 @@ struct SenseArgs {
   double mox, moy, moz, mres;
   int mx, my, mz, stage;
   const fh_vehicle* vehicles;
+  const fh_heading* headings;  // FOV only
+  double th, tv;               // FOV only: tan of half the horizontal / vertical field of view
 };
 
 __device__ __forceinline__ int sense_clamp_cell(double v, int lo, int hi) {  // floor(v) clamped to [lo, hi], safe for any v
@@ -274,6 +371,7 @@ __device__ __forceinline__ int sense_clamp_cell(double v, int lo, int hi) {  // 
   return !(f > (double)lo) ? lo : (f > (double)hi ? hi : (int)f);
 }
 
+template <bool FOV>
 __global__ void __launch_bounds__(256) fleet_sense_kernel(SenseArgs a) {
 #pragma clang fp contract(off)
   __shared__ int queue[FH_SENSE_QUEUE];
@@ -287,16 +385,31 @@ __global__ void __launch_bounds__(256) fleet_sense_kernel(SenseArgs a) {
   const double px = a.vehicles[b].state.pos[0], py = a.vehicles[b].state.pos[1], pz = a.vehicles[b].state.pos[2];
   if (!(fabs(px) < 1e300) || !(fabs(py) < 1e300) || !(fabs(pz) < 1e300)) return;  // (NaN or infinite: sees nothing)
   const double r = a.r_sense;
-  // lattice cells whose centre can be in range: one cell of slack on each side of the sphere's bounding box
-  const int x0 = sense_clamp_cell((px - r - a.ox) / a.res - 1.0, 0, a.nx), x1 = sense_clamp_cell((px + r - a.ox) / a.res + 1.0, -1, a.nx - 1);
-  const int y0 = sense_clamp_cell((py - r - a.oy) / a.res - 1.0, 0, a.ny), y1 = sense_clamp_cell((py + r - a.oy) / a.res + 1.0, -1, a.ny - 1);
-  const int z0 = sense_clamp_cell((pz - r - a.oz) / a.res - 1.0, 0, a.nz), z1 = sense_clamp_cell((pz + r - a.oz) / a.res + 1.0, -1, a.nz - 1);
+  // what the box around the scanned volume spans from p, per axis: the sphere's, or (FOV) the frustum's inside it
+  double slx = -r, shx = r, sly = -r, shy = r, slz = -r, shz = r;
+  double hc = 1.0, hs = 0.0;  // the heading's dir
+  if (FOV) {
+    hc = a.headings[b].dir[0]; hs = a.headings[b].dir[1];
+    if (!(fabs(hc) < 1e300) || !(fabs(hs) < 1e300)) return;  // (NaN or infinite: sees nothing)
+    const double big = fmax(fabs(hc), fabs(hs));
+    if (!(big > 0.0)) return;                                // ((0, 0): f = 0 for every voxel, nothing is in view)
+    const double uc = hc / big, us = hs / big;               // (scaled first: the squares of a very long or very short dir must not leave the range)
+    const double len = sqrt(uc * uc + us * us);              // (in [1, sqrt 2])
+    const double cn = uc / len, sn = us / len;               // (the predicate does not depend on the length of dir; the box must not either)
+    slx = fmax(-r, fmin(0.0, r * (cn - fabs(sn) * a.th))); shx = fmin(r, fmax(0.0, r * (cn + fabs(sn) * a.th)));
+    sly = fmax(-r, fmin(0.0, r * (sn - fabs(cn) * a.th))); shy = fmin(r, fmax(0.0, r * (sn + fabs(cn) * a.th)));
+    slz = fmax(-r, -r * a.tv); shz = fmin(r, r * a.tv);
+  }
+  // lattice cells whose centre can be in range (and in view): one cell of slack on each side of that box
+  const int x0 = sense_clamp_cell((px + slx - a.ox) / a.res - 1.0, 0, a.nx), x1 = sense_clamp_cell((px + shx - a.ox) / a.res + 1.0, -1, a.nx - 1);
+  const int y0 = sense_clamp_cell((py + sly - a.oy) / a.res - 1.0, 0, a.ny), y1 = sense_clamp_cell((py + shy - a.oy) / a.res + 1.0, -1, a.ny - 1);
+  const int z0 = sense_clamp_cell((pz + slz - a.oz) / a.res - 1.0, 0, a.nz), z1 = sense_clamp_cell((pz + shz - a.oz) / a.res + 1.0, -1, a.nz - 1);
   const int cx = x1 - x0 + 1, cy = y1 - y0 + 1, cz = z1 - z0 + 1;
-  if (cx <= 0 || cy <= 0 || cz <= 0) return;  // the sphere misses the lattice
+  if (cx <= 0 || cy <= 0 || cz <= 0) return;  // the box misses the lattice
   // the map cells a sample point can fall into: the same box in the map's cells
-  const int bx0 = sense_clamp_cell((px - r - a.mox) / a.mres - 1.0, 0, a.mx), bx1 = sense_clamp_cell((px + r - a.mox) / a.mres + 1.0, -1, a.mx - 1);
-  const int by0 = sense_clamp_cell((py - r - a.moy) / a.mres - 1.0, 0, a.my), by1 = sense_clamp_cell((py + r - a.moy) / a.mres + 1.0, -1, a.my - 1);
-  const int bz0 = sense_clamp_cell((pz - r - a.moz) / a.mres - 1.0, 0, a.mz), bz1 = sense_clamp_cell((pz + r - a.moz) / a.mres + 1.0, -1, a.mz - 1);
+  const int bx0 = sense_clamp_cell((px + slx - a.mox) / a.mres - 1.0, 0, a.mx), bx1 = sense_clamp_cell((px + shx - a.mox) / a.mres + 1.0, -1, a.mx - 1);
+  const int by0 = sense_clamp_cell((py + sly - a.moy) / a.mres - 1.0, 0, a.my), by1 = sense_clamp_cell((py + shy - a.moy) / a.mres + 1.0, -1, a.my - 1);
+  const int bz0 = sense_clamp_cell((pz + slz - a.moz) / a.mres - 1.0, 0, a.mz), bz1 = sense_clamp_cell((pz + shz - a.moz) / a.mres + 1.0, -1, a.mz - 1);
   const int bcx = bx1 - bx0 + 1, bcy = by1 - by0 + 1, bcz = bz1 - bz0 + 1;
   const int row_words = (bcx + 31) >> 5;
   const bool box_ok = bcx > 0 && bcy > 0 && bcz > 0;
@@ -333,6 +446,10 @@ __global__ void __launch_bounds__(256) fleet_sense_kernel(SenseArgs a) {
         const double dx = ((double)ix + 0.5) * a.res + a.ox - px, dy = ((double)iy + 0.5) * a.res + a.oy - py,
                      dz = ((double)iz + 0.5) * a.res + a.oz - pz;
         cand = sqrt(dx * dx + dy * dy + dz * dz) < r;
+        if (FOV) {
+          const double f = hc * dx + hs * dy, l = hc * dy - hs * dx;
+          cand = cand && f > 0.0 && fabs(l) <= f * a.th && fabs(dz) <= f * a.tv;
+        }
       }
       const unsigned long long m = __ballot(cand);
       if (m) {

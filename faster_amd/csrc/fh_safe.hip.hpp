@@ -131,12 +131,15 @@ __device__ inline void shorten_by(P3* path, int& n, double d) {
 
 // One wavefront per pair.  Writes the safe path (<= max_poly_safe + 1 vertices, R first) and its length (0: no safe trajectory is
 // needed, or there is no whole trajectory), x0 = R of the safe problem, the sphere of known space of the pair.
+// headings (fh_fleet_set_headings_device; NULL: none, and nothing below differs from a build without it): look_at of pair b = M_.pos as
+// faster.cpp:452 and :496 write it — what the march returns (the last vertex of the cut path), for every pair with a whole trajectory,
+// so the march then also runs for a pair that needs no safe path; and the last vertex of JPS_safe when one is needed.
 __global__ void __launch_bounds__(64) safe_path_kernel(const fh_problem* __restrict__ whole, const fh_result* __restrict__ wres,
                                                        const double* __restrict__ paths, const int32_t* __restrict__ n_points, int n,
                                                        int max_points, double r_frac, fh_pair_rule rule, int max_poly_safe,
                                                        fh_problem* __restrict__ safe, double* __restrict__ safe_paths,
                                                        int32_t* __restrict__ safe_np, double* __restrict__ spheres, UnknownGrid ug,
-                                                       UnknownViews vw) {
+                                                       UnknownViews vw, fh_heading* __restrict__ headings) {
   __shared__ P3 s_orig[SAFE_PATH_CAP + 2], s_cur[SAFE_PATH_CAP + 2];  // (LDS, not per-lane arrays: those would be 2 KB of scratch per lane)
   const int b = blockIdx.x, lane = threadIdx.x;
   if (b >= n) return;
@@ -148,7 +151,8 @@ __global__ void __launch_bounds__(64) safe_path_kernel(const fh_problem* __restr
   const int np_in = n_points[b];
   if (rw.solved && pw.n_seg >= 1 && pw.n_seg <= FH_MAX_SEG && np_in >= 2 && np_in <= SAFE_PATH_CAP) {
     int k;
-    if (choose_r_index(pw, rw, r_frac, rule, lane, k, &ug)) {
+    const bool need = choose_r_index(pw, rw, r_frac, rule, lane, k, &ug);
+    if (need || headings) {
       const int N = pw.n_seg;
       const double dt = rw.dt, DC = pw.dc;
       const int size = sample_count(pw, rw);
@@ -157,7 +161,7 @@ __global__ void __launch_bounds__(64) safe_path_kernel(const fh_problem* __restr
       clock_at(k, DC, dt, N, t, interval);  // the reference's clock at sample k (solverGurobi.cpp:131-135): fh_clock.hpp
       fh_state R;
       eval_state(rw.coeff[interval], t - interval * dt, k == size - 1, R);
-      if (lane < 3) {
+      if (need && lane < 3) {
         safe[b].x0[lane] = lane == 0 ? R.pos[0] : (lane == 1 ? R.pos[1] : R.pos[2]);
         safe[b].x0[3 + lane] = lane == 0 ? R.vel[0] : (lane == 1 ? R.vel[1] : R.vel[2]);
         safe[b].x0[6 + lane] = lane == 0 ? R.accel[0] : (lane == 1 ? R.accel[1] : R.accel[2]);
@@ -220,13 +224,21 @@ __global__ void __launch_bounds__(64) safe_path_kernel(const fh_problem* __restr
           iteration++;
         }
         __syncthreads();
+        if (headings && lane == 0) {  // M_.pos = getFirstCollisionJPS(...) (:452): the last vertex of the path as the march left it
+          double* la = headings[b].look_at;
+          la[0] = orig[no - 1].x; la[1] = orig[no - 1].y; la[2] = orig[no - 1].z;
+        }
         // JPS_safe: R first, at most max_poly_safe legs (:478-490)
-        np_out = no < mp ? no : mp;
-        if (lane == 0) {
+        np_out = need ? (no < mp ? no : mp) : 0;
+        if (need && lane == 0) {
           orig[0] = p3(R.pos[0], R.pos[1], R.pos[2]);
           for (int i = 0; i < np_out; i++) {
             double* o = safe_paths + 3 * ((size_t)b * mp + i);
             o[0] = orig[i].x; o[1] = orig[i].y; o[2] = orig[i].z;
+          }
+          if (headings) {             // M_.pos = JPS_safe.back() (:496)
+            double* la = headings[b].look_at;
+            la[0] = orig[np_out - 1].x; la[1] = orig[np_out - 1].y; la[2] = orig[np_out - 1].z;
           }
         }
       }
@@ -251,7 +263,8 @@ __global__ void safe_spheres_kernel(const double* __restrict__ pair_spheres, int
 __global__ void __launch_bounds__(64) safe_finalize_kernel(const int32_t* __restrict__ safe_np, const double* __restrict__ goal_m,
                                                            const double* __restrict__ goals_g, const fh_face* __restrict__ faces,
                                                            const int32_t* __restrict__ face_off, const int32_t* __restrict__ n_poly, int n,
-                                                           int faces_per_problem, int n_seg_safe, fh_problem* __restrict__ safe) {
+                                                           int faces_per_problem, int n_seg_safe, fh_problem* __restrict__ safe,
+                                                           fh_heading* __restrict__ headings) {
   const int b = blockIdx.x, lane = threadIdx.x;
   if (b >= n) return;
   const int P = n_poly[b];
@@ -269,6 +282,7 @@ __global__ void __launch_bounds__(64) safe_finalize_kernel(const int32_t* __rest
   }
   const bool inside = __ballot(out) == 0ull;
   if (lane < 3) safe[b].xf[lane] = inside ? goals_g[3 * (size_t)b + lane] : goal_m[3 * (size_t)b + lane];
+  if (headings && inside && lane < 3) headings[b].look_at[lane] = goals_g[3 * (size_t)b + lane];  // M_.pos = G (:503-504)
   if (lane <= FH_MAX_POLY) safe[b].face_off[lane] = face_off[9 * (size_t)b + lane];
   if (lane == 0) {
     safe[b].n_seg = n_seg_safe;

@@ -11,7 +11,10 @@ view per vehicle or team (set_unknown_views) that the vehicles grow on the devic
 
     sense -> replan -> next_goals
 
-with no host data in it.  The host restatement every cycle is checked against is fhreplan::Planner (faster_amd/host/replan_stub.hpp);
+with no host data in it.  enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
+that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
+
+The host restatement every cycle is checked against is fhreplan::Planner (faster_amd/host/replan_stub.hpp);
 tests/test_gpu_fleet.py and tests/test_gpu_fleet_views.py compare the two cycle by cycle.
 """
 import numpy as np
@@ -62,6 +65,8 @@ class Fleet:
         self.cloud, self.n_cloud, self.grid = None, 0, None
         self.flags = self.view_flags = self.view_of = None
         self.n_views = 0
+        self.dc = float(dc)
+        self.d_headings = self.d_goal_yaw = self.yaw_params = None  # enable_heading
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -153,14 +158,53 @@ class Fleet:
         self.ctx.set_unknown_views_device(self.view_flags.data_ptr(), cells, None if self.view_of is None else self.view_of.data_ptr(), self.n_views,
                                           self.grid[0], self.grid[1], self.grid[2])
 
-    def sense(self, r_sense):
+    def enable_heading(self, yaw0=None, w_max=4.0, alpha_filter_dyaw=0.0):
+        """Allocates one fh_heading per vehicle (yaw = previous_yaw = yaw0[i], None: 0) and attaches the records to the context: from
+        now on replan() writes look_at (M_.pos), next_goals() computes yaw and dyaw, and sense(fov=...) can look forward."""
+        t = self.torch
+        self.yaw_params = abi.default_yaw_params(self.dc)
+        self.yaw_params["w_max"], self.yaw_params["alpha_filter_dyaw"] = w_max, alpha_filter_dyaw
+        self.d_headings = t.zeros(self.n * abi.heading_dtype.itemsize, dtype=t.uint8, device=self.dev)
+        self.d_goal_yaw = t.zeros((self.n, 2), dtype=t.float64, device=self.dev)
+        d_yaw0 = None if yaw0 is None else self._host_to_device(np.asarray(yaw0, dtype=np.float64).reshape(self.n), t.float64)
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            self.ctx.fleet_heading_init_device(None if d_yaw0 is None else d_yaw0.data_ptr(), self.n, self.d_headings.data_ptr())
+            if d_yaw0 is not None:
+                d_yaw0.record_stream(self.stream)
+        self.ctx.fleet_set_headings_device(self.d_headings.data_ptr(), self.n)
+
+    def set_goals(self, goals, mask=None):
+        """setTerminalGoal for the vehicles with mask[i] != 0 (None: all): a vehicle that had reached its goal becomes YAWING."""
+        t = self.torch
+        d_goals = self._host_to_device(np.asarray(goals, dtype=np.float64).reshape(self.n, 3) if not isinstance(goals, t.Tensor) else goals, t.float64)
+        d_mask = None
+        if mask is not None:
+            d_mask = self._host_to_device(np.asarray(mask).astype(np.int32).reshape(self.n) if not isinstance(mask, t.Tensor) else mask, t.int32)
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            self.ctx.fleet_set_goals_device(self.params, self.d_vehicles.data_ptr(), d_goals.data_ptr(), None if d_mask is None else d_mask.data_ptr(),
+                                            self.n)
+            d_goals.record_stream(self.stream)
+            if d_mask is not None:
+                d_mask.record_stream(self.stream)
+
+    def sense(self, r_sense, fov=None):
         """Every vehicle looks around from its current position and clears, in its view, the unknown flag of each voxel within r_sense
         that the occupied cells of the map do not hide (fh_fleet_sense_device: the sensor model is stated in include/fasterhip.h).  One
-        launch on the fleet's stream."""
+        launch on the fleet's stream.  fov = (tan_half_h, tan_half_v): only what lies in that field of view along the vehicle's heading
+        (fh_fleet_sense_fov_device; needs enable_heading)."""
         if self.view_flags is None or self.cloud is None:
             raise capi.FasterHipError("Fleet.sense: set_map and set_unknown_views first")
         self._follow_current()
         origin, res, dims = self.grid
+        if fov is not None:
+            if self.d_headings is None:
+                raise capi.FasterHipError("Fleet.sense: a field of view needs enable_heading first")
+            self.ctx.fleet_sense_fov_device(self.map, r_sense, origin, res, dims, self.view_flags.data_ptr(), self.view_flags.shape[1],
+                                            None if self.view_of is None else self.view_of.data_ptr(), self.n_views, self.d_vehicles.data_ptr(), self.n,
+                                            self.d_headings.data_ptr(), fov[0], fov[1])
+            return
         self.ctx.fleet_sense_device(self.map, r_sense, origin, res, dims, self.view_flags.data_ptr(), self.view_flags.shape[1],
                                     None if self.view_of is None else self.view_of.data_ptr(), self.n_views, self.d_vehicles.data_ptr(), self.n)
 
@@ -206,7 +250,12 @@ class Fleet:
 
     def next_goals(self, ticks, follow=True):
         """getNextGoal `ticks` times for every vehicle; returns the device buffer of the last goals ([n] fh_state as bytes).  follow: the
-        current state becomes that goal (updateState of a vehicle that tracks its plan perfectly)."""
+        current state becomes that goal (updateState of a vehicle that tracks its plan perfectly).  With enable_heading the yaw entry
+        runs instead (1 <= ticks <= 65536): the same goals, and (yaw, dyaw) of the last one in self.d_goal_yaw ([n][2], goal_yaw())."""
+        if self.d_headings is not None:
+            self.ctx.fleet_next_goals_yaw_device(self.yaw_params, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.d_headings.data_ptr(),
+                                                 self.n, self.max_states, int(ticks), follow, self.d_next.data_ptr(), self.d_goal_yaw.data_ptr())
+            return self.d_next
         self.ctx.fleet_next_goals_device(self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.n, self.max_states, int(ticks), follow,
                                          self.d_next.data_ptr())
         return self.d_next
@@ -230,6 +279,19 @@ class Fleet:
     def goals(self):
         """[n] abi.state_dtype: what the last next_goals returned."""
         return self._host(self.d_next, abi.state_dtype)
+
+    def headings(self):
+        """[n] abi.heading_dtype: yaw, previous_yaw, the filtered yaw rate, the last goal's yaw and dyaw, look_at (M_) and dir."""
+        if self.d_headings is None:
+            raise capi.FasterHipError("Fleet.headings: enable_heading first")
+        return self._host(self.d_headings, abi.heading_dtype)
+
+    def goal_yaw(self):
+        """[n][2] (yaw, dyaw) of what the last next_goals returned."""
+        if self.d_goal_yaw is None:
+            raise capi.FasterHipError("Fleet.goal_yaw: enable_heading first")
+        self.sync()
+        return self.d_goal_yaw.cpu().numpy().copy()
 
     def plans(self):
         """[n] lists of committed states (abi.state_dtype arrays), front first."""

@@ -6,7 +6,8 @@
 // build the safe corridor in unknown+occupied space from R and solve the safe trajectory; splice A->R->safe into the plan and adapt
 // the two factor windows.  This header restates that control flow so that the solver behind the SolverGurobi surface (SolverHip)
 // is exercised exactly the way the reference drives it — same setter order, same public members, same use of X_temp_ and
-// factor_that_worked_ — with the ROS node, the mutexes, the visual outputs and the yaw logic left out.
+// factor_that_worked_ — with the ROS node, the mutexes and the visual outputs left out.  The yaw logic (getDesiredYaw, yaw, the YAWING
+// status, M_) is restated beside the yaw-free calls: setNewTerminalGoal, getNextGoalYaw; a caller that uses neither sees none of it.
 //
 // Reference pieces restated here (file:line relative to faster/src/):
 //   replan ............................. faster.cpp:296-595        findIndexH / findIndexR ...... faster.cpp:218-251 / :173-216
@@ -14,7 +15,7 @@
 //   createMoreVertexes ................. faster.cpp:80-97          getFirstCollisionJPS ......... faster.cpp:767-926
 //   deleteVertexes / reduceJPSbyDistance utils.cpp:1117-1124 / :690-710
 //   getFirstIntersectionWithSphere ..... utils.cpp:782-870 (+ getIntersectionWithSphere :713-776, float arithmetic kept)
-//   projectPointToBox .................. utils.cpp:1065-1115
+//   projectPointToBox .................. utils.cpp:1065-1115        getDesiredYaw / yaw / angle_wrap  faster.cpp:666-697 / :650-664 / utils.cpp:496-502
 // The kd-tree queries of the reference (pcl::KdTreeFLANN, faster.hpp:139-141) are brute-force nearest-neighbour scans here.
 #pragma once
 #include <algorithm>
@@ -43,6 +44,7 @@ struct Params {  // the planner-relevant subset of `parameters` (faster_types.hp
   int deltaT = 10;  // states between "now" and the start state A (faster.hpp:131)
   double wdx = 20, wdy = 20, wdz = 4, res = 0.15;
   double z_ground = 0.0, z_max = 3.0, inflation_jps = 0.47, factor_jps = 1.0;
+  double w_max = 4.0, alpha_filter_dyaw = 0.0;  // faster_types.hpp:30-31, faster.yaml (getNextGoalYaw only)
   // ---- what a test may pin down (defaults: the behaviour described above) ----
   bool jps = false;               // true: the path search is jump point search in jps3d's own order (plan_path_jps: what FASTER runs,
                                   //       jps_manager.cpp:166); false: the A* with a total order of its own (plan_path: the same cost)
@@ -53,7 +55,13 @@ struct Params {  // the planner-relevant subset of `parameters` (faster_types.hp
   int map_cells[3] = {0, 0, 0};
 };
 
-enum class Status { TRAVELING, GOAL_SEEN, GOAL_REACHED };
+enum class Status { TRAVELING, GOAL_SEEN, GOAL_REACHED, YAWING };  // (the numbers of FH_VEHICLE_*)
+
+inline void angle_wrap(double& diff) {  // utils.cpp:496-502
+  diff = std::fmod(diff + M_PI, 2 * M_PI);
+  if (diff < 0) diff += 2 * M_PI;
+  diff -= M_PI;
+}
 
 inline V3 pos_of(const state& s) { return V3(s.pos.x(), s.pos.y(), s.pos.z()); }
 
@@ -195,6 +203,7 @@ inline std::vector<LinearConstraint3D> to_solver_constraints(const std::vector<f
 
 struct ReplanLog {
   int stage = 0;  // 0 not started, 1 no path, 2 whole failed, 3 safe failed, 4 append failed, 5 committed
+  int m_writes = 0;  // which of the three places wrote M_ this replan: bit 0 the march (:452), bit 1 JPS_safe.back() (:496), bit 2 G (:504)
   bool needed_safe = false;
   int k_end_whole = 0, k_safe = 0, index_H = 0;
   double whole_factor = 0, safe_factor = 0;
@@ -248,6 +257,58 @@ public:
     if (plan_.size() > 1) plan_.pop_front();
     return true;
   }
+  // ---- the heading (additions: none of the calls above or replan's results change through them) ----
+  // setTerminalGoal as the reference has it for a RUNNING vehicle (:139-159): after GOAL_REACHED the vehicle turns first (YAWING);
+  // every other status is kept (:149-152).  (setTerminalGoal above starts a vehicle: TRAVELING.)
+  void setNewTerminalGoal(const state& g) {
+    G_term_ = g;
+    goal_set_ = true;
+    if (status_ == Status::GOAL_REACHED) status_ = Status::YAWING;
+  }
+  // getNextGoal with getDesiredYaw (:699-723): next.yaw and next.dyaw are set, previous_yaw_ follows.  state_.yaw is what the last
+  // updateState gave (a caller that tracks its goals perfectly passes the last goal, yaw included).
+  bool getNextGoalYaw(state& next) {
+    if (!getNextGoal(next)) return false;
+    getDesiredYaw(next);
+    previous_yaw_ = next.yaw;
+    return true;
+  }
+  void getDesiredYaw(state& next_goal) {  // :666-697
+    double diff = 0.0, desired_yaw = 0.0;
+    switch (status_) {
+      case Status::YAWING:
+        desired_yaw = std::atan2(G_term_.pos[1] - next_goal.pos[1], G_term_.pos[0] - next_goal.pos[0]);
+        diff = desired_yaw - state_.yaw;
+        break;
+      case Status::TRAVELING:
+      case Status::GOAL_SEEN:
+        desired_yaw = std::atan2(M_.pos[1] - next_goal.pos[1], M_.pos[0] - next_goal.pos[0]);
+        diff = desired_yaw - state_.yaw;
+        break;
+      case Status::GOAL_REACHED:
+        next_goal.dyaw = 0.0;
+        next_goal.yaw = previous_yaw_;
+        return;
+    }
+    angle_wrap(diff);
+    if (std::fabs(diff) < 0.04 && status_ == Status::YAWING) status_ = Status::TRAVELING;
+    yaw(diff, next_goal);
+  }
+  void yaw(double diff, state& next_goal) {  // :650-664 (saturate(diff, ...) there changes a local copy whose sign alone is used)
+    const double dyaw_not_filtered = std::copysign(1.0, diff) * par_.w_max;
+    dyaw_filtered_ = (1 - par_.alpha_filter_dyaw) * dyaw_not_filtered + par_.alpha_filter_dyaw * dyaw_filtered_;
+    next_goal.dyaw = dyaw_filtered_;
+    next_goal.yaw = previous_yaw_ + dyaw_filtered_ * par_.dc;
+  }
+  const state& M() const { return M_; }
+  double previous_yaw() const { return previous_yaw_; }
+  double dyaw_filtered() const { return dyaw_filtered_; }
+  // a test's way in: the members a scenario starts from
+  void setHeadingState(Status st, double previous_yaw, double dyaw_filtered, const state& M) {
+    status_ = st; previous_yaw_ = previous_yaw; dyaw_filtered_ = dyaw_filtered; M_ = M;
+  }
+  void setPlan(const std::deque<state>& plan) { plan_ = plan; }
+  void setYawParams(double w_max, double alpha) { par_.w_max = w_max; par_.alpha_filter_dyaw = alpha; }
   Status status() const { return status_; }
   const std::deque<state>& plan() const { return plan_; }
   // A fresh vehicle for the same planner object (a batch of independent start/goal pairs through one pair of solver contexts): no
@@ -257,6 +318,9 @@ public:
     goal_set_ = false;
     status_ = Status::TRAVELING;
     plan_.clear();
+    M_ = state();
+    previous_yaw_ = 0.0;
+    dyaw_filtered_ = 0.0;
     sg_whole_.setFactorInitialAndFinalAndIncrement(1, 10, par_.increment_whole);
     sg_safe_.setFactorInitialAndFinalAndIncrement(1, 10, par_.increment_safe);
   }
@@ -272,7 +336,7 @@ public:
     const V3 G = project_to_box(here, gterm, par_.wdx, par_.wdy, par_.wdz);
     const double dist_to_goal = (gterm - here).norm();
     if (dist_to_goal < par_.goal_radius) status_ = Status::GOAL_REACHED;
-    if (status_ == Status::GOAL_REACHED) return false;
+    if (status_ == Status::GOAL_REACHED || status_ == Status::YAWING) return false;  // :334
 
     // ---- start state A: deltaT states before the end of the committed plan (:351-352)
     const int k_end_whole = std::max((int)plan_.size() - par_.deltaT, 0);
@@ -321,6 +385,8 @@ public:
     std::vector<V3> tmp = JPS_in;
     bool hit = false;
     V3 Mpos = march_to_cloud(tmp, unknown_, par_.drone_radius, &hit);
+    M_.setPos(Mpos.x, Mpos.y, Mpos.z);  // :452
+    L.m_writes |= 1;
     bool need_safe = false;
     const int indexH = find_index_H(need_safe);
     L.index_H = indexH;
@@ -337,9 +403,15 @@ public:
       std::vector<V3> JPS_safe = tmp;
       keep_first(JPS_safe, par_.max_poly_safe);
       Mpos = JPS_safe.back();
+      M_.setPos(Mpos.x, Mpos.y, Mpos.z);  // :496
+      L.m_writes |= 2;
       l_constraints_safe_ = to_solver_constraints(decompose_(JPS_safe, unknown_and_occupied_, decomp_r, par_.z_ground));
       if (l_constraints_safe_.empty()) { L.stage = 3; return false; }  // failed (device) decomposition: no safe corridor, as for the whole one
-      if (l_constraints_safe_.back().inside(fhstub::Vec3(G.x, G.y, G.z))) Mpos = G;
+      if (l_constraints_safe_.back().inside(fhstub::Vec3(G.x, G.y, G.z))) {
+        Mpos = G;
+        M_.setPos(Mpos.x, Mpos.y, Mpos.z);  // :503-504
+        L.m_writes |= 4;
+      }
       L.safe_path = JPS_safe;
       L.safe_goal = Mpos;
       for (const auto& c : l_constraints_safe_) L.safe_rows.push_back((int)c.b().rows());
@@ -405,6 +477,8 @@ private:
 
   Params par_;
   state state_, G_term_;
+  state M_;                                          // faster.hpp: kept across replans, written at :452, :496, :504
+  double previous_yaw_ = 0.0, dyaw_filtered_ = 0.0;  // faster.hpp (getNextGoalYaw)
   bool state_set_ = false, goal_set_ = false, map_set_ = false;
   Status status_ = Status::TRAVELING;
   std::deque<state> plan_;

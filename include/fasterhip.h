@@ -603,13 +603,16 @@ int fh_map_plan_batch_radius_device(fh_map* map, const double* d_starts, const d
  * Supported: one shared map of occupied space per cycle (fh_map_read_device); unknown space in rule mode 2 either as one grid for the
  * whole fleet (fh_set_unknown_grid_device) or as a view per vehicle or team (fh_set_unknown_views_device), which the vehicles grow on
  * the device by sensing (fh_fleet_sense_device): a closed-loop period is sense -> the chain above -> next goals with no host data in it;
- * the staged faithful chain above.  Not supported: yaw (getDesiredYaw, the YAWING status), a map of occupied space per vehicle, and
- * the fused fh_solve_pairs_device as the committed path (its safe corridor is not FASTER's, and it takes no views).
+ * the staged faithful chain above; the vehicle's heading (getDesiredYaw, the YAWING status, a new terminal goal after arrival and a
+ * forward-looking sensor: the fh_heading block below).  Not supported: a map of occupied space per vehicle, and the fused
+ * fh_solve_pairs_device as the committed path (its safe corridor is not FASTER's, and it takes no views).
  * Plan storage: plan of vehicle i = d_plans[i * max_states + plan_head .. + plan_size); a commit moves the kept prefix to index 0. */
 enum {
   FH_VEHICLE_TRAVELING = 0,     /* faster.cpp: TRAVELING */
   FH_VEHICLE_GOAL_SEEN = 1,     /* |G_term - plan.back()| < goal_radius after a commit (:563-570) */
-  FH_VEHICLE_GOAL_REACHED = 2   /* |G_term - state| < goal_radius (:326-339): no more replans */
+  FH_VEHICLE_GOAL_REACHED = 2,  /* |G_term - state| < goal_radius (:326-339): no more replans */
+  FH_VEHICLE_YAWING = 3         /* a new terminal goal after GOAL_REACHED (fh_fleet_set_goals_device, :149-152): the vehicle turns towards
+                                   it without replanning (:334) until fh_fleet_next_goals_yaw_device finds |diff| < 0.04 (:690-693) */
 };
 /* fh_vehicle.stage: what the last replan did (fhreplan::ReplanLog::stage) */
 enum {
@@ -694,8 +697,9 @@ int fh_fleet_next_goals_device(fh_ctx* ctx, fh_vehicle* d_vehicles, const fh_sta
  *   in range and visible: flags_view[(iz ny + iy) nx + ix] = 0.
  * Nothing is ever set to non-zero: knowledge only grows.  Every vehicle senses, whatever its status.  Vehicles that share a view
  * clear the union of what they see; because only zeros are stored the result does not depend on scheduling.  A vehicle with a view
- * number outside [0, n_views) or a position that is not finite senses nothing.  The sensor is omnidirectional (the fleet has no yaw),
- * has no noise and no minimum range, and sees through nothing: limits of the model, not of the implementation.
+ * number outside [0, n_views) or a position that is not finite senses nothing.  The sensor is omnidirectional
+ * (fh_fleet_sense_fov_device is the forward-looking one), has no noise and no minimum range, and sees through nothing: limits of the
+ * model, not of the implementation.
  * r_sense > 0, at most 4096 res_map.  Asynchronous on the stream of `ctx`; `map` is only read, and must have been filled on the same
  * stream (faster_amd.fleet.Fleet sets both to one stream).  A voxel that is already known costs one byte read and no ray, so a fleet
  * in steady state pays for the shell it moved into. */
@@ -704,6 +708,72 @@ int fh_fleet_sense_device(fh_ctx* ctx, fh_map* map, double r_sense, const struct
 /* Measurement only (results do not depend on it): 1 (default) a vehicle that has rays to cast copies the occupancy bits of the bounding
  * box of its sphere to LDS first; 0 every sample point reads the map in memory. */
 int fh_set_sense_staging(fh_ctx* ctx, int on);
+
+/* ---- heading: yaw, the YAWING status, new terminal goals and a forward sensor ------------------------------------------------
+ * Faster::getNextGoal calls getDesiredYaw and yaw on every tick (faster.cpp:699-723, :666-697, :650-664): the vehicle looks towards
+ * M_, the point where its path enters unknown space, because its depth camera looks forward; after GOAL_REACHED a new terminal goal
+ * makes it turn on the spot (YAWING) before it travels again.  All of that state lives in one fh_heading per vehicle, in a
+ * caller-owned device array next to the fh_vehicle array; nothing above this block changes when no headings are used. */
+typedef struct fh_heading {
+  double yaw;                       /* state_.yaw as the caller's updateState gave it (follow != 0: the last goal's yaw)     */
+  double previous_yaw;              /* previous_yaw_ (:718)                                                                  */
+  double dyaw_filtered;             /* dyaw_filtered_ (:657)                                                                 */
+  double goal_yaw, goal_dyaw;       /* yaw and dyaw of the last goal handed out                                              */
+  double look_at[3];                /* M_.pos: 0 until a replan first reaches :452 (state M_ is default-constructed)         */
+  double dir[2];                    /* (cos previous_yaw, sin previous_yaw), written by the device whenever previous_yaw changes:
+                                       the direction the forward sensor looks in                                             */
+  double reserved[2];
+} fh_heading;
+/* faster_types.hpp:30-31, faster.yaml: w_max 4.0, alpha_filter_dyaw 0; dc is the period of a tick (par_.dc) */
+typedef struct fh_yaw_params {
+  double w_max;
+  double alpha_filter_dyaw;
+  double dc;
+} fh_yaw_params;
+/* yaw = previous_yaw = d_yaw0[i] (NULL: 0), dyaw_filtered = goal_yaw = goal_dyaw = 0, look_at = 0, dir = (cos yaw0, sin yaw0). */
+int fh_fleet_heading_init_device(fh_ctx* ctx, const double* d_yaw0, int n, fh_heading* d_headings);
+/* Attaches n heading records to the context (NULL: none), as fh_set_unknown_views_device attaches views.  While attached,
+ * fh_safe_corridor_batch_device (n queries at most) writes d_headings[i].look_at for every query i whose whole problem was solved
+ * (a path of >= 2 points and a whole trajectory): first the point getFirstCollisionJPS returns for the path inside the sphere against
+ * unknown space (:452), computed whether or not a safe path turns out to be needed; then, when one is needed, the last vertex of
+ * JPS_safe after deleteVertexes (:496), replaced by G when G lies inside the last safe polytope (:503-504) — the xf of the safe
+ * problem.  A query that is inactive, has no path or has no whole trajectory leaves look_at as it was (the reference returns before
+ * :452); a safe solve that fails later does not undo the write.  With nothing attached every stage does exactly what it did before
+ * headings existed. */
+int fh_fleet_set_headings_device(fh_ctx* ctx, fh_heading* d_headings, int n);
+/* setTerminalGoal (:139-159) for the vehicles with d_mask[i] != 0 (d_mask NULL: all): g_term = d_new_goals[i] ([n][3]), goal =
+ * projectPointToBox(state, g_term, wdx, wdy, wdz) (the arithmetic of fh_fleet_begin_device), GOAL_REACHED becomes YAWING; every other
+ * status is kept, GOAL_SEEN included (:149-152).  fh_fleet_begin_device tests GOAL_REACHED first (:326-331), also for a YAWING vehicle;
+ * a vehicle that is still YAWING after that does not replan (:334): stage NONE, inactive. */
+int fh_fleet_set_goals_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicle* d_vehicles, const double* d_new_goals,
+                              const int32_t* d_mask, int n);
+/* getNextGoal WITH getDesiredYaw, `ticks` times in a row (1 <= ticks <= 65536: the yaw needs every tick's goal position, so the work
+ * is linear in ticks).  Positions, plan cursor and d_goals are exactly what fh_fleet_next_goals_device gives for the same arguments.
+ * Per tick, with g the goal of that tick and h the vehicle's heading record, in double, no fused multiply-add, in this order:
+ *   GOAL_REACHED: dyaw = 0, yaw = h.previous_yaw (:683-686);
+ *   else desired = atan2(t.y - g.pos.y, t.x - g.pos.x), t = g_term (YAWING) or h.look_at (TRAVELING, GOAL_SEEN); diff = desired - h.yaw;
+ *     angle_wrap (utils.cpp:496-502): diff = fmod(diff + pi, 2 pi); if (diff < 0) diff += 2 pi; diff -= pi;
+ *     YAWING and |diff| < 0.04: status = TRAVELING;
+ *     h.dyaw_filtered = (1 - alpha) (copysign(1, diff) w_max) + alpha h.dyaw_filtered; dyaw = h.dyaw_filtered;
+ *     yaw = h.previous_yaw + h.dyaw_filtered dc;
+ *   h.previous_yaw = h.goal_yaw = yaw; h.goal_dyaw = dyaw; follow != 0: h.yaw = yaw (and state = goal, as fh_fleet_next_goals_device).
+ * follow == 0: h.yaw is the caller's and stays.  At the end h.dir = (cos h.previous_yaw, sin h.previous_yaw) and d_goal_yaw[i] =
+ * (yaw, dyaw) of the last tick ([n][2]).  A vehicle with an empty plan is untouched (its d_goals entry is zero as before, its
+ * d_goal_yaw entry (0, 0)). */
+int fh_fleet_next_goals_yaw_device(fh_ctx* ctx, const fh_yaw_params* yaw_params, fh_vehicle* d_vehicles, const fh_state* d_plans,
+                                   fh_heading* d_headings, int n, int max_states, int ticks, int follow, fh_state* d_goals,
+                                   double* d_goal_yaw);
+/* fh_fleet_sense_device with a field of view.  With (c, s) = d_headings[i].dir and d = q - p:
+ *   f = c dx + s dy,  l = c dy - s dx,  u = dz   (double, in this order, no fused multiply-add; no pitch, no roll)
+ *   in view: f > 0 and fabs(l) <= f tan_half_h and fabs(u) <= f tan_half_v.
+ * in range, in view and visible: flags_view[(iz ny + iy) nx + ix] = 0.  Everything else — in range, visible (the ray rule and the
+ * "own map cell" exception), views, what is never written — is word for word the model of fh_fleet_sense_device.  Both tangents must
+ * be finite and positive (else FH_ERR_ARG); a vehicle whose dir is not finite (or is (0, 0)) senses nothing; a finite dir of any length
+ * is a direction (the predicate does not depend on its length).  The sensor reads dir and
+ * not yaw, and takes tangents and not angles, so that the model involves no transcendental function. */
+int fh_fleet_sense_fov_device(fh_ctx* ctx, fh_map* map, double r_sense, const struct fh_voxel_grid* grid, unsigned char* d_flags,
+                              size_t view_stride, const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n,
+                              const fh_heading* d_headings, double tan_half_h, double tan_half_v);
 
 /* Timing of the solve kernel, measured with HIP events recorded around every solve-kernel launch on
  * the context stream (the same stream the kernel runs on).  fh_timing_reset() forgets recorded launches;

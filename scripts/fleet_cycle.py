@@ -10,9 +10,12 @@ stream), the unfenced cycle time, the commit kernel's write rate and a device-to
   "views_sensing": every view starts all unknown, the vehicles sense (Fleet.sense, --r-sense metres, default 3) before every replan: the
       first sense, when every voxel in range still needs its ray ("sense_first_ms"), then the closed loop sense -> replan -> 5 ticks in
       steady state, sensing as a stage of its own.  --no-staging: sensing reads the occupancy in memory instead of staging it in LDS.
+--fov TAN_H TAN_V (implies --views) adds "fov_sensing": the same closed loop with Fleet.enable_heading, the forward sensor
+(Fleet.sense(r, fov=(TAN_H, TAN_V)): tangents of the half angles) in place of the omnidirectional one and the yaw variant of next goals;
+its "sense_first_ms" and stage table stand beside the omnidirectional ones of the same run.
 Memory of the views: vehicles x nx ny nz bytes (printed; 65536 vehicles in this forest: 12.6 GB).  A fleet that does not fit lets vehicles
 share views (view_of).
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--r-sense R] [--no-staging]"""
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--r-sense R] [--no-staging]"""
 import json
 import os
 import sys
@@ -26,8 +29,8 @@ from faster_amd import abi, capi, frontend  # noqa: E402
 from faster_amd.fleet import Fleet  # noqa: E402
 
 
-def timed_cycles(fl, cycles, r_sense=None):
-    """`cycles` cycles, every stage fenced by events: {stage: [ms]} (with r_sense: sensing first, as a stage of its own)."""
+def timed_cycles(fl, cycles, r_sense=None, fov=None):
+    """`cycles` cycles, every stage fenced by events: {stage: [ms]} (with r_sense: sensing first, as a stage of its own; fov: forward)."""
     names = (["sense"] if r_sense else []) + [n for n, _ in fl.stages()] + ["next_goals"]
     per = {n: [] for n in names}
     for _ in range(cycles):
@@ -35,7 +38,7 @@ def timed_cycles(fl, cycles, r_sense=None):
         ev[0].record(fl.stream)
         k = 0
         if r_sense:
-            fl.sense(r_sense)
+            fl.sense(r_sense, fov=fov)
             k = 1
             ev[1].record(fl.stream)
         for j, (n, launch) in enumerate(fl.stages()):
@@ -49,7 +52,39 @@ def timed_cycles(fl, cycles, r_sense=None):
     return {n: float(np.median(v)) for n, v in per.items()}
 
 
-def views_cycles(B, cycles, p, world, r_sense, staging):
+def sensing_loop(fl, views, cycles, states, goals, r_sense, fov=None):
+    """The closed loop from views that are all unknown: the first look, then sense -> replan -> 5 ticks in steady state."""
+    views.fill_(1)
+    fl.init(states, goals)
+    if fov is not None:
+        u = goals - states["pos"]
+        fl.enable_heading(yaw0=np.arctan2(u[:, 1], u[:, 0]))   # (looking towards the goal)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(fl.stream)
+    fl.sense(r_sense, fov=fov)
+    e1.record(fl.stream)
+    fl.sync()
+    first = e0.elapsed_time(e1)
+    fl.replan()
+    fl.next_goals(5)
+    fl.sync()
+    med = timed_cycles(fl, cycles, r_sense, fov)
+    t = []
+    for _ in range(cycles):
+        fl.sync()
+        t0 = time.perf_counter()
+        fl.sense(r_sense, fov=fov)
+        fl.replan()
+        fl.next_goals(5)
+        fl.sync()
+        t.append(1e3 * (time.perf_counter() - t0))
+    v = fl.vehicles()
+    return first, {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "cycle_ms": float(np.median(t)),
+                   "committed_last": int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum()),
+                   "unknown_fraction_end": float(views.float().mean().item())}
+
+
+def views_cycles(B, cycles, p, world, r_sense, staging, fov=None):
     """The cycle with a view per vehicle: see the module docstring."""
     cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims = world
     n_cells = dims[0] * dims[1] * dims[2]
@@ -68,42 +103,27 @@ def views_cycles(B, cycles, p, world, r_sense, staging):
         med = timed_cycles(fl, cycles)
         out["views_same_flags"] = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values()))}
         # the closed loop: everything unknown at first, the vehicles back at their starts
-        views.fill_(1)
-        fl.init(states, goals)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(fl.stream)
-        fl.sense(r_sense)
-        e1.record(fl.stream)
-        fl.sync()
-        out["sense_first_ms"] = e0.elapsed_time(e1)
-        fl.replan()
-        fl.next_goals(5)
-        fl.sync()
-        med = timed_cycles(fl, cycles, r_sense)
-        t = []
-        for _ in range(cycles):
-            fl.sync()
-            t0 = time.perf_counter()
-            fl.sense(r_sense)
-            fl.replan()
-            fl.next_goals(5)
-            fl.sync()
-            t.append(1e3 * (time.perf_counter() - t0))
-        v = fl.vehicles()
-        out["views_sensing"] = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "cycle_ms": float(np.median(t)),
-                                "committed_last": int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum()),
-                                "unknown_fraction_end": float(views.float().mean().item())}
+        out["sense_first_ms"], out["views_sensing"] = sensing_loop(fl, views, cycles, states, goals, r_sense)
+        if fov is not None:
+            first, loop = sensing_loop(fl, views, cycles, states, goals, r_sense, fov)
+            out["fov_sensing"] = dict(loop, sense_first_ms=first, tan_half_h=fov[0], tan_half_v=fov[1])
     finally:
         fl.close()
     return out
 
 
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    r_sense = 3.0
-    if "--r-sense" in sys.argv:
-        r_sense = float(sys.argv[sys.argv.index("--r-sense") + 1])
-        args.remove(sys.argv[sys.argv.index("--r-sense") + 1])
+    argv = sys.argv[1:]
+    r_sense, fov = 3.0, None
+    if "--r-sense" in argv:      # (an option's values leave by position, not by text: `1 3 --fov 1 0.5` keeps its first two)
+        k = argv.index("--r-sense")
+        r_sense = float(argv[k + 1])
+        del argv[k:k + 2]
+    if "--fov" in argv:
+        k = argv.index("--fov")
+        fov = (float(argv[k + 1]), float(argv[k + 2]))
+        del argv[k:k + 3]
+    args = [a for a in argv if not a.startswith("--")]
     B = int(args[0]) if len(args) > 0 else 65536
     cycles = int(args[1]) if len(args) > 1 else 3
     res, infl, zmax = 0.2, 0.3, 3.0
@@ -188,9 +208,9 @@ def main():
                     "commit_write_gbs": cb / (med["commit"] * 1e-3) / 1e9, "hbm_copy_gbs": copy_gbs})
     finally:
         fl.close()
-    if "--views" in sys.argv:
+    if "--views" in sys.argv or fov is not None:
         world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
-        out.update(views_cycles(B, cycles, p, world, r_sense, "--no-staging" not in sys.argv))
+        out.update(views_cycles(B, cycles, p, world, r_sense, "--no-staging" not in sys.argv, fov))
     print(json.dumps(out))
 
 
