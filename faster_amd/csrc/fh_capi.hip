@@ -22,6 +22,50 @@
 #include "fh_decomp.hip.hpp"
 #include "fh_safe.hip.hpp"  // (after fh_solve: it switches FP contraction off for what follows, like fh_decomp)
 #include "fh_fleet.hip.hpp"
+#include "fh_host.hpp"
+
+using fhh::DeviceScope;
+
+// The device buffers of a context: grown on demand (DeviceBuffer::reserve), reused, freed by fh_destroy.  Per name: who writes it,
+// who reads it, and whether a launch in flight may still use it when the next entry point runs.
+enum Buf {
+  // Staging of the host-pointer entry points.  ONLY the synchronous host-pointer entry points may touch these five: each copies its inputs
+  // in, launches, copies its outputs out and waits for the stream before it returns, so no launch in flight ever reads them — and what
+  // they hold differs from one entry point to the next.
+  HOST_STAGE_0,  // fh_solve_batch, fh_sample_batch, fh_dt_initial_batch: the problems; fh_decompose_batch: the cloud
+  HOST_STAGE_1,  // fh_solve_batch: the faces; fh_decompose_batch: the segments
+  HOST_STAGE_2,  // fh_solve_batch: the results (out); fh_sample_batch: the results (in)
+  HOST_STAGE_3,  // fh_sample_batch: the states (out); fh_decompose_batch: the faces (out); fh_fp64_peak: its scratch
+  HOST_STAGE_4,  // fh_sample_batch, fh_decompose_batch: the counts (out); fh_dt_initial_batch: dt (out)
+  // Everything below is working memory of launches on the context's stream: a launch in flight MAY still use it.  Launches of one
+  // stream run in order, so the next launch may reuse it, and reserve() waits for the stream before it frees.
+  SNAPSHOTS,     // launch_solve sizes it; the solve kernel's workgroups write and read their snapshot workspace
+  SHARE_BLOCK,   // work-sharing control block, ring sequence numbers, claims (ShareBlock): share_init_kernel and the solve kernel write; read
+                 // by the solve kernel and, after a synchronisation, by the host (read_share_ctl, fh_solve_batch)
+  DECOMP_WS,     // decompose_device sizes it; decomp_kernel's workgroups write and read their workspace
+  RING_SLOTS,    // task slots of the ring: written and read by the solve kernel's workgroups
+  SHARE_RECS,    // share records: written and read by the solve kernel
+  SEGMENTS,      // corridor_chain: corridor_segments_kernel writes the segments, decomp_kernel reads them
+  SEG_FACES,     // corridor_chain: decomp_kernel writes the polytope rows per segment, corridor_assemble_kernel reads them
+  SEG_COUNTS,    // corridor_chain: decomp_kernel writes the row counts per segment, corridor_assemble_kernel reads them
+  LAUNCH_ORDER,  // launch_solve: 128 counters + the launch order of a batch; order kernels write, the solve kernel reads
+  CLOUD_BLOCKS,  // decompose_device: cloud_blocks_kernel writes the bounding boxes of the cloud's blocks, decomp_kernel reads them
+  BASIS,         // reduced-space basis tables (fh_basis.hip.hpp): uploaded once by fh_create, only read by the solve kernels
+  SAFE_SCRATCH,  // fh_safe_corridor_batch_device: safe paths, spheres, goals, offsets and counts between its kernels
+  SEG_SPHERES,   // fh_safe_corridor_batch_device: safe_spheres_kernel writes the sphere of every segment, decomp_kernel reads them
+  SEG_COUNTER,   // decompose_device zeroes it on the stream; decomp_kernel's workgroups draw their segments from it
+  N_BUFS
+};
+
+// SHARE_BLOCK: the control block in the first 4096 bytes, then FH_QCAP ring sequence numbers, then FH_MAX_GRID claims
+struct ShareBlock {
+  static constexpr size_t SEQS = 4096, CLAIMS = SEQS + sizeof(unsigned long long) * FH_QCAP, BYTES = CLAIMS + sizeof(unsigned int) * FH_MAX_GRID;
+  static_assert(sizeof(fh::ShareCtl) <= SEQS, "the control block has outgrown its part of SHARE_BLOCK");
+  unsigned char* base;
+  fh::ShareCtl* ctl() const { return reinterpret_cast<fh::ShareCtl*>(base); }
+  unsigned long long* seqs() const { return reinterpret_cast<unsigned long long*>(base + SEQS); }
+  unsigned int* claims() const { return reinterpret_cast<unsigned int*>(base + CLAIMS); }
+};
 
 struct fh_ctx {
   int device = 0;
@@ -32,17 +76,9 @@ struct fh_ctx {
   fh_params par;
   fh_sched sched;
   std::string err;
-  // staging buffers of the host-pointer entry points (grown on demand, reused)
-  // slot 5: snapshot workspace, 6: work-sharing control block + ring sequence numbers, 7: decomposition workspace,
-  // 8: task slots of the ring, 9: share records
-  // 10: corridor segments, 11: per-segment polytope rows, 12: per-segment row counts (fh_corridor_batch_device)
-  // 13: launch order of a batch (order_kernel), 14: bounding boxes of the cloud's blocks (decomposition)
-  // 15: reduced-space basis tables (fh_basis.hip.hpp), uploaded once by fh_create
-  void* d_buf[20] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, nullptr, nullptr};
-  size_t d_cap[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  fhh::DeviceBuffer buf[N_BUFS];  // (enum Buf)
   int n_cu = 0;
-  size_t lds_attr[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // largest dynamic-LDS size already set per kernel instantiation
+  size_t lds_attr[20] = {};  // largest dynamic-LDS size already set per kernel instantiation (lds_attr_index)
   unsigned int* h_abort = nullptr;          // mapped host word polled by the kernels (fh_request_stop)
   unsigned int* d_abort = nullptr;          // its device address
   unsigned int* h_report = nullptr;         // pinned: the control block's report words of the last launch (copied with the results)
@@ -84,58 +120,33 @@ static int other_launches_in_flight(const fh_ctx* me) {
   return others;
 }
 
-#define FH_HIP(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e__ = (call);                                                                    \
-    if (e__ != hipSuccess) {                                                                    \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e__);                            \
-      return FH_ERR_DEVICE;                                                                     \
-    }                                                                                           \
-  } while (0)
+#define FH_HIP(call) FHH_HIP(call, ctx->err, return FH_ERR_DEVICE)
 
-// Makes the context's device current for the duration of an entry point (a process may drive several GPUs from one thread)
-// and restores the caller's device on exit.
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceScope(const fh_ctx* ctx) {
-    if (ctx && ctx->device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != ctx->device)
-      switched = hipSetDevice(ctx->device) == hipSuccess;
-  }
-  ~DeviceScope() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-};
-
-static int ensure(fh_ctx* ctx, int slot, size_t bytes) {
-  if (bytes <= ctx->d_cap[slot]) return FH_OK;
-  if (ctx->d_buf[slot]) {
-    // a running launch of this context may still use the old buffer (workspace, ring): wait for it before freeing
-    FH_HIP(hipStreamSynchronize(ctx->stream));
-    FH_HIP(hipFree(ctx->d_buf[slot]));
-  }
-  ctx->d_buf[slot] = nullptr;
-  ctx->d_cap[slot] = 0;
-  size_t want = std::max(bytes, (size_t)4096);
-  FH_HIP(hipMalloc(&ctx->d_buf[slot], want));
-  ctx->d_cap[slot] = want;
+static int ensure(fh_ctx* ctx, Buf b, size_t bytes) {
+  FH_HIP(ctx->buf[b].reserve(bytes, ctx->stream));
   return FH_OK;
 }
 
 // Initialises the work-sharing state (ticket, counters, hand-off counters, ring sequence numbers) before the FIRST solve launch of
 // a context and after a launch that could not be issued; every launch leaves the block initialised for the next one (its last
 // workgroup resets it: solve_kernel), so nothing a launch did can poison the next.
-__global__ void share_init_kernel(fh::ShareCtl* ctl, unsigned long long* seqs) {
+__global__ void share_init_kernel(fh::ShareCtl* ctl, unsigned long long* seqs, unsigned int* claims) {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < (unsigned)FH_QCAP) seqs[i] = (unsigned long long)i;
   if (i < sizeof(fh::ShareCtl) / 4) reinterpret_cast<unsigned int*>(ctl)[i] = 0u;
-  if (i < (unsigned)FH_MAX_GRID) reinterpret_cast<unsigned int*>(seqs + FH_QCAP)[i] = 0u;  // claims[] (ShareArgs)
+  if (i < (unsigned)FH_MAX_GRID) claims[i] = 0u;
 }
 
 #ifndef FH_ORDER_WINDOW
 #define FH_ORDER_WINDOW 2  // the launch order interleaves ranks inside windows of FH_TICKET_CHUNK x FH_ORDER_WINDOW x (resident workgroups) tickets
                            // (measured on C4, one launch alone: 1: 3.5-3.6 ms, 2: 3.1-3.2 ms, the whole batch as one window: 3.3 ms — and 13.1 instead of 12.2 ms on C5)
 #endif
+// Where fh_ctx::lds_attr keeps the instantiation that fh_launch_info names: the four sizes x {single, pairs} x {three, two wavefronts per
+// SIMD}, then the four unknown-space instantiations (always pairs, always two wavefronts)
+static constexpr int lds_attr_index(int nseg, bool pairs, bool two_waves, bool unk) {
+  return (nseg <= 6 ? 0 : (nseg <= 10 ? 1 : (nseg <= 15 ? 2 : 3))) + (unk ? 16 : (pairs ? 4 : 0) + (two_waves ? 8 : 0));
+}
+
 // One solve launch: NSEG selects the kernel instantiation, PAIRS the whole -> hand-off -> safe unit.
 template <int NSEG, bool PAIRS>
 static int launch_solve(fh_ctx* ctx, const fh_problem* d_problems, const fh_face* d_faces, fh_result* d_results, fh::SolveArgs ka) {
@@ -166,23 +177,25 @@ static int launch_solve(fh_ctx* ctx, const fh_problem* d_problems, const fh_face
   }
   const int resident = ctx->n_cu * per_cu;
   ctx->last_launch = {NSEG, PAIRS ? 1 : 0, (two_waves || unk) ? 2 : FH_WAVES_PER_SIMD, 0, per_cu, (int32_t)lds_launch, unk ? 1 : 0, 0};  // (the UNK instantiation is always the two-wavefront one)
+  size_t& lds_have = ctx->lds_attr[lds_attr_index(NSEG, PAIRS, two_waves, unk)];
   const bool share = ctx->par.share != 0 && ctx->par.max_work == 0 && ctx->par.mip_gap == 0.0;
   // small batches get helper workgroups (one per CU) that take over subtrees of hard problems
   const int grid = share ? std::min(resident, std::max(n, ctx->n_cu)) : std::min(resident, n);
   ctx->last_launch.grid = grid;
   int rc;
-  if ((rc = ensure(ctx, 5, sizeof(double) * (size_t)grid * ((size_t)NSEG * SV::SNAP_PADDED + 64))) != FH_OK) return rc;
+  if ((rc = ensure(ctx, SNAPSHOTS, sizeof(double) * (size_t)grid * ((size_t)NSEG * SV::SNAP_PADDED + 64))) != FH_OK) return rc;
   const size_t slot_stride = sizeof(fh::TaskHdr) + sizeof(double) * (size_t)SV::SNAP_PADDED;
-  if (!ctx->d_buf[6]) ctx->ctl_ready = false;
-  if ((rc = ensure(ctx, 6, 4096 + sizeof(unsigned long long) * FH_QCAP + sizeof(unsigned int) * FH_MAX_GRID)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 8, slot_stride * FH_QCAP)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 9, sizeof(fh::ShareRec) * FH_NRECS)) != FH_OK) return rc;
+  if (!ctx->buf[SHARE_BLOCK].ptr) ctx->ctl_ready = false;
+  if ((rc = ensure(ctx, SHARE_BLOCK, ShareBlock::BYTES)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, RING_SLOTS, slot_stride * FH_QCAP)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, SHARE_RECS, sizeof(fh::ShareRec) * FH_NRECS)) != FH_OK) return rc;
+  const ShareBlock block{ctx->buf[SHARE_BLOCK].as<unsigned char>()};
   fh::ShareArgs& sa = ka.sa;
-  sa.ctl = reinterpret_cast<fh::ShareCtl*>(ctx->d_buf[6]);
-  sa.seqs = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(ctx->d_buf[6]) + 4096);
-  sa.slots = reinterpret_cast<unsigned char*>(ctx->d_buf[8]);
+  sa.ctl = block.ctl();
+  sa.seqs = block.seqs();
+  sa.slots = ctx->buf[RING_SLOTS].as<unsigned char>();
   sa.slot_stride = slot_stride;
-  sa.recs = reinterpret_cast<fh::ShareRec*>(ctx->d_buf[9]);
+  sa.recs = ctx->buf[SHARE_RECS].as<fh::ShareRec>();
   sa.host_abort = ctx->d_abort;
   sa.deadline_ticks = ctx->par.deadline_ms > 0 ? (unsigned long long)(ctx->par.deadline_ms * 1e5) : 0ull;  // 100 MHz clock
   sa.enabled = share && grid > 1 ? 1 : 0;
@@ -222,7 +235,7 @@ static int launch_solve(fh_ctx* ctx, const fh_problem* d_problems, const fh_face
 #ifdef FH_NO_DEAL  // (A/B builds: every ticket is drawn)
   sa.claims = nullptr;
 #else
-  sa.claims = grid <= FH_MAX_GRID ? reinterpret_cast<unsigned int*>(reinterpret_cast<unsigned char*>(ctx->d_buf[6]) + 4096 + sizeof(unsigned long long) * FH_QCAP) : nullptr;
+  sa.claims = grid <= FH_MAX_GRID ? block.claims() : nullptr;
 #endif
   sa.whole = PAIRS ? d_problems : nullptr;
   sa.wfaces = d_faces;
@@ -231,14 +244,11 @@ static int launch_solve(fh_ctx* ctx, const fh_problem* d_problems, const fh_face
   sa.shrink = ka.shrink;
   sa.r_margin = ka.r_margin;
   ka.par = ctx->par;
-  ka.workspace = (double*)ctx->d_buf[5];
-  ka.basis = (const double*)ctx->d_buf[15];
-  {  // raise the dynamic-LDS limit of this instantiation only when a launch needs more than any before it
-    size_t& have = ctx->lds_attr[(NSEG <= 6 ? 0 : (NSEG <= 10 ? 1 : (NSEG <= 15 ? 2 : 3))) + (unk ? 16 : (PAIRS ? 4 : 0) + (two_waves ? 8 : 0))];
-    if (lds_launch > have) {
-      FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch));
-      have = lds_launch;
-    }
+  ka.workspace = ctx->buf[SNAPSHOTS].as<double>();
+  ka.basis = ctx->buf[BASIS].as<const double>();
+  if (lds_launch > lds_have) {  // raise the dynamic-LDS limit of this instantiation only when a launch needs more than any before it
+    FH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch));
+    lds_have = lds_launch;
   }
   if (ctx->ev_used + 2 > ctx->ev.size()) {
     if (ctx->ev.size() >= 8192) ctx->ev_used = 0;  // ring: keep the most recent launches only
@@ -250,7 +260,7 @@ static int launch_solve(fh_ctx* ctx, const fh_problem* d_problems, const fh_face
       }
   }
   if (!ctx->ctl_ready) {
-    hipLaunchKernelGGL(share_init_kernel, dim3((std::max(FH_QCAP, FH_MAX_GRID) + 255) / 256), dim3(256), 0, ctx->stream, sa.ctl, sa.seqs);
+    hipLaunchKernelGGL(share_init_kernel, dim3((std::max(FH_QCAP, FH_MAX_GRID) + 255) / 256), dim3(256), 0, ctx->stream, block.ctl(), block.seqs(), block.claims());
     FH_HIP(hipGetLastError());
   }
   ctx->ctl_ready = false;  // (true again once the launch below has been issued: it resets the block when it ends)
@@ -260,10 +270,10 @@ static int launch_solve(fh_ctx* ctx, const fh_problem* d_problems, const fh_face
   // grids (C4, fourteen in flight: 24.0 -> 24.25 M pairs/s without them)
   ka.order = nullptr;
   if (n >= 2048 && (ctx->sched.launch_order >= 2 || (ctx->sched.launch_order == 1 && !busy))) {
-    const bool fresh = ctx->d_cap[13] < sizeof(int) * ((size_t)n + 128) || !ctx->order_ready;
+    const bool fresh = ctx->buf[LAUNCH_ORDER].cap < sizeof(int) * ((size_t)n + 128) || !ctx->order_ready;
     ctx->order_ready = false;  // (true again once all three launches below have been issued: a failed launch must not leave dirty counters behind)
-    if ((rc = ensure(ctx, 13, sizeof(int) * ((size_t)n + 128))) != FH_OK) return rc;
-    int* counters = (int*)ctx->d_buf[13];
+    if ((rc = ensure(ctx, LAUNCH_ORDER, sizeof(int) * ((size_t)n + 128))) != FH_OK) return rc;
+    int* counters = ctx->buf[LAUNCH_ORDER].as<int>();
     int* order = counters + 128;  // (2 * FH_ORDER_CLASSES + 1 = 73 counters)
     if (fresh) FH_HIP(hipMemsetAsync(counters, 0, sizeof(int) * 128, ctx->stream));  // afterwards the scatter kernel leaves them zeroed
     const unsigned blocks = (unsigned)((n + FH_ORDER_BLOCK - 1) / FH_ORDER_BLOCK);
@@ -286,17 +296,39 @@ static int launch_solve(fh_ctx* ctx, const fh_problem* d_problems, const fh_face
   return FH_OK;
 }
 
+// Did a solve launch report a protocol failure (report word 5)?  `tail` ends the message of the entry point that asks.  The launch counts as checked.
+static int share_verdict(fh_ctx* ctx, unsigned int code, const char* tail) {
+  ctx->launched = false;
+  if (!code) return FH_OK;
+  ctx->err = "solve kernel: work-sharing protocol failure (code " + std::to_string(code) + ")" + tail;
+  return FH_ERR_DEVICE;
+}
+static const char* const INCOMPLETE = "; results of the launch are incomplete";
+// The control block as the last solve launch left it (the stream has been synchronised; SHARE_BLOCK exists) and, with `tail`, the verdict on it.
+static int read_share_ctl(fh_ctx* ctx, fh::ShareCtl* h, const char* tail) {
+  std::memset(h, 0, sizeof(*h));
+  if (tail) ctx->launched = false;
+  FH_HIP(hipMemcpy(h, ctx->buf[SHARE_BLOCK].ptr, sizeof(*h), hipMemcpyDeviceToHost));
+  return tail ? share_verdict(ctx, h->report[5], tail) : FH_OK;
+}
 // after the stream has been synchronised: did the last solve launch report a protocol failure?
 static int check_share_error(fh_ctx* ctx) {
-  if (!ctx->launched || !ctx->d_buf[6]) return FH_OK;
-  ctx->launched = false;
   fh::ShareCtl h;
-  FH_HIP(hipMemcpy(&h, ctx->d_buf[6], sizeof(h), hipMemcpyDeviceToHost));
-  if (h.report[5]) {
-    ctx->err = "solve kernel: work-sharing protocol failure (code " + std::to_string(h.report[5]) + "); results of the launch are incomplete";
-    return FH_ERR_DEVICE;
-  }
-  return FH_OK;
+  return ctx->launched && ctx->buf[SHARE_BLOCK].ptr ? read_share_ctl(ctx, &h, INCOMPLETE) : FH_OK;
+}
+
+// The caps as every solve entry point reads them (out of range: the largest), and the instantiation that holds max_seg segments.
+template <bool PAIRS>
+static int dispatch_solve(fh_ctx* ctx, const fh_problem* d_problems, const fh_face* d_faces, fh_result* d_results, int n, int max_seg, int max_faces,
+                          fh::SolveArgs ka) {
+  if (max_seg <= 0 || max_seg > FH_MAX_SEG) max_seg = FH_MAX_SEG;
+  if (max_faces <= 0 || max_faces > FH_MAX_FACES) max_faces = FH_MAX_FACES;
+  ka.n = n;
+  ka.max_faces = (max_faces + 7) & ~7;
+  if (max_seg <= 6) return launch_solve<6, PAIRS>(ctx, d_problems, d_faces, d_results, ka);
+  if (max_seg <= 10) return launch_solve<10, PAIRS>(ctx, d_problems, d_faces, d_results, ka);
+  if (max_seg <= 15) return launch_solve<15, PAIRS>(ctx, d_problems, d_faces, d_results, ka);
+  return launch_solve<FH_MAX_SEG, PAIRS>(ctx, d_problems, d_faces, d_results, ka);
 }
 
 // packed results: the words of an fh_result without the coefficient rows beyond n_seg (one thread per 8-byte word of the output)
@@ -318,7 +350,7 @@ size_t fh_packed_result_size(int n_seg) { return (n_seg < 1 || n_seg > FH_MAX_SE
 int fh_pack_results_device(fh_ctx* ctx, const fh_result* d_results, int n, int n_seg, void* d_packed) {
   if (!ctx || n < 0 || n_seg < 1 || n_seg > FH_MAX_SEG) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_results || !d_packed) return FH_ERR_ARG;
   const int words_out = (int)(fh_packed_result_size(n_seg) / 8);
@@ -467,9 +499,9 @@ int fh_create(fh_ctx** out, int device) {
   FH_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_report), 64, hipHostMallocDefault));
   {  // the reduced-space basis tables: constants of N = 1..FH_MAX_SEG, computed here once and only read by the kernels
     const std::vector<double> tab = fh::build_basis_tables();
-    int rc = ensure(ctx, 15, sizeof(double) * tab.size());
+    int rc = ensure(ctx, BASIS, sizeof(double) * tab.size());
     if (rc != FH_OK) return rc;
-    FH_HIP(hipMemcpy(ctx->d_buf[15], tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    FH_HIP(hipMemcpy(ctx->buf[BASIS].ptr, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
   }
   return FH_OK;
 }
@@ -482,8 +514,7 @@ void fh_destroy(fh_ctx* ctx) {
   }
   if (ctx->device >= 0) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (int i = 0; i < 20; i++)
-      if (ctx->d_buf[i]) (void)hipFree(ctx->d_buf[i]);
+    for (fhh::DeviceBuffer& b : ctx->buf) b.release();
     if (ctx->h_abort) (void)hipHostFree(ctx->h_abort);
     if (ctx->h_report) (void)hipHostFree(ctx->h_report);
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
@@ -507,7 +538,7 @@ int fh_set_stream(fh_ctx* ctx, void* hip_stream) {
   hipStream_t next = hip_stream ? reinterpret_cast<hipStream_t>(hip_stream) : ctx->own_stream;
   if (next != ctx->stream && ctx->device >= 0 && ctx->stream) {
     // one work queue / workspace per context: launches on the old stream must be over before the new stream may use them
-    DeviceScope device_scope(ctx);
+    DeviceScope device_scope(ctx->device);
     FH_HIP(hipStreamSynchronize(ctx->stream));
   }
   ctx->stream = next;
@@ -536,12 +567,10 @@ int fh_set_unknown_grid_device(fh_ctx* ctx, const fh_voxel_grid* grid, const uns
     ctx->views = fh::UnknownViews{0, nullptr, 0, 0};
     return FH_OK;
   }
-  if (!grid || !(grid->res > 0) || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1) return FH_ERR_ARG;
-  if ((long long)grid->dims[0] * grid->dims[1] * grid->dims[2] > (1ll << 30)) return FH_ERR_ARG;
+  if (!fhh::voxel_grid_ok(grid) || fhh::voxel_grid_cells(*grid) > (1ll << 30)) return FH_ERR_ARG;
   ctx->views = fh::UnknownViews{0, nullptr, 0, 0};  // one grid replaces views
   ctx->unknown.flags = d_flags;
-  ctx->unknown.ox = grid->origin[0]; ctx->unknown.oy = grid->origin[1]; ctx->unknown.oz = grid->origin[2]; ctx->unknown.res = grid->res;
-  ctx->unknown.nx = grid->dims[0]; ctx->unknown.ny = grid->dims[1]; ctx->unknown.nz = grid->dims[2];
+  fhh::set_lattice(ctx->unknown, *grid);
   return FH_OK;
 }
 
@@ -549,8 +578,8 @@ int fh_set_unknown_views_device(fh_ctx* ctx, const fh_voxel_grid* grid, const un
                                 int n_views) {
   if (!ctx) return FH_ERR_ARG;
   if (!d_flags) return fh_set_unknown_grid_device(ctx, nullptr, nullptr);
-  if (n_views < 1 || !grid || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1) return FH_ERR_ARG;
-  if (view_stride < (size_t)grid->dims[0] * (size_t)grid->dims[1] * (size_t)grid->dims[2]) {
+  if (n_views < 1 || !fhh::voxel_grid_ok(grid, false)) return FH_ERR_ARG;  // (the cell size: fh_set_unknown_grid_device below)
+  if (view_stride < (size_t)fhh::voxel_grid_cells(*grid)) {
     ctx->err = "fh_set_unknown_views_device: view_stride is smaller than a view (dims[0] * dims[1] * dims[2] bytes)";
     return FH_ERR_ARG;
   }
@@ -562,29 +591,25 @@ int fh_set_unknown_views_device(fh_ctx* ctx, const fh_voxel_grid* grid, const un
   return FH_OK;
 }
 
-int fh_request_stop(fh_ctx* ctx) {
+static int set_stop_word(fh_ctx* ctx, unsigned int value) {
   if (!ctx) return FH_ERR_ARG;
   if (ctx->device < 0 || !ctx->h_abort) return FH_ERR_DEVICE;
-  __atomic_store_n(ctx->h_abort, 1u, __ATOMIC_RELEASE);
+  __atomic_store_n(ctx->h_abort, value, __ATOMIC_RELEASE);
   return FH_OK;
 }
-
-int fh_clear_stop(fh_ctx* ctx) {
-  if (!ctx) return FH_ERR_ARG;
-  if (ctx->device < 0 || !ctx->h_abort) return FH_ERR_DEVICE;
-  __atomic_store_n(ctx->h_abort, 0u, __ATOMIC_RELEASE);
-  return FH_OK;
-}
+int fh_request_stop(fh_ctx* ctx) { return set_stop_word(ctx, 1u); }
+int fh_clear_stop(fh_ctx* ctx) { return set_stop_word(ctx, 0u); }
 
 // diagnostic builds (-DFH_SHARE_PROFILE): the 16 profile words of the last launch (ticks of the 100 MHz clock / counts)
 int fh_share_profile_read(fh_ctx* ctx, unsigned long long* out16) {
   if (!ctx || !out16) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
-  if (!ctx->d_buf[6]) return FH_ERR_ARG;
+  DeviceScope device_scope(ctx->device);
+  if (!ctx->buf[SHARE_BLOCK].ptr) return FH_ERR_ARG;
   FH_HIP(hipStreamSynchronize(ctx->stream));
   fh::ShareCtl h;
-  FH_HIP(hipMemcpy(&h, ctx->d_buf[6], sizeof(h), hipMemcpyDeviceToHost));
+  const int rc = read_share_ctl(ctx, &h, nullptr);
+  if (rc != FH_OK) return rc;
   for (int i = 0; i < 8; i++) { out16[i] = h.prof[i]; out16[8 + i] = h.prof2[i]; }
   return FH_OK;
 }
@@ -592,37 +617,32 @@ int fh_share_profile_read(fh_ctx* ctx, unsigned long long* out16) {
 int fh_share_stats_read(fh_ctx* ctx, fh_share_stats* out) {
   if (!ctx || !out) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   std::memset(out, 0, sizeof(*out));
-  if (!ctx->d_buf[6]) return FH_OK;
+  if (!ctx->buf[SHARE_BLOCK].ptr) return FH_OK;
   FH_HIP(hipStreamSynchronize(ctx->stream));
   fh::ShareCtl h;
-  FH_HIP(hipMemcpy(&h, ctx->d_buf[6], sizeof(h), hipMemcpyDeviceToHost));
+  const int rc = read_share_ctl(ctx, &h, "");  // (a copy that failed leaves the statistics zero)
   out->donated = h.report[0]; out->stolen = h.report[1]; out->queue_full = h.report[2]; out->records_full = h.report[3];
   out->records_used = std::min<unsigned>(h.report[4], FH_NRECS); out->error = h.report[5]; out->interrupted = h.report[6];
   out->workgroups = (uint32_t)ctx->last_grid;
-  ctx->launched = false;
-  if (h.report[5]) {
-    ctx->err = "solve kernel: work-sharing protocol failure (code " + std::to_string(h.report[5]) + ")";
-    return FH_ERR_DEVICE;
-  }
-  return FH_OK;
+  return rc;
 }
 
 int fh_fp64_peak(fh_ctx* ctx, double* tflops) {
   if (!ctx || !tflops) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   int rc;
   const int blocks = ctx->n_cu * 8, threads = 256, iters = 20000;
-  if ((rc = ensure(ctx, 3, sizeof(double) * (size_t)blocks * threads)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_3, sizeof(double) * (size_t)blocks * threads)) != FH_OK) return rc;
   hipEvent_t a, b;
   FH_HIP(hipEventCreate(&a));
   FH_HIP(hipEventCreate(&b));
   double best = 0;
   for (int rep = 0; rep < 4; rep++) {  // first repetition warms up clocks and code
     FH_HIP(hipEventRecord(a, ctx->stream));
-    hipLaunchKernelGGL(fh::fp64_peak_kernel, dim3((unsigned)blocks), dim3(threads), 0, ctx->stream, (double*)ctx->d_buf[3], iters, 1.0);
+    hipLaunchKernelGGL(fh::fp64_peak_kernel, dim3((unsigned)blocks), dim3(threads), 0, ctx->stream, ctx->buf[HOST_STAGE_3].as<double>(), iters, 1.0);
     FH_HIP(hipGetLastError());
     FH_HIP(hipEventRecord(b, ctx->stream));
     FH_HIP(hipEventSynchronize(b));
@@ -640,74 +660,58 @@ int fh_fp64_peak(fh_ctx* ctx, double* tflops) {
 int fh_sync(fh_ctx* ctx) {
   if (!ctx) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   FH_HIP(hipStreamSynchronize(ctx->stream));
   return check_share_error(ctx);
+}
+
+// fh_pair_rule mode 2 asks the caller's unknown voxels: refused until they have been set
+static bool unknown_ready(fh_ctx* ctx, int rule_mode) {
+  if (rule_mode != 2 || ctx->unknown.flags) return true;
+  ctx->err = "fh_pair_rule mode 2 needs the unknown voxels: fh_set_unknown_grid_device";
+  return false;
 }
 
 int fh_solve_batch_device(fh_ctx* ctx, const fh_problem* d_problems, const fh_face* d_faces, int n, int max_seg,
                           int max_faces, fh_result* d_results) {
   if (!ctx || n < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_problems || !d_results) return FH_ERR_ARG;
-  if (max_seg <= 0 || max_seg > FH_MAX_SEG) max_seg = FH_MAX_SEG;
-  if (max_faces <= 0 || max_faces > FH_MAX_FACES) max_faces = FH_MAX_FACES;
-  max_faces = (max_faces + 7) & ~7;
   fh::SolveArgs ka;
   std::memset(&ka, 0, sizeof(ka));
-  ka.n = n; ka.max_faces = max_faces;
-  if (max_seg <= 6) return launch_solve<6, false>(ctx, d_problems, d_faces, d_results, ka);
-  if (max_seg <= 10) return launch_solve<10, false>(ctx, d_problems, d_faces, d_results, ka);
-  if (max_seg <= 15) return launch_solve<15, false>(ctx, d_problems, d_faces, d_results, ka);
-  return launch_solve<FH_MAX_SEG, false>(ctx, d_problems, d_faces, d_results, ka);
+  return dispatch_solve<false>(ctx, d_problems, d_faces, d_results, n, max_seg, max_faces, ka);
 }
 
 int fh_solve_batch(fh_ctx* ctx, const fh_problem* problems, const fh_face* faces, int64_t n_faces, int n,
                    fh_result* results) {
   if (!ctx || n < 0 || n_faces < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!problems || !results || (n_faces > 0 && !faces)) return FH_ERR_ARG;
-  int max_seg = 1, max_faces = 8;
-  for (int i = 0; i < n; i++) {
-    const fh_problem& p = problems[i];
-    if (p.n_seg >= 1 && p.n_seg <= FH_MAX_SEG) max_seg = std::max(max_seg, (int)p.n_seg);
-    if (p.n_poly >= 1 && p.n_poly <= FH_MAX_POLY) {
-      const int nf = p.face_off[p.n_poly];
-      if (nf >= 0 && nf <= FH_MAX_FACES && p.face_begin >= 0) {  // (face_begin < 0: the kernel reports FH_ST_BAD_INPUT before it reads a row)
-        // the kernel cannot see n_faces: reject corridors that point outside the face array here
-        if ((int64_t)p.face_begin + nf > n_faces) {
-          ctx->err = "fh_solve_batch: problem " + std::to_string(i) + " addresses faces outside [0, n_faces)";
-          return FH_ERR_ARG;
-        }
-        max_faces = std::max(max_faces, nf);
-      }
-    }
+  const fhh::BatchScan scan = fhh::scan_batch(problems, n, n_faces);
+  if (scan.first_outside >= 0) {
+    ctx->err = "fh_solve_batch: problem " + std::to_string(scan.first_outside) + " addresses faces outside [0, n_faces)";
+    return FH_ERR_ARG;
   }
   int rc;
-  if ((rc = ensure(ctx, 0, sizeof(fh_problem) * (size_t)n)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 1, sizeof(fh_face) * (size_t)std::max<int64_t>(n_faces, 1))) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 2, sizeof(fh_result) * (size_t)n)) != FH_OK) return rc;
-  FH_HIP(hipMemcpyAsync(ctx->d_buf[0], problems, sizeof(fh_problem) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  if (n_faces > 0)
-    FH_HIP(hipMemcpyAsync(ctx->d_buf[1], faces, sizeof(fh_face) * (size_t)n_faces, hipMemcpyHostToDevice, ctx->stream));
-  rc = fh_solve_batch_device(ctx, (const fh_problem*)ctx->d_buf[0], (const fh_face*)ctx->d_buf[1], n, max_seg, max_faces,
-                             (fh_result*)ctx->d_buf[2]);
-  if (rc != FH_OK) return rc;
-  FH_HIP(hipMemcpyAsync(results, ctx->d_buf[2], sizeof(fh_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = ensure(ctx, HOST_STAGE_0, sizeof(fh_problem) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_1, sizeof(fh_face) * (size_t)std::max<int64_t>(n_faces, 1))) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_2, sizeof(fh_result) * (size_t)n)) != FH_OK) return rc;
+  fh_problem* d_problems = ctx->buf[HOST_STAGE_0].as<fh_problem>();
+  fh_face* d_faces = ctx->buf[HOST_STAGE_1].as<fh_face>();
+  fh_result* d_results = ctx->buf[HOST_STAGE_2].as<fh_result>();
+  FH_HIP(hipMemcpyAsync(d_problems, problems, sizeof(fh_problem) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (n_faces > 0) FH_HIP(hipMemcpyAsync(d_faces, faces, sizeof(fh_face) * (size_t)n_faces, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = fh_solve_batch_device(ctx, d_problems, d_faces, n, scan.max_seg, scan.max_faces, d_results)) != FH_OK) return rc;
+  FH_HIP(hipMemcpyAsync(results, d_results, sizeof(fh_result) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   // the launch's report words ride along with the results (one synchronisation for a single genNewTraj())
-  FH_HIP(hipMemcpyAsync(ctx->h_report, reinterpret_cast<unsigned char*>(ctx->d_buf[6]) + offsetof(fh::ShareCtl, report), 64,
-                        hipMemcpyDeviceToHost, ctx->stream));
+  FH_HIP(hipMemcpyAsync(ctx->h_report, ctx->buf[SHARE_BLOCK].as<unsigned char>() + offsetof(fh::ShareCtl, report), 64, hipMemcpyDeviceToHost,
+                        ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->launched = false;
-  if (ctx->h_report[5]) {
-    ctx->err = "solve kernel: work-sharing protocol failure (code " + std::to_string(ctx->h_report[5]) + "); results of the launch are incomplete";
-    return FH_ERR_DEVICE;
-  }
-  return FH_OK;
+  return share_verdict(ctx, ctx->h_report[5], INCOMPLETE);
 }
 
 int fh_solve_batch_speculative(fh_ctx* ctx, const fh_problem* problems, const fh_face* faces, int64_t n_faces, int n,
@@ -715,7 +719,7 @@ int fh_solve_batch_speculative(fh_ctx* ctx, const fh_problem* problems, const fh
   if (!ctx || n < 0 || n_faces < 0) return FH_ERR_ARG;
   if (width <= 1 || ctx->par.max_work > 0) return fh_solve_batch(ctx, problems, faces, n_faces, n, results);
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!problems || !results || (n_faces > 0 && !faces)) return FH_ERR_ARG;
   // the factors of every problem, accumulated exactly as the reference loop does (repeated += in double)
@@ -825,7 +829,7 @@ int fh_sample_batch_device(fh_ctx* ctx, const fh_problem* d_problems, const fh_r
                            fh_state* d_states, int32_t* d_counts) {
   if (!ctx || n < 0 || max_samples < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_problems || !d_results || !d_counts || (max_samples > 0 && !d_states)) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::sample_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_problems, d_results, n, max_samples,
@@ -838,23 +842,25 @@ int fh_sample_batch(fh_ctx* ctx, const fh_problem* problems, const fh_result* re
                     fh_state* states, int32_t* counts) {
   if (!ctx || n < 0 || max_samples < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!problems || !results || !counts || (max_samples > 0 && !states)) return FH_ERR_ARG;
   int rc;
   const size_t sbytes = sizeof(fh_state) * (size_t)n * (size_t)max_samples;
-  if ((rc = ensure(ctx, 0, sizeof(fh_problem) * (size_t)n)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 2, sizeof(fh_result) * (size_t)n)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 3, std::max(sbytes, (size_t)16))) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 4, sizeof(int32_t) * (size_t)n)) != FH_OK) return rc;
-  FH_HIP(hipMemcpyAsync(ctx->d_buf[0], problems, sizeof(fh_problem) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  FH_HIP(hipMemcpyAsync(ctx->d_buf[2], results, sizeof(fh_result) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  FH_HIP(hipMemsetAsync(ctx->d_buf[3], 0, std::max(sbytes, (size_t)16), ctx->stream));
-  rc = fh_sample_batch_device(ctx, (const fh_problem*)ctx->d_buf[0], (const fh_result*)ctx->d_buf[2], n, max_samples,
-                              (fh_state*)ctx->d_buf[3], (int32_t*)ctx->d_buf[4]);
-  if (rc != FH_OK) return rc;
-  if (sbytes) FH_HIP(hipMemcpyAsync(states, ctx->d_buf[3], sbytes, hipMemcpyDeviceToHost, ctx->stream));
-  FH_HIP(hipMemcpyAsync(counts, ctx->d_buf[4], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = ensure(ctx, HOST_STAGE_0, sizeof(fh_problem) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_2, sizeof(fh_result) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_3, std::max(sbytes, (size_t)16))) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_4, sizeof(int32_t) * (size_t)n)) != FH_OK) return rc;
+  fh_problem* d_problems = ctx->buf[HOST_STAGE_0].as<fh_problem>();
+  fh_result* d_results = ctx->buf[HOST_STAGE_2].as<fh_result>();
+  fh_state* d_states = ctx->buf[HOST_STAGE_3].as<fh_state>();
+  int32_t* d_counts = ctx->buf[HOST_STAGE_4].as<int32_t>();
+  FH_HIP(hipMemcpyAsync(d_problems, problems, sizeof(fh_problem) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  FH_HIP(hipMemcpyAsync(d_results, results, sizeof(fh_result) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  FH_HIP(hipMemsetAsync(d_states, 0, std::max(sbytes, (size_t)16), ctx->stream));
+  if ((rc = fh_sample_batch_device(ctx, d_problems, d_results, n, max_samples, d_states, d_counts)) != FH_OK) return rc;
+  if (sbytes) FH_HIP(hipMemcpyAsync(states, d_states, sbytes, hipMemcpyDeviceToHost, ctx->stream));
+  FH_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
   return FH_OK;
 }
@@ -871,7 +877,7 @@ __global__ void __launch_bounds__(64) dt_initial_kernel(const fh_problem* __rest
 int fh_dt_initial_batch_device(fh_ctx* ctx, const fh_problem* d_problems, int n, double* d_dt) {
   if (!ctx || n < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_problems || !d_dt) return FH_ERR_ARG;
   hipLaunchKernelGGL(dt_initial_kernel, dim3((unsigned)std::min(n, 32 * ctx->n_cu)), dim3(64), 0, ctx->stream, d_problems, n, d_dt);
@@ -882,15 +888,17 @@ int fh_dt_initial_batch_device(fh_ctx* ctx, const fh_problem* d_problems, int n,
 int fh_dt_initial_batch(fh_ctx* ctx, const fh_problem* problems, int n, double* dt) {
   if (!ctx || n < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!problems || !dt) return FH_ERR_ARG;
   int rc;
-  if ((rc = ensure(ctx, 0, sizeof(fh_problem) * (size_t)n)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 4, sizeof(double) * (size_t)n)) != FH_OK) return rc;
-  FH_HIP(hipMemcpyAsync(ctx->d_buf[0], problems, sizeof(fh_problem) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = fh_dt_initial_batch_device(ctx, (const fh_problem*)ctx->d_buf[0], n, (double*)ctx->d_buf[4])) != FH_OK) return rc;
-  FH_HIP(hipMemcpyAsync(dt, ctx->d_buf[4], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = ensure(ctx, HOST_STAGE_0, sizeof(fh_problem) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_4, sizeof(double) * (size_t)n)) != FH_OK) return rc;
+  fh_problem* d_problems = ctx->buf[HOST_STAGE_0].as<fh_problem>();
+  double* d_dt = ctx->buf[HOST_STAGE_4].as<double>();
+  FH_HIP(hipMemcpyAsync(d_problems, problems, sizeof(fh_problem) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = fh_dt_initial_batch_device(ctx, d_problems, n, d_dt)) != FH_OK) return rc;
+  FH_HIP(hipMemcpyAsync(dt, d_dt, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
   return FH_OK;
 }
@@ -899,14 +907,11 @@ int fh_pair_glue_device(fh_ctx* ctx, const fh_problem* d_whole, const fh_result*
                         int n, double r_frac, double shrink, int max_safe_poly, fh_problem* d_safe, fh_face* d_safe_faces) {
   if (!ctx || n < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_whole || !d_whole_results || !d_safe) return FH_ERR_ARG;
   if (max_safe_poly < 0 || max_safe_poly > FH_MAX_POLY || !(r_frac >= 0) || !(r_frac <= 1) || !(shrink >= 0)) return FH_ERR_ARG;
-  if (ctx->pair_rule.mode == 2 && !ctx->unknown.flags) {
-    ctx->err = "fh_pair_rule mode 2 needs the unknown voxels: fh_set_unknown_grid_device";
-    return FH_ERR_ARG;
-  }
+  if (!unknown_ready(ctx, ctx->pair_rule.mode)) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::pair_glue_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_whole,
                      d_whole_results, d_faces, n, r_frac, shrink, max_safe_poly, ctx->pair_margin, ctx->pair_rule, d_safe, d_safe_faces, ctx->unknown, ctx->views);
   FH_HIP(hipGetLastError());
@@ -918,13 +923,10 @@ int fh_append_plans_device(fh_ctx* ctx, const fh_problem* d_whole, const fh_resu
                            int32_t* d_k_safe) {
   if (!ctx || n < 0 || max_states < 0 || !(r_frac >= 0) || !(r_frac <= 1)) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_whole || !d_whole_results || !d_safe || !d_safe_results || !d_counts || (max_states > 0 && !d_plans)) return FH_ERR_ARG;
-  if (ctx->pair_rule.mode == 2 && !ctx->unknown.flags) {
-    ctx->err = "fh_pair_rule mode 2 needs the unknown voxels: fh_set_unknown_grid_device";
-    return FH_ERR_ARG;
-  }
+  if (!unknown_ready(ctx, ctx->pair_rule.mode)) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::plan_append_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_whole, d_whole_results, d_safe, d_safe_results, n,
                      r_frac, ctx->pair_rule, max_states, d_plans, d_counts, d_k_safe, ctx->unknown, ctx->views);
   FH_HIP(hipGetLastError());
@@ -935,7 +937,7 @@ int fh_next_goals_device(fh_ctx* ctx, const fh_state* d_plans, const int32_t* d_
                          fh_state* d_goals, int32_t* d_ok) {
   if (!ctx || n < 0 || max_states < 1 || ticks < 1) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_plans || !d_counts || !d_cursor || !d_goals) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::next_goal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_plans, d_counts, d_cursor, n, max_states,
@@ -949,32 +951,22 @@ int fh_solve_pairs_device(fh_ctx* ctx, const fh_problem* d_whole, const fh_face*
                           fh_face* d_safe_faces, fh_result* d_safe_results) {
   if (!ctx || n < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_whole || !d_whole_results || !d_safe || !d_safe_results) return FH_ERR_ARG;
   if (max_safe_poly < 0 || max_safe_poly > FH_MAX_POLY || !(r_frac >= 0) || !(r_frac <= 1) || !(shrink >= 0)) return FH_ERR_ARG;
-  if (ctx->pair_rule.mode == 2 && !ctx->unknown.flags) {
-    ctx->err = "fh_pair_rule mode 2 needs the unknown voxels: fh_set_unknown_grid_device";
-    return FH_ERR_ARG;
-  }
+  if (!unknown_ready(ctx, ctx->pair_rule.mode)) return FH_ERR_ARG;
   if (ctx->views.stride) {
     ctx->err = "fh_solve_pairs_device does not support unknown-voxel views (fh_set_unknown_views_device): use the staged chain, or one grid "
                "(fh_set_unknown_grid_device)";
     return FH_ERR_ARG;
   }
-  if (max_seg <= 0 || max_seg > FH_MAX_SEG) max_seg = FH_MAX_SEG;
-  if (max_faces <= 0 || max_faces > FH_MAX_FACES) max_faces = FH_MAX_FACES;
-  max_faces = (max_faces + 7) & ~7;
   fh::SolveArgs ka;
   std::memset(&ka, 0, sizeof(ka));
-  ka.n = n; ka.max_faces = max_faces;
   ka.safe = d_safe; ka.sfaces = d_safe_faces; ka.sres = d_safe_results;
   ka.r_frac = r_frac; ka.shrink = shrink; ka.max_safe_poly = max_safe_poly; ka.r_margin = ctx->pair_margin; ka.rule = ctx->pair_rule;
   ka.unknown = ctx->unknown;
-  if (max_seg <= 6) return launch_solve<6, true>(ctx, d_whole, d_faces, d_whole_results, ka);
-  if (max_seg <= 10) return launch_solve<10, true>(ctx, d_whole, d_faces, d_whole_results, ka);
-  if (max_seg <= 15) return launch_solve<15, true>(ctx, d_whole, d_faces, d_whole_results, ka);
-  return launch_solve<FH_MAX_SEG, true>(ctx, d_whole, d_faces, d_whole_results, ka);
+  return dispatch_solve<true>(ctx, d_whole, d_faces, d_whole_results, n, max_seg, max_faces, ka);
 }
 
 int fh_last_launch(const fh_ctx* ctx, fh_launch_info* out) {
@@ -992,7 +984,7 @@ int fh_timing_reset(fh_ctx* ctx) {
 int fh_timing_read(fh_ctx* ctx, double* ms, int cap) {
   if (!ctx || cap < 0 || (cap > 0 && !ms)) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   const int count = (int)(ctx->ev_used / 2);
   if (count == 0) return 0;
   FH_HIP(hipEventSynchronize(ctx->ev[ctx->ev_used - 1]));
@@ -1004,19 +996,7 @@ int fh_timing_read(fh_ctx* ctx, double* ms, int cap) {
   return count;
 }
 
-static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, const double* d_segments, int n_segments,
-                            const double local_bbox[3], double drone_radius, double z_ground, int max_faces, fh_face* d_faces, int32_t* d_counts,
-                            const fh::UnknownLattice& lat, const double* d_seg_spheres, const fh::UnknownViews& views = fh::UnknownViews{0, nullptr, 0, 0},
-                            int segs_per_query = 1);
-
-int fh_decompose_batch_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, const double* d_segments, int n_segments,
-                              const double local_bbox[3], double drone_radius, double z_ground, int max_faces, fh_face* d_faces,
-                              int32_t* d_counts) {
-  fh::UnknownLattice lat;
-  std::memset(&lat, 0, sizeof(lat));
-  return decompose_device(ctx, d_cloud_xyz, n_cloud, d_segments, n_segments, local_bbox, drone_radius, z_ground, max_faces, d_faces, d_counts, lat,
-                          nullptr);
-}
+static const fh::UnknownViews NO_VIEWS = {0, nullptr, 0, 0};
 
 // lat.on + d_seg_spheres: the unknown voxels of a grid (cells farther than sphere[3] from sphere[0..2], per segment) are points of the
 // decomposition as well, listed before the cloud (fh_safe.hip.hpp)
@@ -1025,24 +1005,24 @@ static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud,
                             const fh::UnknownLattice& lat, const double* d_seg_spheres, const fh::UnknownViews& views, int segs_per_query) {
   if (!ctx || n_cloud < 0 || n_segments < 0 || max_faces < 8 || !local_bbox) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n_segments == 0) return FH_OK;
   if (!d_segments || !d_faces || !d_counts || (n_cloud > 0 && !d_cloud_xyz)) return FH_ERR_ARG;
   if (!(local_bbox[0] > 0) || !(local_bbox[1] > 0) || !(local_bbox[2] > 0) || !(drone_radius >= 0)) return FH_ERR_ARG;
   const int grid = std::min(n_segments, ctx->n_cu * 12);  // LDS: 10.5 KB per workgroup
   int rc;
-  if ((rc = ensure(ctx, 7, sizeof(double) * (size_t)grid * (size_t)FH_DECOMP_WS_DOUBLES)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, DECOMP_WS, sizeof(double) * (size_t)grid * (size_t)FH_DECOMP_WS_DOUBLES)) != FH_OK) return rc;
   // bounding boxes of the blocks of 64 cloud points: most blocks cannot touch a segment's local box and are skipped (same results)
   double* d_blocks = nullptr;
   const int n_blocks = (n_cloud + 63) / 64;
   if (n_blocks >= 8 && ctx->sched.cloud_blocks) {
-    if ((rc = ensure(ctx, 14, sizeof(double) * 6 * (size_t)n_blocks)) != FH_OK) return rc;
-    d_blocks = (double*)ctx->d_buf[14];
+    if ((rc = ensure(ctx, CLOUD_BLOCKS, sizeof(double) * 6 * (size_t)n_blocks)) != FH_OK) return rc;
+    d_blocks = ctx->buf[CLOUD_BLOCKS].as<double>();
     hipLaunchKernelGGL(fh::cloud_blocks_kernel, dim3((unsigned)n_blocks), dim3(64), 0, ctx->stream, d_cloud_xyz, n_cloud, d_blocks);
     FH_HIP(hipGetLastError());
   }
-  if ((rc = ensure(ctx, 18, 64)) != FH_OK) return rc;
-  FH_HIP(hipMemsetAsync(ctx->d_buf[18], 0, sizeof(int), ctx->stream));  // the segment counter of this launch
+  if ((rc = ensure(ctx, SEG_COUNTER, 64)) != FH_OK) return rc;
+  FH_HIP(hipMemsetAsync(ctx->buf[SEG_COUNTER].ptr, 0, sizeof(int), ctx->stream));  // the segment counter of this launch
 #ifdef FHD_EXPERIMENT
   {
     const char* e = std::getenv("FHD_STOP_AFTER");
@@ -1051,8 +1031,8 @@ static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud,
   }
 #endif
   hipLaunchKernelGGL(fh::decomp_kernel, dim3((unsigned)grid), dim3(64), 0, ctx->stream, d_cloud_xyz, n_cloud, d_segments, n_segments,
-                     local_bbox[0], local_bbox[1], local_bbox[2], drone_radius, z_ground, max_faces, (double*)ctx->d_buf[7], d_faces,
-                     d_counts, d_blocks, lat, lat.on ? d_seg_spheres : nullptr, (int*)ctx->d_buf[18], views, segs_per_query > 0 ? segs_per_query : 1);
+                     local_bbox[0], local_bbox[1], local_bbox[2], drone_radius, z_ground, max_faces, ctx->buf[DECOMP_WS].as<double>(), d_faces,
+                     d_counts, d_blocks, lat, lat.on ? d_seg_spheres : nullptr, ctx->buf[SEG_COUNTER].as<int>(), views, segs_per_query > 0 ? segs_per_query : 1);
   FH_HIP(hipGetLastError());
 #ifdef FHD_EXPERIMENT
   if (std::getenv("FHD_HIST")) {  // (diagnostic: how long the lists of this launch were)
@@ -1067,28 +1047,39 @@ static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud,
   return FH_OK;
 }
 
+int fh_decompose_batch_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, const double* d_segments, int n_segments,
+                              const double local_bbox[3], double drone_radius, double z_ground, int max_faces, fh_face* d_faces,
+                              int32_t* d_counts) {
+  fh::UnknownLattice lat;
+  std::memset(&lat, 0, sizeof(lat));
+  return decompose_device(ctx, d_cloud_xyz, n_cloud, d_segments, n_segments, local_bbox, drone_radius, z_ground, max_faces, d_faces, d_counts, lat,
+                          nullptr, NO_VIEWS, 1);
+}
+
 int fh_decompose_batch(fh_ctx* ctx, const double* cloud_xyz, int n_cloud, const double* segments, int n_segments,
                        const double local_bbox[3], double drone_radius, double z_ground, int max_faces, fh_face* faces, int32_t* counts) {
   if (!ctx || n_cloud < 0 || n_segments < 0 || max_faces < 8) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n_segments == 0) return FH_OK;
   if (!segments || !faces || !counts || (n_cloud > 0 && !cloud_xyz)) return FH_ERR_ARG;
   int rc;
   const size_t cb = sizeof(double) * 3 * (size_t)std::max(n_cloud, 1), sb = sizeof(double) * 6 * (size_t)n_segments;
   const size_t fb = sizeof(fh_face) * (size_t)n_segments * (size_t)max_faces, nb = sizeof(int32_t) * (size_t)n_segments;
-  if ((rc = ensure(ctx, 0, cb)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 1, sb)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 3, fb)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 4, nb)) != FH_OK) return rc;
-  if (n_cloud > 0) FH_HIP(hipMemcpyAsync(ctx->d_buf[0], cloud_xyz, sizeof(double) * 3 * (size_t)n_cloud, hipMemcpyHostToDevice, ctx->stream));
-  FH_HIP(hipMemcpyAsync(ctx->d_buf[1], segments, sb, hipMemcpyHostToDevice, ctx->stream));
-  FH_HIP(hipMemsetAsync(ctx->d_buf[3], 0, fb, ctx->stream));
-  rc = fh_decompose_batch_device(ctx, (const double*)ctx->d_buf[0], n_cloud, (const double*)ctx->d_buf[1], n_segments, local_bbox,
-                                 drone_radius, z_ground, max_faces, (fh_face*)ctx->d_buf[3], (int32_t*)ctx->d_buf[4]);
+  if ((rc = ensure(ctx, HOST_STAGE_0, cb)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_1, sb)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_3, fb)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_4, nb)) != FH_OK) return rc;
+  double *d_cloud = ctx->buf[HOST_STAGE_0].as<double>(), *d_segments = ctx->buf[HOST_STAGE_1].as<double>();
+  fh_face* d_faces = ctx->buf[HOST_STAGE_3].as<fh_face>();
+  int32_t* d_counts = ctx->buf[HOST_STAGE_4].as<int32_t>();
+  if (n_cloud > 0) FH_HIP(hipMemcpyAsync(d_cloud, cloud_xyz, sizeof(double) * 3 * (size_t)n_cloud, hipMemcpyHostToDevice, ctx->stream));
+  FH_HIP(hipMemcpyAsync(d_segments, segments, sb, hipMemcpyHostToDevice, ctx->stream));
+  FH_HIP(hipMemsetAsync(d_faces, 0, fb, ctx->stream));
+  rc = fh_decompose_batch_device(ctx, d_cloud, n_cloud, d_segments, n_segments, local_bbox, drone_radius, z_ground, max_faces, d_faces, d_counts);
   if (rc != FH_OK) return rc;
-  FH_HIP(hipMemcpyAsync(faces, ctx->d_buf[3], fb, hipMemcpyDeviceToHost, ctx->stream));
-  FH_HIP(hipMemcpyAsync(counts, ctx->d_buf[4], nb, hipMemcpyDeviceToHost, ctx->stream));
+  FH_HIP(hipMemcpyAsync(faces, d_faces, fb, hipMemcpyDeviceToHost, ctx->stream));
+  FH_HIP(hipMemcpyAsync(counts, d_counts, nb, hipMemcpyDeviceToHost, ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
   return FH_OK;
 }
@@ -1148,32 +1139,48 @@ __global__ void __launch_bounds__(64) corridor_assemble_kernel(const int32_t* __
 }
 }  // namespace
 
+// The chain both corridor entry points end in, over SEGMENTS / SEG_FACES / SEG_COUNTS: the legs of every path as segments, their
+// decomposition (lat, d_seg_spheres, views: decompose_device), and the rows of every path's polytopes back to back.
+static int corridor_chain(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, const double* d_paths, const int32_t* d_n_points, int n, int max_points,
+                          int max_poly, const double local_bbox[3], double drone_radius, double z_ground, const fh::UnknownLattice& lat,
+                          const double* d_seg_spheres, const fh::UnknownViews& views, int faces_per_problem, fh_face* d_faces, int32_t* d_face_off,
+                          int32_t* d_n_poly, double* d_goal) {
+  const size_t nseg = (size_t)n * max_poly;
+  const int seg_cap = FH_MAX_FACES_POLY;
+  int rc;
+  if ((rc = ensure(ctx, SEGMENTS, sizeof(double) * 6 * nseg)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, SEG_FACES, sizeof(fh_face) * nseg * seg_cap)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, SEG_COUNTS, sizeof(int32_t) * nseg)) != FH_OK) return rc;
+  double* segments = ctx->buf[SEGMENTS].as<double>();
+  fh_face* seg_faces = ctx->buf[SEG_FACES].as<fh_face>();
+  int32_t* seg_counts = ctx->buf[SEG_COUNTS].as<int32_t>();
+  hipLaunchKernelGGL(corridor_segments_kernel, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, ctx->stream, d_paths, d_n_points, n, max_points,
+                     max_poly, segments, d_goal);
+  FH_HIP(hipGetLastError());
+  if ((rc = decompose_device(ctx, d_cloud_xyz, n_cloud, segments, (int)nseg, local_bbox, drone_radius, z_ground, seg_cap, seg_faces, seg_counts, lat,
+                             d_seg_spheres, views, max_poly)) != FH_OK)
+    return rc;
+  hipLaunchKernelGGL(corridor_assemble_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_n_points, n, max_poly, seg_cap, seg_faces, seg_counts,
+                     faces_per_problem, d_faces, d_face_off, d_n_poly);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
 int fh_corridor_batch_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, const double* d_paths, const int32_t* d_n_points, int n,
                              int max_points, int max_poly, const double local_bbox[3], double drone_radius, double z_ground,
                              int faces_per_problem, fh_face* d_faces, int32_t* d_face_off, int32_t* d_n_poly, double* d_goal) {
   if (!ctx || n < 0 || n_cloud < 0 || max_points < 2 || max_poly < 1 || max_poly > FH_MAX_POLY || faces_per_problem < 8 || !local_bbox)
     return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_paths || !d_n_points || !d_faces || !d_face_off || !d_n_poly || (n_cloud > 0 && !d_cloud_xyz)) return FH_ERR_ARG;
   const size_t nseg = (size_t)n * max_poly;
   if (nseg > (size_t)0x7fffffff) return FH_ERR_ARG;
-  const int seg_cap = FH_MAX_FACES_POLY;
-  int rc;
-  if ((rc = ensure(ctx, 10, sizeof(double) * 6 * nseg)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 11, sizeof(fh_face) * nseg * seg_cap)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 12, sizeof(int32_t) * nseg)) != FH_OK) return rc;
-  hipLaunchKernelGGL(corridor_segments_kernel, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, ctx->stream, d_paths, d_n_points, n, max_points,
-                     max_poly, (double*)ctx->d_buf[10], d_goal);
-  FH_HIP(hipGetLastError());
-  if ((rc = fh_decompose_batch_device(ctx, d_cloud_xyz, n_cloud, (const double*)ctx->d_buf[10], (int)nseg, local_bbox, drone_radius, z_ground,
-                                      seg_cap, (fh_face*)ctx->d_buf[11], (int32_t*)ctx->d_buf[12])) != FH_OK)
-    return rc;
-  hipLaunchKernelGGL(corridor_assemble_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_n_points, n, max_poly, seg_cap,
-                     (const fh_face*)ctx->d_buf[11], (const int32_t*)ctx->d_buf[12], faces_per_problem, d_faces, d_face_off, d_n_poly);
-  FH_HIP(hipGetLastError());
-  return FH_OK;
+  fh::UnknownLattice lat;
+  std::memset(&lat, 0, sizeof(lat));
+  return corridor_chain(ctx, d_cloud_xyz, n_cloud, d_paths, d_n_points, n, max_points, max_poly, local_bbox, drone_radius, z_ground, lat, nullptr,
+                        NO_VIEWS, faces_per_problem, d_faces, d_face_off, d_n_poly, d_goal);
 }
 
 // Problem records from corridors (fh_corridor_batch_device's outputs): the polytope table and xf of record i — see include/fasterhip.h.
@@ -1182,7 +1189,7 @@ int fh_corridor_problems_device(fh_ctx* ctx, const int32_t* d_n_points, const do
                                 fh_problem* d_problems) {
   if (!ctx || n < 0 || faces_per_problem < 8 || n_seg < 1 || n_seg > FH_MAX_SEG) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_n_points || !d_last_vertex || !d_goals || !d_faces || !d_face_off || !d_n_poly || !d_problems) return FH_ERR_ARG;
   if ((size_t)n * (size_t)faces_per_problem > (size_t)0x7fffffff) return FH_ERR_ARG;
@@ -1199,17 +1206,13 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
                                   double drone_radius, double z_ground, int faces_per_problem, int n_seg_safe, fh_problem* d_safe,
                                   fh_face* d_safe_faces, double* d_safe_paths, int32_t* d_safe_n_points) {
   if (!ctx || n < 0 || n_cloud < 0 || max_points < 2 || max_points > fh::SAFE_PATH_CAP || max_poly_safe < 1 || max_poly_safe > FH_MAX_POLY ||
-      faces_per_problem < 8 || !local_bbox || !grid || n_seg_safe < 1 || n_seg_safe > FH_MAX_SEG)
+      faces_per_problem < 8 || !local_bbox || !fhh::voxel_grid_ok(grid) || n_seg_safe < 1 || n_seg_safe > FH_MAX_SEG || !(r_frac >= 0) || !(r_frac <= 1))
     return FH_ERR_ARG;
-  if (!(grid->res > 0) || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1 || !(r_frac >= 0) || !(r_frac <= 1)) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_whole || !d_whole_results || !d_paths || !d_n_points || !d_goals || !d_safe || !d_safe_faces || (n_cloud > 0 && !d_cloud_xyz)) return FH_ERR_ARG;
-  if (ctx->pair_rule.mode == 2 && !ctx->unknown.flags) {
-    ctx->err = "fh_pair_rule mode 2 needs the unknown voxels: fh_set_unknown_grid_device";
-    return FH_ERR_ARG;
-  }
+  if (!unknown_ready(ctx, ctx->pair_rule.mode)) return FH_ERR_ARG;
   if ((size_t)n * (size_t)faces_per_problem > (size_t)0x7fffffff) return FH_ERR_ARG;
   if (ctx->headings && n > ctx->n_headings) {
     ctx->err = "fh_safe_corridor_batch_device: more queries than heading records attached (fh_fleet_set_headings_device)";
@@ -1222,9 +1225,10 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
                o_off = o_goal + sizeof(double) * 3 * (size_t)n, o_np = o_off + sizeof(int32_t) * 9 * (size_t)n,
                o_cnt = o_np + sizeof(int32_t) * (size_t)n, total = o_cnt + sizeof(int32_t) * (size_t)n;
   int rc;
-  if ((rc = ensure(ctx, 16, total)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 17, sizeof(double) * 4 * nseg)) != FH_OK) return rc;
-  unsigned char* base = (unsigned char*)ctx->d_buf[16];
+  if ((rc = ensure(ctx, SAFE_SCRATCH, total)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, SEG_SPHERES, sizeof(double) * 4 * nseg)) != FH_OK) return rc;
+  unsigned char* base = ctx->buf[SAFE_SCRATCH].as<unsigned char>();
+  double* seg_spheres = ctx->buf[SEG_SPHERES].as<double>();
   double* w_paths = d_safe_paths ? d_safe_paths : (double*)(base + o_paths);
   double* w_sph = (double*)(base + o_sph);
   double* w_goal = (double*)(base + o_goal);
@@ -1234,30 +1238,20 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
   hipLaunchKernelGGL(fh::safe_path_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_whole, d_whole_results, d_paths, d_n_points, n, max_points,
                      r_frac, ctx->pair_rule, max_poly_safe, d_safe, w_paths, w_np, w_sph, ctx->unknown, ctx->views, ctx->headings);
   hipLaunchKernelGGL(fh::safe_spheres_kernel, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, ctx->stream, w_sph, n, max_poly_safe,
-                     (double*)ctx->d_buf[17]);
-  FH_HIP(hipGetLastError());
-  const int seg_cap = FH_MAX_FACES_POLY;
-  if ((rc = ensure(ctx, 10, sizeof(double) * 6 * nseg)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 11, sizeof(fh_face) * nseg * seg_cap)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, 12, sizeof(int32_t) * nseg)) != FH_OK) return rc;
-  hipLaunchKernelGGL(corridor_segments_kernel, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, ctx->stream, w_paths, w_np, n, mp, max_poly_safe,
-                     (double*)ctx->d_buf[10], w_goal);
+                     seg_spheres);
   FH_HIP(hipGetLastError());
   fh::UnknownLattice lat;
-  lat.ox = grid->origin[0]; lat.oy = grid->origin[1]; lat.oz = grid->origin[2]; lat.res = grid->res;
-  lat.nx = grid->dims[0]; lat.ny = grid->dims[1]; lat.nz = grid->dims[2]; lat.on = 1;
+  fhh::set_lattice(lat, *grid);
+  lat.on = 1;
   lat.flags = nullptr;
-  if (ctx->pair_rule.mode == 2) {  // the caller's unknown voxels (the lattice of THAT grid), not the sphere model
-    lat.ox = ctx->unknown.ox; lat.oy = ctx->unknown.oy; lat.oz = ctx->unknown.oz; lat.res = ctx->unknown.res;
-    lat.nx = ctx->unknown.nx; lat.ny = ctx->unknown.ny; lat.nz = ctx->unknown.nz;
+  const bool voxels = ctx->pair_rule.mode == 2;  // the caller's unknown voxels (the lattice of THAT grid), not the sphere model
+  if (voxels) {
+    fhh::copy_lattice(lat, ctx->unknown);
     lat.flags = ctx->unknown.flags;
   }
-  if ((rc = decompose_device(ctx, d_cloud_xyz, n_cloud, (const double*)ctx->d_buf[10], (int)nseg, local_bbox, drone_radius, z_ground, seg_cap,
-                             (fh_face*)ctx->d_buf[11], (int32_t*)ctx->d_buf[12], lat, (const double*)ctx->d_buf[17],
-                             ctx->pair_rule.mode == 2 ? ctx->views : fh::UnknownViews{0, nullptr, 0, 0}, max_poly_safe)) != FH_OK)
+  if ((rc = corridor_chain(ctx, d_cloud_xyz, n_cloud, w_paths, w_np, n, mp, max_poly_safe, local_bbox, drone_radius, z_ground, lat, seg_spheres,
+                           voxels ? ctx->views : NO_VIEWS, faces_per_problem, d_safe_faces, w_off, w_npoly, w_goal)) != FH_OK)
     return rc;
-  hipLaunchKernelGGL(corridor_assemble_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, w_np, n, max_poly_safe, seg_cap,
-                     (const fh_face*)ctx->d_buf[11], (const int32_t*)ctx->d_buf[12], faces_per_problem, d_safe_faces, w_off, w_npoly);
   hipLaunchKernelGGL(fh::safe_finalize_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, w_np, w_goal, d_goals, d_safe_faces, w_off, w_npoly, n,
                      faces_per_problem, n_seg_safe, d_safe, ctx->headings);
   FH_HIP(hipGetLastError());
@@ -1273,7 +1267,7 @@ int fh_fleet_init_device(fh_ctx* ctx, const fh_fleet_params* params, const fh_st
                          fh_vehicle* d_vehicles, fh_state* d_plans) {
   if (!ctx || n < 0 || max_states < 1 || !fleet_params_ok(params)) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_states || !d_goals || !d_vehicles || !d_plans) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::fleet_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *params, d_states, d_goals, n, max_states,
@@ -1286,7 +1280,7 @@ int fh_fleet_begin_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicle
                           fh_problem* d_whole, fh_problem* d_safe, double* d_starts, double* d_goals, double* d_radius, int32_t* d_active) {
   if (!ctx || n < 0 || max_states < 1 || !fleet_params_ok(params)) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_vehicles || !d_plans || !d_whole || !d_safe || !d_starts || !d_goals || !d_radius || !d_active) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::fleet_begin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *params, d_vehicles, d_plans, n, max_states,
@@ -1300,13 +1294,10 @@ int fh_fleet_commit_device(fh_ctx* ctx, const fh_fleet_params* params, fh_vehicl
                            const fh_result* d_safe_results) {
   if (!ctx || n < 0 || max_states < 1 || !fleet_params_ok(params)) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_vehicles || !d_plans || !d_n_points || !d_whole || !d_whole_results || !d_safe || !d_safe_results) return FH_ERR_ARG;
-  if (params->rule.mode == 2 && !ctx->unknown.flags) {
-    ctx->err = "fh_pair_rule mode 2 needs the unknown voxels: fh_set_unknown_grid_device";
-    return FH_ERR_ARG;
-  }
+  if (!unknown_ready(ctx, params->rule.mode)) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::fleet_commit_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, *params, d_vehicles, d_plans, n, max_states, d_n_points,
                      d_whole, d_whole_results, d_safe, d_safe_results, ctx->unknown, ctx->views);
   FH_HIP(hipGetLastError());
@@ -1317,7 +1308,7 @@ int fh_fleet_next_goals_device(fh_ctx* ctx, fh_vehicle* d_vehicles, const fh_sta
                                fh_state* d_goals) {
   if (!ctx || n < 0 || max_states < 1 || ticks < 1) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_vehicles || !d_plans || !d_goals) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::fleet_next_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_vehicles, d_plans, n, max_states, ticks,
@@ -1335,9 +1326,8 @@ int fh_set_sense_staging(fh_ctx* ctx, int on) {
 static int fleet_sense(fh_ctx* ctx, fh_map* map, double r_sense, const fh_voxel_grid* grid, unsigned char* d_flags, size_t view_stride,
                        const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n, const fh_heading* d_headings, double th, double tv,
                        const char* who) {
-  if (!ctx || !map || n < 0 || n_views < 1 || !grid || !(r_sense > 0) || !(r_sense < 1e300)) return FH_ERR_ARG;
-  if (!(grid->res > 0) || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1) return FH_ERR_ARG;
-  const long long cells = (long long)grid->dims[0] * grid->dims[1] * grid->dims[2];
+  if (!ctx || !map || n < 0 || n_views < 1 || !fhh::voxel_grid_ok(grid) || !(r_sense > 0) || !(r_sense < 1e300)) return FH_ERR_ARG;
+  const long long cells = fhh::voxel_grid_cells(*grid);
   if (cells > (1ll << 30) || view_stride < (size_t)cells) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
   fh::SenseArgs a;
@@ -1353,12 +1343,12 @@ static int fleet_sense(fh_ctx* ctx, fh_map* map, double r_sense, const fh_voxel_
     ctx->err = std::string(who) + ": r_sense is more than 4096 cells of the map";
     return FH_ERR_ARG;
   }
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_flags || !d_vehicles) return FH_ERR_ARG;
   a.r_sense = r_sense;
-  a.ox = grid->origin[0]; a.oy = grid->origin[1]; a.oz = grid->origin[2]; a.res = grid->res;
-  a.nx = grid->dims[0]; a.ny = grid->dims[1]; a.nz = grid->dims[2]; a.n = n;
+  fhh::set_lattice(a, *grid);
+  a.n = n;
   a.flags = d_flags;
   a.views.stride = view_stride; a.views.view_of = d_view_of; a.views.n_views = n_views;
   a.occ = d_occ;
@@ -1392,7 +1382,7 @@ int fh_fleet_sense_fov_device(fh_ctx* ctx, fh_map* map, double r_sense, const fh
 int fh_fleet_heading_init_device(fh_ctx* ctx, const double* d_yaw0, int n, fh_heading* d_headings) {
   if (!ctx || n < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_headings) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::fleet_heading_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_yaw0, n, d_headings);
@@ -1411,7 +1401,7 @@ int fh_fleet_set_goals_device(fh_ctx* ctx, const fh_fleet_params* params, fh_veh
                               int n) {
   if (!ctx || n < 0 || !fleet_params_ok(params)) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_vehicles || !d_new_goals) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::fleet_set_goals_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *params, d_vehicles, d_new_goals, d_mask,
@@ -1427,7 +1417,7 @@ int fh_fleet_next_goals_yaw_device(fh_ctx* ctx, const fh_yaw_params* yaw_params,
       !(yaw_params->dc > 0) || !(yaw_params->dc < 1e300))
     return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx);
+  DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_vehicles || !d_plans || !d_headings || !d_goals || !d_goal_yaw) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::fleet_next_yaw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *yaw_params, d_vehicles, d_plans,

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/fasterhip.h"
+#include "fh_host.hpp"
 
 namespace {
 
@@ -28,8 +29,10 @@ struct PoolDev {
   int device = -1;
   fh_ctx* ctx = nullptr;
   hipStream_t stream = nullptr;
-  void* buf[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // problems, faces, results, safe problems, safe faces, safe results,
-  size_t cap[7] = {0, 0, 0, 0, 0, 0, 0};                                            // the unknown voxel flags (fh_pool_set_unknown_grid)
+  // this device's block of a job (no launch is in flight between two jobs: run_shard ends in fh_sync), and the unknown voxel flags
+  // (fh_pool_set_unknown_grid), which the context's launches read until they are set again
+  enum Buf { PROBLEMS, FACES, RESULTS, SAFE_PROBLEMS, SAFE_FACES, SAFE_RESULTS, UNKNOWN_FLAGS, N_BUFS };
+  fhh::DeviceBuffer buf[N_BUFS];
   std::string err;
   int rc = FH_OK;
 };
@@ -43,26 +46,7 @@ struct fh_pool {
 
 namespace {
 
-#define POOL_HIP(call)                                                            \
-  do {                                                                            \
-    hipError_t e__ = (call);                                                      \
-    if (e__ != hipSuccess) {                                                      \
-      d.err = std::string(#call) + ": " + hipGetErrorString(e__);                 \
-      d.rc = FH_ERR_DEVICE;                                                       \
-      return;                                                                     \
-    }                                                                             \
-  } while (0)
-
-bool grow(PoolDev& d, int slot, size_t bytes) {
-  if (bytes <= d.cap[slot]) return true;
-  if (d.buf[slot]) (void)hipFree(d.buf[slot]);
-  d.buf[slot] = nullptr;
-  d.cap[slot] = 0;
-  const size_t want = std::max(bytes, (size_t)4096);
-  if (hipMalloc(&d.buf[slot], want) != hipSuccess) return false;
-  d.cap[slot] = want;
-  return true;
-}
+#define POOL_HIP(call) FHH_HIP(call, d.err, d.rc = FH_ERR_DEVICE; return)
 
 // contiguous block partition (pairs are never split): the rule of faster_amd/shard.py::shard_range
 void shard_range(int n, int g, int G, int& lo, int& hi) {
@@ -99,40 +83,35 @@ void run_shard(fh_pool* pool, int g, const Job& job) {
   POOL_HIP(hipSetDevice(d.device));
   // this shard's rows of the face array, and its problems rebased onto them
   std::vector<fh_problem> pr(job.problems + lo, job.problems + hi);
-  int64_t f_lo = job.n_faces, f_hi = 0;
-  int max_seg = 1, max_faces = 8;
-  for (const fh_problem& p : pr) {
-    if (p.n_seg >= 1 && p.n_seg <= FH_MAX_SEG) max_seg = std::max(max_seg, (int)p.n_seg);
-    if (p.n_poly < 1 || p.n_poly > FH_MAX_POLY) continue;
-    const int nf = p.face_off[p.n_poly];
-    if (nf < 0 || nf > FH_MAX_FACES || p.face_begin < 0) continue;  // the kernel reports FH_ST_BAD_INPUT (before it reads a row)
-    if ((int64_t)p.face_begin + nf > job.n_faces) {
-      d.err = "fh_pool: a problem addresses faces outside [0, n_faces)";
-      d.rc = FH_ERR_ARG;
-      return;
-    }
-    f_lo = std::min<int64_t>(f_lo, p.face_begin);
-    f_hi = std::max<int64_t>(f_hi, (int64_t)p.face_begin + nf);
-    max_faces = std::max(max_faces, nf);
+  const fhh::BatchScan scan = fhh::scan_batch(pr.data(), m, job.n_faces);
+  if (scan.first_outside >= 0) {
+    d.err = "fh_pool: a problem addresses faces outside [0, n_faces)";
+    d.rc = FH_ERR_ARG;
+    return;
   }
-  if (f_hi < f_lo) f_lo = f_hi = 0;
+  const int64_t f_lo = scan.face_lo, f_hi = scan.face_hi;
   for (fh_problem& p : pr)
     if (p.n_poly >= 1 && p.n_poly <= FH_MAX_POLY && p.face_begin >= f_lo) p.face_begin -= (int32_t)f_lo;
   const size_t pb = sizeof(fh_problem) * (size_t)m, fb = sizeof(fh_face) * (size_t)std::max<int64_t>(f_hi - f_lo, 1), rb = sizeof(fh_result) * (size_t)m;
-  if (!grow(d, 0, pb) || !grow(d, 1, fb) || !grow(d, 2, rb) || (job.pairs && (!grow(d, 3, pb) || !grow(d, 4, fb) || !grow(d, 5, rb)))) {
-    d.err = "fh_pool: out of device memory";
-    d.rc = FH_ERR_NOMEM;
-    return;
-  }
-  POOL_HIP(hipMemcpyAsync(d.buf[0], pr.data(), pb, hipMemcpyHostToDevice, d.stream));
-  if (f_hi > f_lo) POOL_HIP(hipMemcpyAsync(d.buf[1], job.faces + f_lo, sizeof(fh_face) * (size_t)(f_hi - f_lo), hipMemcpyHostToDevice, d.stream));
+  const size_t need[6] = {pb, fb, rb, pb, fb, rb};  // (in the order of PoolDev::Buf; the safe three for pairs only)
+  for (int b = 0; b < (job.pairs ? 6 : 3); b++)
+    if (d.buf[b].reserve(need[b], d.stream) != hipSuccess) {
+      d.err = "fh_pool: out of device memory";
+      d.rc = FH_ERR_NOMEM;
+      return;
+    }
+  fh_problem *d_problems = d.buf[PoolDev::PROBLEMS].as<fh_problem>(), *d_safe = d.buf[PoolDev::SAFE_PROBLEMS].as<fh_problem>();
+  fh_face *d_faces = d.buf[PoolDev::FACES].as<fh_face>(), *d_safe_faces = d.buf[PoolDev::SAFE_FACES].as<fh_face>();
+  fh_result *d_results = d.buf[PoolDev::RESULTS].as<fh_result>(), *d_safe_results = d.buf[PoolDev::SAFE_RESULTS].as<fh_result>();
+  POOL_HIP(hipMemcpyAsync(d_problems, pr.data(), pb, hipMemcpyHostToDevice, d.stream));
+  if (f_hi > f_lo) POOL_HIP(hipMemcpyAsync(d_faces, job.faces + f_lo, sizeof(fh_face) * (size_t)(f_hi - f_lo), hipMemcpyHostToDevice, d.stream));
   int rc;
   if (job.pairs) {
-    POOL_HIP(hipMemcpyAsync(d.buf[3], job.safe_templates + lo, pb, hipMemcpyHostToDevice, d.stream));
-    rc = fh_solve_pairs_device(d.ctx, (const fh_problem*)d.buf[0], (const fh_face*)d.buf[1], m, max_seg, max_faces, job.r_frac, job.shrink,
-                               job.max_safe_poly, (fh_result*)d.buf[2], (fh_problem*)d.buf[3], (fh_face*)d.buf[4], (fh_result*)d.buf[5]);
+    POOL_HIP(hipMemcpyAsync(d_safe, job.safe_templates + lo, pb, hipMemcpyHostToDevice, d.stream));
+    rc = fh_solve_pairs_device(d.ctx, d_problems, d_faces, m, scan.max_seg, scan.max_faces, job.r_frac, job.shrink, job.max_safe_poly, d_results,
+                               d_safe, d_safe_faces, d_safe_results);
   } else {
-    rc = fh_solve_batch_device(d.ctx, (const fh_problem*)d.buf[0], (const fh_face*)d.buf[1], m, max_seg, max_faces, (fh_result*)d.buf[2]);
+    rc = fh_solve_batch_device(d.ctx, d_problems, d_faces, m, scan.max_seg, scan.max_faces, d_results);
   }
   if (rc != FH_OK) {
     d.err = fh_last_error(d.ctx);
@@ -140,13 +119,13 @@ void run_shard(fh_pool* pool, int g, const Job& job) {
     return;
   }
   // the gather: complete fh_result blocks to the host array, or into the root device's memory over xGMI
-  if (job.results) POOL_HIP(hipMemcpyAsync(job.results + lo, d.buf[2], rb, hipMemcpyDeviceToHost, d.stream));
-  if (job.pairs && job.safe_results) POOL_HIP(hipMemcpyAsync(job.safe_results + lo, d.buf[5], rb, hipMemcpyDeviceToHost, d.stream));
+  if (job.results) POOL_HIP(hipMemcpyAsync(job.results + lo, d_results, rb, hipMemcpyDeviceToHost, d.stream));
+  if (job.pairs && job.safe_results) POOL_HIP(hipMemcpyAsync(job.safe_results + lo, d_safe_results, rb, hipMemcpyDeviceToHost, d.stream));
   if (job.d_results_root) {
     const int root_dev = pool->dev[(size_t)job.root].device;
-    POOL_HIP(hipMemcpyPeerAsync(job.d_results_root + lo, root_dev, d.buf[2], d.device, rb, d.stream));
+    POOL_HIP(hipMemcpyPeerAsync(job.d_results_root + lo, root_dev, d_results, d.device, rb, d.stream));
     if (job.pairs && job.d_safe_results_root)
-      POOL_HIP(hipMemcpyPeerAsync(job.d_safe_results_root + lo, root_dev, d.buf[5], d.device, rb, d.stream));
+      POOL_HIP(hipMemcpyPeerAsync(job.d_safe_results_root + lo, root_dev, d_safe_results, d.device, rb, d.stream));
   }
   rc = fh_sync(d.ctx);
   if (rc != FH_OK) {
@@ -157,14 +136,12 @@ void run_shard(fh_pool* pool, int g, const Job& job) {
 
 int run_job(fh_pool* pool, const Job& job) {
   if (job.n == 0) return FH_OK;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
+  fhh::DeviceScope restore(pool->dev[0].device);  // (run_shard makes its device current: the caller's comes back when the job is over)
   std::vector<std::thread> threads;
   const int G = (int)pool->dev.size();
   for (int g = 1; g < G; g++) threads.emplace_back(run_shard, pool, g, std::cref(job));
   run_shard(pool, 0, job);
   for (std::thread& t : threads) t.join();
-  if (prev >= 0) (void)hipSetDevice(prev);
   for (const PoolDev& d : pool->dev)
     if (d.rc != FH_OK) {
       pool->err = "device " + std::to_string(d.device) + ": " + d.err;
@@ -190,8 +167,6 @@ int fh_pool_create(fh_pool** out, const int* devices, int n_devices) {
     return FH_ERR_DEVICE;
   }
   if (n_devices <= 0) n_devices = count;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
   for (int g = 0; g < n_devices; g++) {
     PoolDev d;
     d.device = devices ? devices[g] : g;
@@ -199,7 +174,8 @@ int fh_pool_create(fh_pool** out, const int* devices, int n_devices) {
       pool->err = "fh_pool_create: device index out of range";
       return FH_ERR_ARG;
     }
-    if (hipSetDevice(d.device) != hipSuccess || hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking) != hipSuccess) {
+    fhh::DeviceScope scope(d.device);
+    if (!scope.ok || hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking) != hipSuccess) {
       pool->err = "fh_pool_create: cannot create a stream on device " + std::to_string(d.device);
       return FH_ERR_DEVICE;
     }
@@ -217,26 +193,21 @@ int fh_pool_create(fh_pool** out, const int* devices, int n_devices) {
     for (const PoolDev& b : pool->dev)
       if (a.device != b.device) {
         int can = 0;
-        if (hipDeviceCanAccessPeer(&can, a.device, b.device) == hipSuccess && can && hipSetDevice(a.device) == hipSuccess)
-          (void)hipDeviceEnablePeerAccess(b.device, 0);
+        fhh::DeviceScope scope(a.device);
+        if (hipDeviceCanAccessPeer(&can, a.device, b.device) == hipSuccess && can && scope.ok) (void)hipDeviceEnablePeerAccess(b.device, 0);
       }
   (void)hipGetLastError();
-  if (prev >= 0) (void)hipSetDevice(prev);
   return FH_OK;
 }
 
 void fh_pool_destroy(fh_pool* pool) {
   if (!pool) return;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
   for (PoolDev& d : pool->dev) {
-    (void)hipSetDevice(d.device);
+    fhh::DeviceScope scope(d.device);
     if (d.ctx) fh_destroy(d.ctx);
-    for (int i = 0; i < 7; i++)
-      if (d.buf[i]) (void)hipFree(d.buf[i]);
+    for (fhh::DeviceBuffer& b : d.buf) b.release();
     if (d.stream) (void)hipStreamDestroy(d.stream);
   }
-  if (prev >= 0) (void)hipSetDevice(prev);
   delete pool;
 }
 
@@ -274,25 +245,23 @@ int fh_pool_set_pair_rule(fh_pool* pool, const fh_pair_rule* rule) {
 // (synchronous) and its context is told (fh_set_unknown_grid_device).  flags = NULL: none.
 int fh_pool_set_unknown_grid(fh_pool* pool, const fh_voxel_grid* grid, const unsigned char* flags) {
   if (!pool) return FH_ERR_ARG;
-  if (flags && (!grid || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1)) return FH_ERR_ARG;
+  if (flags && !fhh::voxel_grid_ok(grid, false)) return FH_ERR_ARG;  // (the cell size: fh_set_unknown_grid_device)
   for (PoolDev& d : pool->dev) {
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(d.device);
+    fhh::DeviceScope scope(d.device);
     int rc = FH_OK;
     if (!flags) {
       rc = fh_set_unknown_grid_device(d.ctx, nullptr, nullptr);
     } else {
-      const size_t bytes = (size_t)grid->dims[0] * (size_t)grid->dims[1] * (size_t)grid->dims[2];
-      // the context must not keep pointing at a buffer that grow() may free: no launch of it is running (fh_sync waits for the CONTEXT's
+      const size_t bytes = (size_t)fhh::voxel_grid_cells(*grid);
+      fhh::DeviceBuffer& d_flags = d.buf[PoolDev::UNKNOWN_FLAGS];
+      // the context must not keep pointing at a buffer that reserve() may free: no launch of it is running (fh_sync waits for the CONTEXT's
       // stream, whichever it is), it forgets the old flags first, and learns the new ones only once they are in place
       (void)fh_sync(d.ctx);
       (void)hipStreamSynchronize(d.stream);
       (void)fh_set_unknown_grid_device(d.ctx, nullptr, nullptr);
-      if (!grow(d, 6, bytes) || hipMemcpy(d.buf[6], flags, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = FH_ERR_DEVICE;
-      else rc = fh_set_unknown_grid_device(d.ctx, grid, (const unsigned char*)d.buf[6]);
+      if (d_flags.reserve(bytes, d.stream) != hipSuccess || hipMemcpy(d_flags.ptr, flags, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = FH_ERR_DEVICE;
+      else rc = fh_set_unknown_grid_device(d.ctx, grid, d_flags.as<const unsigned char>());
     }
-    if (prev >= 0) (void)hipSetDevice(prev);
     if (rc != FH_OK) {
       pool->err = "fh_pool_set_unknown_grid: device " + std::to_string(d.device);
       return rc;
