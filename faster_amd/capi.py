@@ -665,6 +665,12 @@ class Context:
         return faces, counts
 
     # ---- device-pointer entry points (raw addresses; memory owned by the caller, e.g. torch tensors) ----
+    def decompose_batch_device(self, d_cloud, n_cloud, d_segments, n_segments, max_faces, d_faces, d_counts, drone_radius=0.05, z_ground=0.0,
+                               bbox=(2.0, 2.0, 1.0)):
+        bbox = np.ascontiguousarray(bbox, dtype=np.float64)
+        self._check(lib().fh_decompose_batch_device(self._h, d_cloud, n_cloud, d_segments, n_segments, abi.ptr(bbox), float(drone_radius),
+                                                    float(z_ground), max_faces, d_faces, d_counts), "fh_decompose_batch_device")
+
     def corridor_batch_device(self, d_cloud, n_cloud, d_paths, d_n_points, n, max_points, max_poly, faces_per_problem, d_faces, d_face_off,
                               d_n_poly, d_goal=None, drone_radius=0.05, z_ground=0.0, bbox=(2.0, 2.0, 1.0)):
         bbox = np.ascontiguousarray(bbox, dtype=np.float64)

@@ -1040,8 +1040,8 @@ static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud,
     FH_HIP(hipStreamSynchronize(ctx->stream));
     FH_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(fh::fhd_hist), sizeof(h)));
     FH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(fh::fhd_hist), z, sizeof(z)));
-    std::fprintf(stderr, "FHD_HIST segments %d lattice %d | lists <=256: %llu <=1536: %llu <=16384: %llu more: %llu | points %llu cells swept %llu\n", n_segments, lat.on,
-                 h[0], h[1], h[2], h[3], h[4], h[5]);
+    std::fprintf(stderr, "FHD_HIST segments %d lattice %d | lists <=%d: %llu <=%d: %llu <=%d: %llu more: %llu | points %llu cells swept %llu\n", n_segments, lat.on,
+                 FH_DECOMP_CAP, h[0], FH_DECOMP_CAP_IDS, h[1], FH_DECOMP_CAP_GLOBAL, h[2], h[3], h[4], h[5]);
   }
 #endif
   return FH_OK;

@@ -88,7 +88,7 @@ __device__ __forceinline__ int sgn_i(double v) { return (0.0 < v) - (v < 0.0); }
 // arg-min of the ellipsoid distance over the list entries whose flag has `bit`; returns the list index (-1 if none)
 #ifdef FHD_EXPERIMENT
 __constant__ int fhd_stop_after;
-__device__ unsigned long long fhd_hist[8];  // segments whose list has <= 256, <= 1536, <= 16384, more points; sum of the counts; cells swept
+__device__ unsigned long long fhd_hist[8];  // segments whose list has <= FH_DECOMP_CAP, <= FH_DECOMP_CAP_IDS, <= FH_DECOMP_CAP_GLOBAL, more points; sum of the counts; cells swept
 #endif
 template <class L>
 __device__ __forceinline__ int closest_in(const L& list, int cnt, unsigned char bit, const Rot& R, D3 ax, D3 c, int lane) {
@@ -383,7 +383,7 @@ __global__ void __launch_bounds__(64, 3) decomp_kernel(const double* __restrict_
                                                     int32_t* __restrict__ counts, const double* __restrict__ blocks, UnknownLattice lat,
                                                     const double* __restrict__ spheres, int* __restrict__ ticket, UnknownViews views,
                                                     int segs_per_query) {
-  // the segment's list of box points: 256 inflated points (3 x 256 doubles + 256 flag bytes) or, in the same bytes, 1536 ids + flag bytes.
+  // the segment's list of box points: FH_DECOMP_CAP inflated points (3 doubles each + a flag byte) or, in the same bytes, FH_DECOMP_CAP_IDS ids + flag bytes.
   // flags: bit0 first (inside the initial sphere), bit1 inside (current loop), bit2 remain
   static_assert(FH_DECOMP_CAP_IDS % 64 == 0 && FH_DECOMP_CAP <= FH_DECOMP_CAP_IDS, "the id list aliases the coordinate list; blocks of 64 do not straddle its end");
   constexpr int LIST_DOUBLES = (FH_DECOMP_CAP_IDS / 2 > 3 * FH_DECOMP_CAP) ? FH_DECOMP_CAP_IDS / 2 : 3 * FH_DECOMP_CAP;  // ids or coordinates

@@ -520,9 +520,13 @@ def test_gpu_decomposition_edge_cases(ctx):
         keep &= np.linalg.norm(dense - (a + t[:, None] * (b - a)), axis=1) > 0.4
     dense = dense[keep]
     check(dense, path, drone_radius=0.1)
-    # the three homes of a segment's point list: coordinates in LDS (<= 256 points), ids in LDS (<= 1536), ids in the workgroup's
-    # HBM workspace (the sweep is repeated into it) — one cloud per regime, the same rows as the host every time
-    for size, lo, hi in ((600, 1, 256), (9000, 257, 1536), (45000, 1537, 16384)):
+    # the three homes of a segment's point list: coordinates in LDS (<= FH_DECOMP_CAP points), ids in LDS (<= FH_DECOMP_CAP_IDS), the
+    # first FH_DECOMP_CAP_IDS ids in LDS and the rest in the workgroup's HBM workspace (<= FH_DECOMP_CAP_GLOBAL) — one cloud per regime,
+    # the same rows as the host every time (the caps are read from the kernel's header; lists of exactly those lengths:
+    # tests/test_gpu_decomp_edges.py)
+    from decomp_edge_cases import CAP, CAP_GLOBAL, CAP_IDS
+
+    for size, lo, hi in ((600, 1, CAP), (9000, CAP + 1, CAP_IDS), (45000, CAP_IDS + 1, CAP_GLOBAL)):
         cl = rng.uniform([-2.5, -2.5, 0.0], [5.5, 3.0, 3.5], size=(size, 3))
         keep = np.ones(len(cl), bool)
         for a, b in zip(path[:-1], path[1:]):
