@@ -232,11 +232,7 @@ static int launch_solve(fh_ctx* ctx, const fh_problem* d_problems, const fh_face
     sa.look_mask = period - 1;
     ctx->last_launch.look_every = period;
   }
-#ifdef FH_NO_DEAL  // (A/B builds: every ticket is drawn)
-  sa.claims = nullptr;
-#else
-  sa.claims = grid <= FH_MAX_GRID ? block.claims() : nullptr;
-#endif
+  sa.claims = grid <= FH_MAX_GRID ? block.claims() : nullptr;  // (null: every ticket is drawn, none dealt)
   sa.whole = PAIRS ? d_problems : nullptr;
   sa.wfaces = d_faces;
   sa.safe = PAIRS ? ka.safe : nullptr;

@@ -50,13 +50,7 @@ namespace fh {
 
 // A workgroup is ONE wavefront (launch bounds 64): its LDS operations are issued and performed in program order, so what a
 // multi-wave kernel would need a barrier for only needs the compiler not to reorder the accesses.
-#ifdef FH_SYNC_BARRIER
-#define FH_SYNC() __syncthreads()
-#elif defined(FH_SYNC_ASM)
-#define FH_SYNC() asm volatile("" ::: "memory")
-#else
 #define FH_SYNC() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
-#endif
 // -DFH_PROFILE: per-phase cycle counters (s_memtime) accumulated per problem and written into the unused last
 // coefficient row of the result (diagnostic builds only; scripts/phase_profile.py).
 // a cycle stamp that the compiler does not move memory operations across (the kernel-loop probes of the diagnostic builds)
@@ -94,14 +88,6 @@ __device__ __forceinline__ unsigned long long pinned_clock() {
 #ifndef FH_REORTH_THRESHOLD
 #define FH_REORTH_THRESHOLD 0.05
 #endif
-// Tree levels (of a worker's own stack) whose snapshot tail — the parent's optimum, its multipliers and active row ids — and child
-// bounds stay in LDS instead of the HBM workspace: going back to a parent whose factor columns are still intact in LDS then costs two
-// LDS copies and no memory round trip.  N <= 6 only, where LDS does not limit the resident workgroups: at N = 10 two levels cost a
-// workgroup per CU (11 -> 10) and, measured, 3 % of the throughput — with the child bound a tree goes back to a parent 0.6 times per
-// problem and a restore is 4 k cycles; the N = 15 / 16 carves have no LDS to spare.
-#ifndef FH_TAIL_LEVELS
-#define FH_TAIL_LEVELS 0
-#endif
 // Tickets are drawn FH_TICKET_CHUNK at a time while every workgroup still has that many ahead of it (then 2, then 1), and finished
 // units are reported FH_DONE_BATCH at a time: the ticket counter and the `done` counter are single words that every workgroup of the
 // launch hits with a device-scope atomic — once per unit each, that is 65 000 same-address atomics per 3.5 ms launch, one every
@@ -115,9 +101,6 @@ __device__ __forceinline__ unsigned long long pinned_clock() {
 #endif
 #ifndef FH_TICKET_BACKLOG
 #define FH_TICKET_BACKLOG 512  // ticket frames (give_tickets) that may wait ahead of the takers (the ring has FH_QCAP = 1024 slots)
-#endif
-#ifndef FH_TAIL_LEVELS_BIG
-#define FH_TAIL_LEVELS_BIG 0
 #endif
 
 enum { K_EQ = 0, K_JBOX = 1, K_VBOX = 2, K_ABOX = 3, K_POLY = 4 };
@@ -382,9 +365,11 @@ __device__ __attribute__((noinline)) double dt_initial_exact(const PR& pr, doubl
 // with B != 0, a start or goal within 1e-30 on an axis.  What DECIDES a value is the oracle's arithmetic: MinPositiveElement, the float
 // casts, and the quadratic's roots, which are used as they come (correctly rounded sqrt and divisions, no polish).  The polished cubic
 // root can still differ from the exact path's by an ulp of the double, i.e. the float the reference stores can land on the other side
-// of a rounding boundary about once in 1e8 roots: fh_dt_initial_batch against orc_dt_initial_batch on 2.1 M problems (tests/test_gpu_round5.py)
-// and the A/B test against the FH_DT_EXACT_ONLY build (tests/test_gpu_round6.py) are statistical evidence, not a proof of bit equality —
-// include/fasterhip.h says so.  dx = 0 exactly takes the exact path, where the convention of cubic_root_of_lane applies.
+// of a rounding boundary about once in 1e8 roots.  The evidence there is: fh_dt_initial_batch against orc_dt_initial_batch on 2.1 M problems,
+// bit for bit (tests/test_gpu_round5.py, row a5: test_time_allocation_alone_on_two_million_problems) — statistical evidence against the
+// oracle, not a proof of bit equality; include/fasterhip.h says so.  No committed test compares this path with the FH_DT_EXACT_ONLY build
+// (every lane on the exact path); that build exists to make such a comparison by hand.  dx = 0 exactly takes the exact path, where the
+// convention of cubic_root_of_lane applies.
 // Lane = 4 * axis + j (an axis' candidates share a quad: their minimum is two quad permutes), nine useful lanes.
 __device__ __forceinline__ double cbrt_start(double a) {  // relative error ~1e-6
   const int e = __builtin_amdgcn_frexp_exp(a);              // a = m 2^e, |m| in [0.5, 1)
@@ -512,10 +497,7 @@ __device__ __attribute__((noinline)) void write_safe_problem(const fh_problem* w
 }
 
 // -----------------------------------------------------------------------------------------------------------------
-// NORMS_TABLE: the per-lane inverse row norms are re-read from the basis table by every scan (the build for three wavefronts per SIMD:
-// eight registers that are not spilled) instead of being kept in registers from setup_trial on (the build for two: nothing spills there,
-// and the extra loads cost the N = 15 kernel 2.4 %).  The same doubles either way.
-template <int NSEG, bool NORMS_TABLE = false>
+template <int NSEG>
 struct Solver {
   static constexpr int NX = 3 * NSEG;        // jerks of the trajectory (x space)
   static constexpr int NXP = (NX + 7) & ~7;
@@ -533,7 +515,12 @@ struct Solver {
   double *Q, *R;                                      // Q1 column major [NVP cols][S] (column c = active slot); R packed upper triangular [RPSZ]
   double *x, *z, *g, *d, *r, *u, *rinv;               // [NVP] x = the reduced unknowns y (r aliases d: only live inside the re-orthogonalisation pass)
   double *tcache, *tbnd;                              // [TC][SNAP_TAIL] snapshot tails and [TC][FH_MAX_POLY] child bounds of the first TC tree levels
-  static constexpr int TC = NSEG <= 6 ? 2 : (NSEG <= 10 ? FH_TAIL_LEVELS : FH_TAIL_LEVELS_BIG);
+  // TC: tree levels (of a worker's own stack) whose snapshot tail — the parent's optimum, its multipliers and active row ids — and child
+  // bounds stay in LDS instead of the HBM workspace: going back to a parent whose factor columns are still intact in LDS then costs two
+  // LDS copies and no memory round trip.  N <= 6 only, where LDS does not limit the resident workgroups: at N = 10 two levels cost a
+  // workgroup per CU (11 -> 10) and, measured, 3 % of the throughput — with the child bound a tree goes back to a parent 0.6 times per
+  // problem and a restore is 4 k cycles; the N = 15 / 16 carves have no LDS to spare.
+  static constexpr int TC = NSEG <= 6 ? 2 : 0;
   double* xs;                                         // [NXP] x-space scratch: Z y (compute_states), a row normal in x space (build_g)
   double* Zm;                                         // [NSEG][ZS] orthogonal basis of this N (fh_basis.hip.hpp), kept across problems
   double *Pc, *Vc, *Ac;                               // [NT*3] current states at segment starts
@@ -547,7 +534,9 @@ struct Solver {
   int* tb;                                            // [TB_WORDS] wave-uniform words that would otherwise sit in SGPRs for the whole solve
   enum { TB_B = 0, TB_PHASE = 1, TB_F = 2, TB_TRIALS = 4, TB_BASE = 5, TB_H = 7, TB_REC = 9, TB_DEPTH0 = 10, TB_KEY = 11, TB_QE = 13,
          TB_T0 = 14, TB_WORK = 16, TB_ZN = 17, TB_NEXT = 18, TB_NEXT_EI = 20, TB_NEXT_WT = 22, TB_DONE_N = 24, TB_DONE_IT = 25, TB_SAFE = 26, TB_POOL2 = 27, TB_FRESH = 29, TB_WORDS = 30 };
-                                                                 // TB_FRESH: the states and jerks in LDS / registers are those of the incumbent leaf (no node was solved since it was found)
+                                                                 // TB_FRESH: the states and jerks in LDS / registers are those of the incumbent leaf (no node was solved since it was found).  Written (qp_run, the
+                                                                 // incumbent leaf in search()), read by nothing since the epilogue that skipped the recomputation was tried and not kept (run_problem);
+                                                                 // the word and its two stores stay until a change of device code is measured: the allocation of <10, true, 3> is brittle
                                                                  // TB_POOL2 / + 1: a second range of tickets [next, end): tickets another workgroup gave away (give_tickets) while this one
                                                                  // still had some of its own; it becomes the pool when the pool is empty
                                                                  // TB_SAFE: the safe problem of the fused pair in hand — bits 0..7 the polytope of the whole corridor its corridor starts
@@ -570,30 +559,10 @@ struct Solver {
                           //   contribution of xp (per trial)
   double xpr;             // lane = (s, i) < 3 N: jerk xp of the minimum-norm solution of the final-state equalities (per trial)
   double xj;              // lane = (s, i) < 3 N: current jerk xp + (Z y) (compute_states -> scan)
-  // [r5] NORMS_TABLE: the inverse row norms of a lane's rows are re-read from the basis table (L1 / L2 resident) by every scan instead of
-  // living in 8 registers across the whole search: same values, same throughput in the three-wavefront build (A/B: 19.96 / 20.00 M
-  // pairs/s), but 112 instead of 160 B of scratch and 0.58 instead of 0.80 GB of HBM traffic per launch — the registers freed are
-  // registers not spilled at the scope of a problem.
-  const double* btab;     // the basis table of this N (uniform)
-  double ih_trial;        // 1 / h of the trial (uniform)
-  // the inverse row norms of this lane's rows (reduced space) from the table, as setup_trial computes them
-  __device__ __forceinline__ void row_norms(double& wbj_, double& wbv_, double& wba_, double& wcp_) const {
-#pragma clang fp contract(off)
-    const int lane = opaque(this->lane);
-    const double* C = btab + BT_C + (force_final ? BT_C_WORDS : 0);
-    const double* CJ = btab + BT_CJ + (force_final ? BT_CJ_WORDS : 0);
-    const int t = lane < nx ? lane / 3 : 0;
-    const int tc = lane < 4 * N ? (lane >> 2) : 0, k = lane & 3;
-    const double cj_ = CJ[t], cv_ = C[W_V * BT_C_TT + t], ca_ = C[W_A * BT_C_TT + t], cc_ = C[(k == 3 ? W_P : k) * BT_C_TT + tc + (k == 3 ? 1 : 0)];
-    const double ih = ih_trial;
-    const bool box = lane < nx;
-    wbj_ = box ? cj_ : 0.0;
-    wbv_ = box ? cv_ * (ih * ih) : 0.0;
-    wba_ = box ? ca_ * ih : 0.0;
-    wcp_ = (lane < 4 * N) ? cc_ * (ih * ih * ih) : 0.0;
-  }
   double wbj, wbv, wba, wcp;  // inverse row norms IN THE REDUCED SPACE of this lane's box rows (lane = (t, i)) and corridor rows
-                          //   (lane = (t, k)); 0: the row does not depend on y (per trial)
+                          //   (lane = (t, k)); 0: the row does not depend on y (per trial).  Tried in round 5: re-reading them from the
+                          //   basis table in every scan instead of keeping 8 registers across the search (same values; 19.96 / 20.00 M
+                          //   pairs/s in the three-wavefront build, 112 instead of 160 B of scratch), not kept: see solve_kernel
   double* bestx_g;        // [NVP] incumbent y (lane < n) in the workgroup's workspace: written when a better leaf is found, read when the problem ends or is first shared
   double cp_r[3];         // lane = (t, k): control point k of segment t at the current x (compute_states -> scan)
   int scan_f0, scan_F;    // lane = (t, k): first row and row count of the polytope segment t is assigned to (0 rows: free) (per node)
@@ -607,7 +576,7 @@ struct Solver {
   double box_ub;          // 3N j_max^2 (1 + 1e-9): no feasible trajectory costs more
   double gx2;             // |normal in jerk space|^2 of the row build_g built last
   int maxF;  // max faces of one polytope of this problem (wave-uniform trip count of the face sweeps)
-  int scan_trip;  // max faces of a polytope that a segment is ASSIGNED to in this active-set run (bind_assignment): the scan's trip count
+  int scan_trip;  // the scan's trip count (bind_assignment: maxF)
   unsigned poly_ok;  // polytopes without a violated zero-normal face (such a polytope can never hold a segment)
 #ifdef FH_PROFILE
   unsigned long long prof[24];   // 0-15: see scripts/phase_profile.py; 16 look-around + donations, 17 result write, 18 hand-off of the pair (charged to
@@ -889,12 +858,9 @@ struct Solver {
       xpr = xp;
       if (lane < NXP) xs[lane] = xp;
       c0 = wave_sum(xp * xp);
-#ifndef FH_NO_L1_BOUND
       l1 = may_end_early ? wave_sum(fabs(xp)) : 0.0;
-#endif
     }
     FH_SYNC();
-#ifndef FH_NO_EARLY_OUT
     // The cheapest trajectory that meets the final-state equalities already costs more than any trajectory inside the jerk box may
     // (|x|^2 <= 3N j_max^2, setMaxConstraints :403-405): the root of this trial is infeasible before its first active-set iteration —
     // what qp_loop finds at y = 0 with the same comparison.  Most failed trials of a whole problem (94 % on C4) and a third of a safe
@@ -904,14 +870,7 @@ struct Solver {
     // most |xp|_1 (j_max + tol).  |xp|^2 > |xp|_1 (j_max + tol) therefore refutes the trial too (by Cauchy-Schwarz never later than
     // the 2-norm test): on C4 it ends 41 % instead of 34 % of a safe problem's failed trials at y = 0 (whole: 97 % instead of 94 %), and
     // fired on none of the 10 655 feasible trials of the sample.
-#ifndef FH_EARLY_IN_SEARCH
-#ifndef FH_NO_L1_BOUND
     if (may_end_early && eq_ok && (!(c0 <= box_ub) || c0 > l1 * (jmax + tol) * (1.0 + 1e-9))) return true;
-#else
-    if (may_end_early && eq_ok && !(c0 <= box_ub)) return true;
-#endif
-#endif
-#endif
     {
       double dp, dv, da;
       moments(dp, dv, da);
@@ -919,16 +878,11 @@ struct Solver {
     }
     {  // each lane keeps the inverse norms (reduced space) of the rows it scans; they scale with h^-3 (positions), h^-2, h^-1
       const double ih = 1.0 / h;
-      if constexpr (NORMS_TABLE) {
-        btab = bt;
-        ih_trial = ih;
-      } else {
-        const bool box = lane < nx;
-        wbj = box ? cj_ : 0.0;
-        wbv = box ? cv_ * (ih * ih) : 0.0;
-        wba = box ? ca_ * ih : 0.0;
-        wcp = (lane < 4 * N) ? cc_ * (ih * ih * ih) : 0.0;
-      }
+      const bool box = lane < nx;
+      wbj = box ? cj_ : 0.0;
+      wbv = box ? cv_ * (ih * ih) : 0.0;
+      wba = box ? ca_ * ih : 0.0;
+      wcp = (lane < 4 * N) ? cc_ * (ih * ih * ih) : 0.0;
     }
     FH_SYNC();  // (xs and z are rewritten in full before they are read again)
     return false;
@@ -1007,21 +961,9 @@ struct Solver {
       v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xf, 0xf, true);
       rows4 = __builtin_amdgcn_readlane(v, 63);
     }
-#ifdef FH_SCAN_TRIP  // the trip count of this run's face sweeps: the longest row list any lane scans (0 at a root with no segment assigned).
-                     // Measured (A/B, C4): 19.4 M pairs/s with and without it — the sweeps are not what a node waits for; off by default
-    {
-      int m = scan_F;
-      m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x111, 0xf, 0xf, true));
-      m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x112, 0xf, 0xf, true));
-      m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x114, 0xf, 0xf, true));
-      m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x118, 0xf, 0xf, true));
-      m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x142, 0xf, 0xf, true));
-      m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x143, 0xf, 0xf, true));
-      scan_trip = __builtin_amdgcn_readlane(m, 63);
-    }
-#else
+    // (tried: the longest row list any lane scans in THIS run as the trip count, a wave maximum of scan_F — 19.4 M pairs/s on C4 with
+    // and without it, the sweeps are not what a node waits for; not kept)
     scan_trip = maxF;
-#endif
   }
 
   // ---- most violated inactive inequality row; violation relative to the row norm. id<0: none. ----
@@ -1035,7 +977,6 @@ struct Solver {
     bool bad = false;
     bool badb = false;  // a violated box row that does not depend on y (N < 4 only; the t = 0 rows are checked before the search)
     double wbj = this->wbj, wbv = this->wbv, wba = this->wba, wcp = this->wcp;
-    if constexpr (NORMS_TABLE) row_norms(wbj, wbv, wba, wcp);
     if (lane < nx) {
       const int t = lane / 3, i = lane - 3 * t;
       const double xv = xj;
@@ -1388,7 +1329,7 @@ struct Solver {
   // comes earlier in depth-first order than this node: the sequential search keeps the FIRST leaf of minimal cost)
   __device__ int qp_run(double ub, bool tie, int max_iters, int& iters, double& cost) {
     int it = 0;
-    if (lane == 0) tb[TB_FRESH] = 0;  // (the states of the incumbent leaf, if they were still there, are about to be overwritten)
+    if (lane == 0) tb[TB_FRESH] = 0;  // (the states of the incumbent leaf, if they were still there, are about to be overwritten; unread: see TB_FRESH)
     bind_assignment();
     const int q0 = q;
     const int st = qp_loop(ub, tie, max_iters, it, cost);
@@ -1418,24 +1359,17 @@ struct Solver {
            // mistaken for an independent one and answered with a step of 1e24.  (NaN-safe: !(cost <= ub).)
           const double xl = (lane < n) ? x[lane] : 0.0;
           cost = c0 + wave_sum(xl * xl);
-#ifndef FH_NO_L1_NODE_BOUND
           // [r5] The same certificate in the 1-norm (setup_trial has it for y = 0): the current point x* = xp + Z y* is the cheapest one that
           // satisfies the ACTIVE rows, x* = xp - sum mu_k a_k with mu >= 0 (the invariant of the dual method), so every feasible x has
           // x* . x >= |x*|^2 = cost; inside the jerk box x* . x <= |x*|_1 (j_max + tol).  cost > |x*|_1 (j_max + tol) is therefore
           // infeasible with the same conflict as the 2-norm bound, and never later (Cauchy-Schwarz): a refuted node ends iterations sooner.
           const double l1x = wave_sum(fabs(xj));
           if (!(cost <= box_ub) || cost > l1x * (jmax + tol) * (1.0 + 1e-9)) {
-#else
-          if (!(cost <= box_ub)) {
-#endif
             // Infeasible, with a certificate: the current point is the cheapest one that satisfies the ACTIVE rows (the invariant of
             // the dual method), so the active rows and the jerk box exclude each other — the conflict is the segments whose corridor
             // rows are active (box rows do not depend on any decision).
             const int al = lane < NVP ? act[lane] : 0;
             conflict = wave_or((lane < q && (al >> 24) == K_POLY) ? (1u << ((al >> 16) & 31)) : 0u);
-#ifdef FH_TRACE
-            trace_src = 3; trace_id = 0; trace_v = cost;
-#endif
             return 1;
           }
           if (cost > ub || (tie && cost == ub)) return 2;
@@ -1443,9 +1377,6 @@ struct Solver {
         bool cbad;
         scan(id, vp, cbad);
         FH_T1(3);
-#ifdef FH_TRACE
-        if (cbad) { trace_src = 1; trace_id = id; trace_v = vp; }
-#endif
         if (cbad) return 1;
         if (id < 0) return 0;  // optimal (cost: above)
       }
@@ -1488,20 +1419,10 @@ struct Solver {
           }
           conflict = wave_or((in && (al >> 24) == K_POLY) ? (1u << ((al >> 16) & 31)) : 0u) |
                      ((id >> 24) == K_POLY ? (1u << ((id >> 16) & 31)) : 0u);
-#ifdef FH_TRACE
-          trace_src = 2; trace_id = id; trace_v = vp;
-#endif
           return 1;
         }
         const double t2 = dependent ? INFINITY : vp / zz;
         const double t = fmin(t1, t2);
-#if defined(FH_TRACE) && FH_TRACE == 2
-        if (lane == 0 && trace) {
-          double* tr = trace + 6 * (trace_it % 32);
-          tr[0] = (double)trace_it; tr[1] = (double)(unsigned)id; tr[2] = vp; tr[3] = zz; tr[4] = gg; tr[5] = t1 < INFINITY ? -t1 : t2;
-        }
-        trace_it++;
-#endif
         if (lane < q) u[lane] -= t * rc;
         up += t;
         if (!dependent) {
@@ -1669,11 +1590,6 @@ struct Solver {
   // that level are infeasible for the same reason and are skipped (every complete assignment below them contains one of the
   // certificates).  Infeasible subtrees hold no leaf, so the result is unchanged; mostly-infeasible trials — the refutations that
   // dominate the hardest problems — shrink 2-6x (measured on the CPU restatement first).
-#ifdef FH_TRACE
-  double* trace;
-  int trace_src, trace_id, trace_it;
-  double trace_v;
-#endif
   int fin_solved;                      // of the problem run_problem finished last (the fused pair kernel's hand-off reads them and the
   double fin_dt;                       //   coefficient table left in the LDS of Q instead of the result record in memory)
   unsigned conflict;                   // of the node just found infeasible
@@ -2319,9 +2235,6 @@ struct Solver {
 #ifdef FH_SHARE_PROFILE
       if (c == (RES_HEAD + (FH_MAX_SEG - 1) * 12 + 8) / 2) continue;  // (diagnostic: the owner's start time, written when the problem was begun)
 #endif
-#ifdef FH_TRACE
-      if (!fin_solved && c >= RES_HEAD / 2 && c < body) continue;  // (diagnostic: the trace of an unsolved problem lives in its coefficient rows)
-#endif
       const double2 v = T2[c];
       *reinterpret_cast<double2*>(out + (c < body ? (size_t)16 * c : offsetof(fh_result, assign))) = v;
     }
@@ -2476,12 +2389,6 @@ struct Solver {
       if (lane < NSEG) assign[lane] = -1;
       // jerk-independent rows of the box: |v0| <= v_max, |a0| <= a_max (setMaxConstraints t = 0, :397-401)
       if (x0_outside_box(pr)) return FH_ST_INFEASIBLE;
-#ifdef FH_EARLY_IN_SEARCH  // (A/B: the same refutation, after the complete set-up of the trial)
-      if (eq_ok && !(c0 <= box_ub) && par.max_nodes > 0 && !(par.max_work > 0 && iters >= par.max_work)) {
-        nodes += 1;
-        return FH_ST_INFEASIBLE;
-      }
-#endif
       {
         FH_T0();
         screen_constant_rows(pr);
@@ -2592,9 +2499,7 @@ struct Solver {
         FH_T0();
         int fl = look_around(sa, local_nodes, iters);
         if (fl & 1) { status_limit = FH_ST_INTERRUPTED; break; }
-#ifndef FH_NO_GIVE_TICKETS
         if (sa.enabled) give_tickets(sa);  // the tickets this workgroup holds behind the problem in hand: not hostages of a long problem
-#endif
         // somebody is out of work: a problem that has proved hard (it already has a share record, or sa.min_nodes nodes so far)
         // gives its shallowest open frame away, and — once it is shared — the factor trials after this one, or a second frame.
         // (sa.enabled is 0 with a work cap or a MIP gap.)
@@ -2639,13 +2544,6 @@ struct Solver {
       if (st == 3) { status_limit = FH_ST_ITER_LIMIT; break; }
       carry_inf = st == 1;
       carry = conflict;
-#if defined(FH_TRACE) && FH_TRACE == 1
-      if (lane == 0 && trace && local_nodes <= 32) {  // diagnostic builds: one record per node of an UNSOLVED single-trial problem
-        double* tr = trace + 6 * (local_nodes - 1);
-        tr[0] = (double)st + 10.0 * (double)depth; tr[1] = (double)(st == 1 ? conflict : 0u); tr[2] = (double)q + 100.0 * (double)iters;
-        tr[3] = cost; tr[4] = (double)trace_src * 1e10 + (double)(unsigned)trace_id; tr[5] = trace_v;
-      }
-#endif
       if (st == 0) {
         int bseg;
         { FH_T0(); bseg = analyze(pr, entry == 0 && local_nodes == 1); FH_T1(9); }
@@ -2656,7 +2554,7 @@ struct Solver {
             best_key = cur_key;
             if (lane < n) bestx_g[lane] = x[lane];
             if (lane < N) bestassign[lane] = fullassign[lane];
-            if (lane == 0) tb[TB_FRESH] = 1;  // Pc / Vc / Ac and the jerks xj are this leaf's until the next node is solved
+            if (lane == 0) tb[TB_FRESH] = 1;  // Pc / Vc / Ac and the jerks xj are this leaf's until the next node is solved (unread: see TB_FRESH)
             FH_SYNC();
             if (rec >= 0) publish_incumbent(sa, cost);
           }
@@ -2700,8 +2598,7 @@ struct Solver {
                 m = (f < Fb && vt > m) ? vt : m;
               }
               double w = 0.0;
-              double wcp = this->wcp;
-              if constexpr (NORMS_TABLE) { double a_, b_, c_; row_norms(a_, b_, c_, wcp); }
+              const double wcp = this->wcp;
 #pragma unroll
               for (int k2 = 0; k2 < 4; k2++) {
                 const double wk = readlane_f64(wcp, 4 * sb + k2);
@@ -2782,7 +2679,7 @@ __device__ inline bool bad_corridor(const PR& pr, int face_cap) {
 // coefficient rows of a result record that a kernel built for NSEG segments writes (Solver::emit_result; fh_sched.compact_results)
 template <int NSEG>
 __device__ __forceinline__ int result_rows(const ShareArgs& sa) {
-#if defined(FH_PROFILE) || defined(FH_SHARE_PROFILE) || defined(FH_TRACE)
+#if defined(FH_PROFILE) || defined(FH_SHARE_PROFILE)
   return FH_MAX_SEG;  // (the diagnostic builds keep their numbers in the rows a problem does not use)
 #else
   return sa.compact_results ? NSEG : FH_MAX_SEG;
@@ -2835,7 +2732,6 @@ __device__ __forceinline__ bool run_problem(SV& sv, const PR& pr, const fh_face*
   }
   bool bad = interrupted;
   if (entry == 0 && !bad) bad = bad_scalars(pr, NSEG, staged ? sv.P : (int)pr.n_poly) || (staged == 0 && bad_corridor(pr, max_faces));
-#ifndef FH_NO_EARLY_FACES
   // [r6] the first 64 rows of the corridor are requested NOW — the layout has just been checked — so that they travel together with x0
   // and xf: one memory round trip for the staging of a problem instead of two (both are first touches of their lines)
   fh_face fc_first = {{0.0, 0.0, 0.0}, 0.0};
@@ -2843,7 +2739,6 @@ __device__ __forceinline__ bool run_problem(SV& sv, const PR& pr, const fh_face*
     const int nf_ = pr.n_poly ? pr.face_off[pr.n_poly] : 0;
     if (lane < nf_) fc_first = gfaces[pr.face_begin + lane];
   }
-#endif
   if (staged == 0) {
     if (lane < 9) *sv.x0_slot(lane) = x0xf;
     else if (lane < 18) sv.xfl[lane - 9] = x0xf;
@@ -2868,10 +2763,6 @@ __device__ __forceinline__ bool run_problem(SV& sv, const PR& pr, const fh_face*
     const unsigned long long t00 = ((unsigned long long)(unsigned)sv.tb[sv.TB_T0 + 1] << 32) | (unsigned)sv.tb[sv.TB_T0];
     res.coeff[FH_MAX_SEG - 1][8] = (double)(wall_ticks() - t00) / 100.0;
   }
-#endif
-#ifdef FH_TRACE
-  sv.trace = &res.coeff[0][0];
-  sv.trace_it = 0;
 #endif
   sv.N = pr.n_seg;
   sv.nx = 3 * pr.n_seg;
@@ -2914,11 +2805,7 @@ __device__ __forceinline__ bool run_problem(SV& sv, const PR& pr, const fh_face*
     for (int f0_ = 0; f0_ < nf; f0_ += 64) {
       const int f = f0_ + lane;
       bool degenerate_violated = false;
-#ifndef FH_NO_EARLY_FACES
       if (f < nf) sv.stage_face(f0_ == 0 ? fc_first : gfaces[pr.face_begin + f], par.feas_tol, f, degenerate_violated);
-#else
-      if (f < nf) sv.stage_face(gfaces[pr.face_begin + f], par.feas_tol, f, degenerate_violated);
-#endif
       if (wave_any(degenerate_violated)) {
         int pf = 0;
         for (int p = 0; p < pr.n_poly; p++) pf = (f >= pr.face_off[p]) ? p : pf;
@@ -2938,14 +2825,6 @@ __device__ __forceinline__ bool run_problem(SV& sv, const PR& pr, const fh_face*
   const double base = fmax(dt0, 2 * pr.dc);  // findDT :494-497
 #ifdef FH_PROFILE
   sv.prof[14] = pinned_clock() - tstart__ - sv.prof[0]; sv.cnt[14] = 1;
-#ifdef FH_PROFILE_ICACHE  // the same code again, now warm in the instruction cache: how much of the first call was instruction fetch?
-  {
-    const unsigned long long t2__ = __builtin_readcyclecounter();
-    const double again = dt_initial(pr, x0l, opaque(lane));
-    if (again != dt0) sv.cnt[22] += 1000;
-    sv.prof[22] = __builtin_readcyclecounter() - t2__; sv.cnt[22] += 1;
-  }
-#endif
 #endif
   // entry 0: a fresh problem, from its first factor.  entry 1: a stack frame of the tree of trial tb[TB_TRIALS] - 1 taken from the
   // queue.  entry 2: the trials of the problem from number tb[TB_TRIALS] - 1 (factor tb[TB_F]) on, taken from the queue.
@@ -2992,7 +2871,6 @@ __device__ __forceinline__ bool run_problem(SV& sv, const PR& pr, const fh_face*
     const unsigned long long ts0__ = __builtin_readcyclecounter();
 #endif
     int st;
-#ifndef FH_NO_EARLY_OUT
     // (the limits that search() tests before it opens a node keep their say: a node cap of zero, a work cap already used up)
     if (early_inf && !sv.x0_outside_box(pr) && par.max_nodes > 0 && !(par.max_work > 0 && iters >= par.max_work)) {  // the root node, refuted without an iteration
       st = FH_ST_INFEASIBLE;
@@ -3014,8 +2892,7 @@ __device__ __forceinline__ bool run_problem(SV& sv, const PR& pr, const fh_face*
         if (uniform_i32((int)stop) != 0) st = FH_ST_INTERRUPTED;
       }
     } else  // (x0 outside the v / a box: search() says so before it touches what setup_trial skipped, and counts no node)
-#endif
-    st = sv.search(pr, par, sa, ws, entry == 1 ? 1 : 0, best, nodes, iters);
+      st = sv.search(pr, par, sa, ws, entry == 1 ? 1 : 0, best, nodes, iters);
 #ifdef FH_PROFILE
     sv.prof[15] += __builtin_readcyclecounter() - ts0__; sv.cnt[15] += 1;
 #endif
@@ -3087,21 +2964,14 @@ __device__ __forceinline__ bool run_problem(SV& sv, const PR& pr, const fh_face*
 #endif
   if (solved) {  // the jerks and the states of the optimum: what the coefficient rows are made of (emit_result)
     FH_SYNC();
-    // [r6] ... which are still in LDS and registers when no node was solved after the incumbent leaf (the siblings behind it were
-    // pruned by their bounds: half of the solved problems) — the same numbers compute_states would produce again from the same y
-    // (Off by default: with the branch around compute_states the allocator of <10, true, 3> spills 49 vector registers instead of 19 — 112
-    // instead of 80 B of scratch per lane, 0.35 instead of 0.29 GB of HBM traffic per launch, rocprofv3 counters — for +0.5 % of throughput.)
-#ifdef FH_FRESH_STATES
-    const bool fresh = sv.rec < 0 && uniform_i32(sv.tb[sv.TB_FRESH]) != 0;
-#else
-    const bool fresh = false;
-#endif
-    if (!fresh) {
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // (the incumbent was stored by this wavefront: its stores are drained before they are read back)
-      if (lane < sv.NVP) sv.x[lane] = (lane < sv.n) ? sv.bestx_g[lane] : 0.0;
-      FH_SYNC();
-      sv.compute_states();
-    }
+    // The incumbent is always restored and its states recomputed.  (Tried in round 6: skipping this when no node was solved after the
+    // incumbent leaf — half of the solved problems, the same numbers are then still in LDS and registers.  With the branch around
+    // compute_states the allocator of <10, true, 3> spilled 49 vector registers instead of 19 — 112 instead of 80 B of scratch per lane,
+    // 0.35 instead of 0.29 GB of HBM traffic per launch, rocprofv3 counters — for +0.5 % of throughput; not kept.)
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // (the incumbent was stored by this wavefront: its stores are drained before they are read back)
+    if (lane < sv.NVP) sv.x[lane] = (lane < sv.n) ? sv.bestx_g[lane] : 0.0;
+    FH_SYNC();
+    sv.compute_states();
     FH_SYNC();
     if (lane < sv.NXP) sv.xs[lane] = (lane < sv.nx) ? sv.xj : 0.0;  // the jerks xp + Z y
     FH_SYNC();
@@ -3181,14 +3051,11 @@ template <int NSEG, bool PAIRS, int WPS = FH_WAVES_PER_SIMD, bool UNK = false>
 __global__ void __launch_bounds__(64, WPS) solve_kernel(const fh_problem* __restrict__ problems, const fh_face* __restrict__ faces,
                                                    fh_result* __restrict__ results, SolveArgs ka) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  // [r6] The row norms stay in registers in every build (NORMS_TABLE = false).  Round 5 re-read them from the basis table in the
-  // three-wavefront build to save eight registers; with x0 in LDS and the safe problem built on chip the allocation is a different one:
-  // the table variant has 41 spilled registers in <10, true, 3>, this one 19, and it is 1 % faster (A/B, same box: 23.15 against 22.9 M
-  // pairs/s, one launch alone 2.77 against 2.9 ms) — the loads the table variant issues in every scan wait behind every store in flight.
-#ifndef FH_NORMS_FROM_TABLE
-#define FH_NORMS_FROM_TABLE false
-#endif
-  typedef Solver<NSEG, FH_NORMS_FROM_TABLE> SolverT;
+  // [r6] The row norms stay in registers (Solver::wbj ..).  Round 5 re-read them from the basis table in the three-wavefront build to
+  // save eight registers; with x0 in LDS and the safe problem built on chip the allocation was a different one: the table variant had 41
+  // spilled registers in <10, true, 3>, this one 19, and was 1 % slower (A/B, same box: 22.9 against 23.15 M pairs/s, one launch alone 2.9
+  // against 2.77 ms) — the loads it issued in every scan waited behind every store in flight.  Not kept.
+  typedef Solver<NSEG> SolverT;
   SolverT sv;
   sv.carve(smem, ka.max_faces);
   sv.lane = threadIdx.x;
@@ -3265,9 +3132,6 @@ __global__ void __launch_bounds__(64, WPS) solve_kernel(const fh_problem* __rest
     if (entry) {
       unit = uniform_i32(sv.tb[sv.TB_B]);
       phase = uniform_i32(sv.tb[sv.TB_PHASE]);
-#ifdef FH_DEBUG_BOUNDS
-      if ((unsigned)unit >= (unsigned)ka.n || (unsigned)phase > 1u || entry > 2) { if (threadIdx.x == 0) ast(&sa.ctl->error, 103u + (unsigned)entry); break; }
-#endif
     } else if (!tickets_left) {
       break;  // every unit is done (or enough others are waiting, or sharing is off)
     } else {
@@ -3338,13 +3202,7 @@ __global__ void __launch_bounds__(64, WPS) solve_kernel(const fh_problem* __rest
       } else {
         // (the launch order was written by order_scatter_kernel before this launch began: a scalar load through the constant address space)
         typedef const __attribute__((address_space(4))) int cint_t;
-#ifdef FH_DEBUG_BOUNDS
-        if (b >= (unsigned)ka.n) { if (threadIdx.x == 0) ast(&sa.ctl->error, 101u); tickets_left = false; continue; }
-#endif
         unit = ka.order ? *(cint_t*)sv.uniform_u64((unsigned long long)(ka.order + b)) : (int)b;
-#ifdef FH_DEBUG_BOUNDS
-        if ((unsigned)unit >= (unsigned)ka.n) { if (threadIdx.x == 0) ast(&sa.ctl->error, 102u); tickets_left = false; continue; }
-#endif
         if (threadIdx.x == 0) { sv.tb[sv.TB_B] = unit; sv.tb[sv.TB_PHASE] = 0; sv.tb[sv.TB_WORK] = 0; }
       }
     }
@@ -3400,11 +3258,7 @@ __global__ void __launch_bounds__(64, WPS) solve_kernel(const fh_problem* __rest
 #endif
           unsigned long long ahead_b = 0ull, ahead_ei = 0ull, ahead_wt = 0ull;
           const int pool_end_now = uniform_i32(sv.tb[sv.TB_NEXT + 1]);
-#ifdef FH_NO_AHEAD  // (A/B builds)
-          const bool draw_ahead = false;
-#else
           const bool draw_ahead = tickets_left && uniform_i32(sv.tb[sv.TB_NEXT]) >= pool_end_now;
-#endif
           const int ahead_ch = sv.ticket_chunk(ka.n, (int)gridDim.x, pool_end_now);
           if (draw_ahead && threadIdx.x == 0) {  // issued here, stored after the hand-off
             ahead_b = aadd(&sa.ctl->ticket, (unsigned long long)ahead_ch) + (unsigned long long)(sa.claims ? sv.static_tickets(ka.n, (int)gridDim.x) : 0);
