@@ -14,7 +14,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fasterhip.h"
-#include "fh_solve.hip.hpp"  // wave reductions
+#include "fh_sample.hip.hpp"  // UnknownViews
+#include "fh_wave.hip.hpp"
 #include "fh_udiv.hpp"
 
 // every decision of the decomposition (which point is closest, on which side of a plane a point lies) must fall as on the host:
@@ -22,6 +23,8 @@
 #pragma clang fp contract(off)
 
 namespace fh {
+
+using fhw::first_lane; using fhw::wave_min; using fhw::wave_min_i32;
 
 #define FH_DECOMP_CAP 256  // points inside the local box whose (inflated) COORDINATES fit the LDS list of a segment
                             // (256: 10.5 KB of LDS, 12 workgroups per CU at 165 VGPRs — with 1024 and 4 per CU the same launches took 1.6x as long)
@@ -108,16 +111,7 @@ __device__ __forceinline__ int closest_in(const L& list, int cnt, unsigned char 
     return l2 >= 0 ? __builtin_amdgcn_readlane(anyi, l2) : -1;
   }
   // exact ties (mirror-symmetric points of a regular cloud): the lowest list index wins, as in the host's sequential scan
-  int v = best == mn ? bi : 0x7fffffff;
-#define FH_DPP_MIN_I32(ctrl, rmask)                                                   \
-  {                                                                                   \
-    const int o = __builtin_amdgcn_update_dpp(0x7fffffff, v, ctrl, rmask, 0xf, false); \
-    v = o < v ? o : v;                                                                \
-  }
-  FH_DPP_MIN_I32(0x111, 0xf) FH_DPP_MIN_I32(0x112, 0xf) FH_DPP_MIN_I32(0x114, 0xf) FH_DPP_MIN_I32(0x118, 0xf)
-  FH_DPP_MIN_I32(0x142, 0xa) FH_DPP_MIN_I32(0x143, 0xc)
-#undef FH_DPP_MIN_I32
-  return __builtin_amdgcn_readlane(v, 63);
+  return wave_min_i32(best == mn ? bi : 0x7fffffff);
 }
 
 // Unknown space as the mapper would report it — one point per voxel it has never seen — MODELLED for a batch of independent

@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(64) fleet_commit_kernel(fh_fleet_params par, f
   ug.flags = view_flags(ug.flags, vw, b);
   const int lane = threadIdx.x;
   fh_vehicle& v = vehicles[b];
-  if (!__builtin_amdgcn_readfirstlane(v.active)) return;  // the log was cleared by fleet_begin_kernel (a GOAL_REACHED vehicle: stage 0)
+  if (!uniform_i32(v.active)) return;  // the log was cleared by fleet_begin_kernel (a GOAL_REACHED vehicle: stage 0)
   const fh_problem& pw = whole[b];
   const fh_result& rw = wres[b];
   const fh_problem& ps = safe[b];
@@ -145,17 +145,17 @@ __global__ void __launch_bounds__(64) fleet_commit_kernel(fh_fleet_params par, f
   } else if (!fleet_problem_ok(pw, rw)) {
     stage = FH_FLEET_STAGE_NO_WHOLE;                         // :427-431 (a missing corridor marks the record n_seg = 0)
   } else {
-    size_w = __builtin_amdgcn_readfirstlane(sample_count(pw, rw));
+    size_w = uniform_i32(sample_count(pw, rw));
     wf = rw.factor;
     need = choose_r_index(pw, rw, 0.0, par.rule, lane, k, &ug, &iH) ? 1 : 0;  // findIndexH / findIndexR, :456-475
-    k = __builtin_amdgcn_readfirstlane(k);
-    iH = __builtin_amdgcn_readfirstlane(iH);
+    k = uniform_i32(k);
+    iH = uniform_i32(iH);
     have_safe = need && fleet_problem_ok(ps, rs);
     if (need && !have_safe) {
       stage = FH_FLEET_STAGE_NO_SAFE;                        // :529-533
     } else {
       if (have_safe) {
-        size_s = __builtin_amdgcn_readfirstlane(sample_count(ps, rs));
+        size_s = uniform_i32(sample_count(ps, rs));
         sf = rs.factor;
       }
       const int kept = v.plan_size - v.k_end_whole - 1;      // appendToPlan: the last k_end_whole + 1 states go (:617-623)
@@ -163,12 +163,12 @@ __global__ void __launch_bounds__(64) fleet_commit_kernel(fh_fleet_params par, f
       stage = total > max_states ? FH_FLEET_STAGE_OVERFLOW : FH_FLEET_STAGE_COMMITTED;
     }
   }
-  stage = __builtin_amdgcn_readfirstlane(stage);
+  stage = uniform_i32(stage);
   int new_size = 0, status = v.status;
   if (stage == FH_FLEET_STAGE_COMMITTED) {
     fh_state* base = plans + (size_t)b * (size_t)max_states;
-    const int head = __builtin_amdgcn_readfirstlane(v.plan_head);
-    const int kept = __builtin_amdgcn_readfirstlane(v.plan_size - v.k_end_whole - 1);
+    const int head = uniform_i32(v.plan_head);
+    const int kept = uniform_i32(v.plan_size - v.k_end_whole - 1);
     // the kept prefix [head, head + kept) to [0, kept): chunk c reads head + 64 c + lane and writes 64 c + lane, each state read into
     // registers before it is written (a store of chunk c never touches what chunk c + 1 reads: head + 64 (c + 1) >= 64 c + 64)
     if (head != 0)
@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(256) fleet_sense_kernel(SenseArgs a) {
   __shared__ int queue[FH_SENSE_QUEUE];
   __shared__ unsigned occ_lds[FH_SENSE_OCC_WORDS];
   __shared__ int q_count;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = uniform_i32(tid >> 6);
   if (b >= a.n) return;
   const int view = a.views.view_of ? a.views.view_of[b] : b;
   if (view < 0 || view >= a.views.n_views) return;
@@ -455,7 +455,7 @@ __global__ void __launch_bounds__(256) fleet_sense_kernel(SenseArgs a) {
       if (m) {
         int base = 0;
         if (lane == 0) base = atomicAdd(&q_count, __popcll(m));
-        base = __builtin_amdgcn_readfirstlane(base);
+        base = uniform_i32(base);
         if (cand) queue[base + __popcll(m & ((1ull << lane) - 1ull))] = cell[k];  // (drained below before it can overflow: 512 a trip)
       }
     }

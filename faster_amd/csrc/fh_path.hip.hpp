@@ -27,7 +27,9 @@
 
 #pragma clang fp contract(off)   // cell indices must equal the host's: no fused multiply-adds in the coordinate arithmetic
 
+#include "fh_sphere.hip.hpp"
 #include "fh_udiv.hpp"
+#include "fh_wave.hip.hpp"
 
 namespace fhp {
 
@@ -77,47 +79,9 @@ struct PlanArgs {
   int profile_slot;                 // FHP_PROFILE builds only (scripts/jps_phase_profile.py): which phase's cycles `expansions` receives
 };
 
-__device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
 // (cell indices are split with fhu::div, fh_udiv.hpp: on a wave-uniform index three scalar instructions instead of 45 vector ones)
-__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ int rank_in(unsigned long long m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_min_step(int v) {
-  const int o = __builtin_amdgcn_update_dpp(0x7fffffff, v, CTRL, ROW_MASK, 0xf, false);
-  return o < v ? o : v;
-}
-__device__ __forceinline__ int wave_min_i32(int v) {
-  v = dpp_min_step<0x111, 0xf>(v);
-  v = dpp_min_step<0x112, 0xf>(v);
-  v = dpp_min_step<0x114, 0xf>(v);
-  v = dpp_min_step<0x118, 0xf>(v);
-  v = dpp_min_step<0x142, 0xa>(v);
-  v = dpp_min_step<0x143, 0xc>(v);
-  return __builtin_amdgcn_readlane(v, 63);
-}
-
-// getIntersectionWithSphere (faster/src/utils.cpp:713-776) with its arithmetic: single precision, except that pow(float, 2) is a
-// double (the squares are summed in double, rounded once) and `- r * r` is a double subtraction.  The same expressions as
-// fhfront::sphere_crossing (host/corridor_frontend.hpp).
-__device__ inline void sphere_crossing(const double a_in[3], const double b_in[3], double r, const double c[3], double out[3]) {
-  auto solve = [&](const double* A, const double* B, float& disc) {
-    const float x1 = (float)A[0], y1 = (float)A[1], z1 = (float)A[2], x2 = (float)B[0], y2 = (float)B[1], z2 = (float)B[2];
-    const float x3 = (float)c[0], y3 = (float)c[1], z3 = (float)c[2];
-    const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
-    const float a = (float)((double)dx * (double)dx + (double)dy * (double)dy + (double)dz * (double)dz);
-    const float b = 2.0f * (dx * (x1 - x3) + dy * (y1 - y3) + dz * (z1 - z3));
-    const float cf = x3 * x3 + y3 * y3 + z3 * z3 + x1 * x1 + y1 * y1 + z1 * z1 - 2.0f * (x3 * x1 + y3 * y1 + z3 * z1);
-    const float cc = (float)((double)cf - r * r);
-    disc = b * b - 4.0f * a * cc;
-    const float t = (-b + sqrtf(disc)) / (2.0f * a);
-    out[0] = (double)(x1 + dx * t); out[1] = (double)(y1 + dy * t); out[2] = (double)(z1 + dz * t);
-  };
-  float disc;
-  solve(a_in, b_in, disc);
-  if (disc <= 0) solve(c, a_in, disc);
-}
+using fhw::lane_id; using fhw::rank_in; using fhw::uniform_f64; using fhw::uniform_i32; using fhw::wave_min_i32;
+using fhs::sphere_crossing;  // getIntersectionWithSphere (faster/src/utils.cpp:713-776) with its arithmetic: fh_sphere.hip.hpp
 
 // FHP_PROFILE builds: the cycles a wavefront spends in one phase of the jump point search (PlanArgs::profile_slot) are written to
 // `expansions` instead of the popped nodes.  0 pop + candidate addresses, 1 heap sift-down, 2 candidates settled from the tables,
@@ -260,15 +224,15 @@ struct Planner {
       return n;
     }
     double prev[3], a[3], b[3];
-    center(rfl(in[0]), prev);
-    center(rfl(in[1]), b);
+    center(uniform_i32(in[0]), prev);
+    center(uniform_i32(in[1]), b);
     if (lane == 0) out[0] = in[0];
     int no = 1;
     double c1 = blocked(prev, b) ? INFINITY : dist(prev, b);
     for (int i = 1; i + 1 < n; i++) {
-      const int ia = rfl(in[i]);
+      const int ia = uniform_i32(in[i]);
       center(ia, a);
-      center(rfl(in[i + 1]), b);
+      center(uniform_i32(in[i + 1]), b);
       const double dab = dist(a, b);
       const double c2 = blocked(a, b) ? INFINITY : dab;
       const double c3 = blocked(prev, b) ? INFINITY : dist(prev, b);
@@ -310,7 +274,7 @@ struct Planner {
       const double f = 0.0 + heur(s[0], s[1], s[2]);
       if (f >= 2040.0) return -2;
       const int key = (int)(f * KEY_SCALE), h2 = dist2(s[0], s[1], s[2]);
-      const int c = rfl((int)fstack[--ftop]);
+      const int c = uniform_i32((int)fstack[--ftop]);
       if (lane == 0) {
         unsigned* e = chunks + (size_t)c * CHUNK_WORDS;
         e[0] = (unsigned)key; e[64] = (unsigned)h2; e[128] = (unsigned)sid;
@@ -345,7 +309,7 @@ struct Planner {
       const int id = wave_min_i32(cand ? lid : 0x7fffffff);
       cand = cand && lid == id;
       const int wsub = __builtin_amdgcn_readlane(ls, (int)__builtin_ctzll(__ballot(cand)));  // the sub-list that holds it
-      const int whc = rfl(r_hc[wsub]);
+      const int whc = uniform_i32(r_hc[wsub]);
       const int hc = whc >> 8, cnt = whc & 255;
       // the loads of the expansion depend on `id` only: issue them now
       int cx, cy, cz;
@@ -381,7 +345,7 @@ struct Planner {
             if (tslot < 0) tslot = cc * 64 + lane;
             matches++;
           } else if (f < bf || (f == bf && (h < bh || (h == bh && eid < bi)))) { bf = f; bh = h; bi = eid; }
-          cc = rfl((int)cnext[cc]);
+          cc = uniform_i32((int)cnext[cc]);
           ccnt = 64;
         }
       }
@@ -410,7 +374,7 @@ struct Planner {
       {
         int nhc = (hc << 8) | last;
         if (last == 0) {
-          const int nhead = rfl((int)cnext[hc]);
+          const int nhead = uniform_i32((int)cnext[hc]);
           nhc = nhead >= 0 ? ((nhead << 8) | 64) : 0;
           fstack[ftop++] = (short)hc;
         }
@@ -513,12 +477,12 @@ struct Planner {
     for (;;) {
       const unsigned long long k = hk[slot];
       const CellState c = hr[slot];
-      const unsigned klo = (unsigned)rfl((int)(unsigned)k), khi = (unsigned)rfl((int)(unsigned)(k >> 32));
+      const unsigned klo = (unsigned)uniform_i32((int)(unsigned)k), khi = (unsigned)uniform_i32((int)(unsigned)(k >> 32));
       const unsigned long long ku = ((unsigned long long)khi << 32) | klo;
       if (ku == key) {
-        r.g = __hiloint2double(rfl(__double2hiint(c.g)), rfl(__double2loint(c.g)));
-        r.parent = rfl(c.parent);
-        r.stamp = (unsigned)rfl((int)c.stamp);
+        r.g = uniform_f64(c.g);
+        r.parent = uniform_i32(c.parent);
+        r.stamp = (unsigned)uniform_i32((int)c.stamp);
         present = true;
         return r;
       }
@@ -594,7 +558,7 @@ struct Planner {
         bool present;
         id = hfind_uniform(id, slot, present).parent;
       } else {
-        id = rfl(cells[id].parent);
+        id = uniform_i32(cells[id].parent);
       }
       if (id < 0) break;
     }
@@ -730,12 +694,11 @@ struct Planner {
   // ---- the heap: entry i in LDS below CAP_L, in HBM above
   // (an entry read by all lanes at once is the same in all of them: said to the compiler, what is computed from it — heap sizes,
   // positions, loop conditions — stays on the scalar unit)
-  __device__ __forceinline__ static double ufl(double v) { return __hiloint2double(rfl(__double2hiint(v)), rfl(__double2loint(v))); }
   __device__ __forceinline__ HE hget(int i) const {
     HE e;
     if (i < CAP_L) { e.id = hid[i]; e.f = hf[i]; e.g = hg[i]; }
     else { const int j = i - CAP_L; e.id = gi[j]; e.f = gf[j]; e.g = gg[j]; }
-    e.id = rfl(e.id); e.f = ufl(e.f); e.g = ufl(e.g);
+    e.id = uniform_i32(e.id); e.f = uniform_f64(e.f); e.g = uniform_f64(e.g);
     return e;
   }
   __device__ __forceinline__ void hset(int i, const HE& e) {
@@ -836,8 +799,8 @@ struct Planner {
         const int first = 2 * i + 1;
         if (first >= n) break;
         const int j = first - CAP_L, j1 = first + 1 < n ? j + 1 : j;
-        const double f0 = ufl(gf[j]), g0 = ufl(gg[j]), f1 = ufl(gf[j1]), g1 = ufl(gg[j1]);
-        const int i0 = rfl(gi[j]), i1 = rfl(gi[j1]);
+        const double f0 = uniform_f64(gf[j]), g0 = uniform_f64(gg[j]), f1 = uniform_f64(gf[j1]), g1 = uniform_f64(gg[j1]);
+        const int i0 = uniform_i32(gi[j]), i1 = uniform_i32(gi[j1]);
         const bool right = first + 1 < n && lower_fg(f0, g0, f1, g1);
         HE b;
         b.f = right ? f1 : f0; b.g = right ? g1 : g0; b.id = right ? i1 : i0;
@@ -1056,7 +1019,7 @@ struct Planner {
     int bx = cx, by = cy, bz = cz;
     if (n1 == 1) {
       for (;;) {
-        const int J = rfl(entry(code, bx, by, bz));
+        const int J = uniform_i32(entry(code, bx, by, bz));
         if (J != 0) {
           const int kend = abs(J);
           const int k0 = tube_contact(bx, by, bz, dx, dy, dz, kend), kt = goal_on_ray(bx, by, bz, dx, dy, dz);
@@ -1099,11 +1062,11 @@ struct Planner {
       b = nat(c2, 1);
     } else takes = false;
     for (;;) {
-      const int Jd = rfl(entry(code, bx, by, bz));
+      const int Jd = uniform_i32(entry(code, bx, by, bz));
       if (!cone_dirty(bx, by, bz, dx, dy, dz, Jd)) {
         int kk = 0;
-        const int st = rfl(diag_jump(bx, by, bz, dx, dy, dz, kk, Jd));
-        kk = rfl(kk);
+        const int st = uniform_i32(diag_jump(bx, by, bz, dx, dy, dz, kk, Jd));
+        kk = uniform_i32(kk);
         if (st == 0) return false;
         if (st == 1) { ox = bx + kk * dx; oy = by + kk * dy; oz = bz + kk * dz; return true; }
       }
@@ -1186,7 +1149,7 @@ struct Planner {
       if (++pops > (long long)mv.total) return FHP_LIMIT(1);  // (a cell is opened once: cannot happen)
       FHP_T(-2);
       const HE top = hget(0);
-      const int cur = rfl(top.id) & IDMASK, code = (rfl(top.id) >> 27) & 31;  // (the heap entry carries the direction the node was reached in)
+      const int cur = uniform_i32(top.id) & IDMASK, code = (uniform_i32(top.id) >> 27) & 31;  // (the heap entry carries the direction the node was reached in)
       unsigned long long ckey = 0ull;  // (hashed records: the key in the home slot of the popped cell, on its way while the heap is put in order)
       if (HASHED) ckey = hk[home(cur)];
       else if (lane == 0) cells[cur].stamp = (serial << 6) | ((unsigned)code << 1) | 1u;  // closed
@@ -1227,7 +1190,7 @@ struct Planner {
       if (cur == tid) break;
       if (HASHED) {  // closed
         unsigned cslot = home(cur);
-        const unsigned long long ku = ((unsigned long long)(unsigned)rfl((int)(unsigned)(ckey >> 32)) << 32) | (unsigned)rfl((int)(unsigned)ckey);
+        const unsigned long long ku = ((unsigned long long)(unsigned)uniform_i32((int)(unsigned)(ckey >> 32)) << 32) | (unsigned)uniform_i32((int)(unsigned)ckey);
         if (ku != (hser | (unsigned long long)(unsigned)cur)) {
           bool present;
           (void)hfind_uniform(cur, cslot, present);
@@ -1320,8 +1283,8 @@ struct Planner {
           CellState again;
           if (HASHED) again = hfind_uniform(nj, jslot, jpresent);
           else again = cells[nj];
-          const unsigned nstamp = (unsigned)rfl((int)again.stamp);
-          const double ng = __hiloint2double(rfl(__double2hiint(again.g)), rfl(__double2loint(again.g)));
+          const unsigned nstamp = (unsigned)uniform_i32((int)again.stamp);
+          const double ng = uniform_f64(again.g);
           const bool v2 = (nstamp >> 6) == serial, c2 = v2 && (nstamp & 1u);
           me.g = top.g + __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lcost), j), __builtin_amdgcn_readlane(__double2loint(lcost), j));
           if (v2 && !(me.g < ng)) continue;
@@ -1383,16 +1346,16 @@ __global__ void __launch_bounds__(64, JPS ? 5 : 3) plan_kernel(MapView mv, PlanA
   for (;;) {
     int q = 0;
     if (lane == 0) q = atomicAdd(pa.ticket, 1);
-    q = rfl(q);
+    q = uniform_i32(q);
     if (q >= pa.n) break;
-    if (pa.order) q = rfl(pa.order[q]);
+    if (pa.order) q = uniform_i32(pa.order[q]);
     double st[3], gl[3];
     for (int k = 0; k < 3; k++) { st[k] = pa.starts[3 * q + k]; gl[k] = pa.goals[3 * q + k]; }
     st[2] = fmax(st[2], 0.0);  // jps_manager.cpp:143-144
     gl[2] = fmax(gl[2], 0.0);
     pl.to_cell(st[0], st[1], st[2], pl.s);
     pl.to_cell(gl[0], gl[1], gl[2], pl.t);
-    for (int k = 0; k < 3; k++) { pl.s[k] = rfl(pl.s[k]); pl.t[k] = rfl(pl.t[k]); }
+    for (int k = 0; k < 3; k++) { pl.s[k] = uniform_i32(pl.s[k]); pl.t[k] = uniform_i32(pl.t[k]); }
     long long expansions = 0;
     int nv = 0;
 #ifdef FHP_PROFILE
@@ -1400,7 +1363,7 @@ __global__ void __launch_bounds__(64, JPS ? 5 : 3) plan_kernel(MapView mv, PlanA
     pl.prof_acc = 0;
     const long long q_t0 = (long long)__builtin_readcyclecounter();
 #endif
-    const bool live = !pa.active || rfl(pa.active[q]) != 0;
+    const bool live = !pa.active || uniform_i32(pa.active[q]) != 0;
     if (live && !pl.outside(pl.s[0], pl.s[1], pl.s[2]) && !pl.outside(pl.t[0], pl.t[1], pl.t[2])) {
       serial++;
       if (serial >= (JPS ? JPS_SERIAL_LIMIT : 0x7fffffffu)) {  // 2^31 (2^26) queries of this wavefront: its stamps start over, so its cell states are cleared first
@@ -1480,7 +1443,7 @@ __global__ void __launch_bounds__(64, JPS ? 5 : 3) plan_kernel(MapView mv, PlanA
         if (pa.max_poly > 0 && w > pa.max_poly + 1) w = pa.max_poly + 1;
         np = w > pa.max_points ? -1 : w;
       }
-      np = rfl(np);
+      np = uniform_i32(np);
     }
     if (lane == 0) {
       pa.n_points[q] = np;

@@ -16,10 +16,13 @@
 
 #include "../../include/fasterhip.h"
 #include "fh_sample.hip.hpp"
+#include "fh_sphere.hip.hpp"
 
 #pragma clang fp contract(off)  // (single- and double-precision expressions restated in numpy: the same roundings)
 
 namespace fh {
+
+using fhw::wave_min;
 
 struct P3 { double x, y, z; };
 __device__ __forceinline__ P3 p3(double x, double y, double z) { P3 r; r.x = x; r.y = y; r.z = z; return r; }
@@ -28,25 +31,12 @@ __device__ __forceinline__ double dist3(P3 a, P3 b) {
   return sqrt(dx * dx + dy * dy + dz * dz);
 }
 
-// point where the segment a -> b leaves the sphere (centre c, radius r): the reference's arithmetic (utils.cpp:713-776; the same
-// expressions as fhfront::sphere_crossing, host/corridor_frontend.hpp)
-__device__ inline P3 sphere_crossing(P3 a_in, P3 b_in, double r, P3 c) {
-  auto solve = [&](P3 A, P3 B, float& disc) {
-    const float x1 = (float)A.x, y1 = (float)A.y, z1 = (float)A.z, x2 = (float)B.x, y2 = (float)B.y, z2 = (float)B.z;
-    const float x3 = (float)c.x, y3 = (float)c.y, z3 = (float)c.z;
-    const float dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
-    const float a = (float)((double)dx * (double)dx + (double)dy * (double)dy + (double)dz * (double)dz);  // pow(float, 2) is a double
-    const float b = 2.0f * (dx * (x1 - x3) + dy * (y1 - y3) + dz * (z1 - z3));
-    const float cf = x3 * x3 + y3 * y3 + z3 * z3 + x1 * x1 + y1 * y1 + z1 * z1 - 2.0f * (x3 * x1 + y3 * y1 + z3 * z1);
-    const float cc = (float)((double)cf - r * r);                                                            // `- r * r`: a double subtraction
-    disc = b * b - 4.0f * a * cc;
-    const float t = (-b + sqrtf(disc)) / (2.0f * a);
-    return p3((double)(x1 + dx * t), (double)(y1 + dy * t), (double)(z1 + dz * t));
-  };
-  float disc;
-  const P3 first = solve(a_in, b_in, disc);
-  if (disc <= 0) return solve(c, a_in, disc);  // tangent / no crossing: the ray centre -> a
-  return first;
+// point where the segment a -> b leaves the sphere (centre c, radius r): fhs::sphere_crossing (fh_sphere.hip.hpp) on P3
+__device__ inline P3 sphere_crossing(P3 a, P3 b, double r, P3 c) {
+  const double av[3] = {a.x, a.y, a.z}, bv[3] = {b.x, b.y, b.z}, cv[3] = {c.x, c.y, c.z};
+  double out[3];
+  fhs::sphere_crossing(av, bv, r, cv, out);
+  return p3(out[0], out[1], out[2]);
 }
 
 constexpr int SAFE_PATH_CAP = 40;
@@ -81,8 +71,7 @@ __device__ inline double nearest_unknown(const UnknownGrid& ug, P3 p, int lane, 
         }
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = fmin(best, __shfl_xor(best, o));
+    best = wave_min(best);  // (no NaN reaches it: `d2 < best ? d2 : best` keeps best)
     const double d = sqrt(best);
     if (w >= wmax || d <= ((double)w + 0.5) * ug.res) return d;
     if (((double)w + 0.5) * ug.res > cap) return fmin(d, 1e300);  // every unknown voxel is farther than cap: all the caller asks
@@ -206,7 +195,7 @@ __global__ void __launch_bounds__(64) safe_path_kernel(const fh_problem* __restr
                 shorten_by(orig, no, rule.drone_radius);
               }
             }
-            no = __shfl(no, 0);
+            no = uniform_i32(no);
             break;
           }
           bool none_outside;

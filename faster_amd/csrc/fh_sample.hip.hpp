@@ -16,8 +16,11 @@
 
 #include "../../include/fasterhip.h"
 #include "fh_clock.hpp"
+#include "fh_wave.hip.hpp"
 
 namespace fh {
+
+using fhw::uniform_i32; using fhw::wave_max; using fhw::wave_min_i32_xor;
 
 // (PW / RW: anything with the members of fh_problem / fh_result that are used — the records in memory, or the views the fused pair
 // kernel builds from what its wavefront still holds in registers and LDS: ProblemView, ResultView)
@@ -41,7 +44,7 @@ __device__ __forceinline__ void eval_state(const double* c, double tau, bool las
 // The first `nwrite` samples of one trajectory (of `size`) to out[0 .. nwrite): the body of sample_kernel.  tile: [64 * 12], coef: [FH_MAX_SEG * 12] (LDS).
 __device__ inline void sample_into(const fh_problem& pr, const fh_result& rs, int size, int nwrite, fh_state* __restrict__ out, double* tile,
                                    double* coef, int lane) {
-  const int N = __builtin_amdgcn_readfirstlane(pr.n_seg);
+  const int N = uniform_i32(pr.n_seg);
   const double dt = rs.dt, DC = pr.dc;
   __syncthreads();
   for (int i = lane; i < N * 12; i += 64) coef[i] = rs.coeff[i / 12][i % 12];
@@ -52,7 +55,7 @@ __device__ inline void sample_into(const fh_problem& pr, const fh_result& rs, in
   for (int base = 0; base < nwrite; base += 64) {
     double my_t = 0;
     int my_int = 0;
-    const int lim = __builtin_amdgcn_readfirstlane((nwrite - base) < 64 ? (nwrite - base) : 64);
+    const int lim = uniform_i32((nwrite - base) < 64 ? (nwrite - base) : 64);
     for (int j = 0; j < lim; j++) {  // the reference's scalar clock, :131-135: every lane runs it and keeps its own tick
       t = t + DC;
       if (__ballot(t > knot) != 0ull) {  // wave-uniform; a real (rarely taken) branch, not two selects per tick
@@ -95,7 +98,7 @@ __global__ void __launch_bounds__(64) sample_kernel(const fh_problem* __restrict
     if (lane == 0) counts[b] = 0;
     return;
   }
-  const int size = __builtin_amdgcn_readfirstlane(sample_count(pr, rs));  // wave-uniform: scalar loop counters below
+  const int size = uniform_i32(sample_count(pr, rs));  // wave-uniform: scalar loop counters below
   if (lane == 0) counts[b] = size;
   sample_into(pr, rs, size, size < max_samples ? size : max_samples, states + (size_t)b * (size_t)max_samples, tile, coef, lane);
 }
@@ -192,31 +195,6 @@ struct ResultView {
   double dt;
   const double (*coeff)[12];  // [n_seg][12], createVars order
 };
-// max over the wavefront (DPP row_shr 1/2/4/8, row_bcast 15/31; total in lane 63), any sign
-__device__ __forceinline__ double glue_wave_max(double v) {
-  auto step = [](double x, int ctrl_sel) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    const int nlo = __double2loint(-INFINITY), nhi = __double2hiint(-INFINITY);
-    switch (ctrl_sel) {
-      case 0: lo = __builtin_amdgcn_update_dpp(nlo, lo, 0x111, 0xf, 0xf, false); hi = __builtin_amdgcn_update_dpp(nhi, hi, 0x111, 0xf, 0xf, false); break;
-      case 1: lo = __builtin_amdgcn_update_dpp(nlo, lo, 0x112, 0xf, 0xf, false); hi = __builtin_amdgcn_update_dpp(nhi, hi, 0x112, 0xf, 0xf, false); break;
-      case 2: lo = __builtin_amdgcn_update_dpp(nlo, lo, 0x114, 0xf, 0xf, false); hi = __builtin_amdgcn_update_dpp(nhi, hi, 0x114, 0xf, 0xf, false); break;
-      case 3: lo = __builtin_amdgcn_update_dpp(nlo, lo, 0x118, 0xf, 0xf, false); hi = __builtin_amdgcn_update_dpp(nhi, hi, 0x118, 0xf, 0xf, false); break;
-      case 4: lo = __builtin_amdgcn_update_dpp(nlo, lo, 0x142, 0xa, 0xf, false); hi = __builtin_amdgcn_update_dpp(nhi, hi, 0x142, 0xa, 0xf, false); break;
-      default: lo = __builtin_amdgcn_update_dpp(nlo, lo, 0x143, 0xc, 0xf, false); hi = __builtin_amdgcn_update_dpp(nhi, hi, 0x143, 0xc, 0xf, false); break;
-    }
-    return __hiloint2double(hi, lo);
-  };
-#pragma unroll
-  for (int k = 0; k < 6; k++) v = fmax(v, step(v, k));
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
 
 // Which sample of the whole trajectory is R (k_safe of Faster::replan): mode 0 sample (int)(r_frac * size); mode 1 FASTER's own rule —
 // findIndexH (faster.cpp:218-251) against the modelled unknown space, then findIndexR (:173-216).  Returns false when no safe
@@ -246,7 +224,7 @@ __device__ inline bool choose_r_index(const PW& pw, const RW& rw, double r_frac,
           if (sqrt(dx * dx + dy * dy + dz * dz) > lim) mine = i;
         }
       }
-      iH = wave_min_i32(mine);
+      iH = wave_min_i32_xor(mine);
     }
     if (iH == 0x7fffffff) {  // needToComputeSafePath == false (:462-466): the pair ends with its whole trajectory
       k = size - 1;
@@ -276,7 +254,7 @@ __device__ inline bool choose_r_index(const PW& pw, const RW& rw, double r_frac,
         }
         if (collision) mine = i;
       }
-      iR = wave_min_i32(mine);
+      iR = wave_min_i32_xor(mine);
     }
     k = iR;
   }
@@ -424,7 +402,7 @@ __device__ inline void pair_glue_one(const PW& pw, const RW& rw, const fh_face* 
     }
 #pragma unroll
     for (int p = 0; p < FH_MAX_POLY; p++)
-      if (p < P) worst_p[p] = fmax(worst_p[p], glue_wave_max(pf == p ? v : -INFINITY));
+      if (p < P) worst_p[p] = fmax(worst_p[p], wave_max(pf == p ? v : -INFINITY));
   }
   if (probe) probe[2] = __builtin_readcyclecounter();
   const int start = glue_pick_start(worst_p, P, slack_ok);
@@ -465,14 +443,14 @@ __global__ void __launch_bounds__(64) plan_append_kernel(const fh_problem* __res
   const fh_result& rw = wres[b];
   int count = 0, k = -1;
   if (rw.solved && pw.n_seg >= 1 && pw.n_seg <= FH_MAX_SEG) {
-    const int size_w = __builtin_amdgcn_readfirstlane(sample_count(pw, rw));
+    const int size_w = uniform_i32(sample_count(pw, rw));
     const bool need_safe = choose_r_index(pw, rw, r_frac, rule, lane, k, &ug);
-    k = __builtin_amdgcn_readfirstlane(k);
+    k = uniform_i32(k);
     const fh_problem& ps = safe[b];
     const fh_result& rs = sres[b];
     const bool have_safe = need_safe && rs.solved && ps.n_seg >= 1 && ps.n_seg <= FH_MAX_SEG;
     if (!need_safe || have_safe) {
-      const int size_s = have_safe ? __builtin_amdgcn_readfirstlane(sample_count(ps, rs)) : 0;
+      const int size_s = have_safe ? uniform_i32(sample_count(ps, rs)) : 0;
       count = k + 1 + size_s;
       fh_state* out = plans + (size_t)b * (size_t)max_states;
       const int nw = (k + 1) < max_states ? (k + 1) : max_states;

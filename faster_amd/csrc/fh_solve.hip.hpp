@@ -109,18 +109,10 @@ enum { W_P = 0, W_CP1 = 1, W_CP2 = 2, W_V = 3, W_A = 4, W_KINDS = 5 };
 
 __device__ __forceinline__ int mk_id(int kind, int t, int k, int f) { return (kind << 24) | (t << 16) | (k << 8) | f; }
 
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_readlane(lo, lane);
-  hi = __builtin_amdgcn_readlane(hi, lane);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double uniform_f64(double v) {
-  int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// the wave64 vocabulary (fh_wave.hip.hpp)
+using fhw::dpp_f64; using fhw::first_lane; using fhw::halves_sum; using fhw::readlane_f64; using fhw::uniform_f64;
+using fhw::uniform_i32; using fhw::vmax_f64; using fhw::vmin_f64; using fhw::wave_any; using fhw::wave_max; using fhw::wave_max_nonneg;
+using fhw::wave_min; using fhw::wave_or; using fhw::wave_sum; using fhw::wave_sum_i32;
 
 // Scheduling fences.  in_flight(a): every element of `a` (just loaded) must be in its register here, so the loads are issued
 // back to back and their LDS latencies overlap (the scheduler of this register-tight kernel otherwise serialises
@@ -158,85 +150,6 @@ __device__ __forceinline__ int opaque(int v) {
   asm volatile("" : "+v"(v));
   return v;
 }
-
-// Wave64 reductions on the DPP network (row_shr 1/2/4/8 inside each 16-lane row, then row_bcast:15 / row_bcast:31
-// across rows; the total lands in lane 63) instead of ds_bpermute round trips through the LDS crossbar.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_f64(double identity, double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(__double2loint(identity), lo, CTRL, ROW_MASK, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(__double2hiint(identity), hi, CTRL, ROW_MASK, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-// Zero-filling variant (bound_ctrl, every row written): no `old` operand to initialise.  Rows 0 and 2 pick up partial sums
-// they do not need in the row_bcast steps; only lane 63 is read, and it sees the values of before each step.
-template <int CTRL>
-__device__ __forceinline__ double dpp0_f64(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-// v_max_f64 / v_min_f64 without the canonicalising self-max the fmax/fmin lowering adds (no NaNs reach the reductions)
-__device__ __forceinline__ double vmax_f64(double a, double b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ double vmin_f64(double a, double b) {
-  double r;
-  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-// lanes l and l+32 exchange a double and add: both halves end up with the same sum (v_permlane32_swap, gfx950)
-__device__ __forceinline__ double halves_sum(double v) {
-  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-  const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
-}
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp0_f64<0x111>(v);
-  v += dpp0_f64<0x112>(v);
-  v += dpp0_f64<0x114>(v);
-  v += dpp0_f64<0x118>(v);
-  v += dpp0_f64<0x142>(v);
-  v += dpp0_f64<0x143>(v);
-  return readlane_f64(v, 63);
-}
-__device__ __forceinline__ unsigned wave_or(unsigned v) {
-  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
-  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
-  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
-  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xf, 0xf, true);
-  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xf, 0xf, true);
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-// max(0, max over the lanes): every caller only asks whether the maximum is positive and where it sits
-__device__ __forceinline__ double wave_max_nonneg(double v) {
-  v = vmax_f64(v, dpp0_f64<0x111>(v));
-  v = vmax_f64(v, dpp0_f64<0x112>(v));
-  v = vmax_f64(v, dpp0_f64<0x114>(v));
-  v = vmax_f64(v, dpp0_f64<0x118>(v));
-  v = vmax_f64(v, dpp0_f64<0x142>(v));
-  v = vmax_f64(v, dpp0_f64<0x143>(v));
-  return readlane_f64(v, 63);
-}
-__device__ __forceinline__ double wave_min(double v) {
-  v = vmin_f64(v, dpp_f64<0x111, 0xf>(INFINITY, v));
-  v = vmin_f64(v, dpp_f64<0x112, 0xf>(INFINITY, v));
-  v = vmin_f64(v, dpp_f64<0x114, 0xf>(INFINITY, v));
-  v = vmin_f64(v, dpp_f64<0x118, 0xf>(INFINITY, v));
-  v = vmin_f64(v, dpp_f64<0x142, 0xa>(INFINITY, v));
-  v = vmin_f64(v, dpp_f64<0x143, 0xc>(INFINITY, v));
-  return readlane_f64(v, 63);
-}
-__device__ __forceinline__ int first_lane(bool pred) {  // lowest lane with pred, -1 if none (uniform)
-  unsigned long long m = __ballot(pred);
-  return m ? (int)__builtin_ctzll(m) : -1;
-}
-__device__ __forceinline__ bool wave_any(bool pred) { return __ballot(pred) != 0ull; }
 
 // coefficient of jerk j_s in functional `kind` of the state at the start of segment tt, m = tt-1-s >= 0
 __device__ __forceinline__ double wcoef(int kind, int m, double h) {
@@ -951,16 +864,7 @@ struct Solver {
     const int p = live ? assign[lane >> 2] : -1;
     scan_f0 = p >= 0 ? face_off[p] : 0;
     scan_F = p >= 0 ? face_off[p + 1] - scan_f0 : 0;
-    {  // flop accounting: rows x control points scanned per iteration of this run (integer sum over the lanes)
-      int v = scan_F;
-      v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
-      v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-      v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-      v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-      v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xf, 0xf, true);
-      v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xf, 0xf, true);
-      rows4 = __builtin_amdgcn_readlane(v, 63);
-    }
+    rows4 = wave_sum_i32(scan_F);  // flop accounting: rows x control points scanned per iteration of this run
     // (tried: the longest row list any lane scans in THIS run as the trip count, a wave maximum of scan_F — 19.4 M pairs/s on C4 with
     // and without it, the sweeps are not what a node waits for; not kept)
     scan_trip = maxF;
@@ -2308,7 +2212,7 @@ struct Solver {
         for (int p = 1; p < Pw; p++) pf += (f >= face_off[p]) ? 1 : 0;
       }
       for (int p = 0; p < Pw; p++) {
-        const double m = glue_wave_max(pf == p ? v : -INFINITY);
+        const double m = wave_max(pf == p ? v : -INFINITY);
         worst = lane == p ? fmax(worst, m) : worst;
       }
     }

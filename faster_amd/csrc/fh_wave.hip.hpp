@@ -1,0 +1,129 @@
+// fh_wave.hip.hpp — the wave64 vocabulary of the device code (gfx950): lane numbers, wave-uniform values, reductions over the 64
+// lanes of a wavefront.  The one place where the cross-lane builtins are spelled out (tests/test_wave_primitives_home.py); every
+// other device header names what it uses with `using fhw::...`.
+// Includes nothing of the project: fh_path.hip.hpp is compiled into fh_map.hip without the fh headers.  Sets no file-level pragma
+// and tests no macro: what is included after it is compiled as if this header were not there.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace fhw {
+
+__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+// how many lanes below this one have their bit set in m (the slot of a lane in a ballot compaction)
+__device__ __forceinline__ int rank_in(unsigned long long m) {
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+__device__ __forceinline__ int first_lane(bool pred) {  // lowest lane with pred, -1 if none (uniform)
+  unsigned long long m = __ballot(pred);
+  return m ? (int)__builtin_ctzll(m) : -1;
+}
+__device__ __forceinline__ bool wave_any(bool pred) { return __ballot(pred) != 0ull; }
+
+// the value of the first active lane, in scalar registers (v_readfirstlane): sizes, positions and loop conditions read by all lanes
+__device__ __forceinline__ int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ double uniform_f64(double v) {
+  int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+  int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_readlane(lo, lane);
+  hi = __builtin_amdgcn_readlane(hi, lane);
+  return __hiloint2double(hi, lo);
+}
+
+// Wave64 reductions on the DPP network (row_shr 1/2/4/8 inside each 16-lane row, then row_bcast:15 / row_bcast:31
+// across rows; the total lands in lane 63) instead of ds_bpermute round trips through the LDS crossbar.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_f64(double identity, double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_update_dpp(__double2loint(identity), lo, CTRL, ROW_MASK, 0xf, false);
+  hi = __builtin_amdgcn_update_dpp(__double2hiint(identity), hi, CTRL, ROW_MASK, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+// Zero-filling variant (bound_ctrl, every row written): no `old` operand to initialise.  Rows 0 and 2 pick up partial sums
+// they do not need in the row_bcast steps; only lane 63 is read, and it sees the values of before each step.
+template <int CTRL>
+__device__ __forceinline__ double dpp0_f64(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
+  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+template <int CTRL>
+__device__ __forceinline__ int dpp0_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+// v_max_f64 / v_min_f64 without the canonicalising self-max the fmax/fmin lowering adds (no NaNs reach the reductions)
+__device__ __forceinline__ double vmax_f64(double a, double b) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ double vmin_f64(double a, double b) {
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// lanes l and l+32 exchange a double and add: both halves end up with the same sum (v_permlane32_swap, gfx950)
+__device__ __forceinline__ double halves_sum(double v) {
+  const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+  const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  return __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
+}
+__device__ __forceinline__ double wave_sum(double v) {
+  v += dpp0_f64<0x111>(v); v += dpp0_f64<0x112>(v); v += dpp0_f64<0x114>(v); v += dpp0_f64<0x118>(v);  // inside each row of 16 lanes
+  v += dpp0_f64<0x142>(v); v += dpp0_f64<0x143>(v);  // across the rows
+  return readlane_f64(v, 63);
+}
+__device__ __forceinline__ int wave_sum_i32(int v) {
+  v += dpp0_i32<0x111>(v); v += dpp0_i32<0x112>(v); v += dpp0_i32<0x114>(v); v += dpp0_i32<0x118>(v);  // inside each row of 16 lanes
+  v += dpp0_i32<0x142>(v); v += dpp0_i32<0x143>(v);  // across the rows
+  return __builtin_amdgcn_readlane(v, 63);
+}
+__device__ __forceinline__ unsigned wave_or(unsigned v) {
+  v |= (unsigned)dpp0_i32<0x111>((int)v); v |= (unsigned)dpp0_i32<0x112>((int)v);  // inside each row of 16 lanes: row_shr 1, 2,
+  v |= (unsigned)dpp0_i32<0x114>((int)v); v |= (unsigned)dpp0_i32<0x118>((int)v);  // 4, 8
+  v |= (unsigned)dpp0_i32<0x142>((int)v); v |= (unsigned)dpp0_i32<0x143>((int)v);  // across the rows
+  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+// max(0, max over the lanes): every caller only asks whether the maximum is positive and where it sits
+__device__ __forceinline__ double wave_max_nonneg(double v) {
+  v = vmax_f64(v, dpp0_f64<0x111>(v)); v = vmax_f64(v, dpp0_f64<0x112>(v));  // inside each row of 16 lanes: row_shr 1, 2,
+  v = vmax_f64(v, dpp0_f64<0x114>(v)); v = vmax_f64(v, dpp0_f64<0x118>(v));  // 4, 8
+  v = vmax_f64(v, dpp0_f64<0x142>(v)); v = vmax_f64(v, dpp0_f64<0x143>(v));  // across the rows
+  return readlane_f64(v, 63);
+}
+__device__ __forceinline__ double wave_min(double v) {
+  v = vmin_f64(v, dpp_f64<0x111, 0xf>(INFINITY, v)); v = vmin_f64(v, dpp_f64<0x112, 0xf>(INFINITY, v));  // inside each row of 16 lanes: row_shr 1, 2,
+  v = vmin_f64(v, dpp_f64<0x114, 0xf>(INFINITY, v)); v = vmin_f64(v, dpp_f64<0x118, 0xf>(INFINITY, v));  // 4, 8
+  v = vmin_f64(v, dpp_f64<0x142, 0xa>(INFINITY, v)); v = vmin_f64(v, dpp_f64<0x143, 0xc>(INFINITY, v));  // across the rows
+  return readlane_f64(v, 63);
+}
+// max over the wavefront, any sign (identity -INFINITY).  fmax, not vmax_f64: its callers have not been shown to be free of NaNs.
+__device__ __forceinline__ double wave_max(double v) {
+  v = fmax(v, dpp_f64<0x111, 0xf>(-INFINITY, v)); v = fmax(v, dpp_f64<0x112, 0xf>(-INFINITY, v));  // inside each row of 16 lanes: row_shr 1, 2,
+  v = fmax(v, dpp_f64<0x114, 0xf>(-INFINITY, v)); v = fmax(v, dpp_f64<0x118, 0xf>(-INFINITY, v));  // 4, 8
+  v = fmax(v, dpp_f64<0x142, 0xa>(-INFINITY, v)); v = fmax(v, dpp_f64<0x143, 0xc>(-INFINITY, v));  // across the rows
+  return readlane_f64(v, 63);
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_min_step(int v) {
+  const int o = __builtin_amdgcn_update_dpp(0x7fffffff, v, CTRL, ROW_MASK, 0xf, false);
+  return o < v ? o : v;
+}
+__device__ __forceinline__ int wave_min_i32(int v) {
+  v = dpp_min_step<0x111, 0xf>(v); v = dpp_min_step<0x112, 0xf>(v);  // inside each row of 16 lanes: row_shr 1, 2,
+  v = dpp_min_step<0x114, 0xf>(v); v = dpp_min_step<0x118, 0xf>(v);  // 4, 8
+  v = dpp_min_step<0x142, 0xa>(v); v = dpp_min_step<0x143, 0xc>(v);  // across the rows
+  return __builtin_amdgcn_readlane(v, 63);
+}
+// The same minimum as a __shfl_xor butterfly, the result in every lane.  Pinned by solve_kernel<.., PAIRS = true, ..>, which inlines
+// choose_r_index: with the DPP form its twelve instantiations no longer have the instruction bytes they had.
+__device__ __forceinline__ int wave_min_i32_xor(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
+
+}  // namespace fhw
