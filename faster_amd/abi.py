@@ -73,10 +73,15 @@ sched_dtype = np.dtype([("launch_order", "<i4"), ("publish_factor", "<i4"), ("ba
                         ("min_nodes", "<i4"), ("cloud_blocks", "<i4"), ("workgroups_per_cu", "<i4"), ("no_child_bound", "<i4"), ("compact_results", "<i4"), ("pair_outputs", "<i4"),
                         ("look_every", "<i4"), ("struct_size", "<i4")])
 assert sched_dtype.itemsize == 48
-FH_ABI_VERSION = 8   # include/fasterhip.h: the layout generation of its structs (checked against fh_abi_version() when the library is loaded)
+FH_ABI_VERSION = 9   # include/fasterhip.h: the layout generation of its structs (checked against fh_abi_version() when the library is loaded)
 
 launch_info_dtype = np.dtype([("n_seg", "<i4"), ("pairs", "<i4"), ("waves_per_simd", "<i4"), ("grid", "<i4"), ("workgroups_per_cu", "<i4"),
                               ("lds_bytes", "<i4"), ("unknown_space", "<i4"), ("look_every", "<i4")])
+
+
+def point_mask_words(n_cloud):
+    """Words of one row of the point masks (fh_set_point_views_device): one bit per cloud point, 32 to a uint32."""
+    return (int(n_cloud) + 31) // 32
 
 
 voxel_grid_dtype = np.dtype([("origin", "<f8", (3,)), ("res", "<f8"), ("dims", "<i4", (3,)), ("reserved", "<i4")])

@@ -10,7 +10,8 @@ SOURCES = [os.path.join(HERE, "csrc", "fh_capi.hip"), os.path.join(HERE, "csrc",
            os.path.join(HERE, "csrc", "fh_map.hip")]
 import glob  # noqa: E402
 
-DEPS = SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + [os.path.join(ROOT, "include", "fasterhip.h")]
+DEPS = SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + [os.path.join(ROOT, "include", "fasterhip.h"),
+                                                                                    os.path.join(ROOT, "include", "fasterhip_occupancy.h")]
 HOST_SO = os.path.join(HERE, "libsolverhip.so")
 HOST_SOURCES = [os.path.join(HERE, "host", "solver_hip.cpp"), os.path.join(HERE, "host", "decomp_hip.cpp"),
                 os.path.join(HERE, "host", "jps_hip.cpp"), os.path.join(HERE, "host", "corridor_frontend.cpp")]  # (JpsHip searches ONE query on the host)

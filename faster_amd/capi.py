@@ -29,6 +29,9 @@ SYMBOLS = [
     "fh_fleet_heading_init_device", "fh_fleet_set_headings_device", "fh_fleet_set_goals_device", "fh_fleet_next_goals_yaw_device",
     "fh_fleet_sense_fov_device",
 ]
+# include/fasterhip_occupancy.h (SYMBOLS is what include/fasterhip.h itself declares)
+OCCUPANCY_SYMBOLS = ["fh_map_read_views_device", "fh_map_view_occupancy", "fh_map_plan_batch_radius_views_device", "fh_set_point_views_device",
+                     "fh_fleet_observe_device"]
 
 _LIB = None
 
@@ -240,6 +243,16 @@ def lib():
         L.fh_fleet_sense_fov_device.restype = i32
         L.fh_fleet_sense_fov_device.argtypes = [vp, vp, ctypes.c_double, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, ctypes.c_double,
                                                 ctypes.c_double]
+        L.fh_map_read_views_device.restype = i32
+        L.fh_map_read_views_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, f64, vp, f64, f64, f64]
+        L.fh_map_view_occupancy.restype = i32
+        L.fh_map_view_occupancy.argtypes = [vp, i32, vp]
+        L.fh_map_plan_batch_radius_views_device.restype = i32
+        L.fh_map_plan_batch_radius_views_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, f64, i32, vp, vp, vp, vp, i32]
+        L.fh_set_point_views_device.restype = i32
+        L.fh_set_point_views_device.argtypes = [vp, vp, i32, vp, i32]
+        L.fh_fleet_observe_device.restype = i32
+        L.fh_fleet_observe_device.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, i32]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -436,6 +449,29 @@ class Map:
         self._check(lib().fh_map_plan_batch_device(self._h, d_starts, d_goals, n, max_points, float(max_vertex_dist), int(max_poly), d_paths,
                                                    d_n_points, d_expansions), "fh_map_plan_batch_device")
 
+    def read_views_device(self, d_cloud, n_cloud, d_point_mask, mask_words, n_views, cells, res, center, z_ground, z_max, inflation):
+        """fh_map_read_views_device: n_views occupancy grids on the lattice of read_device; point k marks the grid of view v iff bit k of row
+        v of d_point_mask [n_views][mask_words] is set."""
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        center = np.ascontiguousarray(center, dtype=np.float64)
+        self._check(lib().fh_map_read_views_device(self._h, d_cloud, int(n_cloud), d_point_mask, int(mask_words), int(n_views), abi.ptr(cells),
+                                                   float(res), abi.ptr(center), float(z_ground), float(z_max), float(inflation)),
+                    "fh_map_read_views_device")
+
+    def view_occupancy(self, view):
+        """The grid of one view as occupancy() gives the map's."""
+        d, _ = self.dims()
+        occ = np.zeros(int(d[0]) * int(d[1]) * int(d[2]), dtype=np.int8)
+        self._check(lib().fh_map_view_occupancy(self._h, int(view), abi.ptr(occ)), "fh_map_view_occupancy")
+        return occ.reshape(int(d[2]), int(d[1]), int(d[0]))
+
+    def plan_batch_radius_views_device(self, d_starts, d_goals, d_radius, d_active, n, max_points, d_paths, d_n_points, d_view_of, n_views,
+                                       d_expansions=None, max_vertex_dist=0.0, max_poly=0):
+        """fh_map_plan_batch_radius_views_device: plan_batch_radius_device in which query i searches the grid of view d_view_of[i] (None: i)."""
+        self._check(lib().fh_map_plan_batch_radius_views_device(self._h, d_starts, d_goals, d_radius, d_active, n, max_points, float(max_vertex_dist),
+                                                                int(max_poly), d_paths, d_n_points, d_expansions, d_view_of, int(n_views)),
+                    "fh_map_plan_batch_radius_views_device")
+
     def plan_batch_radius_device(self, d_starts, d_goals, d_radius, d_active, n, max_points, d_paths, d_n_points, d_expansions=None,
                                  max_vertex_dist=0.0, max_poly=0):
         """fh_map_plan_batch_radius_device: every path clipped to the sphere of its own radius d_radius[i]; d_active (may be None): 0 = no search."""
@@ -539,6 +575,18 @@ class Context:
         g = np.ascontiguousarray(g).reshape(1)
         self._check(lib().fh_set_unknown_views_device(self._h, abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views)),
                     "fh_set_unknown_views_device")
+
+    def set_point_views_device(self, d_point_mask, mask_words=0, d_view_of=None, n_views=0):
+        """fh_set_point_views_device: occupied points per view for both corridor stages (d_point_mask = None: detach)."""
+        self._check(lib().fh_set_point_views_device(self._h, d_point_mask, int(mask_words), d_view_of, int(n_views)), "fh_set_point_views_device")
+
+    def fleet_observe_device(self, origin, res, dims, d_flags, view_stride, d_view_of, n_views, d_cloud, n_cloud, d_point_mask, mask_words):
+        """fh_fleet_observe_device: every view learns the cloud points that lie in voxels it knows (bits are only ORed)."""
+        g = np.zeros((), dtype=abi.voxel_grid_dtype)
+        g["origin"], g["res"], g["dims"] = origin, res, dims
+        g = np.ascontiguousarray(g).reshape(1)
+        self._check(lib().fh_fleet_observe_device(self._h, abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views), d_cloud, int(n_cloud),
+                                                  d_point_mask, int(mask_words)), "fh_fleet_observe_device")
 
     def fleet_sense_device(self, vmap, r_sense, origin, res, dims, d_flags, view_stride, d_view_of, n_views, d_vehicles, n):
         """fh_fleet_sense_device: every vehicle clears, in its view, the unknown flag of each voxel within r_sense that no occupied cell

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/fasterhip.h"
+#include "../../include/fasterhip_occupancy.h"
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
 #include "fh_decomp.hip.hpp"
@@ -86,6 +87,7 @@ struct fh_ctx {
   fh_pair_rule pair_rule = {0, 0, 0.0, 0.0, 1.0, 0.5};  // fh_set_pair_rule
   fh::UnknownGrid unknown = {nullptr, 0.0, 0.0, 0.0, 1.0, 0, 0, 0, 0};  // fh_set_unknown_grid_device (rule mode 2); the flags belong to the caller
   fh::UnknownViews views = {0, nullptr, 0, 0};  // fh_set_unknown_views_device: `unknown` is then view 0 and the lattice of every view (stride 0: one grid)
+  fh::PointViews points = {nullptr, nullptr, 0, 0};  // fh_set_point_views_device: occupied points per view (mask null: every point known to all)
   int sense_staging = 1;                        // fh_set_sense_staging
   fh_heading* headings = nullptr;               // fh_fleet_set_headings_device: the caller's records (look_at is written by the safe-corridor stage)
   int n_headings = 0;
@@ -587,6 +589,25 @@ int fh_set_unknown_views_device(fh_ctx* ctx, const fh_voxel_grid* grid, const un
   return FH_OK;
 }
 
+// Occupied space per view: only records the pointers, like the views above.  What the masks must cover is known when a cloud is: the
+// corridor entry points check mask_words * 32 >= n_cloud.
+int fh_set_point_views_device(fh_ctx* ctx, const uint32_t* d_point_mask, int mask_words, const int32_t* d_view_of, int n_views) {
+  if (!ctx) return FH_ERR_ARG;
+  if (!d_point_mask) {
+    ctx->points = fh::PointViews{nullptr, nullptr, 0, 0};
+    return FH_OK;
+  }
+  if (n_views <= 0 || mask_words <= 0) return FH_ERR_ARG;
+  ctx->points = fh::PointViews{d_point_mask, d_view_of, mask_words, n_views};
+  return FH_OK;
+}
+// the masks of the context against the cloud of a call
+static bool points_cover(fh_ctx* ctx, int n_cloud, const char* who) {
+  if (!ctx->points.mask || (long long)ctx->points.words * 32 >= (long long)n_cloud) return true;
+  ctx->err = std::string(who) + ": the point masks attached (fh_set_point_views_device) hold fewer bits than the cloud has points";
+  return false;
+}
+
 static int set_stop_word(fh_ctx* ctx, unsigned int value) {
   if (!ctx) return FH_ERR_ARG;
   if (ctx->device < 0 || !ctx->h_abort) return FH_ERR_DEVICE;
@@ -957,6 +978,10 @@ int fh_solve_pairs_device(fh_ctx* ctx, const fh_problem* d_whole, const fh_face*
                "(fh_set_unknown_grid_device)";
     return FH_ERR_ARG;
   }
+  if (ctx->points.mask) {
+    ctx->err = "fh_solve_pairs_device does not support point masks (fh_set_point_views_device): use the staged chain, or detach them";
+    return FH_ERR_ARG;
+  }
   fh::SolveArgs ka;
   std::memset(&ka, 0, sizeof(ka));
   ka.safe = d_safe; ka.sfaces = d_safe_faces; ka.sres = d_safe_results;
@@ -993,12 +1018,14 @@ int fh_timing_read(fh_ctx* ctx, double* ms, int cap) {
 }
 
 static const fh::UnknownViews NO_VIEWS = {0, nullptr, 0, 0};
+static const fh::PointViews NO_POINTS = {nullptr, nullptr, 0, 0};
 
 // lat.on + d_seg_spheres: the unknown voxels of a grid (cells farther than sphere[3] from sphere[0..2], per segment) are points of the
 // decomposition as well, listed before the cloud (fh_safe.hip.hpp)
 static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, const double* d_segments, int n_segments,
                             const double local_bbox[3], double drone_radius, double z_ground, int max_faces, fh_face* d_faces, int32_t* d_counts,
-                            const fh::UnknownLattice& lat, const double* d_seg_spheres, const fh::UnknownViews& views, int segs_per_query) {
+                            const fh::UnknownLattice& lat, const double* d_seg_spheres, const fh::UnknownViews& views, int segs_per_query,
+                            const fh::PointViews& points) {
   if (!ctx || n_cloud < 0 || n_segments < 0 || max_faces < 8 || !local_bbox) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
   DeviceScope device_scope(ctx->device);
@@ -1028,7 +1055,8 @@ static int decompose_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud,
 #endif
   hipLaunchKernelGGL(fh::decomp_kernel, dim3((unsigned)grid), dim3(64), 0, ctx->stream, d_cloud_xyz, n_cloud, d_segments, n_segments,
                      local_bbox[0], local_bbox[1], local_bbox[2], drone_radius, z_ground, max_faces, ctx->buf[DECOMP_WS].as<double>(), d_faces,
-                     d_counts, d_blocks, lat, lat.on ? d_seg_spheres : nullptr, ctx->buf[SEG_COUNTER].as<int>(), views, segs_per_query > 0 ? segs_per_query : 1);
+                     d_counts, d_blocks, lat, lat.on ? d_seg_spheres : nullptr, ctx->buf[SEG_COUNTER].as<int>(), views, segs_per_query > 0 ? segs_per_query : 1,
+                     points);
   FH_HIP(hipGetLastError());
 #ifdef FHD_EXPERIMENT
   if (std::getenv("FHD_HIST")) {  // (diagnostic: how long the lists of this launch were)
@@ -1049,7 +1077,7 @@ int fh_decompose_batch_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_clou
   fh::UnknownLattice lat;
   std::memset(&lat, 0, sizeof(lat));
   return decompose_device(ctx, d_cloud_xyz, n_cloud, d_segments, n_segments, local_bbox, drone_radius, z_ground, max_faces, d_faces, d_counts, lat,
-                          nullptr, NO_VIEWS, 1);
+                          nullptr, NO_VIEWS, 1, NO_POINTS);
 }
 
 int fh_decompose_batch(fh_ctx* ctx, const double* cloud_xyz, int n_cloud, const double* segments, int n_segments,
@@ -1154,7 +1182,7 @@ static int corridor_chain(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud, c
                      max_poly, segments, d_goal);
   FH_HIP(hipGetLastError());
   if ((rc = decompose_device(ctx, d_cloud_xyz, n_cloud, segments, (int)nseg, local_bbox, drone_radius, z_ground, seg_cap, seg_faces, seg_counts, lat,
-                             d_seg_spheres, views, max_poly)) != FH_OK)
+                             d_seg_spheres, views, max_poly, ctx->points)) != FH_OK)
     return rc;
   hipLaunchKernelGGL(corridor_assemble_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_n_points, n, max_poly, seg_cap, seg_faces, seg_counts,
                      faces_per_problem, d_faces, d_face_off, d_n_poly);
@@ -1167,6 +1195,7 @@ int fh_corridor_batch_device(fh_ctx* ctx, const double* d_cloud_xyz, int n_cloud
                              int faces_per_problem, fh_face* d_faces, int32_t* d_face_off, int32_t* d_n_poly, double* d_goal) {
   if (!ctx || n < 0 || n_cloud < 0 || max_points < 2 || max_poly < 1 || max_poly > FH_MAX_POLY || faces_per_problem < 8 || !local_bbox)
     return FH_ERR_ARG;
+  if (!points_cover(ctx, n_cloud, "fh_corridor_batch_device")) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
   DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
@@ -1204,6 +1233,7 @@ int fh_safe_corridor_batch_device(fh_ctx* ctx, const fh_problem* d_whole, const 
   if (!ctx || n < 0 || n_cloud < 0 || max_points < 2 || max_points > fh::SAFE_PATH_CAP || max_poly_safe < 1 || max_poly_safe > FH_MAX_POLY ||
       faces_per_problem < 8 || !local_bbox || !fhh::voxel_grid_ok(grid) || n_seg_safe < 1 || n_seg_safe > FH_MAX_SEG || !(r_frac >= 0) || !(r_frac <= 1))
     return FH_ERR_ARG;
+  if (!points_cover(ctx, n_cloud, "fh_safe_corridor_batch_device")) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
   DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
@@ -1375,6 +1405,34 @@ int fh_fleet_sense_fov_device(fh_ctx* ctx, fh_map* map, double r_sense, const fh
 }
 
 // ---- heading (fh_fleet.hip.hpp): yaw, new terminal goals ----
+// Observing: a view learns the cloud points that lie in voxels it knows (fleet_observe_kernel, fh_fleet.hip.hpp).
+int fh_fleet_observe_device(fh_ctx* ctx, const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of,
+                            int n_views, const double* d_cloud_xyz, int n_cloud, uint32_t* d_point_mask, int mask_words) {
+  (void)d_view_of;  // (a row of the masks belongs to a VIEW, as a block of d_flags does: the table that maps vehicles to views is not needed here)
+  if (!ctx || n_views <= 0 || n_cloud < 0 || mask_words < 0 || (long long)mask_words * 32 < (long long)n_cloud) return FH_ERR_ARG;
+  if (!fhh::voxel_grid_ok(grid)) return FH_ERR_ARG;
+  if (view_stride < (size_t)fhh::voxel_grid_cells(*grid)) {
+    ctx->err = "fh_fleet_observe_device: view_stride is smaller than a view (dims[0] * dims[1] * dims[2] bytes)";
+    return FH_ERR_ARG;
+  }
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n_cloud == 0) return FH_OK;
+  if (!d_flags || !d_cloud_xyz || !d_point_mask) return FH_ERR_ARG;
+  fh::ObserveArgs a;
+  a.ox = grid->origin[0]; a.oy = grid->origin[1]; a.oz = grid->origin[2]; a.res = grid->res;
+  a.nx = grid->dims[0]; a.ny = grid->dims[1]; a.nz = grid->dims[2];
+  a.flags = d_flags; a.stride = view_stride; a.n_views = n_views;
+  a.cloud = d_cloud_xyz; a.n_cloud = n_cloud; a.mask = d_point_mask; a.words = mask_words;
+  const long long chunks = ((long long)n_cloud + 63) / 64;  // 64 consecutive points of one view per wavefront, four wavefronts per workgroup
+  const long long blocks = (chunks + 3) / 4;
+  if (blocks * n_views > 0x7fffffffll) return FH_ERR_ARG;
+  a.blocks_per_view = (int)blocks;
+  hipLaunchKernelGGL(fh::fleet_observe_kernel, dim3((unsigned)(blocks * n_views)), dim3(256), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
 int fh_fleet_heading_init_device(fh_ctx* ctx, const double* d_yaw0, int n, fh_heading* d_headings) {
   if (!ctx || n < 0) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;

@@ -376,7 +376,7 @@ __global__ void __launch_bounds__(64, 3) decomp_kernel(const double* __restrict_
                                                     int max_faces, double* __restrict__ workspace, fh_face* __restrict__ faces,
                                                     int32_t* __restrict__ counts, const double* __restrict__ blocks, UnknownLattice lat,
                                                     const double* __restrict__ spheres, int* __restrict__ ticket, UnknownViews views,
-                                                    int segs_per_query) {
+                                                    int segs_per_query, PointViews pts) {
   // the segment's list of box points: FH_DECOMP_CAP inflated points (3 doubles each + a flag byte) or, in the same bytes, FH_DECOMP_CAP_IDS ids + flag bytes.
   // flags: bit0 first (inside the initial sphere), bit1 inside (current loop), bit2 remain
   static_assert(FH_DECOMP_CAP_IDS % 64 == 0 && FH_DECOMP_CAP <= FH_DECOMP_CAP_IDS, "the id list aliases the coordinate list; blocks of 64 do not straddle its end");
@@ -524,6 +524,10 @@ __global__ void __launch_bounds__(64, 3) decomp_kernel(const double* __restrict_
         note(in, q, (int)(0x80000000u | (unsigned)packed));
       }
     }
+    // occupied points per view (fh_set_point_views_device): a point whose bit is clear in the row of this segment's query is not a point
+    // of this sweep — the list, its home and its caps are those of the compacted sub-cloud, in the cloud's order.  The block list stays
+    // the whole cloud's: its boxes can only be looser than the sub-cloud's.
+    const unsigned* prow = point_row(pts, seg / segs_per_query);
     const int n_sweep = nb >= 0 ? nb : (n_cloud + 63) / 64;
     for (int j = 0; j < n_sweep; j++) {
       const int base = (nb >= 0 ? lblist[j] : j) * 64;
@@ -532,7 +536,7 @@ __global__ void __launch_bounds__(64, 3) decomp_kernel(const double* __restrict_
       D3 q = d3(0, 0, 0);
       if (i < n_cloud) {
         q = d3(cloud[3 * i], cloud[3 * i + 1], cloud[3 * i + 2]);
-        in = true;
+        in = !pts.mask || (prow && ((prow[i >> 5] >> (i & 31)) & 1u));
       }
       note(in, q, i);
     }

@@ -11,6 +11,8 @@
 // fleet_next_yaw_kernel  : getNextGoal with getDesiredYaw and yaw, `ticks` times (:650-723).                One lane per vehicle.
 // fleet_sense_kernel  : every vehicle clears, in its own unknown-voxel view, what it can see (no reference counterpart: the sensor
 //                       model of include/fasterhip.h, checked against a numpy restatement).             One workgroup per vehicle.
+// fleet_observe_kernel : every view learns the cloud points that lie in voxels it knows (no reference counterpart: the mapper's occupied
+//                       cloud per vehicle, modelled on the shared cloud; checked against a numpy restatement). One wavefront per 64 points.
 // The host restatement these kernels are checked against, cycle by cycle, is fhreplan::Planner (faster_amd/host/replan_stub.hpp),
 // compiled by g++ without contraction into fused multiply-adds: the geometry here is written with contraction off, in the same
 // operation order (a last-bit difference in G or ra changes a path, and a cycle later a factor window).
@@ -510,6 +512,55 @@ __global__ void __launch_bounds__(256) fleet_sense_kernel(SenseArgs a) {
     if (tid == 0) q_count = 0;
     __syncthreads();
   }
+}
+
+// ---- observing: a view learns the points of the shared cloud that lie in voxels it knows (fh_fleet_observe_device) ----
+// For view v and cloud point k: the voxel of the views' lattice that holds the point is (floor((x - ox) / res), floor((y - oy) / res),
+// floor((z - oz) / res)), in double, no contraction; if it lies inside the lattice and its flag byte in view v is 0 (known), bit k & 31 of
+// word k >> 5 of row v is set.  A point outside the lattice or with a coordinate that is not finite is never observed.  Bits are only
+// ORed: nothing is cleared, and vehicles or calls that overlap cannot show.
+// One wavefront takes 64 consecutive points of one view: the two mask words they fill.  It reads both words first and leaves when
+// every bit of a point that exists is already set — in steady state nearly every word of what a vehicle has passed — before any
+// coordinate or flag is read.  Otherwise the lanes whose bit is still clear look their voxel up, and one ballot holds both words:
+// lane 0 ORs the low half into the first, lane 32 the high half into the second, each only when it adds a bit.
+struct ObserveArgs {
+  double ox, oy, oz, res;   // the lattice of the views
+  int nx, ny, nz, n_views;
+  const unsigned char* flags;
+  size_t stride;
+  const double* cloud;
+  int n_cloud, words, blocks_per_view, pad;
+  unsigned* mask;           // [n_views][words]
+};
+
+__global__ void __launch_bounds__(256) fleet_observe_kernel(ObserveArgs a) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, wave = uniform_i32(threadIdx.x >> 6);
+  const int view = (int)(blockIdx.x / (unsigned)a.blocks_per_view), blk = (int)(blockIdx.x - (unsigned)view * (unsigned)a.blocks_per_view);
+  const long long k0 = ((long long)blk * 4 + wave) * 64;
+  if (view >= a.n_views || k0 >= (long long)a.n_cloud) return;  // (wave-uniform)
+  const int k = (int)k0 + lane;
+  unsigned* row = a.mask + (size_t)view * (size_t)a.words;
+  const int w0 = (int)(k0 >> 5);
+  const bool two = (k0 + 32) < (long long)a.n_cloud;  // the second word holds a point (and lies inside the row: words * 32 >= n_cloud)
+  const unsigned have_lo = row[w0], have_hi = two ? row[w0 + 1] : 0u;
+  const unsigned long long have = (unsigned long long)have_lo | ((unsigned long long)have_hi << 32);
+  const bool need = k < a.n_cloud && !((have >> lane) & 1ull);
+  if (!__ballot(need)) return;  // both words are full already: no coordinate, no flag is read
+  bool seen = false;
+  if (need) {
+    const double x = a.cloud[3 * (size_t)k], y = a.cloud[3 * (size_t)k + 1], z = a.cloud[3 * (size_t)k + 2];
+    const double fx = floor((x - a.ox) / a.res), fy = floor((y - a.oy) / a.res), fz = floor((z - a.oz) / a.res);
+    // (a NaN or an infinity fails one of these comparisons)
+    if (fx >= 0.0 && fx < (double)a.nx && fy >= 0.0 && fy < (double)a.ny && fz >= 0.0 && fz < (double)a.nz) {
+      const size_t cell = ((size_t)(int)fz * (size_t)a.ny + (size_t)(int)fy) * (size_t)a.nx + (size_t)(int)fx;
+      seen = a.flags[(size_t)view * a.stride + cell] == 0;
+    }
+  }
+  const unsigned long long m = __ballot(seen);
+  const unsigned lo = (unsigned)m, hi = (unsigned)(m >> 32);
+  if (lane == 0 && lo) atomicOr(&row[w0], lo);
+  if (lane == 32 && hi) atomicOr(&row[w0 + 1], hi);  // (hi != 0 only when the second word holds a point)
 }
 
 }  // namespace fh

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/fasterhip.h"
+#include "../../include/fasterhip_occupancy.h"
 #include "../host/jps_tables.hpp"
 #include "fh_path.hip.hpp"
 #include "fh_host.hpp"
@@ -50,6 +51,13 @@ struct fh_map {
   unsigned char* d_jps_tables = nullptr;  // neighbour tables of the jump point search (uploaded by the first fh_map_set_search(1))
   fhh::DeviceBuffer jps_entries;          // jump tables of the current grid [cells][32] shorts (fhp::jps_table_kernel), built by the first search in mode 1
   bool entries_valid = false;
+  // occupancy per view (fh_map_read_views_device): n_views grids on ONE lattice (view_nx..: it must be the lattice of the search workspace,
+  // i.e. of the last fh_map_read*), words_per_view words apart, and — built by the first view search in mode 1 — their jump tables
+  fhh::DeviceBuffer view_bits, view_entries;
+  int n_views = 0, view_nx = 0, view_ny = 0, view_nz = 0;
+  double view_res = 0.0, view_origin[3] = {0, 0, 0}, view_inflation = 0.0;
+  size_t words_per_view = 0;
+  bool view_entries_valid = false;
   // staging of the host-pointer entry points (synchronous: nothing in flight reads them once they have returned)
   enum Stage { CLOUD, QUERIES, PATHS, N_POINTS, EXPANSIONS, N_STAGE };
   fhh::DeviceBuffer stage[N_STAGE];
@@ -154,7 +162,7 @@ void fh_map_destroy(fh_map* m) {
   for (void* p : {(void*)m->ws.d_cells, (void*)m->ws.d_hkeys, (void*)m->ws.d_chunks, (void*)m->ws.d_serials, (void*)m->d_ticket, (void*)m->d_jps_tables,
                   (void*)m->parked.d_cells, (void*)m->parked.d_hkeys, (void*)m->parked.d_chunks, (void*)m->parked.d_serials})
     if (p) (void)hipFree(p);
-  for (fhh::DeviceBuffer* b : {&m->bits, &m->order, &m->jps_entries}) b->release();
+  for (fhh::DeviceBuffer* b : {&m->bits, &m->order, &m->jps_entries, &m->view_bits, &m->view_entries}) b->release();
   for (fhh::DeviceBuffer& b : m->stage) b.release();
   if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
   delete m;
@@ -275,6 +283,62 @@ int fh_map_read_device(fh_map* m, const double* d_cloud_xyz, int n_cloud, const 
   return FH_OK;
 }
 
+// fh_map_read_device's grid for every view at once: the same lattice arithmetic, a point marks the grid of the views that know it.
+int fh_map_read_views_device(fh_map* m, const double* d_cloud_xyz, int n_cloud, const uint32_t* d_point_mask, int mask_words, int n_views,
+                             const int32_t cells[3], double res, const double center[3], double z_ground, double z_max, double inflation) {
+  if (!m || n_views <= 0 || n_cloud < 0 || mask_words < 0 || (long long)mask_words * 32 < (long long)n_cloud) return FH_ERR_ARG;
+  if (!cells || !center || (n_cloud > 0 && (!d_cloud_xyz || !d_point_mask)) || !(res > 0.0) || !(inflation >= 0.0)) return FH_ERR_ARG;
+  if (cells[0] <= 0 || cells[1] <= 0 || cells[2] <= 0) return FH_ERR_ARG;
+  fhh::DeviceScope scope(m->device);
+  int dx = cells[0] + (int)(5 * inflation / res), dy = cells[1] + (int)(5 * inflation / res), dz = cells[2];
+  int down = (int)(dz / 2.0), up = (int)(dz / 2.0);
+  if (center[2] - res * dz / 2.0 < z_ground) down = std::max((int)((center[2] - z_ground) / res), 0);
+  if (center[2] + res * dz / 2.0 > z_max) {
+    up = (int)((z_max - center[2]) / res);
+    up = up > 0 ? up : 1;
+  }
+  dz = down + up;
+  if (dz <= 0 || (long long)dx * dy * dz > (1ll << 27)) return FH_ERR_ARG;
+  const size_t total = (size_t)dx * dy * dz, words = (total + 31) / 32;
+  if (words * (size_t)n_views > ((size_t)1 << 36)) {
+    m->err = "fh_map_read_views_device: more than 256 GB of grids";
+    return FH_ERR_ARG;
+  }
+  m->view_nx = dx; m->view_ny = dy; m->view_nz = dz;
+  m->view_res = res; m->view_inflation = inflation;
+  m->view_origin[0] = center[0] - res * dx / 2.0;
+  m->view_origin[1] = center[1] - res * dy / 2.0;
+  m->view_origin[2] = center[2] - res * down;
+  m->n_views = n_views;
+  m->words_per_view = words;
+  m->view_entries_valid = false;
+  FM_HIP(m->view_bits.reserve(words * 4 * (size_t)n_views, m->stream));
+  FM_HIP(hipMemsetAsync(m->view_bits.ptr, 0, words * 4 * (size_t)n_views, m->stream));
+  if (n_cloud > 0) {
+    const int mcube = (int)std::floor(inflation / res);
+    for (int v0 = 0; v0 < n_views; v0 += 32768) {  // (the second grid dimension holds 65535 blocks)
+      const int nv = std::min(32768, n_views - v0);
+      hipLaunchKernelGGL(fhp::mark_views_kernel, dim3((unsigned)((n_cloud + 255) / 256), (unsigned)nv), dim3(256), 0, m->stream, d_cloud_xyz, n_cloud,
+                         dx, dy, dz, res, m->view_origin[0], m->view_origin[1], m->view_origin[2], mcube, m->view_bits.as<unsigned>(),
+                         (long long)words, (const unsigned*)d_point_mask, mask_words, v0);
+    }
+    FM_HIP(hipGetLastError());
+  }
+  return FH_OK;
+}
+
+// the grid of one view as fh_map_occupancy gives the map's (tests: an all-ones mask gives the map's grid)
+int fh_map_view_occupancy(fh_map* m, int view, int8_t* occ) {
+  if (!m || m->n_views <= 0 || view < 0 || view >= m->n_views || !occ) return FH_ERR_ARG;
+  fhh::DeviceScope scope(m->device);
+  const size_t total = (size_t)m->view_nx * m->view_ny * m->view_nz, words = m->words_per_view;
+  std::vector<unsigned> bits(words);
+  FM_HIP(hipMemcpyAsync(bits.data(), m->view_bits.as<unsigned>() + (size_t)view * words, words * 4, hipMemcpyDeviceToHost, m->stream));
+  FM_HIP(hipStreamSynchronize(m->stream));
+  for (size_t i = 0; i < total; i++) occ[i] = (bits[i >> 5] >> (i & 31)) & 1u ? 100 : 0;
+  return FH_OK;
+}
+
 int fh_map_read(fh_map* m, const double* cloud_xyz, int n_cloud, const int32_t cells[3], double res, const double center[3], double z_ground,
                 double z_max, double inflation) {
   if (!m || n_cloud < 0 || (n_cloud > 0 && !cloud_xyz)) return FH_ERR_ARG;
@@ -317,8 +381,10 @@ int fh_map_occupancy(fh_map* m, int8_t* occ) {
 }
 
 // d_radius / d_active: fh_map_plan_batch_radius_device (null: fh_map_plan_batch_device)
+// d_view_of / use_views: fh_map_plan_batch_radius_views_device (query i searches the grid of its view)
 static int plan_batch_device(fh_map* m, const double* d_starts, const double* d_goals, const double* d_radius, const int32_t* d_active, int n,
-                             int max_points, double max_vertex_dist, int max_poly, double* d_paths, int32_t* d_n_points, int64_t* d_expansions) {
+                             int max_points, double max_vertex_dist, int max_poly, double* d_paths, int32_t* d_n_points, int64_t* d_expansions,
+                             bool use_views = false, const int32_t* d_view_of = nullptr) {
   if (n == 0) return FH_OK;
   fhh::DeviceScope scope(m->device);
   int rc;
@@ -358,6 +424,32 @@ static int plan_batch_device(fh_map* m, const double* d_starts, const double* d_
     }
     pa.jps_entries = m->jps_entries.as<short>();
   }
+  fhp::PlanViews pv = {nullptr, nullptr, nullptr, 0, 0, 0};
+  if (use_views) {
+    pv.bits = m->view_bits.as<unsigned>();
+    pv.view_of = d_view_of;
+    pv.words_per_view = (long long)m->words_per_view;
+    pv.n_views = m->n_views;
+    if (m->search_mode == 1) {
+      const size_t per_view = (size_t)32 * mv.total * sizeof(short);
+      if (!m->view_entries_valid) {  // the jump tables of every view's grid: three launches per 32768 views, once per fh_map_read_views_device
+        FM_HIP(m->view_entries.reserve(per_view * (size_t)m->n_views, m->stream));
+        fhp::MapView mv0 = mv;
+        mv0.bits = pv.bits;
+        for (int v0 = 0; v0 < m->n_views; v0 += 32768) {
+          const int nv = std::min(32768, m->n_views - v0);
+          for (int level = 1; level <= 3; level++) {
+            const long long threads = (long long)mv.total * (level == 1 ? 6 : (level == 2 ? 12 : 8));
+            hipLaunchKernelGGL(fhp::jps_table_views_kernel, dim3((unsigned)((threads + 255) / 256), (unsigned)nv), dim3(256), 0, m->stream, mv0,
+                               m->d_jps_tables, m->view_entries.as<short>(), level, pv.words_per_view, v0);
+          }
+        }
+        FM_HIP(hipGetLastError());
+        m->view_entries_valid = true;
+      }
+      pv.entries = m->view_entries.as<short>();
+    }
+  }
   pa.order = nullptr;
   if (n > m->ws.waves && m->sched_launch_order) {  // more queries than wavefronts: far-apart pairs first
     FM_HIP(m->order.reserve(sizeof(int) * ((size_t)n + 128), m->stream));
@@ -372,7 +464,11 @@ static int plan_batch_device(fh_map* m, const double* d_starts, const double* d_
     pa.order = d_order + 128;
   }
   const int grid = std::min(m->ws.waves, n);
-  if (m->search_mode == 1 && pa.hslots > 0) hipLaunchKernelGGL((fhp::plan_kernel<true, true>), dim3((unsigned)grid), dim3(64), 0, m->stream, mv, pa);
+  if (use_views) {
+    if (m->search_mode == 1 && pa.hslots > 0) hipLaunchKernelGGL((fhp::plan_views_kernel<true, true>), dim3((unsigned)grid), dim3(64), 0, m->stream, mv, pa, pv);
+    else if (m->search_mode == 1) hipLaunchKernelGGL(fhp::plan_views_kernel<true>, dim3((unsigned)grid), dim3(64), 0, m->stream, mv, pa, pv);
+    else hipLaunchKernelGGL(fhp::plan_views_kernel<false>, dim3((unsigned)grid), dim3(64), 0, m->stream, mv, pa, pv);
+  } else if (m->search_mode == 1 && pa.hslots > 0) hipLaunchKernelGGL((fhp::plan_kernel<true, true>), dim3((unsigned)grid), dim3(64), 0, m->stream, mv, pa);
   else if (m->search_mode == 1) hipLaunchKernelGGL(fhp::plan_kernel<true>, dim3((unsigned)grid), dim3(64), 0, m->stream, mv, pa);
   else hipLaunchKernelGGL(fhp::plan_kernel<false>, dim3((unsigned)grid), dim3(64), 0, m->stream, mv, pa);
   FM_HIP(hipGetLastError());
@@ -390,6 +486,22 @@ int fh_map_plan_batch_radius_device(fh_map* m, const double* d_starts, const dou
                                     int64_t* d_expansions) {
   if (!m || !m->have_map || n < 0 || max_points < 2 || (n > 0 && (!d_starts || !d_goals || !d_radius || !d_paths || !d_n_points))) return FH_ERR_ARG;
   return plan_batch_device(m, d_starts, d_goals, d_radius, d_active, n, max_points, max_vertex_dist, max_poly, d_paths, d_n_points, d_expansions);
+}
+
+int fh_map_plan_batch_radius_views_device(fh_map* m, const double* d_starts, const double* d_goals, const double* d_radius, const int32_t* d_active,
+                                          int n, int max_points, double max_vertex_dist, int max_poly, double* d_paths, int32_t* d_n_points,
+                                          int64_t* d_expansions, const int32_t* d_view_of, int n_views) {
+  if (!m || n_views <= 0 || !m->have_map || n < 0 || max_points < 2 || (n > 0 && (!d_starts || !d_goals || !d_radius || !d_paths || !d_n_points)))
+    return FH_ERR_ARG;
+  if (n_views != m->n_views || m->view_nx != m->nx || m->view_ny != m->ny || m->view_nz != m->nz || m->view_res != m->res ||
+      m->view_inflation != m->inflation || m->view_origin[0] != m->origin[0] || m->view_origin[1] != m->origin[1] || m->view_origin[2] != m->origin[2]) {
+    m->err = "fh_map_plan_batch_radius_views_device: n_views grids on the lattice of the map are needed (fh_map_read_views_device with the "
+             "arguments of fh_map_read_device)";
+    return FH_ERR_ARG;
+  }
+  if (!d_view_of && n > n_views) return FH_ERR_ARG;
+  return plan_batch_device(m, d_starts, d_goals, d_radius, d_active, n, max_points, max_vertex_dist, max_poly, d_paths, d_n_points, d_expansions, true,
+                           d_view_of);
 }
 
 int fh_map_plan_batch(fh_map* m, const double* starts, const double* goals, int n, int max_points, double max_vertex_dist, int max_poly,

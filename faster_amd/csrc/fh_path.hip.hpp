@@ -79,6 +79,17 @@ struct PlanArgs {
   int profile_slot;                 // FHP_PROFILE builds only (scripts/jps_phase_profile.py): which phase's cycles `expansions` receives
 };
 
+// Occupancy per view (fh_map_read_views_device, fh_map_plan_batch_radius_views_device): n_views grids on the lattice of the MapView,
+// words_per_view words apart; query q searches the grid of view_of ? view_of[q] : q (a number outside [0, n_views): no path).  The jump
+// point search reads the jump tables of THAT grid: entries + view * total * 32.
+struct PlanViews {
+  const unsigned* bits;
+  const short* entries;
+  const int* view_of;
+  long long words_per_view;
+  int n_views, pad;
+};
+
 // (cell indices are split with fhu::div, fh_udiv.hpp: on a wave-uniform index three scalar instructions instead of 45 vector ones)
 using fhw::lane_id; using fhw::rank_in; using fhw::uniform_f64; using fhw::uniform_i32; using fhw::wave_min_i32;
 using fhs::sphere_crossing;  // getIntersectionWithSphere (faster/src/utils.cpp:713-776) with its arithmetic: fh_sphere.hip.hpp
@@ -1457,6 +1468,153 @@ __global__ void __launch_bounds__(64, JPS ? 5 : 3) plan_kernel(MapView mv, PlanA
   if (lane == 0) pa.serials[wave] = serial;
 }
 
+// The same loop for fh_map_plan_batch_radius_views_device, a copy: plan_kernel above keeps its text, and with it its code (sharing one
+// body between the two changed plan_kernel's instruction bytes and cost its path search 4 %: DESIGN.md).
+// VIEWS: the grid (and its jump tables) is the one of the query's view, taken when the query is drawn (plan_views_kernel)
+template <bool JPS, bool HASHED, bool VIEWS>
+__device__ __forceinline__ void plan_queries(const MapView& mv, MapView* own, const PlanArgs& pa, const PlanViews& pv, char* lds) {
+  Planner pl(mv, lds);
+  if (JPS) pl.init_jps(lds, pa.jps_tables, pa.jps_entries);
+  const int lane = pl.lane;
+  const int wave = (int)blockIdx.x;
+  CellState* cells = pa.cells + (size_t)wave * (HASHED ? pa.hslots : mv.total);
+  if (HASHED) {
+    pl.hk = pa.hkeys + (size_t)wave * pa.hslots;
+    pl.hr = cells;
+    pl.hmask = (unsigned)pa.hslots - 1u;
+    pl.hshift = 32u - (unsigned)(31 - __builtin_clz((unsigned)pa.hslots));
+    pl.cap_g = (pa.hslots >> 2) * 3;
+  }
+  unsigned* chunks = pa.chunks + (size_t)wave * (size_t)pa.chunk_words;
+  unsigned serial = pa.serials[wave];
+  for (;;) {
+    int q = 0;
+    if (lane == 0) q = atomicAdd(pa.ticket, 1);
+    q = uniform_i32(q);
+    if (q >= pa.n) break;
+    if (pa.order) q = uniform_i32(pa.order[q]);
+    double st[3], gl[3];
+    for (int k = 0; k < 3; k++) { st[k] = pa.starts[3 * q + k]; gl[k] = pa.goals[3 * q + k]; }
+    st[2] = fmax(st[2], 0.0);  // jps_manager.cpp:143-144
+    gl[2] = fmax(gl[2], 0.0);
+    pl.to_cell(st[0], st[1], st[2], pl.s);
+    pl.to_cell(gl[0], gl[1], gl[2], pl.t);
+    for (int k = 0; k < 3; k++) { pl.s[k] = uniform_i32(pl.s[k]); pl.t[k] = uniform_i32(pl.t[k]); }
+    long long expansions = 0;
+    int nv = 0;
+#ifdef FHP_PROFILE
+    pl.prof_slot = pa.profile_slot;
+    pl.prof_acc = 0;
+    const long long q_t0 = (long long)__builtin_readcyclecounter();
+#endif
+    bool has_view = true;
+    if (VIEWS) {  // (own: the kernel's copy of the MapView, the one `mv` refers to)
+      const int view = uniform_i32(pv.view_of ? pv.view_of[q] : q);
+      has_view = view >= 0 && view < pv.n_views;
+      const long long v = has_view ? view : 0;
+      own->bits = pv.bits + v * pv.words_per_view;
+      if (JPS) pl.jt = pv.entries + v * (long long)mv.total * 32;
+    }
+    const bool live = has_view && (!pa.active || uniform_i32(pa.active[q]) != 0);
+    if (live && !pl.outside(pl.s[0], pl.s[1], pl.s[2]) && !pl.outside(pl.t[0], pl.t[1], pl.t[2])) {
+      serial++;
+      if (serial >= (JPS ? JPS_SERIAL_LIMIT : 0x7fffffffu)) {  // 2^31 (2^26) queries of this wavefront: its stamps start over, so its cell states are cleared first
+        if (HASHED) for (int c = lane; c < pa.hslots; c += 64) pl.hk[c] = 0ull;
+        else for (int c = lane; c < mv.total; c += 64) cells[c].stamp = 0u;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        serial = 1;
+      }
+      nv = JPS ? pl.template search_jps<HASHED>(cells, chunks, serial, expansions) : pl.search(pa, cells, chunks, serial, expansions);
+    }
+    double* out = pa.paths + (size_t)q * pa.max_points * 3;
+    int np = nv;
+    if (nv > 0) {
+      // vertices in LDS order va[0..nv): ends forced
+      const int count = nv > 1 ? nv : 2;
+      // createMoreVertexes / zero-length legs / deleteVertexes are sequential and short: lane 0 walks the legs
+      if (lane == 0) {
+        int w = 0;
+        double last[3] = {st[0], st[1], st[2]};  // the last vertex kept
+        auto put = [&](const double p[3]) {
+          if (w < pa.max_points) { out[3 * w] = p[0]; out[3 * w + 1] = p[1]; out[3 * w + 2] = p[2]; }
+          w++;
+          last[0] = p[0]; last[1] = p[1]; last[2] = p[2];
+        };
+        // a vertex closer than 1e-9 to the last kept one is dropped (createMoreVertexes repeats the end of a leg that is an exact
+        // multiple of the spacing; the host restatement erases the later of the two)
+        auto emit = [&](const double p[3]) {
+          if (pa.max_vertex_dist > 0.0 && Planner::dist(p, last) < 1e-9) return;
+          put(p);
+        };
+        put(last);
+        // JPS_in (faster.cpp:370-382): the path up to its first crossing of the sphere of radius min(|goal - start| - 0.001, Ra) around
+        // the start, the crossing point E appended (getFirstIntersectionWithSphere, utils.cpp:782-870)
+        auto vertex = [&](int i, double b[3]) {
+          if (i == 0) { b[0] = st[0]; b[1] = st[1]; b[2] = st[2]; }
+          else if (i == count - 1) { b[0] = gl[0]; b[1] = gl[1]; b[2] = gl[2]; }
+          else pl.center(pl.va[i], b);
+        };
+        int n_in = count;
+        bool has_e = false;
+        double E[3] = {0, 0, 0};
+        if (pa.radius || pa.sphere_ra > 0.0) {
+          const double ra = pa.radius ? pa.radius[q] : fmin(Planner::dist(gl, st) - 0.001, pa.sphere_ra);
+          for (int i = 1; i < count; i++) {
+            double b[3];
+            vertex(i, b);
+            if (Planner::dist(b, st) > ra) {
+              double p[3];
+              vertex(i - 1, p);
+              sphere_crossing(p, b, ra, st, E);
+              n_in = i + 1;  // vertices 0 .. i-1, then E
+              has_e = true;
+              break;
+            }
+          }
+        }
+        double a[3] = {st[0], st[1], st[2]};  // start of the current leg: always the ORIGINAL vertex, as in createMoreVertexes
+        for (int i = 1; i < n_in; i++) {
+          double b[3];
+          if (has_e && i == n_in - 1) { b[0] = E[0]; b[1] = E[1]; b[2] = E[2]; }
+          else vertex(i, b);
+          if (pa.max_vertex_dist > 0.0) {
+            const double d = Planner::dist(b, a);
+            if (d > pa.max_vertex_dist) {
+              const int add = (int)floor(d / pa.max_vertex_dist);
+              const double vx = (b[0] - a[0]) / d, vy = (b[1] - a[1]) / d, vz = (b[2] - a[2]) / d;
+              double q[3] = {a[0], a[1], a[2]};
+              for (int k = 0; k < add; k++) {
+                q[0] = q[0] + vx * pa.max_vertex_dist; q[1] = q[1] + vy * pa.max_vertex_dist; q[2] = q[2] + vz * pa.max_vertex_dist;
+                emit(q);
+              }
+            }
+          }
+          emit(b);
+          a[0] = b[0]; a[1] = b[1]; a[2] = b[2];
+        }
+        if (pa.max_poly > 0 && w > pa.max_poly + 1) w = pa.max_poly + 1;
+        np = w > pa.max_points ? -1 : w;
+      }
+      np = uniform_i32(np);
+    }
+    if (lane == 0) {
+      pa.n_points[q] = np;
+#ifdef FHP_PROFILE
+      if (pa.profile_slot == 7) expansions = (long long)__builtin_readcyclecounter() - q_t0;
+      else if (pa.profile_slot >= 0) expansions = pl.prof_acc;
+#endif
+      if (pa.expansions) pa.expansions[q] = expansions;
+    }
+  }
+  if (lane == 0) pa.serials[wave] = serial;
+}
+template <bool JPS, bool HASHED = false>
+__global__ void __launch_bounds__(64, JPS ? 5 : 3) plan_views_kernel(MapView mv, PlanArgs pa, PlanViews pv) {
+  __shared__ __attribute__((aligned(16))) char lds[JPS ? JPS_LDS_BYTES : PLAN_LDS_BYTES];
+  MapView own = mv;
+  plan_queries<JPS, HASHED, true>(own, &own, pa, pv, lds);
+}
+
 // Launch order of a batch of queries: by the distance between start and goal, farthest first (counting sort over 64 classes, two small
 // launches; `counters`: 128 zeroed ints).  The number of expanded cells grows with the distance (correlation 0.47 in the forest
 // maps, and the maximum is 20x the mean), and a long search that starts last is what the launch ends on: simulated makespan of 65536
@@ -1500,6 +1658,69 @@ __global__ void __launch_bounds__(256) plan_order_scatter_kernel(const double* s
 // entries of the levels below).  A thread owns one line of cells in one direction — it starts from the cell whose successor lies
 // outside the grid and walks backwards, so every entry costs one step: entry(c) = -1 if c + d is blocked, +1 if the jump ends at
 // c + d (forced neighbour there, or a lower jump from there that ends), else entry(c + d) one further away.
+__device__ __forceinline__ void jps_table_lines(const MapView& mv, const unsigned char* tb, short* jt, int level) {
+  const int ndirs = level == 1 ? 6 : (level == 2 ? 12 : 8);
+  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (long long)mv.total * ndirs) return;
+  const int cell = (int)(gid % mv.total), which = (int)(gid / mv.total);
+  int code = 0;
+  for (int c = 0, seen = 0; c < 27; c++) {
+    const int n1 = abs(c % 3 - 1) + abs((c / 3) % 3 - 1) + abs(c / 9 - 1);
+    if (n1 == level) {
+      if (seen == which) { code = c; break; }
+      seen++;
+    }
+  }
+  const int dx = code % 3 - 1, dy = (code / 3) % 3 - 1, dz = code / 9 - 1;
+  const int nxy = mv.nx * mv.ny;
+  int z = cell / nxy, y = (cell - z * nxy) / mv.nx, x = cell - z * nxy - y * mv.nx;
+  auto outside = [&](int px, int py, int pz) { return px < 0 || py < 0 || pz < 0 || px >= mv.nx || py >= mv.ny || pz >= mv.nz; };
+  auto occupied = [&](int px, int py, int pz) {
+    if (outside(px, py, pz)) return false;
+    const int id = px + mv.nx * py + nxy * pz;
+    return ((mv.bits[id >> 5] >> (id & 31)) & 1u) != 0u;
+  };
+  if (!outside(x + dx, y + dy, z + dz)) return;  // not the last cell of its line
+  const int nsub = level == 1 ? 0 : (level == 2 ? 2 : 6), nforced = level == 3 ? 6 : 8;
+  short* mine = jt + code;  // [cell][32]: the entries of a cell side by side
+  while (!outside(x, y, z)) {
+    const int X = x + dx, Y = y + dy, Z = z + dz;
+    short val;
+    if (outside(X, Y, Z) || occupied(X, Y, Z)) val = -1;
+    else {
+      const int xid = X + mv.nx * Y + nxy * Z;
+      bool ends = false, unknown = false;
+      for (int fn = 0; fn < nforced; fn++) {
+        const unsigned pk = tb[27 * 28 + code * 12 + fn];
+        ends = ends || occupied(X + (int)(pk & 3u) - 1, Y + (int)((pk >> 2) & 3u) - 1, Z + (int)((pk >> 4) & 3u) - 1);
+      }
+      for (int k = 0; k < nsub && !ends; k++) {
+        const unsigned pk = tb[code * 28 + k];
+        const int c2 = (int)((pk & 3u) + 3u * ((pk >> 2) & 3u) + 9u * ((pk >> 4) & 3u));
+        const short v = jt[(size_t)xid * 32 + c2];
+        ends = v > 0;
+        unknown = unknown || v == 0;
+      }
+      if (ends) val = 1;
+      else if (unknown) val = 0;
+      else {
+        const short nxt = mine[(size_t)xid * 32];
+        val = (nxt == 0 || nxt >= 32766 || nxt <= -32766) ? (short)0 : (short)(nxt > 0 ? nxt + 1 : nxt - 1);
+      }
+    }
+    mine[(size_t)(x + mv.nx * y + nxy * z) * 32] = val;
+    x -= dx; y -= dy; z -= dz;
+  }
+}
+// the same for the grids of views first_view .. first_view + gridDim.y - 1 (mv.bits: view 0, words_per_view words apart; jt alike)
+__global__ void __launch_bounds__(256) jps_table_views_kernel(MapView mv, const unsigned char* tb, short* jt, int level, long long words_per_view,
+                                                              int first_view) {
+  const long long v = (long long)first_view + blockIdx.y;
+  mv.bits += v * words_per_view;
+  jps_table_lines(mv, tb, jt + v * (long long)mv.total * 32, level);
+}
+
+// jps_table_kernel as it always was (its text is kept so that its code is: see plan_kernel)
 __global__ void __launch_bounds__(256) jps_table_kernel(MapView mv, const unsigned char* tb, short* jt, int level) {
   const int ndirs = level == 1 ? 6 : (level == 2 ? 12 : 8);
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -1572,6 +1793,29 @@ __global__ void mark_kernel(const double* cloud, int n, int nx, int ny, int nz, 
       for (int iz = c[2] - m; iz <= c[2] + m; iz++) {
         const long long id = ix + (long long)nx * iy + (long long)nx * ny * iz;
         if (id >= 0 && id < total) atomicOr(&bits[id >> 5], 1u << (id & 31));
+      }
+}
+
+// mark_kernel for n_views grids at once (fh_map_read_views_device): point i marks, with the same arithmetic, the grid of every view
+// whose row of `mask` ([n_views][mask_words], bit i & 31 of word i >> 5) has its bit.  blockIdx.y = the view.  Bits are only ORed.
+__global__ void mark_views_kernel(const double* cloud, int n, int nx, int ny, int nz, double res, double ox, double oy, double oz, int m,
+                                  unsigned* bits, long long words_per_view, const unsigned* mask, int mask_words, int first_view) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const long long v = (long long)first_view + blockIdx.y;
+  if (!((mask[v * mask_words + (i >> 5)] >> (i & 31)) & 1u)) return;
+  unsigned* mine = bits + v * words_per_view;
+  int c[3];
+  c[0] = (int)round((cloud[3 * i] - ox) / res - 0.5);
+  c[1] = (int)round((cloud[3 * i + 1] - oy) / res - 0.5);
+  c[2] = (int)round((cloud[3 * i + 2] - oz) / res - 0.5);
+  for (int k = 0; k < 3; k++) c[k] = c[k] > 0 ? c[k] : 0;
+  const long long total = (long long)nx * ny * nz;
+  for (int ix = c[0] - m; ix <= c[0] + m; ix++)
+    for (int iy = c[1] - m; iy <= c[1] + m; iy++)
+      for (int iz = c[2] - m; iz <= c[2] + m; iz++) {
+        const long long id = ix + (long long)nx * iy + (long long)nx * ny * iz;
+        if (id >= 0 && id < total) atomicOr(&mine[id >> 5], 1u << (id & 31));
       }
 }
 

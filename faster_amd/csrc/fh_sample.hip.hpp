@@ -155,6 +155,19 @@ __device__ __forceinline__ const unsigned char* view_flags(const unsigned char* 
   const int view = vw.view_of ? vw.view_of[query] : query;
   return view >= 0 && view < vw.n_views ? base + (size_t)view * vw.stride : nullptr;
 }
+// Occupied space per query (fh_set_point_views_device): row view(i) of mask [n_views][words] holds one bit per point of the shared cloud,
+// bit k & 31 of word k >> 5 set iff that view knows point k; view(i) as above.  mask == null: none, every point is known to everyone.
+// A view number outside [0, n_views) knows no point.  (A struct of its own for the reason UnknownViews is one.)
+struct PointViews {
+  const unsigned* mask;
+  const int32_t* view_of;
+  int words, n_views;
+};
+__device__ __forceinline__ const unsigned* point_row(const PointViews& pv, int query) {
+  if (!pv.mask) return nullptr;
+  const int view = pv.view_of ? pv.view_of[query] : query;
+  return view >= 0 && view < pv.n_views ? pv.mask + (size_t)view * (size_t)pv.words : nullptr;
+}
 // Is an unknown voxel centre closer than `radius` to p?  What `kdtree_unk_.nearestKSearch(p, 1, ...)` followed by `sqrt(d2) < radius`
 // decides in findIndexH (faster.cpp:236-240) — evaluated in DOUBLE precision against double voxel centres.  The reference searches a
 // pcl::PointXYZ cloud: its query point, its voxel centres and d2 are single precision (faster.cpp:233-238); for a sample within float

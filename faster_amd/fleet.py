@@ -11,7 +11,12 @@ view per vehicle or team (set_unknown_views) that the vehicles grow on the devic
 
     sense -> replan -> next_goals
 
-with no host data in it.  enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
+with no host data in it.  set_point_views() gives every view its own knowledge of OCCUPIED space as well — a mask over the points of the
+shared cloud that observe() grows from what the view has seen — and the loop becomes
+
+    sense -> observe -> replan -> next_goals
+
+in which a vehicle searches its path and cuts both corridors around the points its view knows, and no others.  enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
 The host restatement every cycle is checked against is fhreplan::Planner (faster_amd/host/replan_stub.hpp);
@@ -67,6 +72,7 @@ class Fleet:
         self.n_views = 0
         self.dc = float(dc)
         self.d_headings = self.d_goal_yaw = self.yaw_params = None  # enable_heading
+        self.point_mask, self.map_args = None, None                 # set_point_views; what set_map built the map with
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -110,6 +116,9 @@ class Fleet:
         self._follow_current()
         self.cloud.record_stream(self.stream)  # (read by every later cycle's launches on the fleet's stream)
         self.map.read_device(self.cloud.data_ptr(), self.n_cloud, cells, res, center, self.z_ground, z_max, inflation)
+        self.map_args = (tuple(int(c) for c in cells), float(res), tuple(float(c) for c in center), float(z_max), float(inflation))
+        if self.point_mask is not None and self.point_mask.shape[1] * 32 < self.n_cloud:
+            raise capi.FasterHipError("Fleet.set_map: the point masks hold fewer bits than the new cloud has points (set_point_views again)")
 
     def set_unknown(self, flags, origin, res, dims):
         """This cycle's unknown voxels: flags[(iz ny + iy) nx + ix] != 0 (numpy or a device tensor) on the lattice (origin, res, dims)."""
@@ -121,6 +130,8 @@ class Fleet:
         self.ctx.set_unknown_grid_device(self.flags.data_ptr(), self.grid[0], self.grid[1], self.grid[2])
         self.view_flags = self.view_of = None  # (one grid replaces views)
         self.n_views = 0
+        if self.point_mask is not None:        # (point masks are numbered by views: gone with them)
+            self.set_point_views(False)
 
     def set_unknown_views(self, flags=None, view_of=None, n_views=None, *, origin, res, dims):
         """Unknown voxels per vehicle: vehicle i reads and senses view view_of[i] (None: view i, n_views = n) of a [n_views][cells] uint8
@@ -157,6 +168,54 @@ class Fleet:
             self.view_of.record_stream(self.stream)
         self.ctx.set_unknown_views_device(self.view_flags.data_ptr(), cells, None if self.view_of is None else self.view_of.data_ptr(), self.n_views,
                                           self.grid[0], self.grid[1], self.grid[2])
+        if self.point_mask is not None:  # (the masks are numbered by the same views: the table that was just replaced must not stay attached)
+            if self.point_mask.shape[0] != self.n_views:
+                raise capi.FasterHipError("Fleet.set_unknown_views: %d views, the point masks hold %d (set_point_views again)" % (self.n_views, self.point_mask.shape[0]))
+            self.ctx.set_point_views_device(self.point_mask.data_ptr(), self.point_mask.shape[1], None if self.view_of is None else self.view_of.data_ptr(),
+                                            self.n_views)
+
+    def set_point_views(self, mask=None):
+        """Occupied space per view: mask [n_views][ceil(n_cloud / 32)] uint32 (numpy or a device tensor, adopted as it is when it is on the
+        device: observe() writes into it), bit k & 31 of word k >> 5 of row v set iff view v knows point k of set_map's cloud.  The views
+        are those of set_unknown_views (the same view_of, the same count), which comes first.  mask = None allocates all zeros: nothing is
+        known.  From now on replan() rebuilds one occupancy grid per view from the masks ("map_views"), searches every vehicle's path in
+        the grid of its view and cuts both corridors around the points its view knows.  mask = False detaches: replan() is what it was.
+        Memory per view: a grid of ceil(cells / 32) words and a mask row; the jump point search adds 64 bytes per cell and view."""
+        t = self.torch
+        if mask is False:
+            self.point_mask = None
+            self.ctx.set_point_views_device(None)
+            return
+        if self.view_flags is None or self.cloud is None:
+            raise capi.FasterHipError("Fleet.set_point_views: set_map and set_unknown_views first")
+        words = abi.point_mask_words(self.n_cloud)
+        if mask is None:
+            self.point_mask = t.zeros((self.n_views, words), dtype=t.int32, device=self.dev)
+        else:
+            m = mask if isinstance(mask, t.Tensor) else t.from_numpy(np.ascontiguousarray(mask, dtype=np.uint32).view(np.int32))
+            self.point_mask = m.to(self.dev).view(t.int32).reshape(self.n_views, -1).contiguous()
+            if self.point_mask.shape[1] < words:
+                raise capi.FasterHipError("Fleet.set_point_views: %d words per view, the cloud needs %d" % (self.point_mask.shape[1], words))
+        self._follow_current()
+        self.point_mask.record_stream(self.stream)
+        self.ctx.set_point_views_device(self.point_mask.data_ptr(), self.point_mask.shape[1], None if self.view_of is None else self.view_of.data_ptr(),
+                                        self.n_views)
+
+    def observe(self):
+        """Every view learns the cloud points that lie in voxels it knows (fh_fleet_observe_device): after sense(), before replan().  One
+        launch on the fleet's stream; bits are only ORed."""
+        if self.point_mask is None:
+            raise capi.FasterHipError("Fleet.observe: set_point_views first")
+        self._follow_current()
+        origin, res, dims = self.grid
+        self.ctx.fleet_observe_device(origin, res, dims, self.view_flags.data_ptr(), self.view_flags.shape[1],
+                                      None if self.view_of is None else self.view_of.data_ptr(), self.n_views, self.cloud.data_ptr(), self.n_cloud,
+                                      self.point_mask.data_ptr(), self.point_mask.shape[1])
+
+    def point_masks(self):
+        """[n_views][words] uint32 on the host (synchronises)."""
+        self.sync()
+        return self.point_mask.cpu().numpy().view(np.uint32).copy()
 
     def enable_heading(self, yaw0=None, w_max=4.0, alpha_filter_dyaw=0.0):
         """Allocates one fh_heading per vehicle (yaw = previous_yaw = yaw0[i], None: 0) and attaches the records to the context: from
@@ -222,6 +281,21 @@ class Fleet:
         B, P, c, m = self.n, self.params, self.ctx, self.map
         p = lambda t: t.data_ptr()  # noqa: E731
         origin, res, dims = self.grid
+        chain = self._shared_map_stages(B, P, c, m, p, origin, res, dims)
+        if self.point_mask is None:
+            return chain
+        cells, mres, center, z_max, inflation = self.map_args
+        vo = None if self.view_of is None else p(self.view_of)
+        views = [
+            ("map_views", lambda: m.read_views_device(p(self.cloud), self.n_cloud, p(self.point_mask), self.point_mask.shape[1], self.n_views, cells,
+                                                      mres, center, self.z_ground, z_max, inflation)),
+            ("path_search", lambda: m.plan_batch_radius_views_device(p(self.d_starts), p(self.d_goals), p(self.d_radius), p(self.d_active), B, self.mp,
+                                                                     p(self.d_paths), p(self.d_np), vo, self.n_views, p(self.d_ex),
+                                                                     self.dist_max_vertexes, 0)),
+        ]
+        return chain[:1] + views + chain[2:]
+
+    def _shared_map_stages(self, B, P, c, m, p, origin, res, dims):
         return [
             ("begin", lambda: c.fleet_begin_device(P, p(self.d_vehicles), p(self.d_plans), B, self.max_states, p(self.d_whole), p(self.d_safe),
                                                    p(self.d_starts), p(self.d_goals), p(self.d_radius), p(self.d_active))),

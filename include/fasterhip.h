@@ -222,7 +222,7 @@ typedef struct fh_sched {
 } fh_sched;
 /* The layout generation of the structs in this header: bumped whenever a field changes its meaning, offset or size.  A caller compares
  * FH_ABI_VERSION (its compile time) with fh_abi_version() (the loaded library) once; SolverHip does. */
-#define FH_ABI_VERSION 8
+#define FH_ABI_VERSION 9
 int fh_abi_version(void);
 void fh_default_sched(fh_sched* s);
 int fh_set_sched(fh_ctx* ctx, const fh_sched* s);
@@ -604,8 +604,10 @@ int fh_map_plan_batch_radius_device(fh_map* map, const double* d_starts, const d
  * whole fleet (fh_set_unknown_grid_device) or as a view per vehicle or team (fh_set_unknown_views_device), which the vehicles grow on
  * the device by sensing (fh_fleet_sense_device): a closed-loop period is sense -> the chain above -> next goals with no host data in it;
  * the staged faithful chain above; the vehicle's heading (getDesiredYaw, the YAWING status, a new terminal goal after arrival and a
- * forward-looking sensor: the fh_heading block below).  Not supported: a map of occupied space per vehicle, and the fused
- * fh_solve_pairs_device as the committed path (its safe corridor is not FASTER's, and it takes no views).
+ * forward-looking sensor: the fh_heading block below); occupied space per vehicle or team as masks over the points of the shared cloud,
+ * grown on the device by observing (the occupancy block below): the closed loop is then sense -> observe -> replan -> next goals.
+ * Not supported: the fused fh_solve_pairs_device as the committed path (its safe corridor is not FASTER's, and it takes neither views
+ * nor point masks).
  * Plan storage: plan of vehicle i = d_plans[i * max_states + plan_head .. + plan_size); a commit moves the kept prefix to index 0. */
 enum {
   FH_VEHICLE_TRAVELING = 0,     /* faster.cpp: TRAVELING */
@@ -774,6 +776,25 @@ int fh_fleet_next_goals_yaw_device(fh_ctx* ctx, const fh_yaw_params* yaw_params,
 int fh_fleet_sense_fov_device(fh_ctx* ctx, fh_map* map, double r_sense, const struct fh_voxel_grid* grid, unsigned char* d_flags,
                               size_t view_stride, const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n,
                               const fh_heading* d_headings, double tan_half_h, double tan_half_v);
+
+/* ---- occupied space per vehicle or team: masks over the points of the shared cloud, grown by observing ------------------------
+ * In the reference both pclptr_map and pclptr_unk are what THIS vehicle's mapper has produced (faster.cpp:99-137).  Here knowledge of
+ * occupied space lives on the points of the one cloud every entry point shares: d_point_mask is [n_views][mask_words] of uint32,
+ * mask_words >= ceil(n_cloud / 32); bit k & 31 of word k >> 5 of row v is set iff view v knows cloud point k.  Views are numbered as
+ * for fh_set_unknown_views_device: view(i) = d_view_of ? d_view_of[i] : i.  Vehicle i then plans exactly as the host Planner does when
+ * it is handed the sub-cloud cloud[mask_i], in the cloud's order: the path search, the whole corridor, and the safe corridor against
+ * [unknown voxels | occupied points].  The world map (fh_map_read_device) stays the ground truth that fh_fleet_sense_device casts rays
+ * against.  Memory per view: words_per_view * 4 + mask_words * 4 bytes, words_per_view = ceil(cells of the map / 32); the jump point
+ * search (fh_map_set_search 1) adds its jump tables, 64 bytes per cell and view, so it is for teams rather than for a view per vehicle
+ * of a large fleet.
+ * The entry points are declared in include/fasterhip_occupancy.h (fh_map_read_views_device, fh_map_view_occupancy,
+ * fh_map_plan_batch_radius_views_device, fh_set_point_views_device, fh_fleet_observe_device), which includes this file.  Observing, next
+ * to the sensor's limits above: for every view v and every cloud point k, if the voxel of the views' lattice that contains point k is
+ * known in view v, bit k of row v is set; the voxel is floor((x - origin) / res) per axis, in double, no fused multiply-add; a point
+ * outside the lattice, or a point that is not finite, is never observed.  Nothing is ever cleared.  Limit of the model: a point is observed
+ * through the voxel it lies in, and sensing never clears a voxel that is an occupied cell of the world map behind another one.  With
+ * the world map inflated by more than a cell, a point in the interior of its own blob lies in such a voxel and is never observed: the
+ * caller chooses the world inflation accordingly. */
 
 /* Timing of the solve kernel, measured with HIP events recorded around every solve-kernel launch on
  * the context stream (the same stream the kernel runs on).  fh_timing_reset() forgets recorded launches;

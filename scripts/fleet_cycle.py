@@ -15,7 +15,11 @@ stream), the unfenced cycle time, the commit kernel's write rate and a device-to
 its "sense_first_ms" and stage table stand beside the omnidirectional ones of the same run.
 Memory of the views: vehicles x nx ny nz bytes (printed; 65536 vehicles in this forest: 12.6 GB).  A fleet that does not fit lets vehicles
 share views (view_of).
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--r-sense R] [--no-staging]"""
+--occupancy [TEAMS] adds "occupancy": occupied space per team (Fleet.set_point_views; TEAMS views, default 64, vehicle i in team i mod
+TEAMS — the jump point search keeps 64 bytes per cell and view, so a view per vehicle is for small fleets), unknown views and point masks
+all unknown at first, world inflation half a cell (with more than a cell the points inside a blob are never observed), the closed loop
+sense -> observe -> replan -> 5 ticks with "observe" and "map_views" as stages of their own.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]"""
 import json
 import os
 import sys
@@ -29,9 +33,10 @@ from faster_amd import abi, capi, frontend  # noqa: E402
 from faster_amd.fleet import Fleet  # noqa: E402
 
 
-def timed_cycles(fl, cycles, r_sense=None, fov=None):
-    """`cycles` cycles, every stage fenced by events: {stage: [ms]} (with r_sense: sensing first, as a stage of its own; fov: forward)."""
-    names = (["sense"] if r_sense else []) + [n for n, _ in fl.stages()] + ["next_goals"]
+def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False):
+    """`cycles` cycles, every stage fenced by events: {stage: [ms]} (with r_sense: sensing first, as a stage of its own; fov: forward;
+    observe: Fleet.observe after it, as another)."""
+    names = (["sense"] if r_sense else []) + (["observe"] if observe else []) + [n for n, _ in fl.stages()] + ["next_goals"]
     per = {n: [] for n in names}
     for _ in range(cycles):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
@@ -41,6 +46,10 @@ def timed_cycles(fl, cycles, r_sense=None, fov=None):
             fl.sense(r_sense, fov=fov)
             k = 1
             ev[1].record(fl.stream)
+        if observe:
+            fl.observe()
+            k += 1
+            ev[k].record(fl.stream)
         for j, (n, launch) in enumerate(fl.stages()):
             launch()
             ev[k + j + 1].record(fl.stream)
@@ -112,9 +121,54 @@ def views_cycles(B, cycles, p, world, r_sense, staging, fov=None):
     return out
 
 
+def occupancy_cycles(B, cycles, p, world, r_sense, teams):
+    """The closed loop with occupied space per team: see the module docstring."""
+    cloud, cells, res, center, zmax, _, states, goals, flags, _, _ = world
+    infl = 0.5 * res   # (below one cell: a point marks its own cell only, so its voxel can be seen and the point observed)
+    probe = capi.Map(0)
+    probe.read(cloud, cells, res, center, 0.0, zmax, infl)
+    dims, origin = probe.dims()
+    probe.close()
+    dims = [int(d) for d in dims]
+    n_cells = dims[0] * dims[1] * dims[2]
+    words = abi.point_mask_words(len(cloud))
+    out = {"teams": teams, "world_inflation": infl, "bytes_per_view": {"unknown_flags": n_cells, "grid": 4 * ((n_cells + 31) // 32), "mask": 4 * words, "jump_tables": 64 * n_cells}}
+    fl = Fleet(B, p, max_states=1024)
+    try:
+        fl.set_map(cloud, cells, res, center, zmax, infl)
+        fl.set_unknown_views(view_of=np.arange(B, dtype=np.int32) % teams, n_views=teams, origin=origin, res=res, dims=dims)
+        fl.set_point_views()
+        fl.init(states, goals)
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record(fl.stream)
+        fl.sense(r_sense)
+        e[1].record(fl.stream)
+        fl.observe()
+        e[2].record(fl.stream)
+        fl.replan()
+        fl.next_goals(5)
+        fl.sync()
+        out["sense_first_ms"], out["observe_first_ms"] = e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])
+        med = timed_cycles(fl, cycles, r_sense, observe=True)
+        v = fl.vehicles()
+        known = fl.point_masks()
+        out.update({"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())),
+                    "committed_last": int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum()),
+                    "points_known_fraction_end": float(np.unpackbits(known.view(np.uint8)).sum() / (teams * len(cloud))),
+                    "unknown_fraction_end": float(fl.view_flags.float().mean().item())})
+    finally:
+        fl.close()
+    return {"occupancy": out}
+
+
 def main():
     argv = sys.argv[1:]
-    r_sense, fov = 3.0, None
+    r_sense, fov, teams = 3.0, None, 0
+    if "--occupancy" in argv:
+        k = argv.index("--occupancy")
+        has = k + 1 < len(argv) and argv[k + 1].isdigit()
+        teams = int(argv[k + 1]) if has else 64
+        del argv[k:k + (2 if has else 1)]
     if "--r-sense" in argv:      # (an option's values leave by position, not by text: `1 3 --fov 1 0.5` keeps its first two)
         k = argv.index("--r-sense")
         r_sense = float(argv[k + 1])
@@ -211,6 +265,9 @@ def main():
     if "--views" in sys.argv or fov is not None:
         world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
         out.update(views_cycles(B, cycles, p, world, r_sense, "--no-staging" not in sys.argv, fov))
+    if teams:
+        world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
+        out.update(occupancy_cycles(B, cycles, p, world, r_sense, min(teams, B)))
     print(json.dumps(out))
 
 
