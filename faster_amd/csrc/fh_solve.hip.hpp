@@ -120,6 +120,7 @@ using fhw::wave_min; using fhw::wave_or; using fhw::wave_sum; using fhw::wave_su
 // values derived from it are recomputed where they are used instead of living in registers across the whole solve.
 __device__ __forceinline__ void in_flight(double (&a)[3]) { asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2])); }
 __device__ __forceinline__ void in_flight(double (&a)[4]) { asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])); }
+__device__ __forceinline__ void in_flight(double (&a)[5]) { asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4])); }
 __device__ __forceinline__ void in_flight(double (&a)[6]) {
   asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]));
 }
@@ -421,6 +422,9 @@ struct Solver {
   static constexpr int NT = NSEG + 1;
   static constexpr int ZS = NSEG | 1;        // row stride of the basis Zm[s][l] (odd: lanes of different segments hit different banks)
   static_assert(NSEG >= 3, "reduced space needs N - 2 > 0 columns");
+  // 3 NSEG <= 32 (the N = 6 and N = 10 buckets): the rows of the jerks, of the states and of a reduced normal fit in half a wavefront,
+  // and lanes l and l + 32 share the sum of row l (compute_states, moments) the way project() shares its sweeps
+  static constexpr bool HALF = 3 * NSEG <= 32;
   static constexpr int RPSZ = NVP * (NVP + 1) / 2;  // R is packed upper triangular, column major: R(r, c) = R[c(c+1)/2 + r]
   static __device__ __forceinline__ int rp(int r_, int c_) { return (c_ * (c_ + 1)) / 2 + r_; }
 
@@ -469,7 +473,7 @@ struct Solver {
 
   // ---- per-lane state kept in registers (LDS is what limits the number of resident solves) ----
   double p0r, v0r, a0r;   // lane = (tt, i) < 3 NT: state at the start of segment tt for y = 0: zero-jerk propagation of x0 plus the
-                          //   contribution of xp (per trial)
+                          //   contribution of xp (per trial).  HALF: lane = 3 (tt - 1) + i < 3 NSEG, tt >= 1 (the tt = 0 rows are x0)
   double xpr;             // lane = (s, i) < 3 N: jerk xp of the minimum-norm solution of the final-state equalities (per trial)
   double xj;              // lane = (s, i) < 3 N: current jerk xp + (Z y) (compute_states -> scan)
   double wbj, wbv, wba, wcp;  // inverse row norms IN THE REDUCED SPACE of this lane's box rows (lane = (t, i)) and corridor rows
@@ -663,25 +667,54 @@ struct Solver {
   // ---- x-space jerks in xs[] -> their contribution to the state at the start of segment tt = lane / 3 (lane < 3 NT) ----
   // sum_{s<tt} c(m) x_s with m = tt-1-s and c polynomial in m: three moments S_k = sum m^k x_s carry all three states
   // (cP = h^3 (1/6 + m/2 + m^2/2), cV = h^2 (1/2 + m), cA = h); nothing per-(lane, s) to keep in registers.
+  // HALF: the 3 N rows with tt >= 1 sit in lanes j = 3 (tt - 1) + i (the tt = 0 rows are x0 and are not computed); lane j sums the
+  // segments s < NSEG / 2 and lane j + 32 the segments s >= NSEG / 2 of row j, each in ascending s, and one halves_sum per moment
+  // joins them: both halves return the states of row j.  Every lane of the wavefront calls it.
   __device__ __forceinline__ void moments(double& dp, double& dv, double& da) const {
 #pragma clang fp contract(off)  // (inlined at several sites: the same roundings at each of them)
     const int lane = opaque(this->lane);  // (lane-derived constants are recomputed here, not kept in registers across the whole solve)
-    const int tt = lane / 3, i = lane - 3 * tt;
-    const int ii = lane < 3 * NT ? i : 0;
-    double xr[NSEG];
-#pragma unroll
-    for (int s = 0; s < NSEG; s++) xr[s] = xs[3 * s + ii];  // unpredicated (xs is zero beyond 3 N)
-    in_flight(xr);
     double s0 = 0, s1 = 0, s2 = 0;
-    const double dm0 = opaque((double)(tt - 1));
+    if constexpr (HALF) {
+      static_assert(!HALF || NSEG % 2 == 0, "the two halves take NSEG / 2 segments each");
+      constexpr int H = NSEG / 2;
+      const int row = lane & 31, hh = lane >> 5;
+      const int t1 = row / 3, i = row - 3 * t1;  // tt = t1 + 1
+      const double* xh = xs + 3 * H * hh + (row < 3 * NSEG ? i : 0);
+      double xr[H];
 #pragma unroll
-    for (int s = 0; s < NSEG; s++) {
-      const double dm = dm0 - (double)s;
-      const double xv = xr[s] * fmin(fmax(dm + 1.0, 0.0), 1.0);  // segments s >= tt contribute nothing
-      const double t1 = dm * xv;
-      s0 += xv;
-      s1 += t1;
-      s2 = fma(dm, t1, s2);
+      for (int s = 0; s < H; s++) xr[s] = xh[3 * s];  // unpredicated (xs is zero beyond 3 N)
+      in_flight(xr);
+      const int lim = opaque(t1 + 1 - H * hh);  // this half's segments below lim lie before tt
+      const double dm0 = (double)(lim - 1);
+#pragma unroll
+      for (int s = 0; s < H; s++) {
+        const double dm = dm0 - (double)s;
+        const double xv = s < lim ? xr[s] : 0.0;  // segments s >= tt contribute nothing (the sums start at +0: a select gives the
+        const double t1_ = dm * xv;               // bits the product with a 0 / 1 mask gave)
+        s0 += xv;
+        s1 += t1_;
+        s2 = fma(dm, t1_, s2);
+      }
+      s0 = halves_sum(s0);
+      s1 = halves_sum(s1);
+      s2 = halves_sum(s2);
+    } else {
+      const int tt = lane / 3, i = lane - 3 * tt;
+      const int ii = lane < 3 * NT ? i : 0;
+      double xr[NSEG];
+#pragma unroll
+      for (int s = 0; s < NSEG; s++) xr[s] = xs[3 * s + ii];  // unpredicated (xs is zero beyond 3 N)
+      in_flight(xr);
+      const double dm0 = opaque((double)(tt - 1));
+#pragma unroll
+      for (int s = 0; s < NSEG; s++) {
+        const double dm = dm0 - (double)s;
+        const double xv = xr[s] * fmin(fmax(dm + 1.0, 0.0), 1.0);  // segments s >= tt contribute nothing
+        const double t1 = dm * xv;
+        s0 += xv;
+        s1 += t1;
+        s2 = fma(dm, t1, s2);
+      }
     }
     const double h2 = h * h, h3 = h2 * h;
     dp = h3 * (s0 * (1.0 / 6.0) + 0.5 * s1 + 0.5 * s2);
@@ -710,9 +743,10 @@ struct Solver {
       cc_ = C[(k == 3 ? W_P : k) * BT_C_TT + tc + (k == 3 ? 1 : 0)];
     }
     double p, v, a;
-    {  // zero-jerk propagation of x0 to the start of segment tt = lane / 3
-      const int tt = lane / 3, i = lane - 3 * tt;
-      const bool on = lane < 3 * NT;
+    {  // zero-jerk propagation of x0 to the start of segment tt = lane / 3 (HALF: tt = lane / 3 + 1, the lane map of moments())
+      const int t0 = lane / 3, i = lane - 3 * t0;
+      const int tt = HALF ? t0 + 1 : t0;
+      const bool on = lane < (HALF ? 3 * NSEG : 3 * NT);
       // x0 lives in LDS: entries 0..2 of Pc / Vc / Ac (the state at the start of segment 0 IS x0; compute_states leaves them alone)
       const double p0 = on ? Pc[i] : 0.0;
       const double v0 = on ? Vc[i] : 0.0;
@@ -732,7 +766,8 @@ struct Solver {
       double endP = 0, endV = 0, endA = 0;
 #pragma unroll
       for (int i = 0; i < 3; i++) {
-        const double ep = readlane_f64(p, 3 * N + i), ev = readlane_f64(v, 3 * N + i), ea = readlane_f64(a, 3 * N + i);
+        const int le = 3 * (HALF ? N - 1 : N) + i;  // the lane that holds axis i of the state at the end of the trajectory (tt = N)
+        const double ep = readlane_f64(p, le), ev = readlane_f64(v, le), ea = readlane_f64(a, le);
         if (lane == i) { endP = ep; endV = ev; endA = ea; }
       }
       const int nrow = force_final ? 3 : 2, koff = 3 - nrow;
@@ -811,7 +846,31 @@ struct Solver {
   // ---- jerks x = xp + Z y, states at segment starts and Bezier control points of the current y ----
   __device__ void compute_states() {
     const int lane = opaque(this->lane);  // (lane-derived constants are recomputed here, not kept in registers across the whole solve)
-    {  // lane = (s, i): (Z y)_(s,i) = sum_k Zm[s][zc0 + k] y[3 k + i]
+    if constexpr (HALF) {  // lanes l and l + 32 = (s, i): the even and the odd k of (Z y)_(s,i), each in the order of a0 / a1 below
+      const int row = lane & 31, hh = lane >> 5;
+      const int s = row / 3, i = row - 3 * s;
+      const bool on = row < nx;
+      const double* zr = Zm + (on ? s : 0) * ZS + zc0 + hh;
+      const double* yr = x + (on ? i : 0) + 3 * hh;
+      double a = 0;
+      const int Kh = (K - hh + 1) >> 1;  // this half's terms k = 2 m + hh < K, m < Kh
+      const int kl = Kh > 0 ? Kh - 1 : 0;
+      for (int m0 = 0; m0 < ((K + 1) >> 1); m0 += 4) {
+        double zv[4], yv[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int m = min(m0 + j, kl);
+          zv[j] = zr[2 * m];
+          yv[j] = yr[6 * m];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) a += (m0 + j < Kh) ? zv[j] * yv[j] : 0.0;
+      }
+      const double az = halves_sum(a);  // a0 + a1, the roundings of the unsplit sweep
+      const double xz = lane < nx ? az : 0.0;
+      xj = xpr + xz;
+      if (lane < NXP) xs[lane] = xz;
+    } else {  // lane = (s, i): (Z y)_(s,i) = sum_k Zm[s][zc0 + k] y[3 k + i]
       const int s = lane / 3, i = lane - 3 * s;
       const bool on = lane < nx;
       const double* zr = Zm + (on ? s : 0) * ZS + zc0;
@@ -837,11 +896,15 @@ struct Solver {
       if (lane < NXP) xs[lane] = xz;
     }
     FH_SYNC();
-    if (lane < (N + 1) * 3) {
+    // (the start of segment 0 would store x0 + 0: the slots hold x0 itself, staged once per problem, and everything
+    // that needs x0 reads it there: setup_trial, dt_initial, the screening, the hand-off of a fused pair)
+    if constexpr (HALF) {
+      double dp, dv, da;
+      moments(dp, dv, da);  // (both halves of the wavefront work on the sums)
+      if (lane < 3 * N) { Pc[lane + 3] = p0r + dp; Vc[lane + 3] = v0r + dv; Ac[lane + 3] = a0r + da; }
+    } else if (lane < (N + 1) * 3) {
       double dp, dv, da;
       moments(dp, dv, da);
-      // (lanes 0..2 — the start of segment 0 — would store x0 + 0: the slots hold x0 itself, staged once per problem, and everything
-      // that needs x0 reads it there: setup_trial, dt_initial, the screening, the hand-off of a fused pair)
       if (lane >= 3) { Pc[lane] = p0r + dp; Vc[lane] = v0r + dv; Ac[lane] = a0r + da; }
     }
     FH_SYNC();
