@@ -183,11 +183,13 @@ def _norm3(v):
     return np.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
 
 
-def safe_path(jps_in, A, R_pos, r_known, drone_radius, max_poly_safe, unknown_pts=None):
+def safe_path(jps_in, A, R_pos, r_known, drone_radius, max_poly_safe, unknown_pts=None, trace=None):
     """JPS_safe of Faster::replan: JPS_in cut where it first comes within drone_radius of unknown space (getFirstCollisionJPS against the
     unknown map, :451-452 -> :767-926) and backed off by drone_radius, first vertex replaced by R, at most max_poly_safe legs (:478-490).
     Distance to unknown space: modelled as r_known - |p - A|, or — unknown_pts given (fh_pair_rule mode 2) — the distance to the nearest
-    of those points, as the reference's kd-tree returns it (no point at all: the path as it was)."""
+    of those points, as the reference's kd-tree returns it (no point at all: the path as it was).
+    trace: a list that receives (r, last_id, len(cur)) per iteration of the march — last_id is None for the iteration that ends it (the
+    cut, or a clear sphere around everything left); the result does not depend on it."""
     orig = [np.array(v, dtype=np.float64) for v in jps_in]
     cur = [v.copy() for v in orig]
     iteration = 0
@@ -200,6 +202,8 @@ def safe_path(jps_in, A, R_pos, r_known, drone_radius, max_poly_safe, unknown_pt
         else:
             r = max(r_known - _norm3(cur[0] - A), 0.0)
         if r < drone_radius:
+            if trace is not None:
+                trace.append((r, None, len(cur)))
             if iteration == 0:
                 orig = [orig[0], orig[0] + np.array([0.01, 0.0, 0.0])]
             else:
@@ -208,6 +212,8 @@ def safe_path(jps_in, A, R_pos, r_known, drone_radius, max_poly_safe, unknown_pt
                 orig = _shorten_by(orig, drone_radius)
             break
         inters, last_id, none_outside = _sphere_exit(cur, r, cur[0])
+        if trace is not None:
+            trace.append((r, None if none_outside else last_id, len(cur)))
         if none_outside:
             break
         cur = [inters] + cur[last_id + 1:]

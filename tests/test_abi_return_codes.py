@@ -13,6 +13,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from safe_corridor_edge_cases import SAFE_PATH_CAP
 from faster_amd import abi
 
 OK, ARG, DEV = 0, -1, -2
@@ -208,9 +209,10 @@ def context_table():
                                       bbox=bbox, radius=0.05, zg=0.0, fpp=96, n_seg=6, safe=d, sfaces=d, spaths=None, snp=None), **kw}.values())
     t += [("fh_safe_corridor_batch_device", safe(), DEV)]
     t += [("fh_safe_corridor_batch_device", safe(**kw), ARG) for kw in (
-        dict(n=-1), dict(n_cloud=-1), dict(max_points=1), dict(max_points=100), dict(max_poly=0), dict(max_poly=9), dict(fpp=7), dict(bbox=None),
+        dict(n=-1), dict(n_cloud=-1), dict(max_points=1), dict(max_points=100), dict(max_points=SAFE_PATH_CAP + 1), dict(max_poly=0), dict(max_poly=9),
+        dict(fpp=7), dict(bbox=None),
         dict(grid=None), dict(grid=g_res), dict(grid=g_dims), dict(n_seg=0), dict(n_seg=17), dict(r_frac=2.0), dict(r_frac=NAN))]
-    t += [("fh_safe_corridor_batch_device", safe(w=None), DEV)]
+    t += [("fh_safe_corridor_batch_device", safe(w=None), DEV), ("fh_safe_corridor_batch_device", safe(max_points=SAFE_PATH_CAP), DEV)]
     bad_fleet = [None, k(record(fp, delta_t=0)), k(record(fp, goal_radius=-1.0)), k(record(fp, wdy=0.0)), k(record(fp, ra=0.0)), k(record(fp, rule_mode=0))]
     for name, args in (("fh_fleet_init_device", lambda q, n, ms: (q, d, d, n, ms, d, d)),
                        ("fh_fleet_begin_device", lambda q, n, ms: (q, d, d, n, ms, d, d, d, d, d, d)),
