@@ -115,6 +115,26 @@ assert heading_dtype.itemsize == 96, heading_dtype.itemsize
 yaw_params_dtype = np.dtype([("w_max", "<f8"), ("alpha_filter_dyaw", "<f8"), ("dc", "<f8")], align=True)
 assert yaw_params_dtype.itemsize == 24, yaw_params_dtype.itemsize
 
+# fh_certificate / fh_certify_tol: certificates of solved trajectories (include/fasterhip_certify.h)
+FH_CERT_UNSOLVED, FH_CERT_BAD_INPUT, FH_CERT_NOT_FINITE, FH_CERT_CORRIDOR, FH_CERT_ASSIGNMENT = 1, 2, 4, 8, 16
+FH_CERT_X0, FH_CERT_XF, FH_CERT_CONTINUITY, FH_CERT_BOX, FH_CERT_COST = 32, 64, 128, 256, 512
+FH_CERT_STRUCTURAL = FH_CERT_UNSOLVED | FH_CERT_BAD_INPUT | FH_CERT_NOT_FINITE
+CERT_NUMBERS = ("corridor_assigned", "corridor_best", "x0_defect", "xf_defect", "continuity_defect", "v_excess", "a_excess", "j_excess", "v_peak",
+                "a_peak", "cost", "cost_defect")
+certificate_dtype = np.dtype([("flags", "<i4"), ("worst_seg", "<i4"), ("reserved_i", "<i4", (2,))] + [(k, "<f8") for k in CERT_NUMBERS]
+                             + [("reserved_d", "<f8", (2,))], align=True)
+assert certificate_dtype.itemsize == 128, certificate_dtype.itemsize
+certify_tol_dtype = np.dtype([("corridor", "<f8"), ("state", "<f8"), ("box", "<f8"), ("cost_rel", "<f8")], align=True)
+assert certify_tol_dtype.itemsize == 32
+
+
+def certify_tol(corridor, state=None, box=None, cost_rel=None):
+    """fh_certify_tol; one number stands for all four (the project's own number for "violated" is fh_params.feas_tol)."""
+    t = np.zeros((), dtype=certify_tol_dtype)
+    t["corridor"] = corridor
+    t["state"], t["box"], t["cost_rel"] = (corridor if v is None else v for v in (state, box, cost_rel))
+    return t
+
 
 def default_yaw_params(dc=0.01):
     """fh_yaw_params with the values of faster/param/faster.yaml: w_max 4.0, alpha_filter_dyaw 0."""

@@ -32,6 +32,8 @@ SYMBOLS = [
 # include/fasterhip_occupancy.h (SYMBOLS is what include/fasterhip.h itself declares)
 OCCUPANCY_SYMBOLS = ["fh_map_read_views_device", "fh_map_view_occupancy", "fh_map_plan_batch_radius_views_device", "fh_set_point_views_device",
                      "fh_fleet_observe_device"]
+# include/fasterhip_certify.h
+CERTIFY_SYMBOLS = ["fh_certify_batch_device", "fh_certify_batch"]
 
 _LIB = None
 
@@ -253,6 +255,10 @@ def lib():
         L.fh_set_point_views_device.argtypes = [vp, vp, i32, vp, i32]
         L.fh_fleet_observe_device.restype = i32
         L.fh_fleet_observe_device.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, i32]
+        L.fh_certify_batch_device.restype = i32
+        L.fh_certify_batch_device.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp]
+        L.fh_certify_batch.restype = i32
+        L.fh_certify_batch.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -669,6 +675,29 @@ class Context:
         self._check(lib().fh_dt_initial_batch(self._h, abi.ptr(problems), problems.shape[0], abi.ptr(dt)), "fh_dt_initial_batch")
         return dt
 
+    @staticmethod
+    def _certify_tol(tol):
+        """None, or a C-contiguous fh_certify_tol record (kept alive by the caller for the length of the call)."""
+        if tol is None:
+            return None
+        t = np.ascontiguousarray(tol)
+        if t.dtype != abi.certify_tol_dtype or t.size != 1:
+            raise FasterHipError("certify: tol must be None or one abi.certify_tol_dtype record (abi.certify_tol), got dtype %s, %d elements"
+                                 % (t.dtype, t.size))
+        return t.reshape(1)
+
+    def certify_batch(self, problems, faces, results, tol=None):
+        """fh_certify_batch: [n] abi.certificate_dtype, the certificate of results[i] as a solution of problems[i] over `faces`
+        (include/fasterhip_certify.h).  tol: None (only the structural flags) or abi.certify_tol(...)."""
+        problems, faces, results = np.ascontiguousarray(problems), np.ascontiguousarray(faces), np.ascontiguousarray(results)
+        assert problems.dtype == abi.problem_dtype and faces.dtype == abi.face_dtype and results.dtype == abi.result_dtype
+        assert problems.shape[0] == results.shape[0]
+        out = np.zeros(problems.shape[0], dtype=abi.certificate_dtype)
+        t = self._certify_tol(tol)
+        self._check(lib().fh_certify_batch(self._h, abi.ptr(problems), abi.ptr(faces) if faces.shape[0] else None, faces.shape[0], abi.ptr(results),
+                                           problems.shape[0], None if t is None else abi.ptr(t), abi.ptr(out)), "fh_certify_batch")
+        return out
+
     def solve_batch(self, problems, faces):
         problems = np.ascontiguousarray(problems)
         faces = np.ascontiguousarray(faces)
@@ -729,6 +758,12 @@ class Context:
     def solve_batch_device(self, d_problems, d_faces, n, max_seg, max_faces, d_results):
         self._check(lib().fh_solve_batch_device(self._h, d_problems, d_faces, n, max_seg, max_faces, d_results),
                     "fh_solve_batch_device")
+
+    def certify_batch_device(self, d_problems, d_faces, n_faces, d_results, n, d_out, tol=None):
+        """fh_certify_batch_device: d_out [n] fh_certificate; asynchronous on the context's stream.  tol as for certify_batch."""
+        t = self._certify_tol(tol)
+        self._check(lib().fh_certify_batch_device(self._h, d_problems, d_faces, int(n_faces), d_results, n, None if t is None else abi.ptr(t),
+                                                  d_out), "fh_certify_batch_device")
 
     def sample_batch_device(self, d_problems, d_results, n, max_samples, d_states, d_counts):
         self._check(lib().fh_sample_batch_device(self._h, d_problems, d_results, n, max_samples, d_states, d_counts),

@@ -18,11 +18,13 @@
 
 #include "../../include/fasterhip.h"
 #include "../../include/fasterhip_occupancy.h"
+#include "../../include/fasterhip_certify.h"
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
 #include "fh_decomp.hip.hpp"
 #include "fh_safe.hip.hpp"  // (after fh_solve: it switches FP contraction off for what follows, like fh_decomp)
 #include "fh_fleet.hip.hpp"
+#include "fh_certify.hip.hpp"
 #include "fh_host.hpp"
 
 using fhh::DeviceScope;
@@ -33,10 +35,10 @@ enum Buf {
   // Staging of the host-pointer entry points.  ONLY the synchronous host-pointer entry points may touch these five: each copies its inputs
   // in, launches, copies its outputs out and waits for the stream before it returns, so no launch in flight ever reads them — and what
   // they hold differs from one entry point to the next.
-  HOST_STAGE_0,  // fh_solve_batch, fh_sample_batch, fh_dt_initial_batch: the problems; fh_decompose_batch: the cloud
-  HOST_STAGE_1,  // fh_solve_batch: the faces; fh_decompose_batch: the segments
-  HOST_STAGE_2,  // fh_solve_batch: the results (out); fh_sample_batch: the results (in)
-  HOST_STAGE_3,  // fh_sample_batch: the states (out); fh_decompose_batch: the faces (out); fh_fp64_peak: its scratch
+  HOST_STAGE_0,  // fh_solve_batch, fh_sample_batch, fh_dt_initial_batch, fh_certify_batch: the problems; fh_decompose_batch: the cloud
+  HOST_STAGE_1,  // fh_solve_batch, fh_certify_batch: the faces; fh_decompose_batch: the segments
+  HOST_STAGE_2,  // fh_solve_batch: the results (out); fh_sample_batch, fh_certify_batch: the results (in)
+  HOST_STAGE_3,  // fh_sample_batch: the states (out); fh_decompose_batch: the faces (out); fh_fp64_peak: its scratch; fh_certify_batch: the certificates (out)
   HOST_STAGE_4,  // fh_sample_batch, fh_decompose_batch: the counts (out); fh_dt_initial_batch: dt (out)
   // Everything below is working memory of launches on the context's stream: a launch in flight MAY still use it.  Launches of one
   // stream run in order, so the next launch may reuse it, and reserve() waits for the stream before it frees.
@@ -916,6 +918,50 @@ int fh_dt_initial_batch(fh_ctx* ctx, const fh_problem* problems, int n, double* 
   FH_HIP(hipMemcpyAsync(d_problems, problems, sizeof(fh_problem) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = fh_dt_initial_batch_device(ctx, d_problems, n, d_dt)) != FH_OK) return rc;
   FH_HIP(hipMemcpyAsync(dt, d_dt, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  FH_HIP(hipStreamSynchronize(ctx->stream));
+  return FH_OK;
+}
+
+// ---- certificates (include/fasterhip_certify.h): one wavefront per result, no working buffer of the context ----
+static bool certify_tol_ok(const fh_certify_tol* tol) {  // (a NaN fails every comparison)
+  return !tol || (tol->corridor >= 0 && tol->state >= 0 && tol->box >= 0 && tol->cost_rel >= 0);
+}
+
+int fh_certify_batch_device(fh_ctx* ctx, const fh_problem* d_problems, const fh_face* d_faces, int64_t n_faces, const fh_result* d_results,
+                            int n, const fh_certify_tol* tol, fh_certificate* d_out) {
+  if (!ctx || n < 0 || n_faces < 0 || !certify_tol_ok(tol)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_problems || !d_results || !d_out || (n_faces > 0 && !d_faces)) return FH_ERR_ARG;
+  const fh::CertTol t = tol ? fh::CertTol{tol->corridor, tol->state, tol->box, tol->cost_rel, 1} : fh::CertTol{0.0, 0.0, 0.0, 0.0, 0};
+  hipLaunchKernelGGL(fh::certify_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, d_problems, d_faces, (long long)n_faces, d_results,
+                     n, t, d_out);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_certify_batch(fh_ctx* ctx, const fh_problem* problems, const fh_face* faces, int64_t n_faces, const fh_result* results, int n,
+                     const fh_certify_tol* tol, fh_certificate* out) {
+  if (!ctx || n < 0 || n_faces < 0 || !certify_tol_ok(tol)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!problems || !results || !out || (n_faces > 0 && !faces)) return FH_ERR_ARG;
+  int rc;
+  if ((rc = ensure(ctx, HOST_STAGE_0, sizeof(fh_problem) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_1, sizeof(fh_face) * (size_t)std::max<int64_t>(n_faces, 1))) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_2, sizeof(fh_result) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, HOST_STAGE_3, sizeof(fh_certificate) * (size_t)n)) != FH_OK) return rc;
+  fh_problem* d_problems = ctx->buf[HOST_STAGE_0].as<fh_problem>();
+  fh_face* d_faces = ctx->buf[HOST_STAGE_1].as<fh_face>();
+  fh_result* d_results = ctx->buf[HOST_STAGE_2].as<fh_result>();
+  fh_certificate* d_out = ctx->buf[HOST_STAGE_3].as<fh_certificate>();
+  FH_HIP(hipMemcpyAsync(d_problems, problems, sizeof(fh_problem) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (n_faces > 0) FH_HIP(hipMemcpyAsync(d_faces, faces, sizeof(fh_face) * (size_t)n_faces, hipMemcpyHostToDevice, ctx->stream));
+  FH_HIP(hipMemcpyAsync(d_results, results, sizeof(fh_result) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = fh_certify_batch_device(ctx, d_problems, d_faces, n_faces, d_results, n, tol, d_out)) != FH_OK) return rc;
+  FH_HIP(hipMemcpyAsync(out, d_out, sizeof(fh_certificate) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
   return FH_OK;
 }

@@ -107,6 +107,14 @@ __device__ __forceinline__ double wave_max(double v) {
   v = fmax(v, dpp_f64<0x142, 0xa>(-INFINITY, v)); v = fmax(v, dpp_f64<0x143, 0xc>(-INFINITY, v));  // across the rows
   return readlane_f64(v, 63);
 }
+// max over each aligned group of four lanes, the result in all four of them (quad_perm [1,0,3,2], then [2,3,0,1]).  Written as the
+// comparison `o > v ? o : v`, not fmax: with no NaN among the inputs there is none in the result.  All 64 lanes must be active.
+__device__ __forceinline__ double quad_max(double v) {
+  double o = dpp0_f64<0xB1>(v);
+  v = o > v ? o : v;
+  o = dpp0_f64<0x4E>(v);
+  return o > v ? o : v;
+}
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ int dpp_min_step(int v) {
   const int o = __builtin_amdgcn_update_dpp(0x7fffffff, v, CTRL, ROW_MASK, 0xf, false);

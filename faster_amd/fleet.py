@@ -367,6 +367,25 @@ class Fleet:
         self.sync()
         return self.d_goal_yaw.cpu().numpy().copy()
 
+    def certify(self, tol=None):
+        """Certificates of the last replan() (include/fasterhip_certify.h), computed on the device from the fleet's own problem, face and
+        result buffers: {"whole": [n] abi.certificate_dtype, "safe": [n] abi.certificate_dtype}.  A vehicle whose stage never reached a
+        solve has FH_CERT_UNSOLVED.  A measurement: nothing of the fleet changes, committing stays unconditional (synchronises)."""
+        t, B = self.torch, self.n
+        d_cw, d_cs = (t.zeros(B * abi.certificate_dtype.itemsize, dtype=t.uint8, device=self.dev) for _ in range(2))
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            self.ctx.certify_batch_device(self.d_whole.data_ptr(), self.d_wf.data_ptr(), B * self.fpp, self.d_wr.data_ptr(), B, d_cw.data_ptr(), tol)
+            self.ctx.certify_batch_device(self.d_safe.data_ptr(), self.d_sf.data_ptr(), B * self.fpp, self.d_sr.data_ptr(), B, d_cs.data_ptr(), tol)
+            d_cw.record_stream(self.stream)
+            d_cs.record_stream(self.stream)
+        return {"whole": self._host(d_cw, abi.certificate_dtype), "safe": self._host(d_cs, abi.certificate_dtype)}
+
+    def faces(self):
+        """The face rows of the last cycle on the host: {"whole": [n * faces_per_problem] abi.face_dtype, "safe": the same}; the problems
+        of results() address them through face_begin / face_off (diagnostics)."""
+        return {"whole": self._host(self.d_wf, abi.face_dtype), "safe": self._host(self.d_sf, abi.face_dtype)}
+
     def plans(self):
         """[n] lists of committed states (abi.state_dtype arrays), front first."""
         v = self.vehicles()
