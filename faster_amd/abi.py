@@ -128,6 +128,31 @@ certify_tol_dtype = np.dtype([("corridor", "<f8"), ("state", "<f8"), ("box", "<f
 assert certify_tol_dtype.itemsize == 32
 
 
+# fh_audit_params / fh_plan_audit: the audit of committed plans (include/fasterhip_audit.h)
+FH_AUDIT_BAD_PLAN, FH_AUDIT_NO_VIEW, FH_AUDIT_NOT_FINITE, FH_AUDIT_UNKNOWN, FH_AUDIT_OCCUPIED = 1, 2, 4, 8, 16
+FH_AUDIT_LIST_POINTS, FH_AUDIT_SLAB_CELLS = 256, 65536   # the kernel's LDS point list and the cells of one LDS slab
+audit_params_dtype = np.dtype([("r_unknown", "<f8"), ("r_occupied", "<f8"), ("cap", "<f8"), ("stride", "<i4"), ("count", "<i4")], align=True)
+assert audit_params_dtype.itemsize == 32
+plan_audit_dtype = np.dtype([("flags", "<i4"), ("n_tested", "<i4"), ("first_unknown", "<i4"), ("worst_unknown", "<i4"), ("first_occupied", "<i4"),
+                             ("worst_occupied", "<i4"), ("view", "<i4"), ("reserved", "<i4"), ("min_unknown_d2", "<f8"), ("min_occupied_d2", "<f8"),
+                             ("reserved_d", "<f8", (2,))], align=True)
+assert plan_audit_dtype.itemsize == 64, plan_audit_dtype.itemsize
+
+
+def default_audit_params(drone_radius):
+    """fh_audit_params: near is closer than drone_radius on both sides, nothing beyond two radii is looked at, every state is tested."""
+    p = np.zeros((), dtype=audit_params_dtype)
+    p["r_unknown"] = p["r_occupied"] = drone_radius
+    p["cap"], p["stride"], p["count"] = 2.0 * drone_radius, 1, 0
+    return p
+
+
+def audit_distances(audit):
+    """(unknown, occupied): the distances of [n] plan_audit_dtype records, the square roots of the squared distances the device reports
+    (inf: nothing within cap)."""
+    return np.sqrt(audit["min_unknown_d2"]), np.sqrt(audit["min_occupied_d2"])
+
+
 def certify_tol(corridor, state=None, box=None, cost_rel=None):
     """fh_certify_tol; one number stands for all four (the project's own number for "violated" is fh_params.feas_tol)."""
     t = np.zeros((), dtype=certify_tol_dtype)

@@ -34,6 +34,8 @@ OCCUPANCY_SYMBOLS = ["fh_map_read_views_device", "fh_map_view_occupancy", "fh_ma
                      "fh_fleet_observe_device"]
 # include/fasterhip_certify.h
 CERTIFY_SYMBOLS = ["fh_certify_batch_device", "fh_certify_batch"]
+# include/fasterhip_audit.h
+AUDIT_SYMBOLS = ["fh_fleet_audit_device"]
 
 _LIB = None
 
@@ -259,6 +261,8 @@ def lib():
         L.fh_certify_batch_device.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp]
         L.fh_certify_batch.restype = i32
         L.fh_certify_batch.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp]
+        L.fh_fleet_audit_device.restype = i32
+        L.fh_fleet_audit_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, i32, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -764,6 +768,25 @@ class Context:
         t = self._certify_tol(tol)
         self._check(lib().fh_certify_batch_device(self._h, d_problems, d_faces, int(n_faces), d_results, n, None if t is None else abi.ptr(t),
                                                   d_out), "fh_certify_batch_device")
+
+    def fleet_audit_device(self, par, d_vehicles, d_plans, n, max_states, d_out, grid=None, d_flags=None, view_stride=0, d_view_of=None, n_views=0,
+                           d_cloud=None, n_cloud=0, d_point_mask=None, mask_words=0):
+        """fh_fleet_audit_device: d_out [n] fh_plan_audit, the committed plans against unknown space (d_flags on grid = (origin, res, dims),
+        one view per vehicle as in fleet_sense_device) and against the cloud (through d_point_mask, or every point); par: one
+        abi.audit_params_dtype record.  Asynchronous on the context's stream (include/fasterhip_audit.h)."""
+        p = np.ascontiguousarray(par)
+        if p.dtype != abi.audit_params_dtype or p.size != 1:
+            raise FasterHipError("fleet_audit_device: par must be one abi.audit_params_dtype record (abi.default_audit_params), got dtype %s, %d elements"
+                                 % (p.dtype, p.size))
+        p = p.reshape(1)
+        g = None
+        if grid is not None:
+            g = np.zeros((), dtype=abi.voxel_grid_dtype)
+            g["origin"], g["res"], g["dims"] = grid
+            g = np.ascontiguousarray(g).reshape(1)
+        self._check(lib().fh_fleet_audit_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states), None if g is None else abi.ptr(g),
+                                                d_flags, int(view_stride), d_view_of, int(n_views), d_cloud, int(n_cloud), d_point_mask, int(mask_words),
+                                                d_out), "fh_fleet_audit_device")
 
     def sample_batch_device(self, d_problems, d_results, n, max_samples, d_states, d_counts):
         self._check(lib().fh_sample_batch_device(self._h, d_problems, d_results, n, max_samples, d_states, d_counts),

@@ -19,12 +19,14 @@
 #include "../../include/fasterhip.h"
 #include "../../include/fasterhip_occupancy.h"
 #include "../../include/fasterhip_certify.h"
+#include "../../include/fasterhip_audit.h"
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
 #include "fh_decomp.hip.hpp"
 #include "fh_safe.hip.hpp"  // (after fh_solve: it switches FP contraction off for what follows, like fh_decomp)
 #include "fh_fleet.hip.hpp"
 #include "fh_certify.hip.hpp"
+#include "fh_audit.hip.hpp"
 #include "fh_host.hpp"
 
 using fhh::DeviceScope;
@@ -963,6 +965,44 @@ int fh_certify_batch(fh_ctx* ctx, const fh_problem* problems, const fh_face* fac
   if ((rc = fh_certify_batch_device(ctx, d_problems, d_faces, n_faces, d_results, n, tol, d_out)) != FH_OK) return rc;
   FH_HIP(hipMemcpyAsync(out, d_out, sizeof(fh_certificate) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   FH_HIP(hipStreamSynchronize(ctx->stream));
+  return FH_OK;
+}
+
+// ---- the audit of committed plans (include/fasterhip_audit.h): one wavefront per vehicle, no working buffer of the context ----
+static bool audit_radius_ok(double r) { return r >= 0 && r < INFINITY; }  // (a NaN fails the first comparison)
+
+int fh_fleet_audit_device(fh_ctx* ctx, const fh_audit_params* par, const fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states,
+                          const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                          const double* d_cloud_xyz, int n_cloud, const uint32_t* d_point_mask, int mask_words, fh_plan_audit* d_out) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->r_unknown) || !audit_radius_ok(par->r_occupied) || !audit_radius_ok(par->cap) || !(par->cap > 0)) return FH_ERR_ARG;
+  if (par->r_unknown > par->cap || par->r_occupied > par->cap || par->stride < 1 || par->count < 0) return FH_ERR_ARG;
+  if (n < 0 || max_states < 1) return FH_ERR_ARG;
+  if (d_flags) {
+    if (!fhh::voxel_grid_ok(grid) || par->cap > 64.0 * grid->res || n_views < 1) return FH_ERR_ARG;
+    if (view_stride != 0 && view_stride < (size_t)fhh::voxel_grid_cells(*grid)) {
+      ctx->err = "fh_fleet_audit_device: view_stride is smaller than a view (dims[0] * dims[1] * dims[2] bytes)";
+      return FH_ERR_ARG;
+    }
+  }
+  if (d_point_mask && (mask_words < 0 || (long long)mask_words * 32 < (long long)n_cloud || n_views < 1)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_out) return FH_ERR_ARG;
+  fh::AuditArgs a;
+  a.r2_unknown = par->r_unknown * par->r_unknown; a.r2_occupied = par->r_occupied * par->r_occupied;
+  a.cap = par->cap; a.cap2 = par->cap * par->cap;
+  a.stride = par->stride; a.count = par->count; a.n = n; a.max_states = max_states;
+  a.vehicles = d_vehicles; a.plans = d_plans;
+  a.ox = a.oy = a.oz = 0.0; a.res = 1.0; a.nx = a.ny = a.nz = 1;
+  if (d_flags) fhh::set_lattice(a, *grid);
+  a.n_views = n_views; a.flags = d_flags; a.view_stride = view_stride; a.view_of = d_view_of;
+  a.cloud = n_cloud > 0 ? d_cloud_xyz : nullptr; a.n_cloud = n_cloud > 0 ? n_cloud : 0;
+  a.mask = d_point_mask; a.mask_words = mask_words;
+  a.out = d_out;
+  hipLaunchKernelGGL(fh::audit_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
   return FH_OK;
 }
 

@@ -381,6 +381,44 @@ class Fleet:
             d_cs.record_stream(self.stream)
         return {"whole": self._host(d_cw, abi.certificate_dtype), "safe": self._host(d_cs, abi.certificate_dtype)}
 
+    def audit_device(self, r_unknown=None, r_occupied=None, cap=None, stride=1, count=0, truth=False):
+        """audit() without the copy to the host: one launch on the fleet's stream; returns the device tensor of [n] fh_plan_audit records
+        as bytes (asynchronous)."""
+        t, B = self.torch, self.n
+        radius = float(self.params["rule"]["drone_radius"])
+        par = abi.default_audit_params(radius)
+        if r_unknown is not None:
+            par["r_unknown"] = r_unknown
+        if r_occupied is not None:
+            par["r_occupied"] = r_occupied
+        par["cap"] = 2.0 * max(float(par["r_unknown"]), float(par["r_occupied"])) if cap is None else cap
+        par["stride"], par["count"] = stride, count
+        kw = {}
+        if not truth:
+            if self.view_flags is not None:
+                kw = dict(grid=self.grid, d_flags=self.view_flags.data_ptr(), view_stride=self.view_flags.shape[1],
+                          d_view_of=None if self.view_of is None else self.view_of.data_ptr(), n_views=self.n_views)
+                if self.point_mask is not None:
+                    kw.update(d_point_mask=self.point_mask.data_ptr(), mask_words=self.point_mask.shape[1])
+            elif self.flags is not None:
+                kw = dict(grid=self.grid, d_flags=self.flags.data_ptr(), view_stride=0, n_views=1)
+        if self.cloud is not None and self.n_cloud > 0:
+            kw.update(d_cloud=self.cloud.data_ptr(), n_cloud=self.n_cloud)
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            d_out = t.empty(B * abi.plan_audit_dtype.itemsize, dtype=t.uint8, device=self.dev)  # (the kernel writes every byte of every record)
+            self.ctx.fleet_audit_device(par, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), B, self.max_states, d_out.data_ptr(), **kw)
+        return d_out
+
+    def audit(self, r_unknown=None, r_occupied=None, cap=None, stride=1, count=0, truth=False):
+        """The committed plans, the states the vehicles fly, against unknown and occupied space (include/fasterhip_audit.h): [n]
+        abi.plan_audit_dtype with squared distances (abi.audit_distances takes the roots).  The radii default to
+        params["rule"]["drone_radius"], cap to twice the larger of them.  Unknown space is whatever the fleet has: one grid, views, or none;
+        occupied space is the cloud through the point masks of set_point_views, else the whole cloud.  truth=True passes no flags and no
+        masks: the occupied side against every point.  count=params["delta_t"] audits the states the next replan cannot change.  A
+        measurement: nothing of the fleet is written (synchronises)."""
+        return self._host(self.audit_device(r_unknown, r_occupied, cap, stride, count, truth), abi.plan_audit_dtype)
+
     def faces(self):
         """The face rows of the last cycle on the host: {"whole": [n * faces_per_problem] abi.face_dtype, "safe": the same}; the problems
         of results() address them through face_begin / face_off (diagnostics)."""

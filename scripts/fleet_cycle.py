@@ -19,7 +19,11 @@ share views (view_of).
 TEAMS — the jump point search keeps 64 bytes per cell and view, so a view per vehicle is for small fleets), unknown views and point masks
 all unknown at first, world inflation half a cell (with more than a cell the points inside a blob are never observed), the closed loop
 sense -> observe -> replan -> 5 ticks with "observe" and "map_views" as stages of their own.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]"""
+--audit adds "audit" beside every stage table: the plan audit (Fleet.audit_device: every committed state against the unknown space and the
+points the fleet of that table has, radii = drone_radius, cap = twice that) after the last replan of that table, fenced by events like a
+stage ("ms", the median of as many calls as there are timed cycles), with the states it tested and the vehicles it flags.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+                                         [--audit]"""
 import json
 import os
 import sys
@@ -31,6 +35,27 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from faster_amd import abi, capi, frontend  # noqa: E402
 from faster_amd.fleet import Fleet  # noqa: E402
+
+
+AUDIT = "--audit" in sys.argv
+
+
+def timed_audit(fl, cycles):
+    """The audit of the plans as they stand, `cycles` times, fenced by events like a stage; the last records on the host for the counts."""
+    ms = []
+    fl.audit_device()   # (warm-up)
+    for _ in range(max(cycles, 1)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(fl.stream)
+        d_out = fl.audit_device()
+        e1.record(fl.stream)
+        fl.sync()
+        ms.append(e0.elapsed_time(e1))
+    rec = d_out.cpu().numpy().view(abi.plan_audit_dtype)
+    return {"ms": float(np.median(ms)), "tested_states": int(rec["n_tested"].sum()),
+            "near_unknown": int(((rec["flags"] & abi.FH_AUDIT_UNKNOWN) != 0).sum()),
+            "near_occupied": int(((rec["flags"] & abi.FH_AUDIT_OCCUPIED) != 0).sum()),
+            "not_finite": int(((rec["flags"] & abi.FH_AUDIT_NOT_FINITE) != 0).sum())}
 
 
 def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False):
@@ -88,9 +113,12 @@ def sensing_loop(fl, views, cycles, states, goals, r_sense, fov=None):
         fl.sync()
         t.append(1e3 * (time.perf_counter() - t0))
     v = fl.vehicles()
-    return first, {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "cycle_ms": float(np.median(t)),
-                   "committed_last": int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum()),
-                   "unknown_fraction_end": float(views.float().mean().item())}
+    loop = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "cycle_ms": float(np.median(t)),
+            "committed_last": int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum()),
+            "unknown_fraction_end": float(views.float().mean().item())}
+    if AUDIT:
+        loop["audit"] = timed_audit(fl, cycles)
+    return first, loop
 
 
 def views_cycles(B, cycles, p, world, r_sense, staging, fov=None):
@@ -111,6 +139,8 @@ def views_cycles(B, cycles, p, world, r_sense, staging, fov=None):
         fl.sync()
         med = timed_cycles(fl, cycles)
         out["views_same_flags"] = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values()))}
+        if AUDIT:
+            out["views_same_flags"]["audit"] = timed_audit(fl, cycles)
         # the closed loop: everything unknown at first, the vehicles back at their starts
         out["sense_first_ms"], out["views_sensing"] = sensing_loop(fl, views, cycles, states, goals, r_sense)
         if fov is not None:
@@ -156,6 +186,8 @@ def occupancy_cycles(B, cycles, p, world, r_sense, teams):
                     "committed_last": int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum()),
                     "points_known_fraction_end": float(np.unpackbits(known.view(np.uint8)).sum() / (teams * len(cloud))),
                     "unknown_fraction_end": float(fl.view_flags.float().mean().item())})
+        if AUDIT:
+            out["audit"] = timed_audit(fl, cycles)
     finally:
         fl.close()
     return {"occupancy": out}
@@ -260,6 +292,8 @@ def main():
                     "fleet_kernels_ms": fleet_ms, "fleet_kernels_share": fleet_ms / float(sum(med.values())),
                     "committed": committed, "committed_with_k_end_whole": kend, "commit_bytes": cb,
                     "commit_write_gbs": cb / (med["commit"] * 1e-3) / 1e9, "hbm_copy_gbs": copy_gbs})
+        if AUDIT:
+            out["audit"] = timed_audit(fl, cycles)
     finally:
         fl.close()
     if "--views" in sys.argv or fov is not None:
