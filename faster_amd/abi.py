@@ -153,6 +153,31 @@ def audit_distances(audit):
     return np.sqrt(audit["min_unknown_d2"]), np.sqrt(audit["min_occupied_d2"])
 
 
+# fh_separation_params / fh_plan_separation: the committed plans against each other (include/fasterhip_separation.h)
+FH_SEP_BAD_PLAN, FH_SEP_NOT_FINITE, FH_SEP_NEAR = 1, 4, 8
+FH_SEP_LIST_VEHICLES, FH_SEP_MAX_CELLS = 256, 1 << 20   # the narrow phase's LDS list of vehicles; the most cells of the broad phase's grid
+separation_params_dtype = np.dtype([("r", "<f8"), ("cap", "<f8"), ("stride", "<i4"), ("count", "<i4"), ("reserved", "<i4", (2,))], align=True)
+assert separation_params_dtype.itemsize == 32
+plan_separation_dtype = np.dtype([("flags", "<i4"), ("n_tested", "<i4"), ("first", "<i4"), ("first_other", "<i4"), ("worst", "<i4"),
+                                  ("worst_other", "<i4"), ("n_near", "<i4"), ("reserved", "<i4"), ("min_d2", "<f8"), ("reserved_d", "<f8", (3,))],
+                                 align=True)
+assert plan_separation_dtype.itemsize == 64, plan_separation_dtype.itemsize
+
+
+def default_separation_params(radius):
+    """fh_separation_params: two vehicles are near when their centres are closer than `radius` (two hulls of drone_radius touch at twice
+    that), nothing beyond two radii is looked at, every state is tested."""
+    p = np.zeros((), dtype=separation_params_dtype)
+    p["r"], p["cap"], p["stride"], p["count"] = radius, 2.0 * radius, 1, 0
+    return p
+
+
+def separation_distances(separation):
+    """The distances of [n] plan_separation_dtype records: the square roots of the squared distances the device reports (inf: no other
+    vehicle within cap)."""
+    return np.sqrt(separation["min_d2"])
+
+
 def certify_tol(corridor, state=None, box=None, cost_rel=None):
     """fh_certify_tol; one number stands for all four (the project's own number for "violated" is fh_params.feas_tol)."""
     t = np.zeros((), dtype=certify_tol_dtype)

@@ -36,6 +36,8 @@ OCCUPANCY_SYMBOLS = ["fh_map_read_views_device", "fh_map_view_occupancy", "fh_ma
 CERTIFY_SYMBOLS = ["fh_certify_batch_device", "fh_certify_batch"]
 # include/fasterhip_audit.h
 AUDIT_SYMBOLS = ["fh_fleet_audit_device"]
+# include/fasterhip_separation.h
+SEPARATION_SYMBOLS = ["fh_fleet_separation_device"]
 
 _LIB = None
 
@@ -263,6 +265,8 @@ def lib():
         L.fh_certify_batch.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp]
         L.fh_fleet_audit_device.restype = i32
         L.fh_fleet_audit_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, i32, vp]
+        L.fh_fleet_separation_device.restype = i32
+        L.fh_fleet_separation_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -787,6 +791,23 @@ class Context:
         self._check(lib().fh_fleet_audit_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states), None if g is None else abi.ptr(g),
                                                 d_flags, int(view_stride), d_view_of, int(n_views), d_cloud, int(n_cloud), d_point_mask, int(mask_words),
                                                 d_out), "fh_fleet_audit_device")
+
+    def fleet_separation_device(self, par, d_vehicles, d_plans, n, max_states, cells, d_out):
+        """fh_fleet_separation_device: d_out [n] fh_plan_separation, the committed plans against each other; par: one
+        abi.separation_params_dtype record; cells = (origin, res, dims): the grid of the broad phase, on which no field of a record
+        depends.  Asynchronous on the context's stream (include/fasterhip_separation.h)."""
+        p = np.ascontiguousarray(par)
+        if p.dtype != abi.separation_params_dtype or p.size != 1:
+            raise FasterHipError("fleet_separation_device: par must be one abi.separation_params_dtype record (abi.default_separation_params), "
+                                 "got dtype %s, %d elements" % (p.dtype, p.size))
+        p = p.reshape(1)
+        g = None
+        if cells is not None:
+            g = np.zeros((), dtype=abi.voxel_grid_dtype)
+            g["origin"], g["res"], g["dims"] = cells
+            g = np.ascontiguousarray(g).reshape(1)
+        self._check(lib().fh_fleet_separation_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states),
+                                                     None if g is None else abi.ptr(g), d_out), "fh_fleet_separation_device")
 
     def sample_batch_device(self, d_problems, d_results, n, max_samples, d_states, d_counts):
         self._check(lib().fh_sample_batch_device(self._h, d_problems, d_results, n, max_samples, d_states, d_counts),

@@ -20,6 +20,7 @@
 #include "../../include/fasterhip_occupancy.h"
 #include "../../include/fasterhip_certify.h"
 #include "../../include/fasterhip_audit.h"
+#include "../../include/fasterhip_separation.h"
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
 #include "fh_decomp.hip.hpp"
@@ -27,6 +28,7 @@
 #include "fh_fleet.hip.hpp"
 #include "fh_certify.hip.hpp"
 #include "fh_audit.hip.hpp"
+#include "fh_separation.hip.hpp"
 #include "fh_host.hpp"
 
 using fhh::DeviceScope;
@@ -59,6 +61,14 @@ enum Buf {
   SAFE_SCRATCH,  // fh_safe_corridor_batch_device: safe paths, spheres, goals, offsets and counts between its kernels
   SEG_SPHERES,   // fh_safe_corridor_batch_device: safe_spheres_kernel writes the sphere of every segment, decomp_kernel reads them
   SEG_COUNTER,   // decompose_device zeroes it on the stream; decomp_kernel's workgroups draw their segments from it
+  SEP_BOXES,     // fh_fleet_separation_device: sep_boxes_kernel writes box, checked plan extent and validity word of every vehicle;
+                 // sep_fill_kernel and sep_narrow_kernel read them
+  SEP_COUNTS,    // fh_fleet_separation_device zeroes them on the stream; sep_boxes_kernel counts the vehicles of every cell, sep_scan_kernel
+                 // reads them and leaves zeros, sep_fill_kernel draws the places inside a cell from them
+  SEP_STARTS,    // sep_scan_kernel writes the first item of every cell (and the total behind the last); sep_fill_kernel and sep_narrow_kernel read
+  SEP_ITEMS,     // sep_fill_kernel writes the vehicle numbers sorted by cell; sep_narrow_kernel reads them
+  SEP_EXTENT,    // fh_fleet_separation_device zeroes it on the stream; sep_boxes_kernel raises the largest half-extent per axis (three words),
+                 // sep_narrow_kernel reads it
   N_BUFS
 };
 
@@ -1002,6 +1012,49 @@ int fh_fleet_audit_device(fh_ctx* ctx, const fh_audit_params* par, const fh_vehi
   a.mask = d_point_mask; a.mask_words = mask_words;
   a.out = d_out;
   hipLaunchKernelGGL(fh::audit_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// ---- the separation of committed plans (include/fasterhip_separation.h): boxes, cell starts, cell items, one wavefront per vehicle ----
+int fh_fleet_separation_device(fh_ctx* ctx, const fh_separation_params* par, const fh_vehicle* d_vehicles, const fh_state* d_plans, int n,
+                               int max_states, const fh_voxel_grid* cells, fh_plan_separation* d_out) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->r) || !audit_radius_ok(par->cap) || !(par->cap > 0)) return FH_ERR_ARG;
+  if (par->r > par->cap || par->stride < 1 || par->count < 0) return FH_ERR_ARG;
+  if (n < 0 || max_states < 1) return FH_ERR_ARG;
+  if (!fhh::voxel_grid_ok(cells) || fhh::voxel_grid_cells(*cells) > (long long)FH_SEP_MAX_CELLS) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_out) return FH_ERR_ARG;
+  const int n_cells = (int)fhh::voxel_grid_cells(*cells);
+  int rc;
+  if ((rc = ensure(ctx, SEP_BOXES, sizeof(fh::SepBox) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, SEP_COUNTS, sizeof(int) * (size_t)n_cells)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, SEP_STARTS, sizeof(int) * ((size_t)n_cells + 1))) != FH_OK) return rc;
+  if ((rc = ensure(ctx, SEP_ITEMS, sizeof(int) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, SEP_EXTENT, sizeof(unsigned long long) * 3)) != FH_OK) return rc;
+  fh::SepArgs a;
+  a.r2 = par->r * par->r; a.cap = par->cap; a.cap2 = par->cap * par->cap;
+  a.stride = par->stride; a.count = par->count; a.n = n; a.max_states = max_states;
+  a.vehicles = d_vehicles; a.plans = d_plans;
+  fhh::set_lattice(a, *cells);
+  a.boxes = ctx->buf[SEP_BOXES].as<fh::SepBox>();
+  a.extent = ctx->buf[SEP_EXTENT].as<unsigned long long>();
+  a.counts = ctx->buf[SEP_COUNTS].as<int>();
+  a.starts = ctx->buf[SEP_STARTS].as<int>();
+  a.items = ctx->buf[SEP_ITEMS].as<int>();
+  a.out = d_out;
+  FH_HIP(hipMemsetAsync(a.counts, 0, sizeof(int) * (size_t)n_cells, ctx->stream));
+  FH_HIP(hipMemsetAsync(a.extent, 0, sizeof(unsigned long long) * 3, ctx->stream));
+  hipLaunchKernelGGL(fh::sep_boxes_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fh::sep_scan_kernel, dim3(1), dim3(fh::SEP_SCAN_THREADS), 0, ctx->stream, a.counts, a.starts, n_cells);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fh::sep_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fh::sep_narrow_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }

@@ -419,6 +419,45 @@ class Fleet:
         measurement: nothing of the fleet is written (synchronises)."""
         return self._host(self.audit_device(r_unknown, r_occupied, cap, stride, count, truth), abi.plan_audit_dtype)
 
+    def separation_cells(self, cap):
+        """The default grid of the separation's broad phase, (origin, res, dims): the box of set_map with res = max(cap, 1 m), coarsened
+        until it has at most FH_SEP_MAX_CELLS cells.  Without a map: one cell (all pairs)."""
+        if self.map_args is None:
+            return ((0.0, 0.0, 0.0), 1.0, (1, 1, 1))
+        cells, mres, center, z_max, _ = self.map_args
+        size = [cells[a] * mres for a in range(3)]
+        origin = tuple(center[a] - 0.5 * size[a] for a in range(3))
+        res = max(float(cap), 1.0)
+        while True:
+            dims = tuple(max(1, int(np.ceil(size[a] / res))) for a in range(3))
+            if dims[0] * dims[1] * dims[2] <= abi.FH_SEP_MAX_CELLS:
+                return (origin, res, dims)
+            res *= 2.0
+
+    def separation_device(self, r=None, cap=None, stride=1, count=0, cells=None):
+        """separation() without the copy to the host: four launches on the fleet's stream; returns the device tensor of [n]
+        fh_plan_separation records as bytes (asynchronous)."""
+        t, B = self.torch, self.n
+        par = abi.default_separation_params(2.0 * float(self.params["rule"]["drone_radius"]) if r is None else r)
+        par["cap"] = 2.0 * float(par["r"]) if cap is None else cap
+        par["stride"], par["count"] = stride, count
+        if cells is None:
+            cells = self.separation_cells(float(par["cap"]))
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            d_out = t.empty(B * abi.plan_separation_dtype.itemsize, dtype=t.uint8, device=self.dev)  # (the kernel writes every byte of every record)
+            self.ctx.fleet_separation_device(par, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), B, self.max_states, cells, d_out.data_ptr())
+        return d_out
+
+    def separation(self, r=None, cap=None, stride=1, count=0, cells=None):
+        """The committed plans against each other, instant by instant (include/fasterhip_separation.h): [n] abi.plan_separation_dtype with
+        squared distances (abi.separation_distances takes the roots).  r defaults to 2 params["rule"]["drone_radius"], where two hulls
+        touch, cap to 2 r.  cells = (origin, res, dims) is the grid of the broad phase, by default separation_cells(cap); no field of a
+        record depends on it.  Record i tests the instants of plan i only: the closest approach of a pair is the smaller of its two
+        records' values.  count=params["delta_t"] looks at the states the next replan cannot change.  A measurement: nothing of the
+        fleet is written, vehicles still do not avoid each other (synchronises)."""
+        return self._host(self.separation_device(r, cap, stride, count, cells), abi.plan_separation_dtype)
+
     def faces(self):
         """The face rows of the last cycle on the host: {"whole": [n * faces_per_problem] abi.face_dtype, "safe": the same}; the problems
         of results() address them through face_begin / face_off (diagnostics)."""

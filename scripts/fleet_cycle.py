@@ -22,8 +22,12 @@ sense -> observe -> replan -> 5 ticks with "observe" and "map_views" as stages o
 --audit adds "audit" beside every stage table: the plan audit (Fleet.audit_device: every committed state against the unknown space and the
 points the fleet of that table has, radii = drone_radius, cap = twice that) after the last replan of that table, fenced by events like a
 stage ("ms", the median of as many calls as there are timed cycles), with the states it tested and the vehicles it flags.
+--separation adds "separation" beside the shared-grid stage table: the plans against each other (Fleet.separation_device: r = two
+drone radii, cap = twice that, the default cell grid) after the last replan, fenced by events like a stage, twice: "head" with count =
+delta_t, the states the next replan cannot change, and "all" with count = 0, every state; with the states tested, the vehicles flagged,
+the largest half-extent H of a box and, from a sample of 1024 vehicles, how many candidates the narrow phase lists per vehicle.
     usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
-                                         [--audit]"""
+                                         [--audit] [--separation]"""
 import json
 import os
 import sys
@@ -38,6 +42,7 @@ from faster_amd.fleet import Fleet  # noqa: E402
 
 
 AUDIT = "--audit" in sys.argv
+SEPARATION = "--separation" in sys.argv
 
 
 def timed_audit(fl, cycles):
@@ -56,6 +61,57 @@ def timed_audit(fl, cycles):
             "near_unknown": int(((rec["flags"] & abi.FH_AUDIT_UNKNOWN) != 0).sum()),
             "near_occupied": int(((rec["flags"] & abi.FH_AUDIT_OCCUPIED) != 0).sum()),
             "not_finite": int(((rec["flags"] & abi.FH_AUDIT_NOT_FINITE) != 0).sum())}
+
+
+def listed_candidates(fl, cap, count, sample=1024):
+    """What the broad phase works with, restated with torch on the fleet's plans: the boxes of the positions a vehicle can show (its
+    states below `count`, and its last state where it stands for the others), the largest half-extent per axis, and for a sample of
+    vehicles how many other boxes meet theirs grown by cap: the candidates the narrow phase lists."""
+    v = fl.vehicles()
+    B, S = fl.n, fl.max_states
+    head = torch.from_numpy(v["plan_head"].astype(np.int64)).to(fl.dev)[:, None]
+    size = torch.from_numpy(v["plan_size"].astype(np.int64)).to(fl.dev)[:, None]
+    m = torch.clamp(size, max=count) if count > 0 else size
+    lo, hi = torch.empty((B, 3), dtype=torch.float64, device=fl.dev), torch.empty((B, 3), dtype=torch.float64, device=fl.dev)
+    pos = fl.d_plans.view(torch.float64).view(B, S, 12)
+    idx = torch.arange(S, device=fl.dev)[None, :]
+    for a in range(0, B, 4096):   # (in pieces: the masked copies of the positions are temporaries)
+        sl = slice(a, a + 4096)
+        shown = (idx >= head[sl]) & (idx < head[sl] + m[sl])
+        shown |= (idx == head[sl] + size[sl] - 1) & (size[sl] >= 1) & ((size[sl] < count) if count > 0 else True)
+        p = pos[sl, :, :3]
+        lo[sl] = torch.where(shown[..., None], p, torch.full_like(p, float("inf"))).amin(dim=1)
+        hi[sl] = torch.where(shown[..., None], p, torch.full_like(p, -float("inf"))).amax(dim=1)
+    boxed = (lo <= hi).all(dim=1)
+    half = torch.where(boxed[:, None], 0.5 * (hi - lo), torch.zeros_like(lo))
+    pick = torch.randperm(B, device=fl.dev)[:min(sample, B)]
+    pick = pick[boxed[pick]]
+    meet = ((hi[None, :, :] >= lo[pick][:, None, :] - cap) & (lo[None, :, :] <= hi[pick][:, None, :] + cap)).all(dim=2) & boxed[None, :]
+    return {"half_extent_max": [float(x) for x in half.amax(dim=0)], "half_extent_mean": [float(x) for x in half.mean(dim=0)],
+            "candidates_mean": float(meet.sum(dim=1).double().mean()) - 1.0, "candidates_max": int(meet.sum(dim=1).max()) - 1,
+            "sample": int(pick.numel())}
+
+
+def timed_separation(fl, cycles):
+    """The separation of the plans as they stand, with count = delta_t and with every state, each `cycles` times and fenced by events
+    like a stage; the last records on the host for the counts."""
+    r = 2.0 * float(fl.params["rule"]["drone_radius"])
+    out = {"r": r, "cap": 2.0 * r, "cells": list(fl.separation_cells(2.0 * r)[2]), "cell_res": fl.separation_cells(2.0 * r)[1]}
+    for name, count in (("head", int(fl.params["delta_t"])), ("all", 0)):
+        ms = []
+        fl.separation_device(count=count)   # (warm-up)
+        for _ in range(max(cycles, 1)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(fl.stream)
+            d_out = fl.separation_device(count=count)
+            e1.record(fl.stream)
+            fl.sync()
+            ms.append(e0.elapsed_time(e1))
+        rec = d_out.cpu().numpy().view(abi.plan_separation_dtype)
+        out[name] = dict(listed_candidates(fl, 2.0 * r, count), ms=float(np.median(ms)), count=count, tested_states=int(rec["n_tested"].sum()),
+                         near=int(((rec["flags"] & abi.FH_SEP_NEAR) != 0).sum()), within_cap=int(np.isfinite(rec["min_d2"]).sum()),
+                         near_others_mean=float(rec["n_near"].mean()), not_finite=int(((rec["flags"] & abi.FH_SEP_NOT_FINITE) != 0).sum()))
+    return out
 
 
 def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False):
@@ -294,6 +350,8 @@ def main():
                     "commit_write_gbs": cb / (med["commit"] * 1e-3) / 1e9, "hbm_copy_gbs": copy_gbs})
         if AUDIT:
             out["audit"] = timed_audit(fl, cycles)
+        if SEPARATION:
+            out["separation"] = timed_separation(fl, cycles)
     finally:
         fl.close()
     if "--views" in sys.argv or fov is not None:
