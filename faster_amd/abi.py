@@ -178,6 +178,26 @@ def separation_distances(separation):
     return np.sqrt(separation["min_d2"])
 
 
+# fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
+FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
+traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),
+                                 ("reserved", "<i4", (4,))], align=True)
+assert traffic_params_dtype.itemsize == 48
+
+
+def default_traffic_params(samples, stride, range, hull=0.0, rule=FH_TRAFFIC_ALL, first_point=0):  # noqa: A002  (the header's word)
+    """fh_traffic_params: `samples` instants of every plan, `stride` states apart, shown to the vehicles nearer than `range`; hull > 0
+    inflates every sample to seven points.  first_point: the cloud index of the first traffic point, a multiple of 32."""
+    p = np.zeros((), dtype=traffic_params_dtype)
+    p["range"], p["hull"], p["samples"], p["stride"], p["rule"], p["first_point"] = range, hull, samples, stride, rule, first_point
+    return p
+
+
+def traffic_points_per_sample(hull):
+    """pps of include/fasterhip_traffic.h: seven points per sample with a hull, else one."""
+    return 7 if float(hull) > 0 else 1
+
+
 def certify_tol(corridor, state=None, box=None, cost_rel=None):
     """fh_certify_tol; one number stands for all four (the project's own number for "violated" is fh_params.feas_tol)."""
     t = np.zeros((), dtype=certify_tol_dtype)

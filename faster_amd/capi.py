@@ -38,6 +38,8 @@ CERTIFY_SYMBOLS = ["fh_certify_batch_device", "fh_certify_batch"]
 AUDIT_SYMBOLS = ["fh_fleet_audit_device"]
 # include/fasterhip_separation.h
 SEPARATION_SYMBOLS = ["fh_fleet_separation_device"]
+# include/fasterhip_traffic.h
+TRAFFIC_SYMBOLS = ["fh_fleet_traffic_device"]
 
 _LIB = None
 
@@ -267,6 +269,8 @@ def lib():
         L.fh_fleet_audit_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, i32, vp]
         L.fh_fleet_separation_device.restype = i32
         L.fh_fleet_separation_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+        L.fh_fleet_traffic_device.restype = i32
+        L.fh_fleet_traffic_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, i32]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -808,6 +812,17 @@ class Context:
             g = np.ascontiguousarray(g).reshape(1)
         self._check(lib().fh_fleet_separation_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states),
                                                      None if g is None else abi.ptr(g), d_out), "fh_fleet_separation_device")
+
+    def fleet_traffic_device(self, par, d_vehicles, d_plans, n, max_states, d_cloud, n_cloud, d_point_mask, mask_words):
+        """fh_fleet_traffic_device: the committed plans of the other vehicles as cloud points from par["first_point"] on and as bits of
+        the n mask rows; par: one abi.traffic_params_dtype record.  Asynchronous on the context's stream (include/fasterhip_traffic.h)."""
+        p = np.ascontiguousarray(par)
+        if p.dtype != abi.traffic_params_dtype or p.size != 1:
+            raise FasterHipError("fleet_traffic_device: par must be one abi.traffic_params_dtype record (abi.default_traffic_params), "
+                                 "got dtype %s, %d elements" % (p.dtype, p.size))
+        p = p.reshape(1)
+        self._check(lib().fh_fleet_traffic_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states), d_cloud, int(n_cloud),
+                                                  d_point_mask, int(mask_words)), "fh_fleet_traffic_device")
 
     def sample_batch_device(self, d_problems, d_results, n, max_samples, d_states, d_counts):
         self._check(lib().fh_sample_batch_device(self._h, d_problems, d_results, n, max_samples, d_states, d_counts),

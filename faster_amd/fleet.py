@@ -16,7 +16,13 @@ shared cloud that observe() grows from what the view has seen — and the loop b
 
     sense -> observe -> replan -> next_goals
 
-in which a vehicle searches its path and cuts both corridors around the points its view knows, and no others.  enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
+in which a vehicle searches its path and cuts both corridors around the points its view knows, and no others.  enable_traffic() makes
+the vehicles avoid each other with the same mechanism: traffic() writes the committed plans of the other vehicles as points at the tail
+of the cloud and sets, in the mask row of vehicle i, the bits of those it has to keep clear of (include/fasterhip_traffic.h):
+
+    sense -> observe -> traffic -> replan -> next_goals
+
+enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
 The host restatement every cycle is checked against is fhreplan::Planner (faster_amd/host/replan_stub.hpp);
@@ -73,6 +79,7 @@ class Fleet:
         self.dc = float(dc)
         self.d_headings = self.d_goal_yaw = self.yaw_params = None  # enable_heading
         self.point_mask, self.map_args = None, None                 # set_point_views; what set_map built the map with
+        self.traffic_par, self.n_cloud_all = None, 0                # enable_traffic: the cloud holds n_cloud static points, then the traffic
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -109,10 +116,24 @@ class Fleet:
 
     def set_map(self, cloud, cells, res, center, z_max, inflation):
         """This cycle's occupied points (numpy or a device tensor [m][3]): the occupancy grid of the path search (MapUtil::readMap) and the
-        obstacles of both corridors."""
-        self.cloud = self._host_to_device(np.asarray(cloud, dtype=np.float64).reshape(-1, 3) if not isinstance(cloud, self.torch.Tensor) else cloud,
-                                          self.torch.float64)
-        self.n_cloud = int(self.cloud.shape[0])
+        obstacles of both corridors.  With traffic enabled these are the static points: they are copied in front of the traffic points,
+        which stay, and must end in the same word of the masks as the cloud they replace."""
+        static =self._host_to_device(np.asarray(cloud, dtype=np.float64).reshape(-1, 3) if not isinstance(cloud, self.torch.Tensor) else cloud,
+                                      self.torch.float64)
+        if self.traffic_par is not None:
+            # the tail stays: the new static points are copied in front of it, on the fleet's stream (launches in flight read the cloud)
+            if abi.point_mask_words(static.shape[0]) * 32 != int(self.traffic_par["first_point"]):
+                raise capi.FasterHipError("Fleet.set_map: with traffic enabled the new cloud must end in the same word of the masks (%d points, "
+                                          "the traffic begins at %d): set_point_views and enable_traffic again"
+                                          % (static.shape[0], int(self.traffic_par["first_point"])))
+            self._follow_current()
+            with self.torch.cuda.stream(self.stream):
+                self._write_static(self.cloud, static)
+                static.record_stream(self.stream)
+            self.n_cloud = int(static.shape[0])
+        else:
+            self.cloud = static
+            self.n_cloud = int(self.cloud.shape[0])
         self._follow_current()
         self.cloud.record_stream(self.stream)  # (read by every later cycle's launches on the fleet's stream)
         self.map.read_device(self.cloud.data_ptr(), self.n_cloud, cells, res, center, self.z_ground, z_max, inflation)
@@ -182,6 +203,9 @@ class Fleet:
         the grid of its view and cuts both corridors around the points its view knows.  mask = False detaches: replan() is what it was.
         Memory per view: a grid of ceil(cells / 32) words and a mask row; the jump point search adds 64 bytes per cell and view."""
         t = self.torch
+        if self.traffic_par is not None:   # (the traffic lives in masks that are replaced: enable_traffic again)
+            self.traffic_par, self.n_cloud_all = None, 0
+            self.cloud = self.cloud[:self.n_cloud]
         if mask is False:
             self.point_mask = None
             self.ctx.set_point_views_device(None)
@@ -211,6 +235,65 @@ class Fleet:
         self.ctx.fleet_observe_device(origin, res, dims, self.view_flags.data_ptr(), self.view_flags.shape[1],
                                       None if self.view_of is None else self.view_of.data_ptr(), self.n_views, self.cloud.data_ptr(), self.n_cloud,
                                       self.point_mask.data_ptr(), self.point_mask.shape[1])
+
+    @staticmethod
+    def _write_static(cloud, static):
+        """The static points into the front of an extended cloud; the points up to the next multiple of 32 are copies of a finite point
+        (no bit of theirs is ever set)."""
+        m = int(static.shape[0])
+        cloud[:m] = static
+        first = abi.point_mask_words(m) * 32
+        if first > m:
+            cloud[m:first] = static[0] if m > 0 else 0.0
+
+    def enable_traffic(self, samples, stride, range, hull=None, rule="all"):  # noqa: A002  (the header's word)
+        """The vehicles avoid each other (include/fasterhip_traffic.h): from now on traffic() writes `samples` instants of every committed
+        plan, `stride` states apart, as points behind the static cloud and shows them, through the point masks, to the vehicles nearer
+        than `range`; hull (None: params["rule"]["drone_radius"]; 0: no hull) inflates every sample to seven points.  rule: "all", or
+        "yield": vehicle i sees the vehicles below i only.  After set_map, set_unknown_views with a view per vehicle and
+        set_point_views.  The cloud tensor grows to pad32(n_static) + n samples pps points and every mask row to as many bits, keeping
+        its words; replan() reads the whole cloud, set_map's shared map, observe() and audit() the static points only.  Memory: n rows
+        of ceil(n samples pps / 32) words more."""
+        t = self.torch
+        if self.cloud is None or self.view_flags is None or self.point_mask is None:
+            raise capi.FasterHipError("Fleet.enable_traffic: set_map, set_unknown_views and set_point_views first")
+        if self.view_of is not None or self.n_views != self.n:
+            raise capi.FasterHipError("Fleet.enable_traffic: needs a view per vehicle (set_unknown_views without view_of, n_views = n)")
+        rules = {"all": abi.FH_TRAFFIC_ALL, "yield": abi.FH_TRAFFIC_YIELD_TO_LOWER}
+        if rule not in rules:
+            raise capi.FasterHipError("Fleet.enable_traffic: rule is \"all\" or \"yield\", got %r" % (rule,))
+        hull = float(self.params["rule"]["drone_radius"]) if hull is None else float(hull)
+        static = self.cloud[:self.n_cloud]
+        first = abi.point_mask_words(self.n_cloud) * 32
+        par = abi.default_traffic_params(samples, stride, range, hull, rules[rule], first)
+        total = first + self.n * int(samples) * abi.traffic_points_per_sample(hull)
+        if int(samples) < 1 or total >= 1 << 31:
+            raise capi.FasterHipError("Fleet.enable_traffic: %d samples of %d vehicles do not fit a cloud" % (int(samples), self.n))
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            cloud = t.zeros((total, 3), dtype=t.float64, device=self.dev)
+            self._write_static(cloud, static)
+            words = max(abi.point_mask_words(total), int(self.point_mask.shape[1]))
+            mask = t.zeros((self.n_views, words), dtype=t.int32, device=self.dev)
+            mask[:, :self.point_mask.shape[1]] = self.point_mask
+            if first > self.n_cloud:   # the bits of the padding points stay clear
+                mask[:, first // 32 - 1] &= (1 << (self.n_cloud & 31)) - 1
+            mask[:, first // 32:] = 0
+        self.cloud, self.point_mask = cloud, mask
+        self.cloud.record_stream(self.stream)
+        self.point_mask.record_stream(self.stream)
+        self.ctx.set_point_views_device(self.point_mask.data_ptr(), self.point_mask.shape[1], None, self.n_views)
+        self.traffic_par, self.n_cloud_all = par, total
+
+    def traffic(self):
+        """The committed plans of the other vehicles into the tail of the cloud and into every vehicle's mask row
+        (fh_fleet_traffic_device): after observe(), before replan().  Two launches on the fleet's stream; the traffic words are written
+        whole, so what a vehicle saw of the others last cycle goes."""
+        if self.traffic_par is None:
+            raise capi.FasterHipError("Fleet.traffic: enable_traffic first")
+        self._follow_current()
+        self.ctx.fleet_traffic_device(self.traffic_par, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.n, self.max_states,
+                                      self.cloud.data_ptr(), self.n_cloud_all, self.point_mask.data_ptr(), self.point_mask.shape[1])
 
     def point_masks(self):
         """[n_views][words] uint32 on the host (synchronises)."""
@@ -281,13 +364,14 @@ class Fleet:
         B, P, c, m = self.n, self.params, self.ctx, self.map
         p = lambda t: t.data_ptr()  # noqa: E731
         origin, res, dims = self.grid
-        chain = self._shared_map_stages(B, P, c, m, p, origin, res, dims)
+        n_cloud = self.n_cloud if self.traffic_par is None else self.n_cloud_all   # (with traffic: the static points and the others' plans)
+        chain = self._shared_map_stages(B, P, c, m, p, origin, res, dims, n_cloud)
         if self.point_mask is None:
             return chain
         cells, mres, center, z_max, inflation = self.map_args
         vo = None if self.view_of is None else p(self.view_of)
         views = [
-            ("map_views", lambda: m.read_views_device(p(self.cloud), self.n_cloud, p(self.point_mask), self.point_mask.shape[1], self.n_views, cells,
+            ("map_views", lambda: m.read_views_device(p(self.cloud), n_cloud, p(self.point_mask), self.point_mask.shape[1], self.n_views, cells,
                                                       mres, center, self.z_ground, z_max, inflation)),
             ("path_search", lambda: m.plan_batch_radius_views_device(p(self.d_starts), p(self.d_goals), p(self.d_radius), p(self.d_active), B, self.mp,
                                                                      p(self.d_paths), p(self.d_np), vo, self.n_views, p(self.d_ex),
@@ -295,20 +379,20 @@ class Fleet:
         ]
         return chain[:1] + views + chain[2:]
 
-    def _shared_map_stages(self, B, P, c, m, p, origin, res, dims):
+    def _shared_map_stages(self, B, P, c, m, p, origin, res, dims, n_cloud):
         return [
             ("begin", lambda: c.fleet_begin_device(P, p(self.d_vehicles), p(self.d_plans), B, self.max_states, p(self.d_whole), p(self.d_safe),
                                                    p(self.d_starts), p(self.d_goals), p(self.d_radius), p(self.d_active))),
             ("path_search", lambda: m.plan_batch_radius_device(p(self.d_starts), p(self.d_goals), p(self.d_radius), p(self.d_active), B, self.mp,
                                                                p(self.d_paths), p(self.d_np), p(self.d_ex), self.dist_max_vertexes, 0)),
-            ("corridors", lambda: c.corridor_batch_device(p(self.cloud), self.n_cloud, p(self.d_paths), p(self.d_np), B, self.mp, self.max_poly, self.fpp,
+            ("corridors", lambda: c.corridor_batch_device(p(self.cloud), n_cloud, p(self.d_paths), p(self.d_np), B, self.mp, self.max_poly, self.fpp,
                                                           p(self.d_wf), p(self.d_off), p(self.d_npoly), p(self.d_last), self.decomp_radius,
                                                           self.z_ground, self.local_bbox)),
             ("corridor_problems", lambda: c.corridor_problems_device(p(self.d_np), p(self.d_last), p(self.d_goals), p(self.d_wf), p(self.d_off),
                                                                      p(self.d_npoly), B, self.fpp, self.N, p(self.d_whole))),
             ("whole_solve", lambda: c.solve_batch_device(p(self.d_whole), p(self.d_wf), B, self.N, self.fpp, p(self.d_wr))),
             ("safe_corridor", lambda: c.safe_corridor_batch_device(p(self.d_whole), p(self.d_wr), p(self.d_paths), p(self.d_np), self.mp, p(self.d_goals),
-                                                                   p(self.cloud), self.n_cloud, origin, res, dims, B, 0.5, self.max_poly,
+                                                                   p(self.cloud), n_cloud, origin, res, dims, B, 0.5, self.max_poly,
                                                                    self.local_bbox, self.decomp_radius, self.z_ground, self.fpp, self.N,
                                                                    p(self.d_safe), p(self.d_sf), p(self.d_spaths), p(self.d_snp))),
             ("safe_solve", lambda: c.solve_batch_device(p(self.d_safe), p(self.d_sf), B, self.N, self.fpp, p(self.d_sr))),
@@ -455,7 +539,7 @@ class Fleet:
         touch, cap to 2 r.  cells = (origin, res, dims) is the grid of the broad phase, by default separation_cells(cap); no field of a
         record depends on it.  Record i tests the instants of plan i only: the closest approach of a pair is the smaller of its two
         records' values.  count=params["delta_t"] looks at the states the next replan cannot change.  A measurement: nothing of the
-        fleet is written, vehicles still do not avoid each other (synchronises)."""
+        fleet is written; vehicles still do not avoid each other unless enable_traffic (synchronises)."""
         return self._host(self.separation_device(r, cap, stride, count, cells), abi.plan_separation_dtype)
 
     def faces(self):

@@ -26,8 +26,12 @@ stage ("ms", the median of as many calls as there are timed cycles), with the st
 drone radii, cap = twice that, the default cell grid) after the last replan, fenced by events like a stage, twice: "head" with count =
 delta_t, the states the next replan cannot change, and "all" with count = 0, every state; with the states tested, the vehicles flagged,
 the largest half-extent H of a box and, from a sample of 1024 vehicles, how many candidates the narrow phase lists per vehicle.
+--traffic [SAMPLES STRIDE RANGE] adds "traffic": a fleet with a view per vehicle that holds the shared unknown grid and knows every static
+point (memory per view as for --occupancy, so a fleet of a few thousand at most), its stage table and --separation's report "before";
+then Fleet.enable_traffic(SAMPLES, STRIDE, RANGE; default 8 samples 25 states apart, 6 m; hull = drone_radius, rule "all") and the loop
+traffic -> replan -> 5 ticks with "traffic" as a stage of its own, and the same report "after".
     usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
-                                         [--audit] [--separation]"""
+                                         [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]]"""
 import json
 import os
 import sys
@@ -114,10 +118,10 @@ def timed_separation(fl, cycles):
     return out
 
 
-def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False):
+def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False, traffic=False):
     """`cycles` cycles, every stage fenced by events: {stage: [ms]} (with r_sense: sensing first, as a stage of its own; fov: forward;
-    observe: Fleet.observe after it, as another)."""
-    names = (["sense"] if r_sense else []) + (["observe"] if observe else []) + [n for n, _ in fl.stages()] + ["next_goals"]
+    observe: Fleet.observe after it, as another; traffic: Fleet.traffic after that)."""
+    names = (["sense"] if r_sense else []) + (["observe"] if observe else []) + (["traffic"] if traffic else []) + [n for n, _ in fl.stages()] + ["next_goals"]
     per = {n: [] for n in names}
     for _ in range(cycles):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
@@ -129,6 +133,10 @@ def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False):
             ev[1].record(fl.stream)
         if observe:
             fl.observe()
+            k += 1
+            ev[k].record(fl.stream)
+        if traffic:
+            fl.traffic()
             k += 1
             ev[k].record(fl.stream)
         for j, (n, launch) in enumerate(fl.stages()):
@@ -249,9 +257,49 @@ def occupancy_cycles(B, cycles, p, world, r_sense, teams):
     return {"occupancy": out}
 
 
+def traffic_cycles(B, cycles, p, world, samples, stride, reach):
+    """The cycle before and after Fleet.enable_traffic: see the module docstring."""
+    cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims = world
+    n_cells = dims[0] * dims[1] * dims[2]
+    out = {"samples": samples, "stride": stride, "range": reach, "rule": "all", "hull": float(p["rule"]["drone_radius"]),
+           "static_points": int(len(cloud))}
+    fl = Fleet(B, p, max_states=1024)
+    try:
+        fl.set_map(cloud, cells, res, center, zmax, infl)
+        fl.set_unknown_views(torch.from_numpy(flags.reshape(1, -1)).to(fl.dev).repeat(B, 1), origin=origin, res=res, dims=dims)
+        fl.set_point_views(torch.full((B, abi.point_mask_words(len(cloud))), -1, dtype=torch.int32, device=fl.dev))
+        fl.init(states, goals)
+        fl.replan()
+        fl.next_goals(5)
+        fl.sync()
+        med = timed_cycles(fl, cycles)
+        out["before"] = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "separation": timed_separation(fl, cycles)}
+        fl.enable_traffic(samples, stride, reach)
+        out.update({"traffic_points": fl.n_cloud_all - int(fl.traffic_par["first_point"]), "cloud_points": fl.n_cloud_all,
+                    "mask_bytes": int(fl.point_mask.numel()) * 4, "unknown_views_bytes": B * n_cells})
+        fl.traffic()
+        fl.replan()
+        fl.next_goals(5)
+        fl.sync()
+        med = timed_cycles(fl, cycles, traffic=True)
+        bits = fl.point_mask[:, int(fl.traffic_par["first_point"]) // 32:]
+        shown = sum(int(((bits >> b) & 1).sum().item()) for b in range(32))
+        v = fl.vehicles()
+        out["after"] = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "separation": timed_separation(fl, cycles),
+                        "traffic_bits_set_per_vehicle": shown / B, "committed_last": int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum())}
+    finally:
+        fl.close()
+    return {"traffic": out}
+
+
 def main():
     argv = sys.argv[1:]
-    r_sense, fov, teams = 3.0, None, 0
+    r_sense, fov, teams, traffic = 3.0, None, 0, None
+    if "--traffic" in argv:
+        k = argv.index("--traffic")
+        has = k + 3 < len(argv) and argv[k + 1].isdigit() and argv[k + 2].isdigit()
+        traffic = (int(argv[k + 1]), int(argv[k + 2]), float(argv[k + 3])) if has else (8, 25, 6.0)
+        del argv[k:k + (4 if has else 1)]
     if "--occupancy" in argv:
         k = argv.index("--occupancy")
         has = k + 1 < len(argv) and argv[k + 1].isdigit()
@@ -360,6 +408,9 @@ def main():
     if teams:
         world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
         out.update(occupancy_cycles(B, cycles, p, world, r_sense, min(teams, B)))
+    if traffic:
+        world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
+        out.update(traffic_cycles(B, cycles, p, world, *traffic))
     print(json.dumps(out))
 
 

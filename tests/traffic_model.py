@@ -1,0 +1,131 @@
+"""The traffic stage (include/fasterhip_traffic.h) restated in numpy: brute force over all (i, k, s), the header's model word for word.
+Everything is IEEE double and numpy fuses no multiply-add, so `traffic()` gives the cloud tail and the mask words the device must write,
+byte for byte.  `variant` names one deliberate mistake (tests/test_traffic_model.py shows which hand case each one changes); None is
+the model."""
+import numpy as np
+
+from faster_amd import abi
+
+VARIANTS = ("le", "no_clamp", "self", "or", "hull_order", "per_point")
+HULL_ORDER = ((0, 1.0), (0, -1.0), (1, 1.0), (1, -1.0), (2, 1.0), (2, -1.0))   # +x, -x, +y, -y, +z, -z after the centre
+
+
+def _bad(head, size, max_states):
+    return head < 0 or size < 0 or head + size > max_states
+
+
+def samples(par, vehicles, plans, max_states, variant=None):
+    """(show [n][S] bool, centres [n][S][3], zero where the sample does not show)."""
+    n, S, stride = len(vehicles), int(par["samples"]), int(par["stride"])
+    plans = np.asarray(plans).reshape(n, max_states)
+    show, c = np.zeros((n, S), dtype=bool), np.zeros((n, S, 3))
+    for k in range(n):
+        head, size = int(vehicles["plan_head"][k]), int(vehicles["plan_size"][k])
+        if _bad(head, size, max_states) or size < 1:   # (decided before any plan state is read)
+            continue
+        for s in range(S):
+            j = s * stride
+            if variant == "no_clamp" and j >= size:
+                continue
+            p = plans["pos"][k, head + min(j, size - 1)]   # a vehicle whose plan has ended stands at its last state
+            if np.isfinite(p).all():
+                show[k, s], c[k, s] = True, p
+    return show, c
+
+
+def points(par, show, c, variant=None):
+    """[n][S][pps][3]: the points of every slot."""
+    hull = float(par["hull"])
+    pps = abi.traffic_points_per_sample(hull)
+    pts = np.zeros(show.shape + (pps, 3))
+    pts[:, :, 0] = c
+    if pps == 7:
+        order = HULL_ORDER if variant != "hull_order" else tuple(HULL_ORDER[o] for o in (1, 0, 3, 2, 5, 4))
+        with np.errstate(over="ignore"):
+            for o, (axis, sign) in enumerate(order, start=1):
+                pts[:, :, o] = c
+                pts[:, :, o, axis] = c[:, :, axis] + hull if sign > 0 else c[:, :, axis] - hull   # one add or one subtract
+    pts[~show] = 0.0
+    return pts
+
+
+def traffic(par, vehicles, plans, max_states, cloud, mask, variant=None):
+    """(cloud [n_cloud][3], mask [n][mask_words] uint32) after the call, from those before it (copies)."""
+    n, S, rule, first = len(vehicles), int(par["samples"]), int(par["rule"]), int(par["first_point"])
+    cloud = np.array(cloud, dtype=np.float64).reshape(-1, 3)
+    mask = np.array(mask, dtype=np.uint32).reshape(max(n, 1), -1)[:n]
+    if n == 0:
+        return cloud, mask
+    show, c = samples(par, vehicles, plans, max_states, variant)
+    pts = points(par, show, c, variant)
+    pps = pts.shape[2]
+    total = n * S * pps
+    assert first % 32 == 0 and first + total <= len(cloud) and first + total <= mask.shape[1] * 32
+    cloud[first:first + total] = pts.reshape(-1, 3)   # every traffic point is written
+    r2 = float(par["range"]) * float(par["range"])
+    ks = np.arange(n)
+    bits = np.zeros((n, total), dtype=bool)
+    for i in range(n):
+        p = vehicles["state"]["pos"][i]
+        q = pts if variant == "per_point" else np.broadcast_to(c[:, :, None, :], pts.shape)   # all points of a sample share one decision
+        with np.errstate(over="ignore", invalid="ignore"):
+            d = q - p
+            d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+            near = (d2 <= r2) if variant == "le" else (d2 < r2)
+        seen = (ks != i) | (variant == "self")
+        if rule == abi.FH_TRAFFIC_YIELD_TO_LOWER:
+            seen = seen & (ks < i)
+        on = near & show[:, :, None] & seen[:, None, None] & bool(np.isfinite(p).all())
+        bits[i] = on.reshape(-1)
+    w0, w1 = first // 32, -(-(first + total) // 32)
+    padded = np.zeros((n, (w1 - w0) * 32), dtype=np.uint64)   # bits past the last traffic point in the last word are zero
+    padded[:, :total] = bits
+    words = (padded.reshape(n, w1 - w0, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+    if variant == "or":
+        mask[:, w0:w1] |= words
+    else:
+        mask[:, w0:w1] = words   # whole words: last cycle's bits go
+    return cloud, mask
+
+
+def params(samples, stride, range, hull=0.0, rule=abi.FH_TRAFFIC_ALL, first_point=0):  # noqa: A002
+    return abi.default_traffic_params(samples, stride, range, hull, rule, first_point)
+
+
+def fleet(plan_positions, positions, max_states=None, heads=None):
+    """(vehicles [n], plans [n][max_states]): plans from a list of [size][3] position arrays, state.pos from `positions`.  What lies
+    outside the plans is 1e6, far from everything: reading it shows."""
+    n = len(plan_positions)
+    heads = [0] * n if heads is None else list(heads)
+    ps = [np.asarray(p, dtype=np.float64).reshape(-1, 3) for p in plan_positions]
+    max_states = max_states or max(max(len(p) + h for p, h in zip(ps, heads)), 1)
+    v = np.zeros(n, dtype=abi.vehicle_dtype)
+    pl = np.zeros((n, max_states), dtype=abi.state_dtype)
+    pl["pos"] = 1e6
+    for i, (p, h) in enumerate(zip(ps, heads)):
+        v["plan_head"][i], v["plan_size"][i] = h, len(p)
+        pl["pos"][i, h:h + len(p)] = p
+    v["state"]["pos"] = np.asarray(positions, dtype=np.float64).reshape(n, 3)
+    return v, pl
+
+
+def layout(par, n, n_static=0):
+    """(n_cloud, mask_words) that just hold the traffic of n vehicles behind first_point."""
+    total = int(par["first_point"]) + n * int(par["samples"]) * abi.traffic_points_per_sample(par["hull"])
+    return max(total, n_static), abi.point_mask_words(max(total, n_static))
+
+
+def bit(mask, i, point):
+    return bool((int(mask[i, point >> 5]) >> (point & 31)) & 1)
+
+
+def assert_equal(got_cloud, got_mask, want_cloud, want_mask, what=""):
+    """Every byte of the cloud and of the masks; the first difference for the message."""
+    gc, wc = np.ascontiguousarray(got_cloud, dtype=np.float64).reshape(-1, 3), np.ascontiguousarray(want_cloud, dtype=np.float64).reshape(-1, 3)
+    assert gc.shape == wc.shape, what
+    bad = np.nonzero((gc.view(np.uint64) != wc.view(np.uint64)).any(axis=1))[0]
+    assert not len(bad), "%s: cloud points %s differ: device %s, model %s" % (what, bad[:6], gc[bad[:6]], wc[bad[:6]])
+    gm, wm = np.asarray(got_mask, dtype=np.uint32).reshape(want_mask.shape), np.asarray(want_mask, dtype=np.uint32)
+    bad = np.argwhere(gm != wm)
+    assert not len(bad), "%s: mask words (row, word) %s differ: device %s, model %s" % (
+        what, bad[:6].tolist(), [hex(x) for x in gm[gm != wm][:6]], [hex(x) for x in wm[gm != wm][:6]])
