@@ -178,6 +178,26 @@ def separation_distances(separation):
     return np.sqrt(separation["min_d2"])
 
 
+# fh_check_params / fh_plan_check: every commit against the other plans, the conflicts withheld (include/fasterhip_check.h)
+FH_FLEET_STAGE_CONFLICT = 7   # fh_vehicle.stage of a commit that fh_fleet_revert_device took back
+FH_CHECK_BAD_PLAN, FH_CHECK_NOT_FINITE, FH_CHECK_CANDIDATE, FH_CHECK_CONFLICT = 1, 4, 16, 32
+FH_CHECK_LIST_OTHERS, FH_CHECK_MAX_CELLS = 256, 1 << 20   # the narrow phase's LDS list of others; the most cells of the broad phase's grid
+check_params_dtype = np.dtype([("r", "<f8"), ("stride", "<i4"), ("count", "<i4"), ("reserved", "<i4", (4,))], align=True)
+assert check_params_dtype.itemsize == 32
+plan_check_dtype = np.dtype([("flags", "<i4"), ("n_tested", "<i4"), ("first", "<i4"), ("first_other", "<i4"), ("first_kind", "<i4"),
+                             ("reserved", "<i4"), ("d2", "<f8")], align=True)
+assert plan_check_dtype.itemsize == 32, plan_check_dtype.itemsize
+
+
+def default_check_params(radius):
+    """fh_check_params: a commit conflicts when its centre comes closer than `radius` to another vehicle's at a tested instant (two hulls
+    of drone_radius touch at twice that); every instant from the first new state on is tested, which is the check the header's promise
+    holds for."""
+    p = np.zeros((), dtype=check_params_dtype)
+    p["r"], p["stride"], p["count"] = radius, 1, 0
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

@@ -40,6 +40,8 @@ AUDIT_SYMBOLS = ["fh_fleet_audit_device"]
 SEPARATION_SYMBOLS = ["fh_fleet_separation_device"]
 # include/fasterhip_traffic.h
 TRAFFIC_SYMBOLS = ["fh_fleet_traffic_device"]
+# include/fasterhip_check.h
+CHECK_SYMBOLS = ["fh_fleet_backup_device", "fh_fleet_check_device", "fh_fleet_revert_device"]
 
 _LIB = None
 
@@ -271,6 +273,12 @@ def lib():
         L.fh_fleet_separation_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
         L.fh_fleet_traffic_device.restype = i32
         L.fh_fleet_traffic_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, i32]
+        L.fh_fleet_backup_device.restype = i32
+        L.fh_fleet_backup_device.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+        L.fh_fleet_check_device.restype = i32
+        L.fh_fleet_check_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+        L.fh_fleet_revert_device.restype = i32
+        L.fh_fleet_revert_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -823,6 +831,35 @@ class Context:
         p = p.reshape(1)
         self._check(lib().fh_fleet_traffic_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states), d_cloud, int(n_cloud),
                                                   d_point_mask, int(mask_words)), "fh_fleet_traffic_device")
+
+    def fleet_backup_device(self, d_vehicles, d_plans, n, max_states, d_backup_vehicles, d_backup_plans):
+        """fh_fleet_backup_device: the record and the live plan extent of every vehicle into the backup arrays, between begin and commit.
+        Asynchronous on the context's stream (include/fasterhip_check.h)."""
+        self._check(lib().fh_fleet_backup_device(self._h, d_vehicles, d_plans, int(n), int(max_states), d_backup_vehicles, d_backup_plans),
+                    "fh_fleet_backup_device")
+
+    def fleet_check_device(self, par, d_vehicles, d_plans, d_backup_vehicles, d_backup_plans, n, max_states, cells, d_out):
+        """fh_fleet_check_device: d_out [n] fh_plan_check, every vehicle that committed against the backup of the others and the new plans
+        of the candidates below it; par: one abi.check_params_dtype record; cells = (origin, res, dims): the grid of the broad phase, on
+        which no field of a record depends.  A measurement.  Asynchronous on the context's stream (include/fasterhip_check.h)."""
+        p = np.ascontiguousarray(par)
+        if p.dtype != abi.check_params_dtype or p.size != 1:
+            raise FasterHipError("fleet_check_device: par must be one abi.check_params_dtype record (abi.default_check_params), "
+                                 "got dtype %s, %d elements" % (p.dtype, p.size))
+        p = p.reshape(1)
+        g = None
+        if cells is not None:
+            g = np.zeros((), dtype=abi.voxel_grid_dtype)
+            g["origin"], g["res"], g["dims"] = cells
+            g = np.ascontiguousarray(g).reshape(1)
+        self._check(lib().fh_fleet_check_device(self._h, abi.ptr(p), d_vehicles, d_plans, d_backup_vehicles, d_backup_plans, int(n),
+                                                int(max_states), None if g is None else abi.ptr(g), d_out), "fh_fleet_check_device")
+
+    def fleet_revert_device(self, d_out, d_backup_vehicles, d_backup_plans, n, max_states, d_vehicles, d_plans):
+        """fh_fleet_revert_device: the commits whose record has FH_CHECK_CONFLICT are taken back from the backup, stage =
+        FH_FLEET_STAGE_CONFLICT.  Asynchronous on the context's stream (include/fasterhip_check.h)."""
+        self._check(lib().fh_fleet_revert_device(self._h, d_out, d_backup_vehicles, d_backup_plans, int(n), int(max_states), d_vehicles, d_plans),
+                    "fh_fleet_revert_device")
 
     def sample_batch_device(self, d_problems, d_results, n, max_samples, d_states, d_counts):
         self._check(lib().fh_sample_batch_device(self._h, d_problems, d_results, n, max_samples, d_states, d_counts),

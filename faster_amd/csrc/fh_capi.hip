@@ -22,6 +22,7 @@
 #include "../../include/fasterhip_audit.h"
 #include "../../include/fasterhip_separation.h"
 #include "../../include/fasterhip_traffic.h"
+#include "../../include/fasterhip_check.h"
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
 #include "fh_decomp.hip.hpp"
@@ -31,6 +32,7 @@
 #include "fh_audit.hip.hpp"
 #include "fh_separation.hip.hpp"
 #include "fh_traffic.hip.hpp"
+#include "fh_check.hip.hpp"
 #include "fh_host.hpp"
 
 using fhh::DeviceScope;
@@ -74,6 +76,15 @@ enum Buf {
   TRAFFIC_SAMPLES,  // fh_fleet_traffic_device: traffic_points{1,7}_kernel write centre, show word and vehicle of every sample (whole
                     // chunks of 64); traffic_mask{1,7}_kernel read them
   TRAFFIC_BOXES,    // traffic_points{1,7}_kernel write the grown box of the shown centres of every chunk; traffic_mask{1,7}_kernel read them
+  CHECK_BOXES,      // fh_fleet_check_device: check_boxes_kernel writes box, checked extents, kept states and validity word of every vehicle;
+                    // check_fill_kernel and check_narrow_kernel read them
+  CHECK_COUNTS,     // fh_fleet_check_device zeroes them on the stream; check_boxes_kernel counts the vehicles of every cell, sep_scan_kernel
+                    // reads them and leaves zeros, check_fill_kernel draws the places inside a cell from them
+  CHECK_STARTS,     // sep_scan_kernel (launched by fh_fleet_check_device) writes the first item of every cell and the total;
+                    // check_fill_kernel and check_narrow_kernel read
+  CHECK_ITEMS,      // check_fill_kernel writes the vehicle numbers sorted by cell; check_narrow_kernel reads them
+  CHECK_EXTENT,     // fh_fleet_check_device zeroes it on the stream; check_boxes_kernel raises the largest half-extent per axis (three
+                    // words), check_narrow_kernel reads it
   N_BUFS
 };
 
@@ -1104,6 +1115,79 @@ int fh_fleet_traffic_device(fh_ctx* ctx, const fh_traffic_params* par, const fh_
     FH_HIP(hipGetLastError());
     hipLaunchKernelGGL(fh::traffic_mask1_kernel, rows, dim3(64), 0, ctx->stream, a);
   }
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// ---- the commit check (include/fasterhip_check.h): backup before the commit; boxes, cell starts, cell items, one wavefront per
+// candidate after it; then the revert of the commits in conflict ----
+int fh_fleet_backup_device(fh_ctx* ctx, const fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states,
+                           fh_vehicle* d_backup_vehicles, fh_state* d_backup_plans) {
+  if (!ctx) return FH_ERR_ARG;
+  if (n < 0 || max_states < 1) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_backup_vehicles || !d_backup_plans) return FH_ERR_ARG;
+  hipLaunchKernelGGL(fh::check_backup_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_vehicles, d_plans, n, max_states, d_backup_vehicles,
+                     d_backup_plans);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_check_device(fh_ctx* ctx, const fh_check_params* par, const fh_vehicle* d_vehicles, const fh_state* d_plans,
+                          const fh_vehicle* d_backup_vehicles, const fh_state* d_backup_plans, int n, int max_states,
+                          const fh_voxel_grid* cells, fh_plan_check* d_out) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->r)) return FH_ERR_ARG;
+  if (par->stride < 1 || par->count < 0) return FH_ERR_ARG;
+  if (n < 0 || max_states < 1) return FH_ERR_ARG;
+  if (!fhh::voxel_grid_ok(cells) || fhh::voxel_grid_cells(*cells) > (long long)FH_CHECK_MAX_CELLS) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_backup_vehicles || !d_backup_plans || !d_out) return FH_ERR_ARG;
+  const int n_cells = (int)fhh::voxel_grid_cells(*cells);
+  int rc;
+  if ((rc = ensure(ctx, CHECK_BOXES, sizeof(fh::ChkBox) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, CHECK_COUNTS, sizeof(int) * (size_t)n_cells)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, CHECK_STARTS, sizeof(int) * ((size_t)n_cells + 1))) != FH_OK) return rc;
+  if ((rc = ensure(ctx, CHECK_ITEMS, sizeof(int) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, CHECK_EXTENT, sizeof(unsigned long long) * 3)) != FH_OK) return rc;
+  fh::ChkArgs a;
+  a.r = par->r; a.r2 = par->r * par->r;
+  a.stride = par->stride; a.count = par->count; a.n = n; a.max_states = max_states;
+  a.cur_v = d_vehicles; a.cur_p = d_plans; a.old_v = d_backup_vehicles; a.old_p = d_backup_plans;
+  fhh::set_lattice(a, *cells);
+  a.boxes = ctx->buf[CHECK_BOXES].as<fh::ChkBox>();
+  a.extent = ctx->buf[CHECK_EXTENT].as<unsigned long long>();
+  a.counts = ctx->buf[CHECK_COUNTS].as<int>();
+  a.starts = ctx->buf[CHECK_STARTS].as<int>();
+  a.items = ctx->buf[CHECK_ITEMS].as<int>();
+  a.out = d_out;
+  FH_HIP(hipMemsetAsync(a.counts, 0, sizeof(int) * (size_t)n_cells, ctx->stream));
+  FH_HIP(hipMemsetAsync(a.extent, 0, sizeof(unsigned long long) * 3, ctx->stream));
+  hipLaunchKernelGGL(fh::check_boxes_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fh::sep_scan_kernel, dim3(1), dim3(fh::SEP_SCAN_THREADS), 0, ctx->stream, a.counts, a.starts, n_cells);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fh::check_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fh::check_narrow_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_revert_device(fh_ctx* ctx, const fh_plan_check* d_out, const fh_vehicle* d_backup_vehicles, const fh_state* d_backup_plans, int n,
+                           int max_states, fh_vehicle* d_vehicles, fh_state* d_plans) {
+  if (!ctx) return FH_ERR_ARG;
+  if (n < 0 || max_states < 1) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_out || !d_backup_vehicles || !d_backup_plans || !d_vehicles || !d_plans) return FH_ERR_ARG;
+  hipLaunchKernelGGL(fh::check_revert_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_out, d_backup_vehicles, d_backup_plans, n, max_states,
+                     d_vehicles, d_plans);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }

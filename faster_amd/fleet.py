@@ -22,6 +22,9 @@ of the cloud and sets, in the mask row of vehicle i, the bits of those it has to
 
     sense -> observe -> traffic -> replan -> next_goals
 
+enable_check() lets the fleet refuse: every commit is compared, instant by instant, with the other vehicles' plans and taken back when it
+conflicts (include/fasterhip_check.h); the chain ends ... -> safe solve -> backup -> commit -> check -> revert.
+
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
@@ -80,6 +83,7 @@ class Fleet:
         self.d_headings = self.d_goal_yaw = self.yaw_params = None  # enable_heading
         self.point_mask, self.map_args = None, None                 # set_point_views; what set_map built the map with
         self.traffic_par, self.n_cloud_all = None, 0                # enable_traffic: the cloud holds n_cloud static points, then the traffic
+        self.check_par = self.check_cells = self.d_backup_vehicles = self.d_backup_plans = self.d_check = None   # enable_check
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -295,6 +299,33 @@ class Fleet:
         self.ctx.fleet_traffic_device(self.traffic_par, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.n, self.max_states,
                                       self.cloud.data_ptr(), self.n_cloud_all, self.point_mask.data_ptr(), self.point_mask.shape[1])
 
+    def enable_check(self, r=None, stride=1, count=0, cells=None):
+        """Every commit is checked against the other plans and withheld when it conflicts (include/fasterhip_check.h): from now on
+        stages() holds `backup` before `commit` and `check` and `revert` after it.  A vehicle whose new trajectory comes nearer than r
+        (None: 2 params["rule"]["drone_radius"], where two hulls touch) to what another vehicle flew before this cycle's commit, or to
+        what a vehicle with a lower index committed in it, at the same instant, keeps its previous plan, status and windows and has
+        stage FH_FLEET_STAGE_CONFLICT.  stride > 1 or count > 0 test fewer instants: cheaper and weaker.  cells = (origin, res, dims)
+        is the grid of the broad phase, by default separation_cells(r); no field of a record depends on it.  Works with or without
+        views, traffic and heading.  Memory: a second vehicle array and a second plan array (n max_states states), 32 bytes per record."""
+        t, B = self.torch, self.n
+        par = abi.default_check_params(2.0 * float(self.params["rule"]["drone_radius"]) if r is None else r)
+        par["stride"], par["count"] = stride, count
+        self.check_cells = self.separation_cells(float(par["r"])) if cells is None else cells
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            self.d_backup_vehicles = t.zeros(B * abi.vehicle_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            self.d_backup_plans = t.zeros(B * self.max_states * abi.state_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            self.d_check = t.zeros(B * abi.plan_check_dtype.itemsize, dtype=t.uint8, device=self.dev)
+        for d in (self.d_backup_vehicles, self.d_backup_plans, self.d_check):
+            d.record_stream(self.stream)
+        self.check_par = par
+
+    def check_records(self):
+        """[n] abi.plan_check_dtype: what the last replan()'s check found (synchronises).  FH_CHECK_CONFLICT: the commit was withheld."""
+        if self.check_par is None:
+            raise capi.FasterHipError("Fleet.check_records: enable_check first")
+        return self._host(self.d_check, abi.plan_check_dtype)
+
     def point_masks(self):
         """[n_views][words] uint32 on the host (synchronises)."""
         self.sync()
@@ -366,6 +397,16 @@ class Fleet:
         origin, res, dims = self.grid
         n_cloud = self.n_cloud if self.traffic_par is None else self.n_cloud_all   # (with traffic: the static points and the others' plans)
         chain = self._shared_map_stages(B, P, c, m, p, origin, res, dims, n_cloud)
+        if self.check_par is not None:   # backup -> commit -> check -> revert (include/fasterhip_check.h)
+            chain = chain[:-1] + [
+                ("backup", lambda: c.fleet_backup_device(p(self.d_vehicles), p(self.d_plans), B, self.max_states, p(self.d_backup_vehicles),
+                                                         p(self.d_backup_plans))),
+                chain[-1],
+                ("check", lambda: c.fleet_check_device(self.check_par, p(self.d_vehicles), p(self.d_plans), p(self.d_backup_vehicles),
+                                                       p(self.d_backup_plans), B, self.max_states, self.check_cells, p(self.d_check))),
+                ("revert", lambda: c.fleet_revert_device(p(self.d_check), p(self.d_backup_vehicles), p(self.d_backup_plans), B, self.max_states,
+                                                         p(self.d_vehicles), p(self.d_plans))),
+            ]
         if self.point_mask is None:
             return chain
         cells, mres, center, z_max, inflation = self.map_args

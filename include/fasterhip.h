@@ -611,7 +611,8 @@ int fh_map_plan_batch_radius_device(fh_map* map, const double* d_starts, const d
  * Plan storage: plan of vehicle i = d_plans[i * max_states + plan_head .. + plan_size); a commit moves the kept prefix to index 0.
  * What is flown, those states, is audited against unknown and occupied space by fh_fleet_audit_device of include/fasterhip_audit.h.
  * The plans are compared with each other, instant by instant, by fh_fleet_separation_device of include/fasterhip_separation.h, and
- * shown to each other as occupied points of a view by fh_fleet_traffic_device of include/fasterhip_traffic.h. */
+ * shown to each other as occupied points of a view by fh_fleet_traffic_device of include/fasterhip_traffic.h.  A commit that meets
+ * another vehicle's plan at the same instant is taken back by the check of include/fasterhip_check.h (backup -> commit -> check -> revert). */
 enum {
   FH_VEHICLE_TRAVELING = 0,     /* faster.cpp: TRAVELING */
   FH_VEHICLE_GOAL_SEEN = 1,     /* |G_term - plan.back()| < goal_radius after a commit (:563-570) */

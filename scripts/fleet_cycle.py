@@ -30,8 +30,12 @@ the largest half-extent H of a box and, from a sample of 1024 vehicles, how many
 point (memory per view as for --occupancy, so a fleet of a few thousand at most), its stage table and --separation's report "before";
 then Fleet.enable_traffic(SAMPLES, STRIDE, RANGE; default 8 samples 25 states apart, 6 m; hull = drone_radius, rule "all") and the loop
 traffic -> replan -> 5 ticks with "traffic" as a stage of its own, and the same report "after".
+--check adds "check" after the shared-grid stage table, on the same fleet: Fleet.enable_check (r = two drone radii, stride 1, count 0, the
+default cell grid), one cycle to warm up, then the stage table again with "backup", "check" and "revert" as stages of their own; per
+timed cycle how many vehicles were candidates and how many were withheld, and Fleet.separation_device with the same count, every state,
+fenced like a stage on the plans as they stand at the end.
     usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
-                                         [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]]"""
+                                         [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--check]"""
 import json
 import os
 import sys
@@ -116,6 +120,46 @@ def timed_separation(fl, cycles):
                          near=int(((rec["flags"] & abi.FH_SEP_NEAR) != 0).sum()), within_cap=int(np.isfinite(rec["min_d2"]).sum()),
                          near_others_mean=float(rec["n_near"].mean()), not_finite=int(((rec["flags"] & abi.FH_SEP_NOT_FINITE) != 0).sum()))
     return out
+
+
+def check_cycles(fl, cycles):
+    """The cycle after Fleet.enable_check: see the module docstring."""
+    fl.enable_check()
+    fl.replan()
+    fl.next_goals(5)
+    fl.sync()
+    names = [n for n, _ in fl.stages()] + ["next_goals"]
+    per = {n: [] for n in names}
+    candidates, withheld, committed = [], [], []
+    for _ in range(cycles):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        ev[0].record(fl.stream)
+        for j, (n, launch) in enumerate(fl.stages()):
+            launch()
+            ev[j + 1].record(fl.stream)
+        fl.next_goals(5)
+        ev[-1].record(fl.stream)
+        fl.sync()
+        for j, n in enumerate(names):
+            per[n].append(ev[j].elapsed_time(ev[j + 1]))
+        rec, v = fl.check_records(), fl.vehicles()
+        candidates.append(int(((rec["flags"] & abi.FH_CHECK_CANDIDATE) != 0).sum()))
+        withheld.append(int(((rec["flags"] & abi.FH_CHECK_CONFLICT) != 0).sum()))
+        committed.append(int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum()))
+    med = {n: float(np.median(v)) for n, v in per.items()}
+    ms = []
+    fl.separation_device(count=0)   # (warm-up)
+    for _ in range(max(cycles, 1)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(fl.stream)
+        fl.separation_device(count=0)
+        e1.record(fl.stream)
+        fl.sync()
+        ms.append(e0.elapsed_time(e1))
+    return {"r": float(fl.check_par["r"]), "stride": 1, "count": 0, "cells": list(fl.check_cells[2]), "cell_res": fl.check_cells[1],
+            "stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "check_stages_ms": med["backup"] + med["check"] + med["revert"],
+            "candidates": candidates, "withheld": withheld, "committed_after_revert": committed,
+            "first_kind_1_last": int((rec["first_kind"] == 1).sum()), "separation_count_0_ms": float(np.median(ms))}
 
 
 def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False, traffic=False):
@@ -400,6 +444,8 @@ def main():
             out["audit"] = timed_audit(fl, cycles)
         if SEPARATION:
             out["separation"] = timed_separation(fl, cycles)
+        if "--check" in sys.argv:
+            out["check"] = check_cycles(fl, cycles)
     finally:
         fl.close()
     if "--views" in sys.argv or fov is not None:
