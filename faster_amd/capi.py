@@ -50,6 +50,24 @@ class FasterHipError(RuntimeError):
     pass
 
 
+def _one_record(par, name, where):
+    """`par` as one record of abi.<name>_params_dtype, shape (1,)."""
+    p = np.ascontiguousarray(par)
+    if p.dtype != getattr(abi, name + "_params_dtype") or p.size != 1:
+        raise FasterHipError("%s: par must be one abi.%s_params_dtype record (abi.default_%s_params), got dtype %s, %d elements"
+                             % (where, name, name, p.dtype, p.size))
+    return p.reshape(1)
+
+
+def _grid_record(grid):
+    """(origin, res, dims) as one abi.voxel_grid_dtype record, shape (1,); None stays None."""
+    if grid is None:
+        return None
+    g = np.zeros(1, dtype=abi.voxel_grid_dtype)
+    g["origin"], g["res"], g["dims"] = grid
+    return g
+
+
 def packed_result_size(n_seg):
     return int(lib().fh_packed_result_size(int(n_seg)))
 
@@ -352,9 +370,7 @@ class Pool:
         if flags is None:
             self._check(lib().fh_pool_set_unknown_grid(self._h, None, None), "fh_pool_set_unknown_grid")
             return
-        g = np.zeros((), dtype=abi.voxel_grid_dtype)
-        g["origin"], g["res"], g["dims"] = origin, res, dims
-        g = np.ascontiguousarray(g).reshape(1)
+        g = _grid_record((origin, res, dims))
         flags = np.ascontiguousarray(flags, dtype=np.uint8)
         self._check(lib().fh_pool_set_unknown_grid(self._h, abi.ptr(g), abi.ptr(flags)), "fh_pool_set_unknown_grid")
 
@@ -585,9 +601,7 @@ class Context:
         if d_flags is None:
             self._check(lib().fh_set_unknown_grid_device(self._h, None, None), "fh_set_unknown_grid_device")
             return
-        g = np.zeros((), dtype=abi.voxel_grid_dtype)
-        g["origin"], g["res"], g["dims"] = origin, res, dims
-        g = np.ascontiguousarray(g).reshape(1)
+        g = _grid_record((origin, res, dims))
         self._check(lib().fh_set_unknown_grid_device(self._h, abi.ptr(g), d_flags), "fh_set_unknown_grid_device")
 
     def set_unknown_views_device(self, d_flags, view_stride=0, d_view_of=None, n_views=0, origin=None, res=None, dims=None):
@@ -596,9 +610,7 @@ class Context:
         if d_flags is None:
             self._check(lib().fh_set_unknown_views_device(self._h, None, None, 0, None, 0), "fh_set_unknown_views_device")
             return
-        g = np.zeros((), dtype=abi.voxel_grid_dtype)
-        g["origin"], g["res"], g["dims"] = origin, res, dims
-        g = np.ascontiguousarray(g).reshape(1)
+        g = _grid_record((origin, res, dims))
         self._check(lib().fh_set_unknown_views_device(self._h, abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views)),
                     "fh_set_unknown_views_device")
 
@@ -608,18 +620,14 @@ class Context:
 
     def fleet_observe_device(self, origin, res, dims, d_flags, view_stride, d_view_of, n_views, d_cloud, n_cloud, d_point_mask, mask_words):
         """fh_fleet_observe_device: every view learns the cloud points that lie in voxels it knows (bits are only ORed)."""
-        g = np.zeros((), dtype=abi.voxel_grid_dtype)
-        g["origin"], g["res"], g["dims"] = origin, res, dims
-        g = np.ascontiguousarray(g).reshape(1)
+        g = _grid_record((origin, res, dims))
         self._check(lib().fh_fleet_observe_device(self._h, abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views), d_cloud, int(n_cloud),
                                                   d_point_mask, int(mask_words)), "fh_fleet_observe_device")
 
     def fleet_sense_device(self, vmap, r_sense, origin, res, dims, d_flags, view_stride, d_view_of, n_views, d_vehicles, n):
         """fh_fleet_sense_device: every vehicle clears, in its view, the unknown flag of each voxel within r_sense that no occupied cell
         of `vmap` (a Map) hides (the sensor model: include/fasterhip.h).  Asynchronous on the context's stream."""
-        g = np.zeros((), dtype=abi.voxel_grid_dtype)
-        g["origin"], g["res"], g["dims"] = origin, res, dims
-        g = np.ascontiguousarray(g).reshape(1)
+        g = _grid_record((origin, res, dims))
         self._check(lib().fh_fleet_sense_device(self._h, vmap._h, float(r_sense), abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views),
                                                 d_vehicles, int(n)), "fh_fleet_sense_device")
 
@@ -627,8 +635,7 @@ class Context:
                                tan_half_h, tan_half_v):
         """fh_fleet_sense_fov_device: fleet_sense_device through a field of view along fh_heading.dir, given by the tangents of its half
         angles."""
-        g = np.zeros((), dtype=abi.voxel_grid_dtype)
-        g["origin"], g["res"], g["dims"] = origin, res, dims
+        g = _grid_record((origin, res, dims))
         self._check(lib().fh_fleet_sense_fov_device(self._h, vmap._h, float(r_sense), abi.ptr(g), d_flags, int(view_stride), d_view_of, int(n_views),
                                                     d_vehicles, int(n), d_headings, float(tan_half_h), float(tan_half_v)),
                     "fh_fleet_sense_fov_device")
@@ -790,16 +797,8 @@ class Context:
         """fh_fleet_audit_device: d_out [n] fh_plan_audit, the committed plans against unknown space (d_flags on grid = (origin, res, dims),
         one view per vehicle as in fleet_sense_device) and against the cloud (through d_point_mask, or every point); par: one
         abi.audit_params_dtype record.  Asynchronous on the context's stream (include/fasterhip_audit.h)."""
-        p = np.ascontiguousarray(par)
-        if p.dtype != abi.audit_params_dtype or p.size != 1:
-            raise FasterHipError("fleet_audit_device: par must be one abi.audit_params_dtype record (abi.default_audit_params), got dtype %s, %d elements"
-                                 % (p.dtype, p.size))
-        p = p.reshape(1)
-        g = None
-        if grid is not None:
-            g = np.zeros((), dtype=abi.voxel_grid_dtype)
-            g["origin"], g["res"], g["dims"] = grid
-            g = np.ascontiguousarray(g).reshape(1)
+        p = _one_record(par, "audit", "fleet_audit_device")
+        g = _grid_record(grid)
         self._check(lib().fh_fleet_audit_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states), None if g is None else abi.ptr(g),
                                                 d_flags, int(view_stride), d_view_of, int(n_views), d_cloud, int(n_cloud), d_point_mask, int(mask_words),
                                                 d_out), "fh_fleet_audit_device")
@@ -808,27 +807,15 @@ class Context:
         """fh_fleet_separation_device: d_out [n] fh_plan_separation, the committed plans against each other; par: one
         abi.separation_params_dtype record; cells = (origin, res, dims): the grid of the broad phase, on which no field of a record
         depends.  Asynchronous on the context's stream (include/fasterhip_separation.h)."""
-        p = np.ascontiguousarray(par)
-        if p.dtype != abi.separation_params_dtype or p.size != 1:
-            raise FasterHipError("fleet_separation_device: par must be one abi.separation_params_dtype record (abi.default_separation_params), "
-                                 "got dtype %s, %d elements" % (p.dtype, p.size))
-        p = p.reshape(1)
-        g = None
-        if cells is not None:
-            g = np.zeros((), dtype=abi.voxel_grid_dtype)
-            g["origin"], g["res"], g["dims"] = cells
-            g = np.ascontiguousarray(g).reshape(1)
+        p = _one_record(par, "separation", "fleet_separation_device")
+        g = _grid_record(cells)
         self._check(lib().fh_fleet_separation_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states),
                                                      None if g is None else abi.ptr(g), d_out), "fh_fleet_separation_device")
 
     def fleet_traffic_device(self, par, d_vehicles, d_plans, n, max_states, d_cloud, n_cloud, d_point_mask, mask_words):
         """fh_fleet_traffic_device: the committed plans of the other vehicles as cloud points from par["first_point"] on and as bits of
         the n mask rows; par: one abi.traffic_params_dtype record.  Asynchronous on the context's stream (include/fasterhip_traffic.h)."""
-        p = np.ascontiguousarray(par)
-        if p.dtype != abi.traffic_params_dtype or p.size != 1:
-            raise FasterHipError("fleet_traffic_device: par must be one abi.traffic_params_dtype record (abi.default_traffic_params), "
-                                 "got dtype %s, %d elements" % (p.dtype, p.size))
-        p = p.reshape(1)
+        p = _one_record(par, "traffic", "fleet_traffic_device")
         self._check(lib().fh_fleet_traffic_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states), d_cloud, int(n_cloud),
                                                   d_point_mask, int(mask_words)), "fh_fleet_traffic_device")
 
@@ -842,16 +829,8 @@ class Context:
         """fh_fleet_check_device: d_out [n] fh_plan_check, every vehicle that committed against the backup of the others and the new plans
         of the candidates below it; par: one abi.check_params_dtype record; cells = (origin, res, dims): the grid of the broad phase, on
         which no field of a record depends.  A measurement.  Asynchronous on the context's stream (include/fasterhip_check.h)."""
-        p = np.ascontiguousarray(par)
-        if p.dtype != abi.check_params_dtype or p.size != 1:
-            raise FasterHipError("fleet_check_device: par must be one abi.check_params_dtype record (abi.default_check_params), "
-                                 "got dtype %s, %d elements" % (p.dtype, p.size))
-        p = p.reshape(1)
-        g = None
-        if cells is not None:
-            g = np.zeros((), dtype=abi.voxel_grid_dtype)
-            g["origin"], g["res"], g["dims"] = cells
-            g = np.ascontiguousarray(g).reshape(1)
+        p = _one_record(par, "check", "fleet_check_device")
+        g = _grid_record(cells)
         self._check(lib().fh_fleet_check_device(self._h, abi.ptr(p), d_vehicles, d_plans, d_backup_vehicles, d_backup_plans, int(n),
                                                 int(max_states), None if g is None else abi.ptr(g), d_out), "fh_fleet_check_device")
 
@@ -879,9 +858,7 @@ class Context:
                                    grid_dims, n, r_frac, max_poly_safe, local_bbox, drone_radius, z_ground, faces_per_problem, n_seg_safe, d_safe,
                                    d_safe_faces, d_safe_paths=None, d_safe_n_points=None):
         """fh_safe_corridor_batch_device: the safe corridor of Faster::replan decomposed around R (unknown space modelled)."""
-        g = np.zeros((), dtype=abi.voxel_grid_dtype)
-        g["origin"], g["res"], g["dims"] = grid_origin, grid_res, grid_dims
-        g = np.ascontiguousarray(g).reshape(1)
+        g = _grid_record((grid_origin, grid_res, grid_dims))
         bb = np.ascontiguousarray(local_bbox, dtype=np.float64)
         self._check(lib().fh_safe_corridor_batch_device(self._h, d_whole, d_whole_results, d_paths, d_n_points, max_points, d_goals, d_cloud, n_cloud,
                                                         abi.ptr(g), n, r_frac, max_poly_safe, abi.ptr(bb), drone_radius, z_ground, faces_per_problem,

@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fasterhip_audit.h"
+#include "fh_cells.hip.hpp"
+#include "fh_plans.hip.hpp"
 #include "fh_wave.hip.hpp"
 
 namespace fh {
@@ -51,8 +53,6 @@ struct AuditBest {  // what one lane has seen on one side
   double d2;
   int j_min, j_first;
 };
-
-__device__ __forceinline__ bool audit_finite(double x) { return fabs(x) < INFINITY; }  // false for a NaN
 
 __device__ __forceinline__ void audit_take(AuditBest& b, double d2, double cap2, double r2, int j) {
   if (d2 < cap2) {
@@ -86,8 +86,6 @@ __device__ __forceinline__ void audit_reduce(const AuditBest& b, double& d2, int
   if (first == 0x7fffffff) first = -1;
 }
 
-__device__ __forceinline__ double audit_pack(int lo, int hi) { return __hiloint2double(hi, lo); }
-
 __global__ void __launch_bounds__(64) audit_kernel(AuditArgs a) {
 #pragma clang fp contract(off)
   __shared__ unsigned long long slab[AUDIT_SLAB_WORDS];
@@ -100,12 +98,11 @@ __global__ void __launch_bounds__(64) audit_kernel(AuditArgs a) {
   int flags = 0, n_tested = 0, view = -1;
   int first_u = -1, worst_u = -1, first_o = -1, worst_o = -1;
   double min_u = INFINITY, min_o = INFINITY;
-  const bool bad = head < 0 || size < 0 || (long long)head + (long long)size > (long long)a.max_states;
+  const bool bad = head < 0 || size < 0 || (long long)head + (long long)size > (long long)a.max_states;  // (plan_bad_extent, written out: see there)
   if (bad) {
     flags = FH_AUDIT_BAD_PLAN;
   } else {
-    const int m = a.count > 0 ? min(a.count, size) : size;
-    n_tested = (int)(((long long)m + a.stride - 1) / a.stride);
+    n_tested = plan_instants(plan_limit(a.count, size), a.stride);
     const int rounds = (n_tested + 63) >> 6;
     const fh_state* plan = a.plans + ((size_t)i * (size_t)a.max_states + (size_t)head);
     const bool side_o = a.cloud && a.n_cloud > 0;
@@ -127,7 +124,7 @@ __global__ void __launch_bounds__(64) audit_kernel(AuditArgs a) {
       if (t < n_tested) {
         const double* p = plan[(size_t)t * (size_t)a.stride].pos;
         const double x = p[0], y = p[1], z = p[2];
-        if (audit_finite(x) && audit_finite(y) && audit_finite(z)) {
+        if (plan_finite(x) && plan_finite(y) && plan_finite(z)) {
           lx = x < lx ? x : lx; ly = y < ly ? y : ly; lz = z < lz ? z : lz;
           hx = x > hx ? x : hx; hy = y > hy ? y : hy; hz = z > hz ? z : hz;
         } else {
@@ -174,7 +171,7 @@ __global__ void __launch_bounds__(64) audit_kernel(AuditArgs a) {
               const int j = t * a.stride;
               const double* p = plan[j].pos;
               const double px = p[0], py = p[1], pz = p[2];
-              if (!(audit_finite(px) && audit_finite(py) && audit_finite(pz))) continue;
+              if (!(plan_finite(px) && plan_finite(py) && plan_finite(pz))) continue;
               int xa, xb, ya, yb, za, zb;
               if (!audit_cells(px, px, audit_grow_cells(px, px, a.cap, a.ox, a.res), a.ox, a.res, a.nx, xa, xb)) continue;
               if (!audit_cells(py, py, audit_grow_cells(py, py, a.cap, a.oy, a.res), a.oy, a.res, a.ny, ya, yb)) continue;
@@ -217,8 +214,7 @@ __global__ void __launch_bounds__(64) audit_kernel(AuditArgs a) {
     if (side_o && any_state && !(masked && no_view)) {
       AuditBest best = {INFINITY, 0x7fffffff, 0x7fffffff};
       const unsigned* mrow = masked ? a.mask + (size_t)view * (size_t)a.mask_words : nullptr;
-      const double gx = a.cap + 1e-9 * (a.cap + fabs(lx) + fabs(hx)), gy = a.cap + 1e-9 * (a.cap + fabs(ly) + fabs(hy)),
-                   gz = a.cap + 1e-9 * (a.cap + fabs(lz) + fabs(hz));
+      const double gx = cell_box_margin(a.cap, lx, hx), gy = cell_box_margin(a.cap, ly, hy), gz = cell_box_margin(a.cap, lz, hz);
       const double x0 = lx - gx, x1 = hx + gx, y0 = ly - gy, y1 = hy + gy, z0 = lz - gz, z1 = hz + gz;
       int n_list = 0;  // (uniform)
       for (long long k0 = 0; k0 < (long long)a.n_cloud; k0 += 64) {
@@ -228,7 +224,7 @@ __global__ void __launch_bounds__(64) audit_kernel(AuditArgs a) {
         if (k < a.n_cloud && (!mrow || ((mrow[k >> 5] >> (k & 31)) & 1u))) {
           qx = a.cloud[3 * (size_t)k]; qy = a.cloud[3 * (size_t)k + 1]; qz = a.cloud[3 * (size_t)k + 2];
           // (a NaN fails a comparison; an infinity lies outside a box of finite positions unless the box itself overflowed)
-          keep = qx >= x0 && qx <= x1 && qy >= y0 && qy <= y1 && qz >= z0 && qz <= z1 && audit_finite(qx) && audit_finite(qy) && audit_finite(qz);
+          keep = qx >= x0 && qx <= x1 && qy >= y0 && qy <= y1 && qz >= z0 && qz <= z1 && plan_finite(qx) && plan_finite(qy) && plan_finite(qz);
         }
         const unsigned long long km = __ballot(keep);
         if (keep) {
@@ -245,7 +241,7 @@ __global__ void __launch_bounds__(64) audit_kernel(AuditArgs a) {
               const int j = t * a.stride;
               const double* p = plan[j].pos;
               const double px = p[0], py = p[1], pz = p[2];
-              if (!(audit_finite(px) && audit_finite(py) && audit_finite(pz))) continue;
+              if (!(plan_finite(px) && plan_finite(py) && plan_finite(pz))) continue;
               for (int q = 0; q < n_list; q++) {
                 const double dx = list_x[q] - px, dy = list_y[q] - py, dz = list_z[q] - pz;
                 audit_take(best, dx * dx + dy * dy + dz * dz, a.cap2, a.r2_occupied, j);
@@ -262,8 +258,8 @@ __global__ void __launch_bounds__(64) audit_kernel(AuditArgs a) {
   }
   // words 2 l and 2 l + 1 of the record from lane l < 4: 64 contiguous bytes in one store instruction
   double w0 = 0.0, w1 = 0.0;
-  if (lane == 0) { w0 = audit_pack(flags, n_tested); w1 = audit_pack(first_u, worst_u); }
-  if (lane == 1) { w0 = audit_pack(first_o, worst_o); w1 = audit_pack(view, 0); }
+  if (lane == 0) { w0 = plan_pack(flags, n_tested); w1 = plan_pack(first_u, worst_u); }
+  if (lane == 1) { w0 = plan_pack(first_o, worst_o); w1 = plan_pack(view, 0); }
   if (lane == 2) { w0 = min_u; w1 = min_o; }
   if (lane < 4) reinterpret_cast<double2*>(a.out + i)[lane] = make_double2(w0, w1);
 }

@@ -14,6 +14,7 @@
 #include <new>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/fasterhip.h"
@@ -65,26 +66,18 @@ enum Buf {
   SAFE_SCRATCH,  // fh_safe_corridor_batch_device: safe paths, spheres, goals, offsets and counts between its kernels
   SEG_SPHERES,   // fh_safe_corridor_batch_device: safe_spheres_kernel writes the sphere of every segment, decomp_kernel reads them
   SEG_COUNTER,   // decompose_device zeroes it on the stream; decomp_kernel's workgroups draw their segments from it
-  SEP_BOXES,     // fh_fleet_separation_device: sep_boxes_kernel writes box, checked plan extent and validity word of every vehicle;
-                 // sep_fill_kernel and sep_narrow_kernel read them
-  SEP_COUNTS,    // fh_fleet_separation_device zeroes them on the stream; sep_boxes_kernel counts the vehicles of every cell, sep_scan_kernel
-                 // reads them and leaves zeros, sep_fill_kernel draws the places inside a cell from them
-  SEP_STARTS,    // sep_scan_kernel writes the first item of every cell (and the total behind the last); sep_fill_kernel and sep_narrow_kernel read
-  SEP_ITEMS,     // sep_fill_kernel writes the vehicle numbers sorted by cell; sep_narrow_kernel reads them
-  SEP_EXTENT,    // fh_fleet_separation_device zeroes it on the stream; sep_boxes_kernel raises the largest half-extent per axis (three words),
-                 // sep_narrow_kernel reads it
+  // The cell grid (fh_cells.hip.hpp; cell_broad_phase below), shared by fh_fleet_separation_device and fh_fleet_check_device: both run
+  // on the context's stream, in order, and each call writes all it reads.
+  CELL_BOXES,    // the stage's boxes kernel writes its box record of every vehicle (sized by the stage's record); cell_fill_kernel and the
+                 // stage's narrow kernel read them
+  CELL_COUNTS,   // zeroed on the stream; the boxes kernel counts the vehicles of every cell, cell_scan_kernel reads them and leaves zeros,
+                 // cell_fill_kernel draws the places inside a cell from them
+  CELL_STARTS,   // cell_scan_kernel writes the first item of every cell (and the total behind the last); cell_fill_kernel and the narrow kernel read
+  CELL_ITEMS,    // cell_fill_kernel writes the vehicle numbers sorted by cell; the narrow kernel reads them
+  CELL_EXTENT,   // zeroed on the stream; the boxes kernel raises the largest half-extent per axis (three words), the narrow kernel reads it
   TRAFFIC_SAMPLES,  // fh_fleet_traffic_device: traffic_points{1,7}_kernel write centre, show word and vehicle of every sample (whole
                     // chunks of 64); traffic_mask{1,7}_kernel read them
   TRAFFIC_BOXES,    // traffic_points{1,7}_kernel write the grown box of the shown centres of every chunk; traffic_mask{1,7}_kernel read them
-  CHECK_BOXES,      // fh_fleet_check_device: check_boxes_kernel writes box, checked extents, kept states and validity word of every vehicle;
-                    // check_fill_kernel and check_narrow_kernel read them
-  CHECK_COUNTS,     // fh_fleet_check_device zeroes them on the stream; check_boxes_kernel counts the vehicles of every cell, sep_scan_kernel
-                    // reads them and leaves zeros, check_fill_kernel draws the places inside a cell from them
-  CHECK_STARTS,     // sep_scan_kernel (launched by fh_fleet_check_device) writes the first item of every cell and the total;
-                    // check_fill_kernel and check_narrow_kernel read
-  CHECK_ITEMS,      // check_fill_kernel writes the vehicle numbers sorted by cell; check_narrow_kernel reads them
-  CHECK_EXTENT,     // fh_fleet_check_device zeroes it on the stream; check_boxes_kernel raises the largest half-extent per axis (three
-                    // words), check_narrow_kernel reads it
   N_BUFS
 };
 
@@ -369,6 +362,44 @@ __global__ void __launch_bounds__(256) pack_results_kernel(const double* __restr
   constexpr int WORDS_IN = (int)(sizeof(fh_result) / 8), HEAD = 6, TAIL0 = WORDS_IN - 2;
   const int src = k < HEAD + coeff_words ? k : TAIL0 + (k - HEAD - coeff_words);
   out[w] = in[r * WORDS_IN + src];
+}
+
+// ---- the cell grid (fh_cells.hip.hpp) of the separation and of the commit check ----
+// (judged in the prologue of the entry point, where the order of the return codes puts it)
+static bool cell_grid_ok(const fh_voxel_grid* cells, long long max_cells) {
+  return fhh::voxel_grid_ok(cells) && fhh::voxel_grid_cells(*cells) <= max_cells;
+}
+
+// The working buffers, a.g and a.boxes, and the four launches: the stage's boxes kernel, scan, fill, the stage's narrow kernel.
+template <class Args>
+static int cell_broad_phase(fh_ctx* ctx, const fh_voxel_grid& cells, int n, Args& a, void (*boxes_kernel)(Args), void (*narrow_kernel)(Args)) {
+  using Box = typename std::remove_pointer<decltype(a.boxes)>::type;
+  static_assert(offsetof(Box, c) == 0, "cell_fill_kernel reads the CellBox at the head of a box record");
+  const int n_cells = (int)fhh::voxel_grid_cells(cells);
+  int rc;
+  if ((rc = ensure(ctx, CELL_BOXES, sizeof(Box) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, CELL_COUNTS, sizeof(int) * (size_t)n_cells)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, CELL_STARTS, sizeof(int) * ((size_t)n_cells + 1))) != FH_OK) return rc;
+  if ((rc = ensure(ctx, CELL_ITEMS, sizeof(int) * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, CELL_EXTENT, sizeof(unsigned long long) * 3)) != FH_OK) return rc;
+  fhh::set_lattice(a.g, cells);
+  a.g.extent = ctx->buf[CELL_EXTENT].as<unsigned long long>();
+  a.g.counts = ctx->buf[CELL_COUNTS].as<int>();
+  a.g.starts = ctx->buf[CELL_STARTS].as<int>();
+  a.g.items = ctx->buf[CELL_ITEMS].as<int>();
+  a.boxes = ctx->buf[CELL_BOXES].as<Box>();
+  FH_HIP(hipMemsetAsync(a.g.counts, 0, sizeof(int) * (size_t)n_cells, ctx->stream));
+  FH_HIP(hipMemsetAsync(a.g.extent, 0, sizeof(unsigned long long) * 3, ctx->stream));
+  hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fh::cell_scan_kernel, dim3(1), dim3(fh::CELL_SCAN_THREADS), 0, ctx->stream, a.g.counts, a.g.starts, n_cells);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fh::cell_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a.g,
+                     reinterpret_cast<const unsigned char*>(a.boxes), (int)sizeof(Box), n);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(narrow_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
 }
 
 extern "C" {
@@ -1032,47 +1063,24 @@ int fh_fleet_audit_device(fh_ctx* ctx, const fh_audit_params* par, const fh_vehi
   return FH_OK;
 }
 
-// ---- the separation of committed plans (include/fasterhip_separation.h): boxes, cell starts, cell items, one wavefront per vehicle ----
+// ---- the separation of committed plans (include/fasterhip_separation.h): the cell grid around sep_boxes_kernel and sep_narrow_kernel ----
 int fh_fleet_separation_device(fh_ctx* ctx, const fh_separation_params* par, const fh_vehicle* d_vehicles, const fh_state* d_plans, int n,
                                int max_states, const fh_voxel_grid* cells, fh_plan_separation* d_out) {
   if (!ctx || !par) return FH_ERR_ARG;
   if (!audit_radius_ok(par->r) || !audit_radius_ok(par->cap) || !(par->cap > 0)) return FH_ERR_ARG;
   if (par->r > par->cap || par->stride < 1 || par->count < 0) return FH_ERR_ARG;
   if (n < 0 || max_states < 1) return FH_ERR_ARG;
-  if (!fhh::voxel_grid_ok(cells) || fhh::voxel_grid_cells(*cells) > (long long)FH_SEP_MAX_CELLS) return FH_ERR_ARG;
+  if (!cell_grid_ok(cells, FH_SEP_MAX_CELLS)) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
   DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_vehicles || !d_plans || !d_out) return FH_ERR_ARG;
-  const int n_cells = (int)fhh::voxel_grid_cells(*cells);
-  int rc;
-  if ((rc = ensure(ctx, SEP_BOXES, sizeof(fh::SepBox) * (size_t)n)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, SEP_COUNTS, sizeof(int) * (size_t)n_cells)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, SEP_STARTS, sizeof(int) * ((size_t)n_cells + 1))) != FH_OK) return rc;
-  if ((rc = ensure(ctx, SEP_ITEMS, sizeof(int) * (size_t)n)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, SEP_EXTENT, sizeof(unsigned long long) * 3)) != FH_OK) return rc;
   fh::SepArgs a;
   a.r2 = par->r * par->r; a.cap = par->cap; a.cap2 = par->cap * par->cap;
   a.stride = par->stride; a.count = par->count; a.n = n; a.max_states = max_states;
   a.vehicles = d_vehicles; a.plans = d_plans;
-  fhh::set_lattice(a, *cells);
-  a.boxes = ctx->buf[SEP_BOXES].as<fh::SepBox>();
-  a.extent = ctx->buf[SEP_EXTENT].as<unsigned long long>();
-  a.counts = ctx->buf[SEP_COUNTS].as<int>();
-  a.starts = ctx->buf[SEP_STARTS].as<int>();
-  a.items = ctx->buf[SEP_ITEMS].as<int>();
   a.out = d_out;
-  FH_HIP(hipMemsetAsync(a.counts, 0, sizeof(int) * (size_t)n_cells, ctx->stream));
-  FH_HIP(hipMemsetAsync(a.extent, 0, sizeof(unsigned long long) * 3, ctx->stream));
-  hipLaunchKernelGGL(fh::sep_boxes_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
-  FH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(fh::sep_scan_kernel, dim3(1), dim3(fh::SEP_SCAN_THREADS), 0, ctx->stream, a.counts, a.starts, n_cells);
-  FH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(fh::sep_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
-  FH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(fh::sep_narrow_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
-  FH_HIP(hipGetLastError());
-  return FH_OK;
+  return cell_broad_phase(ctx, *cells, n, a, fh::sep_boxes_kernel, fh::sep_narrow_kernel);
 }
 
 // ---- traffic (include/fasterhip_traffic.h): the other vehicles' plans as cloud points and mask bits; the points, then the words ----
@@ -1119,8 +1127,8 @@ int fh_fleet_traffic_device(fh_ctx* ctx, const fh_traffic_params* par, const fh_
   return FH_OK;
 }
 
-// ---- the commit check (include/fasterhip_check.h): backup before the commit; boxes, cell starts, cell items, one wavefront per
-// candidate after it; then the revert of the commits in conflict ----
+// ---- the commit check (include/fasterhip_check.h): backup before the commit; the cell grid around check_boxes_kernel and
+// check_narrow_kernel after it; then the revert of the commits in conflict ----
 int fh_fleet_backup_device(fh_ctx* ctx, const fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states,
                            fh_vehicle* d_backup_vehicles, fh_state* d_backup_plans) {
   if (!ctx) return FH_ERR_ARG;
@@ -1142,40 +1150,17 @@ int fh_fleet_check_device(fh_ctx* ctx, const fh_check_params* par, const fh_vehi
   if (!audit_radius_ok(par->r)) return FH_ERR_ARG;
   if (par->stride < 1 || par->count < 0) return FH_ERR_ARG;
   if (n < 0 || max_states < 1) return FH_ERR_ARG;
-  if (!fhh::voxel_grid_ok(cells) || fhh::voxel_grid_cells(*cells) > (long long)FH_CHECK_MAX_CELLS) return FH_ERR_ARG;
+  if (!cell_grid_ok(cells, FH_CHECK_MAX_CELLS)) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
   DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_vehicles || !d_plans || !d_backup_vehicles || !d_backup_plans || !d_out) return FH_ERR_ARG;
-  const int n_cells = (int)fhh::voxel_grid_cells(*cells);
-  int rc;
-  if ((rc = ensure(ctx, CHECK_BOXES, sizeof(fh::ChkBox) * (size_t)n)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, CHECK_COUNTS, sizeof(int) * (size_t)n_cells)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, CHECK_STARTS, sizeof(int) * ((size_t)n_cells + 1))) != FH_OK) return rc;
-  if ((rc = ensure(ctx, CHECK_ITEMS, sizeof(int) * (size_t)n)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, CHECK_EXTENT, sizeof(unsigned long long) * 3)) != FH_OK) return rc;
   fh::ChkArgs a;
   a.r = par->r; a.r2 = par->r * par->r;
   a.stride = par->stride; a.count = par->count; a.n = n; a.max_states = max_states;
   a.cur_v = d_vehicles; a.cur_p = d_plans; a.old_v = d_backup_vehicles; a.old_p = d_backup_plans;
-  fhh::set_lattice(a, *cells);
-  a.boxes = ctx->buf[CHECK_BOXES].as<fh::ChkBox>();
-  a.extent = ctx->buf[CHECK_EXTENT].as<unsigned long long>();
-  a.counts = ctx->buf[CHECK_COUNTS].as<int>();
-  a.starts = ctx->buf[CHECK_STARTS].as<int>();
-  a.items = ctx->buf[CHECK_ITEMS].as<int>();
   a.out = d_out;
-  FH_HIP(hipMemsetAsync(a.counts, 0, sizeof(int) * (size_t)n_cells, ctx->stream));
-  FH_HIP(hipMemsetAsync(a.extent, 0, sizeof(unsigned long long) * 3, ctx->stream));
-  hipLaunchKernelGGL(fh::check_boxes_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
-  FH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(fh::sep_scan_kernel, dim3(1), dim3(fh::SEP_SCAN_THREADS), 0, ctx->stream, a.counts, a.starts, n_cells);
-  FH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(fh::check_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
-  FH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(fh::check_narrow_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
-  FH_HIP(hipGetLastError());
-  return FH_OK;
+  return cell_broad_phase(ctx, *cells, n, a, fh::check_boxes_kernel, fh::check_narrow_kernel);
 }
 
 int fh_fleet_revert_device(fh_ctx* ctx, const fh_plan_check* d_out, const fh_vehicle* d_backup_vehicles, const fh_state* d_backup_plans, int n,

@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/fasterhip_traffic.h"
+#include "fh_cells.hip.hpp"
+#include "fh_plans.hip.hpp"
 #include "fh_wave.hip.hpp"
 
 namespace fh {
@@ -54,8 +56,6 @@ struct TrafficArgs {
   TrafficBox* boxes;  // [n_chunks]
 };
 
-__device__ __forceinline__ bool traffic_finite(double x) { return fabs(x) < INFINITY; }  // false for a NaN
-
 template <int PPS>
 __device__ __forceinline__ void traffic_points(const TrafficArgs& a) {
 #pragma clang fp contract(off)
@@ -74,12 +74,12 @@ __device__ __forceinline__ void traffic_points(const TrafficArgs& a) {
     const int s = t - k * a.samples;
     const fh_vehicle& V = a.vehicles[k];
     const int head = V.plan_head, size = V.plan_size;
-    const bool bad = head < 0 || size < 0 || (long long)head + (long long)size > (long long)a.max_states;
+    const bool bad = head < 0 || size < 0 || (long long)head + (long long)size > (long long)a.max_states;  // (plan_bad_extent, written out: see there)
     if (!bad && size >= 1) {
       const long long j = (long long)s * (long long)a.stride, last = (long long)size - 1;
       const double* p = a.plans[(size_t)k * (size_t)a.max_states + (size_t)head + (size_t)(j < last ? j : last)].pos;
       const double x = p[0], y = p[1], z = p[2];
-      if (traffic_finite(x) && traffic_finite(y) && traffic_finite(z)) {
+      if (plan_finite(x) && plan_finite(y) && plan_finite(z)) {
         show = true;
         cx = x; cy = y; cz = z;
       }
@@ -104,8 +104,7 @@ __device__ __forceinline__ void traffic_points(const TrafficArgs& a) {
   const double lx = wave_min(show ? cx : INFINITY), ly = wave_min(show ? cy : INFINITY), lz = wave_min(show ? cz : INFINITY);
   const double hx = wave_max(show ? cx : -INFINITY), hy = wave_max(show ? cy : -INFINITY), hz = wave_max(show ? cz : -INFINITY);
   if (lane == 0) {
-    const double gx = a.range + 1e-9 * (a.range + fabs(lx) + fabs(hx)), gy = a.range + 1e-9 * (a.range + fabs(ly) + fabs(hy)),
-                 gz = a.range + 1e-9 * (a.range + fabs(lz) + fabs(hz));
+    const double gx = cell_box_margin(a.range, lx, hx), gy = cell_box_margin(a.range, ly, hy), gz = cell_box_margin(a.range, lz, hz);
     TrafficBox& B = a.boxes[chunk];
     B.lo[0] = lx - gx; B.lo[1] = ly - gy; B.lo[2] = lz - gz;
     B.hi[0] = hx + gx; B.hi[1] = hy + gy; B.hi[2] = hz + gz;
@@ -147,7 +146,7 @@ __device__ __forceinline__ void traffic_mask(const TrafficArgs& a) {
   for (int i = (int)blockIdx.y; i < a.n; i += (int)gridDim.y) {
     const double* p = a.vehicles[i].state.pos;
     const double px = uniform_f64(p[0]), py = uniform_f64(p[1]), pz = uniform_f64(p[2]);
-    const bool p_finite = traffic_finite(px) && traffic_finite(py) && traffic_finite(pz);
+    const bool p_finite = plan_finite(px) && plan_finite(py) && plan_finite(pz);
     const unsigned long long looked = __ballot(px >= x0 && px <= x1 && py >= y0 && py <= y1 && pz >= z0 && pz <= z1);
     uint32_t* row = a.mask + ((size_t)i * (size_t)a.mask_words + (size_t)a.first_word + (size_t)w0);
     for (int w = lane; w < group_words; w += 64)

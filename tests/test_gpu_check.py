@@ -270,6 +270,59 @@ def test_a_random_fleet_twice_gives_the_same_bytes(ctx):
     assert len(hit) > 20 and set(hit["first_kind"]) == {0, 1} and ((a["flags"] & (C | X)) == C).sum() > 100
 
 
+# ---- 5b. the separation and the check share the working buffers of a context ------------------------------------------------------------------
+def test_separation_and_check_back_to_back_on_shared_buffers(ctx):
+    """Both stages sort their boxes into the same five working buffers of a context.  Four calls on one context with no wait between
+    them: separation of 65 vehicles in one cell; check of 200 on 4 x 4 x 2 cells (every shared buffer grows, the box records go from 64 to
+    80 bytes); separation of 200 on 3 x 3 x 1 cells; check of 65 in one cell.  Each output equals the same call alone on a fresh
+    context, byte for byte, and its model."""
+    import torch
+
+    import separation_model as sm
+
+    MS = 48
+    small, large = random_cycle(np.random.default_rng(91), 65, MS, box=2.0), random_cycle(np.random.default_rng(92), 200, MS, box=6.0)
+    spar, cpar = sm.params(0.3, 0.6), cm.params(0.3)
+    calls = [("separation", small, ONE_CELL), ("check", large, ((0.0, 0.0, 0.0), 1.5, (4, 4, 2))),
+             ("separation", large, ((0.0, 0.0, 0.0), 2.0, (3, 3, 1))), ("check", small, ONE_CELL)]
+    dtype = {"separation": abi.plan_separation_dtype, "check": abi.plan_check_dtype}
+
+    def launch(c, kind, cycle, cells, d_out):
+        d, n = inputs[id(cycle)], len(cycle[0])
+        if kind == "separation":
+            c.fleet_separation_device(spar, d[0].data_ptr(), d[1].data_ptr(), n, MS, cells, d_out.data_ptr())
+        else:
+            c.fleet_check_device(cpar, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), n, MS, cells, d_out.data_ptr())
+
+    def outputs():
+        return [torch.full((len(cy[0]) * dtype[kind].itemsize,), 0xEE, dtype=torch.uint8, device="cuda:0") for kind, cy, _ in calls]
+
+    inputs = {id(cy): [dev(a) for a in cy] for cy in (small, large)}
+    outs, alone = outputs(), outputs()
+    torch.cuda.synchronize()
+    for (kind, cy, cells), d_out in zip(calls, outs):   # back to back: nothing here waits for the stream
+        launch(ctx, kind, cy, cells, d_out)
+    ctx.sync()
+    for (kind, cy, cells), d_out, d_alone in zip(calls, outs, alone):
+        fresh = capi.Context(0)
+        try:
+            launch(fresh, kind, cy, cells, d_alone)
+            fresh.sync()
+        finally:
+            fresh.close()
+        got = d_out.cpu().numpy().view(dtype[kind]).copy()
+        what = "%s of %d vehicles on %s cells" % (kind, len(cy[0]), cells[2])
+        assert got.tobytes() == d_alone.cpu().numpy().tobytes(), what + ": not what the call gives alone on a fresh context"
+        if kind == "separation":
+            sm.assert_equal_records(got, sm.separation(spar, cy[0], cy[1], MS), what)
+        else:
+            cm.assert_equal_records(got, cm.check(cpar, cy[0], cy[1], cy[2], cy[3], MS), what)
+    # (the scene shows something: vehicles near each other and commits in conflict, in both fleets)
+    for (kind, _, _), d_out in zip(calls, outs):
+        rec = d_out.cpu().numpy().view(dtype[kind])
+        assert (rec["flags"] & (abi.FH_SEP_NEAR if kind == "separation" else X)).any()
+
+
 # ---- 6. backup and revert on poisoned buffers ----------------------------------------------------------------------------------------------
 def copy_fleet(rng):
     """Vehicle records of random bytes with extents at the borders that matter: heads of zero and not, sizes whose 6 s chunks of 16
