@@ -213,6 +213,22 @@ def default_traffic_params(samples, stride, range, hull=0.0, rule=FH_TRAFFIC_ALL
     return p
 
 
+# fh_traffic_timed_params: the same points, the bits matched instant by instant (include/fasterhip_traffic_timed.h)
+FH_TRAFFIC_TIMED_MAX_SAMPLES = 512
+traffic_timed_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),
+                                       ("first_instant", "<i4"), ("window", "<i4"), ("reserved", "<i4", (2,))], align=True)
+assert traffic_timed_params_dtype.itemsize == 48
+
+
+def default_traffic_timed_params(samples, stride, range, hull=0.0, rule=FH_TRAFFIC_ALL, first_point=0, first_instant=0, window=0):  # noqa: A002
+    """fh_traffic_timed_params: default_traffic_params' fields, and sample s is the instant first_instant + s stride; sample (k, s) is
+    shown to vehicle i when a shown sample s' of i's own plan with |s - s'| <= window lies nearer than `range`."""
+    p = np.zeros((), dtype=traffic_timed_params_dtype)
+    p["range"], p["hull"], p["samples"], p["stride"], p["rule"], p["first_point"] = range, hull, samples, stride, rule, first_point
+    p["first_instant"], p["window"] = first_instant, window
+    return p
+
+
 def traffic_points_per_sample(hull):
     """pps of include/fasterhip_traffic.h: seven points per sample with a hull, else one."""
     return 7 if float(hull) > 0 else 1

@@ -16,6 +16,7 @@ DEPS = SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + [os.pa
                                                                                     os.path.join(ROOT, "include", "fasterhip_audit.h"),
                                                                                     os.path.join(ROOT, "include", "fasterhip_separation.h"),
                                                                                     os.path.join(ROOT, "include", "fasterhip_traffic.h"),
+                                                                                    os.path.join(ROOT, "include", "fasterhip_traffic_timed.h"),
                                                                                     os.path.join(ROOT, "include", "fasterhip_check.h")]
 HOST_SO = os.path.join(HERE, "libsolverhip.so")
 HOST_SOURCES = [os.path.join(HERE, "host", "solver_hip.cpp"), os.path.join(HERE, "host", "decomp_hip.cpp"),

@@ -40,6 +40,8 @@ AUDIT_SYMBOLS = ["fh_fleet_audit_device"]
 SEPARATION_SYMBOLS = ["fh_fleet_separation_device"]
 # include/fasterhip_traffic.h
 TRAFFIC_SYMBOLS = ["fh_fleet_traffic_device"]
+# include/fasterhip_traffic_timed.h
+TRAFFIC_TIMED_SYMBOLS = ["fh_fleet_traffic_timed_device"]
 # include/fasterhip_check.h
 CHECK_SYMBOLS = ["fh_fleet_backup_device", "fh_fleet_check_device", "fh_fleet_revert_device"]
 
@@ -291,6 +293,8 @@ def lib():
         L.fh_fleet_separation_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
         L.fh_fleet_traffic_device.restype = i32
         L.fh_fleet_traffic_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, i32]
+        L.fh_fleet_traffic_timed_device.restype = i32
+        L.fh_fleet_traffic_timed_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, i32]
         L.fh_fleet_backup_device.restype = i32
         L.fh_fleet_backup_device.argtypes = [vp, vp, vp, i32, i32, vp, vp]
         L.fh_fleet_check_device.restype = i32
@@ -818,6 +822,14 @@ class Context:
         p = _one_record(par, "traffic", "fleet_traffic_device")
         self._check(lib().fh_fleet_traffic_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states), d_cloud, int(n_cloud),
                                                   d_point_mask, int(mask_words)), "fh_fleet_traffic_device")
+
+    def fleet_traffic_timed_device(self, par, d_vehicles, d_plans, n, max_states, d_cloud, n_cloud, d_point_mask, mask_words):
+        """fh_fleet_traffic_timed_device: fleet_traffic_device's points, and in row i the bits of the samples that vehicle i's own plan comes
+        near at the same sampled instant or within par["window"] samples of it; par: one abi.traffic_timed_params_dtype record.
+        Asynchronous on the context's stream (include/fasterhip_traffic_timed.h)."""
+        p = _one_record(par, "traffic_timed", "fleet_traffic_timed_device")
+        self._check(lib().fh_fleet_traffic_timed_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states), d_cloud, int(n_cloud),
+                                                        d_point_mask, int(mask_words)), "fh_fleet_traffic_timed_device")
 
     def fleet_backup_device(self, d_vehicles, d_plans, n, max_states, d_backup_vehicles, d_backup_plans):
         """fh_fleet_backup_device: the record and the live plan extent of every vehicle into the backup arrays, between begin and commit.

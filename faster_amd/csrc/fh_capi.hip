@@ -24,6 +24,7 @@
 #include "../../include/fasterhip_separation.h"
 #include "../../include/fasterhip_traffic.h"
 #include "../../include/fasterhip_check.h"
+#include "../../include/fasterhip_traffic_timed.h"
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
 #include "fh_decomp.hip.hpp"
@@ -34,6 +35,7 @@
 #include "fh_separation.hip.hpp"
 #include "fh_traffic.hip.hpp"
 #include "fh_check.hip.hpp"
+#include "fh_traffic_timed.hip.hpp"  // (after every other device header: its kernels come last in the code object)
 #include "fh_host.hpp"
 
 using fhh::DeviceScope;
@@ -75,8 +77,10 @@ enum Buf {
   CELL_STARTS,   // cell_scan_kernel writes the first item of every cell (and the total behind the last); cell_fill_kernel and the narrow kernel read
   CELL_ITEMS,    // cell_fill_kernel writes the vehicle numbers sorted by cell; the narrow kernel reads them
   CELL_EXTENT,   // zeroed on the stream; the boxes kernel raises the largest half-extent per axis (three words), the narrow kernel reads it
-  TRAFFIC_SAMPLES,  // fh_fleet_traffic_device: traffic_points{1,7}_kernel write centre, show word and vehicle of every sample (whole
-                    // chunks of 64); traffic_mask{1,7}_kernel read them
+  // Shared by fh_fleet_traffic_device and fh_fleet_traffic_timed_device (the traffic_timed_* kernels): both run on the context's stream,
+  // in order, and each call writes all it reads.
+  TRAFFIC_SAMPLES,  // traffic_points{1,7}_kernel write centre, show word and vehicle of every sample (whole chunks of 64);
+                    // traffic_mask{1,7}_kernel read them
   TRAFFIC_BOXES,    // traffic_points{1,7}_kernel write the grown box of the shown centres of every chunk; traffic_mask{1,7}_kernel read them
   N_BUFS
 };
@@ -1122,6 +1126,57 @@ int fh_fleet_traffic_device(fh_ctx* ctx, const fh_traffic_params* par, const fh_
     hipLaunchKernelGGL(fh::traffic_points1_kernel, chunks, dim3(64), 0, ctx->stream, a);
     FH_HIP(hipGetLastError());
     hipLaunchKernelGGL(fh::traffic_mask1_kernel, rows, dim3(64), 0, ctx->stream, a);
+  }
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// ---- time-aware traffic (include/fasterhip_traffic_timed.h): the same points, the bits matched instant by instant ----
+int fh_fleet_traffic_timed_device(fh_ctx* ctx, const fh_traffic_timed_params* par, const fh_vehicle* d_vehicles, const fh_state* d_plans,
+                                  int n, int max_states, double* d_cloud_xyz, int n_cloud, uint32_t* d_point_mask, int mask_words) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->range) || !(par->range > 0)) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->hull)) return FH_ERR_ARG;
+  if (par->samples < 1 || par->samples > FH_TRAFFIC_TIMED_MAX_SAMPLES) return FH_ERR_ARG;
+  if (par->stride < 1) return FH_ERR_ARG;
+  if (par->rule != FH_TRAFFIC_ALL && par->rule != FH_TRAFFIC_YIELD_TO_LOWER) return FH_ERR_ARG;
+  if (par->first_point < 0 || par->first_point % 32 != 0) return FH_ERR_ARG;
+  if (par->first_instant < 0) return FH_ERR_ARG;
+  if (par->window < 0) return FH_ERR_ARG;
+  if (n < 0 || max_states < 1) return FH_ERR_ARG;
+  const int pps = par->hull > 0 ? 7 : 1;
+  const long long n_samples = (long long)n * (long long)par->samples;  // (below 2^41)
+  if (n_samples > (long long)INT32_MAX) return FH_ERR_ARG;             // (more than any n_cloud: n_samples * pps is then safe in 64 bits)
+  const long long end_point = (long long)par->first_point + n_samples * pps;
+  if (end_point > (long long)n_cloud || end_point > (long long)mask_words * 32) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_cloud_xyz || !d_point_mask) return FH_ERR_ARG;
+  fh::TrafficTimedArgs b;
+  fh::TrafficArgs& a = b.t;
+  a.range = par->range; a.range2 = par->range * par->range; a.hull = par->hull;
+  a.samples = par->samples; a.stride = par->stride; a.rule = par->rule; a.first_point = par->first_point;
+  a.n = n; a.max_states = max_states; a.n_samples = (int)n_samples; a.n_chunks = (int)((n_samples + 63) / 64);
+  a.mask_words = mask_words; a.first_word = par->first_point / 32; a.n_words = (int)((end_point + 31) / 32) - a.first_word;
+  a.vehicles = d_vehicles; a.plans = d_plans; a.cloud = d_cloud_xyz; a.mask = d_point_mask;
+  b.first_instant = par->first_instant;
+  b.window = std::min(par->window, par->samples - 1);  // (any window >= S - 1 is every sampled instant)
+  b.span = std::min(2 * b.window + 1, par->samples);
+  int rc;
+  if ((rc = ensure(ctx, TRAFFIC_SAMPLES, sizeof(fh::TrafficRec) * 64 * (size_t)a.n_chunks)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, TRAFFIC_BOXES, sizeof(fh::TrafficBox) * (size_t)a.n_chunks)) != FH_OK) return rc;
+  a.recs = ctx->buf[TRAFFIC_SAMPLES].as<fh::TrafficRec>();
+  a.boxes = ctx->buf[TRAFFIC_BOXES].as<fh::TrafficBox>();
+  const dim3 chunks((unsigned)a.n_chunks), rows((unsigned)((a.n_chunks + 63) / 64), (unsigned)std::min(n, fh::TRAFFIC_GRID_ROWS));
+  if (pps == 7) {
+    hipLaunchKernelGGL(fh::traffic_timed_points7_kernel, chunks, dim3(64), 0, ctx->stream, b);
+    FH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fh::traffic_timed_mask7_kernel, rows, dim3(64), 0, ctx->stream, b);
+  } else {
+    hipLaunchKernelGGL(fh::traffic_timed_points1_kernel, chunks, dim3(64), 0, ctx->stream, b);
+    FH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fh::traffic_timed_mask1_kernel, rows, dim3(64), 0, ctx->stream, b);
   }
   FH_HIP(hipGetLastError());
   return FH_OK;

@@ -18,7 +18,8 @@ shared cloud that observe() grows from what the view has seen — and the loop b
 
 in which a vehicle searches its path and cuts both corridors around the points its view knows, and no others.  enable_traffic() makes
 the vehicles avoid each other with the same mechanism: traffic() writes the committed plans of the other vehicles as points at the tail
-of the cloud and sets, in the mask row of vehicle i, the bits of those it has to keep clear of (include/fasterhip_traffic.h):
+of the cloud and sets, in the mask row of vehicle i, the bits of those it has to keep clear of (include/fasterhip_traffic.h: the samples
+near where vehicle i stands; with timed=True include/fasterhip_traffic_timed.h: the samples its own plan comes near at the same instant):
 
     sense -> observe -> traffic -> replan -> next_goals
 
@@ -250,14 +251,18 @@ class Fleet:
         if first > m:
             cloud[m:first] = static[0] if m > 0 else 0.0
 
-    def enable_traffic(self, samples, stride, range, hull=None, rule="all"):  # noqa: A002  (the header's word)
+    def enable_traffic(self, samples, stride, range, hull=None, rule="all", timed=False, window=0, first_instant=None):  # noqa: A002  (the header's word)
         """The vehicles avoid each other (include/fasterhip_traffic.h): from now on traffic() writes `samples` instants of every committed
         plan, `stride` states apart, as points behind the static cloud and shows them, through the point masks, to the vehicles nearer
         than `range`; hull (None: params["rule"]["drone_radius"]; 0: no hull) inflates every sample to seven points.  rule: "all", or
         "yield": vehicle i sees the vehicles below i only.  After set_map, set_unknown_views with a view per vehicle and
         set_point_views.  The cloud tensor grows to pad32(n_static) + n samples pps points and every mask row to as many bits, keeping
         its words; replan() reads the whole cloud, set_map's shared map, observe() and audit() the static points only.  Memory: n rows
-        of ceil(n samples pps / 32) words more."""
+        of ceil(n samples pps / 32) words more.
+        timed=True matches the plans instant by instant (include/fasterhip_traffic_timed.h): sample s is the instant first_instant +
+        s stride (None: max(params["delta_t"] - 1, 0), the start state of the replan), and a sample of another vehicle is shown to
+        vehicle i only when i's own committed plan is nearer than `range` to it within `window` samples of the same instant; at most
+        abi.FH_TRAFFIC_TIMED_MAX_SAMPLES samples.  With timed=False window and first_instant are ignored."""
         t = self.torch
         if self.cloud is None or self.view_flags is None or self.point_mask is None:
             raise capi.FasterHipError("Fleet.enable_traffic: set_map, set_unknown_views and set_point_views first")
@@ -269,7 +274,14 @@ class Fleet:
         hull = float(self.params["rule"]["drone_radius"]) if hull is None else float(hull)
         static = self.cloud[:self.n_cloud]
         first = abi.point_mask_words(self.n_cloud) * 32
-        par = abi.default_traffic_params(samples, stride, range, hull, rules[rule], first)
+        if timed:
+            if int(samples) > abi.FH_TRAFFIC_TIMED_MAX_SAMPLES:
+                raise capi.FasterHipError("Fleet.enable_traffic: timed traffic takes at most %d samples, got %d"
+                                          % (abi.FH_TRAFFIC_TIMED_MAX_SAMPLES, int(samples)))
+            first_instant = max(int(self.params["delta_t"]) - 1, 0) if first_instant is None else int(first_instant)
+            par = abi.default_traffic_timed_params(samples, stride, range, hull, rules[rule], first, first_instant, window)
+        else:
+            par = abi.default_traffic_params(samples, stride, range, hull, rules[rule], first)
         total = first + self.n * int(samples) * abi.traffic_points_per_sample(hull)
         if int(samples) < 1 or total >= 1 << 31:
             raise capi.FasterHipError("Fleet.enable_traffic: %d samples of %d vehicles do not fit a cloud" % (int(samples), self.n))
@@ -291,13 +303,15 @@ class Fleet:
 
     def traffic(self):
         """The committed plans of the other vehicles into the tail of the cloud and into every vehicle's mask row
-        (fh_fleet_traffic_device): after observe(), before replan().  Two launches on the fleet's stream; the traffic words are written
-        whole, so what a vehicle saw of the others last cycle goes."""
+        (fh_fleet_traffic_device, or fh_fleet_traffic_timed_device after enable_traffic(timed=True)): after observe(), before replan().
+        Two launches on the fleet's stream; the traffic words are written whole, so what a vehicle saw of the others last cycle goes."""
         if self.traffic_par is None:
             raise capi.FasterHipError("Fleet.traffic: enable_traffic first")
         self._follow_current()
-        self.ctx.fleet_traffic_device(self.traffic_par, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.n, self.max_states,
-                                      self.cloud.data_ptr(), self.n_cloud_all, self.point_mask.data_ptr(), self.point_mask.shape[1])
+        timed = self.traffic_par.dtype == abi.traffic_timed_params_dtype
+        (self.ctx.fleet_traffic_timed_device if timed else self.ctx.fleet_traffic_device)(
+            self.traffic_par, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.n, self.max_states, self.cloud.data_ptr(),
+            self.n_cloud_all, self.point_mask.data_ptr(), self.point_mask.shape[1])
 
     def enable_check(self, r=None, stride=1, count=0, cells=None):
         """Every commit is checked against the other plans and withheld when it conflicts (include/fasterhip_check.h): from now on

@@ -30,12 +30,15 @@ the largest half-extent H of a box and, from a sample of 1024 vehicles, how many
 point (memory per view as for --occupancy, so a fleet of a few thousand at most), its stage table and --separation's report "before";
 then Fleet.enable_traffic(SAMPLES, STRIDE, RANGE; default 8 samples 25 states apart, 6 m; hull = drone_radius, rule "all") and the loop
 traffic -> replan -> 5 ticks with "traffic" as a stage of its own, and the same report "after".
+--traffic-timed WINDOW adds "traffic_timed": the same scene and report with Fleet.enable_traffic(..., timed=True, window=WINDOW), the plans
+matched instant by instant (SAMPLES, STRIDE and RANGE are --traffic's when that is given too, else its defaults), and the traffic bits
+set per vehicle, which both reports carry.
 --check adds "check" after the shared-grid stage table, on the same fleet: Fleet.enable_check (r = two drone radii, stride 1, count 0, the
 default cell grid), one cycle to warm up, then the stage table again with "backup", "check" and "revert" as stages of their own; per
 timed cycle how many vehicles were candidates and how many were withheld, and Fleet.separation_device with the same count, every state,
 fenced like a stage on the plans as they stand at the end.
     usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
-                                         [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--check]"""
+                                         [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]"""
 import json
 import os
 import sys
@@ -301,8 +304,8 @@ def occupancy_cycles(B, cycles, p, world, r_sense, teams):
     return {"occupancy": out}
 
 
-def traffic_cycles(B, cycles, p, world, samples, stride, reach):
-    """The cycle before and after Fleet.enable_traffic: see the module docstring."""
+def traffic_cycles(B, cycles, p, world, samples, stride, reach, window=None):
+    """The cycle before and after Fleet.enable_traffic (window: timed, with that window): see the module docstring."""
     cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims = world
     n_cells = dims[0] * dims[1] * dims[2]
     out = {"samples": samples, "stride": stride, "range": reach, "rule": "all", "hull": float(p["rule"]["drone_radius"]),
@@ -318,7 +321,9 @@ def traffic_cycles(B, cycles, p, world, samples, stride, reach):
         fl.sync()
         med = timed_cycles(fl, cycles)
         out["before"] = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "separation": timed_separation(fl, cycles)}
-        fl.enable_traffic(samples, stride, reach)
+        fl.enable_traffic(samples, stride, reach, timed=window is not None, window=window or 0)
+        if window is not None:
+            out.update({"window": int(window), "first_instant": int(fl.traffic_par["first_instant"])})
         out.update({"traffic_points": fl.n_cloud_all - int(fl.traffic_par["first_point"]), "cloud_points": fl.n_cloud_all,
                     "mask_bytes": int(fl.point_mask.numel()) * 4, "unknown_views_bytes": B * n_cells})
         fl.traffic()
@@ -333,12 +338,16 @@ def traffic_cycles(B, cycles, p, world, samples, stride, reach):
                         "traffic_bits_set_per_vehicle": shown / B, "committed_last": int((v["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum())}
     finally:
         fl.close()
-    return {"traffic": out}
+    return {"traffic" if window is None else "traffic_timed": out}
 
 
 def main():
     argv = sys.argv[1:]
-    r_sense, fov, teams, traffic = 3.0, None, 0, None
+    r_sense, fov, teams, traffic, window = 3.0, None, 0, None, None
+    if "--traffic-timed" in argv:
+        k = argv.index("--traffic-timed")
+        window = int(argv[k + 1])
+        del argv[k:k + 2]
     if "--traffic" in argv:
         k = argv.index("--traffic")
         has = k + 3 < len(argv) and argv[k + 1].isdigit() and argv[k + 2].isdigit()
@@ -457,6 +466,9 @@ def main():
     if traffic:
         world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
         out.update(traffic_cycles(B, cycles, p, world, *traffic))
+    if window is not None:
+        world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
+        out.update(traffic_cycles(B, cycles, p, world, *(traffic or (8, 25, 6.0)), window=window))
     print(json.dumps(out))
 
 
