@@ -198,6 +198,25 @@ def default_check_params(radius):
     return p
 
 
+# fh_round_params / fh_plan_round: the priority rounds of a cycle, a class per vehicle (include/fasterhip_rounds.h)
+FH_ROUNDS_MAX, FH_ROUNDS_LIST, FH_ROUNDS_MAX_PASSES, FH_ROUNDS_MAX_CELLS = 64, 64, 1024, 1 << 20
+FH_ROUND_RESTORE, FH_ROUND_RETRY = -1, -2   # the `round` of fh_fleet_round_gate_device below zero
+FH_ROUND_OVERFLOW, FH_ROUND_UNSETTLED, FH_ROUND_NOT_FINITE, FH_ROUND_BAD_PLAN = 1, 2, 4, 8
+round_params_dtype = np.dtype([("reach", "<f8"), ("rounds", "<i4"), ("passes", "<i4"), ("stride", "<i4"), ("count", "<i4"),
+                               ("reserved", "<i4", (2,))], align=True)
+assert round_params_dtype.itemsize == 32
+plan_round_dtype = np.dtype([("round_class", "<i4"), ("decided_pass", "<i4"), ("n_lower", "<i4"), ("flags", "<i4")], align=True)
+assert plan_round_dtype.itemsize == 16
+
+
+def default_round_params(reach, rounds):
+    """fh_round_params: two vehicles whose plans come nearer than `reach` at one instant go into different ones of `rounds` rounds;
+    every instant is tested, 32 passes settle every chain of up to 33 vehicles."""
+    p = np.zeros((), dtype=round_params_dtype)
+    p["reach"], p["rounds"], p["passes"], p["stride"], p["count"] = reach, rounds, 32, 1, 0
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

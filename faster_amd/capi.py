@@ -44,6 +44,8 @@ TRAFFIC_SYMBOLS = ["fh_fleet_traffic_device"]
 TRAFFIC_TIMED_SYMBOLS = ["fh_fleet_traffic_timed_device"]
 # include/fasterhip_check.h
 CHECK_SYMBOLS = ["fh_fleet_backup_device", "fh_fleet_check_device", "fh_fleet_revert_device"]
+# include/fasterhip_rounds.h
+ROUNDS_SYMBOLS = ["fh_fleet_round_classes_device", "fh_fleet_round_gate_device"]
 
 _LIB = None
 
@@ -301,6 +303,10 @@ def lib():
         L.fh_fleet_check_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
         L.fh_fleet_revert_device.restype = i32
         L.fh_fleet_revert_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+        L.fh_fleet_round_classes_device.restype = i32
+        L.fh_fleet_round_classes_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+        L.fh_fleet_round_gate_device.restype = i32
+        L.fh_fleet_round_gate_device.argtypes = [vp, vp, i32, vp, i32, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -851,6 +857,23 @@ class Context:
         FH_FLEET_STAGE_CONFLICT.  Asynchronous on the context's stream (include/fasterhip_check.h)."""
         self._check(lib().fh_fleet_revert_device(self._h, d_out, d_backup_vehicles, d_backup_plans, int(n), int(max_states), d_vehicles, d_plans),
                     "fh_fleet_revert_device")
+
+    def fleet_round_classes_device(self, par, d_vehicles, d_plans, n, max_states, cells, d_out):
+        """fh_fleet_round_classes_device: d_out [n] fh_plan_round, the round every vehicle replans in: neighbours (plans nearer than
+        par["reach"] at one instant) get different classes below the last; par: one abi.round_params_dtype record; cells = (origin, res,
+        dims): the grid of the broad phase, on which no field of a record depends.  A measurement.  Asynchronous on the context's stream
+        (include/fasterhip_rounds.h)."""
+        p = _one_record(par, "round", "fleet_round_classes_device")
+        g = _grid_record(cells)
+        self._check(lib().fh_fleet_round_classes_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states),
+                                                        None if g is None else abi.ptr(g), d_out), "fh_fleet_round_classes_device")
+
+    def fleet_round_gate_device(self, d_rounds, round, d_active_begin, n, d_vehicles, d_active):  # noqa: A002  (the header's word)
+        """fh_fleet_round_gate_device: fh_vehicle.active and d_active of every vehicle = what begin wrote (d_active_begin) and the
+        round's condition: its class is `round`; abi.FH_ROUND_RETRY: its commit was taken back; abi.FH_ROUND_RESTORE: nothing more.
+        Asynchronous on the context's stream (include/fasterhip_rounds.h)."""
+        self._check(lib().fh_fleet_round_gate_device(self._h, d_rounds, int(round), d_active_begin, int(n), d_vehicles, d_active),
+                    "fh_fleet_round_gate_device")
 
     def sample_batch_device(self, d_problems, d_results, n, max_samples, d_states, d_counts):
         self._check(lib().fh_sample_batch_device(self._h, d_problems, d_results, n, max_samples, d_states, d_counts),

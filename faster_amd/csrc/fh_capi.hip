@@ -25,6 +25,7 @@
 #include "../../include/fasterhip_traffic.h"
 #include "../../include/fasterhip_check.h"
 #include "../../include/fasterhip_traffic_timed.h"
+#include "../../include/fasterhip_rounds.h"
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
 #include "fh_decomp.hip.hpp"
@@ -35,7 +36,8 @@
 #include "fh_separation.hip.hpp"
 #include "fh_traffic.hip.hpp"
 #include "fh_check.hip.hpp"
-#include "fh_traffic_timed.hip.hpp"  // (after every other device header: its kernels come last in the code object)
+#include "fh_traffic_timed.hip.hpp"  // (after every other device header of before it: its kernels came last in the code object)
+#include "fh_rounds.hip.hpp"         // (after every other device header: the functions of before keep their place and their bytes)
 #include "fh_host.hpp"
 
 using fhh::DeviceScope;
@@ -82,6 +84,8 @@ enum Buf {
   TRAFFIC_SAMPLES,  // traffic_points{1,7}_kernel write centre, show word and vehicle of every sample (whole chunks of 64);
                     // traffic_mask{1,7}_kernel read them
   TRAFFIC_BOXES,    // traffic_points{1,7}_kernel write the grown box of the shown centres of every chunk; traffic_mask{1,7}_kernel read them
+  // fh_fleet_round_classes_device (its box records live in CELL_BOXES, like those of the other two stages of the cell grid)
+  ROUND_LISTS,      // rounds_narrow_kernel writes the lower neighbours of every vehicle (rows of FH_ROUNDS_LIST), rounds_pass_kernel reads them
   N_BUFS
 };
 
@@ -1228,6 +1232,53 @@ int fh_fleet_revert_device(fh_ctx* ctx, const fh_plan_check* d_out, const fh_veh
   if (!d_out || !d_backup_vehicles || !d_backup_plans || !d_vehicles || !d_plans) return FH_ERR_ARG;
   hipLaunchKernelGGL(fh::check_revert_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, d_out, d_backup_vehicles, d_backup_plans, n, max_states,
                      d_vehicles, d_plans);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// ---- priority rounds (include/fasterhip_rounds.h): the cell grid around rounds_boxes_kernel and rounds_narrow_kernel, the passes; the gate ----
+int fh_fleet_round_classes_device(fh_ctx* ctx, const fh_round_params* par, const fh_vehicle* d_vehicles, const fh_state* d_plans, int n,
+                                  int max_states, const fh_voxel_grid* cells, fh_plan_round* d_out) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->reach)) return FH_ERR_ARG;
+  if (par->rounds < 1 || par->rounds > FH_ROUNDS_MAX) return FH_ERR_ARG;
+  if (par->passes < 0 || par->passes > FH_ROUNDS_MAX_PASSES) return FH_ERR_ARG;
+  if (par->stride < 1 || par->count < 0) return FH_ERR_ARG;
+  if (n < 0 || max_states < 1) return FH_ERR_ARG;
+  if (!cell_grid_ok(cells, FH_ROUNDS_MAX_CELLS)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_out) return FH_ERR_ARG;
+  int rc;
+  if ((rc = ensure(ctx, ROUND_LISTS, sizeof(int) * (size_t)FH_ROUNDS_LIST * (size_t)n)) != FH_OK) return rc;
+  fh::RndArgs a;
+  a.reach = par->reach; a.r2 = par->reach * par->reach;
+  a.rounds = par->rounds; a.stride = par->stride; a.count = par->count; a.n = n; a.max_states = max_states;
+  a.vehicles = d_vehicles; a.plans = d_plans;
+  a.lists = ctx->buf[ROUND_LISTS].as<int>();
+  a.out = d_out;
+  if ((rc = cell_broad_phase(ctx, *cells, n, a, fh::rounds_boxes_kernel, fh::rounds_narrow_kernel)) != FH_OK) return rc;
+  const dim3 blocks((unsigned)((n + 255) / 256));
+  for (int p = 1; p <= par->passes; p++) {
+    hipLaunchKernelGGL(fh::rounds_pass_kernel, blocks, dim3(256), 0, ctx->stream, a.lists, d_out, n, par->rounds, p);
+    FH_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(fh::rounds_finish_kernel, blocks, dim3(256), 0, ctx->stream, d_out, n, par->rounds);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_round_gate_device(fh_ctx* ctx, const fh_plan_round* d_rounds, int round, const int32_t* d_active_begin, int n,
+                               fh_vehicle* d_vehicles, int32_t* d_active) {
+  if (!ctx) return FH_ERR_ARG;
+  if (round < FH_ROUND_RETRY || round >= FH_ROUNDS_MAX || n < 0 || d_active_begin == d_active) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_active_begin || !d_active || !d_vehicles || (round >= 0 && !d_rounds)) return FH_ERR_ARG;
+  hipLaunchKernelGGL(fh::rounds_gate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_rounds, round, d_active_begin, n,
+                     d_vehicles, d_active);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }

@@ -26,6 +26,11 @@ near where vehicle i stands; with timed=True include/fasterhip_traffic_timed.h: 
 enable_check() lets the fleet refuse: every commit is compared, instant by instant, with the other vehicles' plans and taken back when it
 conflicts (include/fasterhip_check.h); the chain ends ... -> safe solve -> backup -> commit -> check -> revert.
 
+enable_rounds() splits a replan into priority rounds (include/fasterhip_rounds.h): vehicles whose plans come near each other replan in
+different rounds, and a later round sees, through traffic and check, what the earlier ones committed moments ago:
+
+    begin -> round_classes -> for every round: gate -> [traffic] -> path search -> ... -> commit [-> check -> revert] -> gate_restore
+
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
@@ -85,6 +90,8 @@ class Fleet:
         self.point_mask, self.map_args = None, None                 # set_point_views; what set_map built the map with
         self.traffic_par, self.n_cloud_all = None, 0                # enable_traffic: the cloud holds n_cloud static points, then the traffic
         self.check_par = self.check_cells = self.d_backup_vehicles = self.d_backup_plans = self.d_check = None   # enable_check
+        self.round_par = self.round_cells = self.d_rounds = self.d_active_begin = self.d_check_rounds = None      # enable_rounds
+        self.round_retries, self.round_fixed = 0, False
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -308,6 +315,9 @@ class Fleet:
         if self.traffic_par is None:
             raise capi.FasterHipError("Fleet.traffic: enable_traffic first")
         self._follow_current()
+        self._traffic_launch()
+
+    def _traffic_launch(self):
         timed = self.traffic_par.dtype == abi.traffic_timed_params_dtype
         (self.ctx.fleet_traffic_timed_device if timed else self.ctx.fleet_traffic_device)(
             self.traffic_par, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.n, self.max_states, self.cloud.data_ptr(),
@@ -333,12 +343,101 @@ class Fleet:
         for d in (self.d_backup_vehicles, self.d_backup_plans, self.d_check):
             d.record_stream(self.stream)
         self.check_par = par
+        if self.round_par is not None:
+            self._alloc_round_checks()
 
     def check_records(self):
-        """[n] abi.plan_check_dtype: what the last replan()'s check found (synchronises).  FH_CHECK_CONFLICT: the commit was withheld."""
+        """[n] abi.plan_check_dtype: what the last replan()'s check found (synchronises).  FH_CHECK_CONFLICT: the commit was withheld.
+        With enable_rounds: per vehicle the record of the last round in which it was a candidate (the last round's record if it never was)."""
         if self.check_par is None:
             raise capi.FasterHipError("Fleet.check_records: enable_check first")
+        if self.round_par is not None:
+            by_round = self.check_records_by_round()
+            out = by_round[-1].copy()
+            found = np.zeros(self.n, dtype=bool)
+            for rec in by_round[::-1]:
+                take = ~found & ((rec["flags"] & abi.FH_CHECK_CANDIDATE) != 0)
+                out[take] = rec[take]
+                found |= take
+            return out
         return self._host(self.d_check, abi.plan_check_dtype)
+
+    def enable_rounds(self, rounds, reach=None, passes=32, stride=1, count=0, retries=0, classes=None, cells=None):
+        """A replan runs in `rounds` priority rounds (include/fasterhip_rounds.h): from now on stages() is
+            begin -> round_classes -> for r in 0 .. rounds - 1: gate@r -> [traffic@r] -> [map_views@r] -> path_search@r -> ... ->
+            safe_solve@r -> [backup@r] -> commit@r -> [check@r -> revert@r]; the same body `retries` times as @retry t; -> gate_restore.
+        begin writes who replans into a buffer of its own; round_classes gives every vehicle a class such that two vehicles whose
+        committed plans come nearer than `reach` (None: the traffic's range if traffic is enabled, else 4 params["rule"]["drone_radius"])
+        at one tested instant (stride, count as in enable_check) get different classes below the last (greedy colouring in index order,
+        settled in `passes` passes: round_records()); gate@r switches the vehicles of class r on and all others off, gate@retry t the
+        vehicles whose commit the check took back (retries > 0 needs enable_check first), gate_restore everyone begin had switched on.
+        With traffic enabled the traffic stage runs inside every round, so a round sees the plans the earlier rounds committed;
+        traffic() before replan() stays legal and is harmless.  With the check enabled every round is backed up, checked against the
+        plans as the earlier rounds left them and reverted on its own; the records of all rounds are check_records_by_round().
+        classes: an [n] int32 array or tensor fixes the classes (0 <= class < rounds): round_classes is then not launched and the
+        records carry the given class with decided_pass = 0.  cells = (origin, res, dims): the grid of the broad phase, by default
+        separation_cells(reach); no field of a record depends on it.
+        LIMITS.  results(), faces() and certify() describe every vehicle's buffers as the LAST round left them: a vehicle of an earlier
+        round then shows an inactive query (its plan and record are what its own round committed).  With point views map_views runs once
+        per round for every view, so a cycle costs about `rounds + retries` times the path search and the views' maps; neither the
+        active vehicles of a round are compacted nor only their views rebuilt.  Rounds change nothing about who a vehicle sees unless
+        traffic or the check is enabled: without them every round plans as if alone, and the result is that of one round.
+        Memory: 16 bytes per vehicle, n ints, and with the check 32 bytes per vehicle and round."""
+        t, B = self.torch, self.n
+        rounds, retries = int(rounds), int(retries)
+        if not 1 <= rounds <= abi.FH_ROUNDS_MAX:
+            raise capi.FasterHipError("Fleet.enable_rounds: 1 <= rounds <= %d, got %d" % (abi.FH_ROUNDS_MAX, rounds))
+        if retries < 0 or (retries > 0 and self.check_par is None):
+            raise capi.FasterHipError("Fleet.enable_rounds: retries > 0 replan what the check withheld: enable_check first")
+        if reach is None:
+            reach = float(self.traffic_par["range"]) if self.traffic_par is not None else 4.0 * float(self.params["rule"]["drone_radius"])
+        par = abi.default_round_params(reach, rounds)
+        par["passes"], par["stride"], par["count"] = passes, stride, count
+        self.round_cells = self.separation_cells(float(par["reach"])) if cells is None else cells
+        records = None
+        if classes is not None:
+            cls = classes.cpu().numpy() if isinstance(classes, t.Tensor) else np.asarray(classes)
+            cls = cls.astype(np.int32).reshape(-1)
+            if cls.size != B or (B and (cls.min() < 0 or cls.max() >= rounds)):
+                raise capi.FasterHipError("Fleet.enable_rounds: classes needs one class in [0, %d) per vehicle" % rounds)
+            records = np.zeros(B, dtype=abi.plan_round_dtype)
+            records["round_class"] = cls
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            self.d_active_begin = t.zeros(B, dtype=t.int32, device=self.dev)
+            if records is None:
+                self.d_rounds = t.zeros(B * abi.plan_round_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            else:
+                self.d_rounds = t.from_numpy(records.view(np.uint8).copy()).to(self.dev)
+        for d in (self.d_active_begin, self.d_rounds):
+            d.record_stream(self.stream)
+        self.round_par, self.round_retries, self.round_fixed = par, retries, records is not None
+        if self.check_par is not None:
+            self._alloc_round_checks()
+
+    def _alloc_round_checks(self):
+        """The check records of every round: [rounds + retries][n] fh_plan_check."""
+        t = self.torch
+        rows = int(self.round_par["rounds"]) + self.round_retries
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            self.d_check_rounds = t.zeros((rows, self.n * abi.plan_check_dtype.itemsize), dtype=t.uint8, device=self.dev)
+        self.d_check_rounds.record_stream(self.stream)
+
+    def round_records(self):
+        """[n] abi.plan_round_dtype: the class of every vehicle in the last replan(), the pass that decided it, its lower neighbours and
+        flags (synchronises); with fixed classes the given ones."""
+        if self.round_par is None:
+            raise capi.FasterHipError("Fleet.round_records: enable_rounds first")
+        return self._host(self.d_rounds, abi.plan_round_dtype)
+
+    def check_records_by_round(self):
+        """[rounds + retries][n] abi.plan_check_dtype: what the check of every round of the last replan() found, the retries behind
+        the rounds (synchronises)."""
+        if self.round_par is None or self.check_par is None:
+            raise capi.FasterHipError("Fleet.check_records_by_round: enable_rounds and enable_check first")
+        self.sync()
+        return self.d_check_rounds.cpu().numpy().view(abi.plan_check_dtype).copy()
 
     def point_masks(self):
         """[n_views][words] uint32 on the host (synchronises)."""
@@ -406,19 +505,46 @@ class Fleet:
         """The launches of one replan of every vehicle, in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
         if self.cloud is None or self.grid is None:
             raise capi.FasterHipError("Fleet.replan: set_map and set_unknown (or set_unknown_views) first")
+        if self.round_par is None:
+            return self._cycle_stages(self.d_active, self.d_check)
+        # priority rounds (include/fasterhip_rounds.h): begin once, into d_active_begin; the rest of the chain once per round, behind its gate
+        B, c = self.n, self.ctx
+        p = lambda t: t.data_ptr()  # noqa: E731
+        rounds = [(r, "@%d" % r) for r in range(int(self.round_par["rounds"]))]
+        rounds += [(abi.FH_ROUND_RETRY, "@retry %d" % t) for t in range(self.round_retries)]
+        out = []
+        for row, (rnd, tag) in enumerate(rounds):
+            body = self._cycle_stages(self.d_active_begin, None if self.check_par is None else self.d_check_rounds[row])
+            if row == 0:
+                out.append(body[0])
+                if not self.round_fixed:
+                    out.append(("round_classes", lambda: c.fleet_round_classes_device(self.round_par, p(self.d_vehicles), p(self.d_plans), B,
+                                                                                      self.max_states, self.round_cells, p(self.d_rounds))))
+            out.append(("gate" + tag, lambda rnd=rnd: c.fleet_round_gate_device(p(self.d_rounds), rnd, p(self.d_active_begin), B,
+                                                                                p(self.d_vehicles), p(self.d_active))))
+            if self.traffic_par is not None:
+                out.append(("traffic" + tag, self._traffic_launch))
+            out += [(name + tag, launch) for name, launch in body[1:]]
+        out.append(("gate_restore", lambda: c.fleet_round_gate_device(None, abi.FH_ROUND_RESTORE, p(self.d_active_begin), B, p(self.d_vehicles),
+                                                                      p(self.d_active))))
+        return out
+
+    def _cycle_stages(self, d_active_begin, d_check):
+        """The chain of one replan: begin writes who replans into d_active_begin (without rounds: d_active, what the path search reads),
+        the check its records into d_check."""
         B, P, c, m = self.n, self.params, self.ctx, self.map
         p = lambda t: t.data_ptr()  # noqa: E731
         origin, res, dims = self.grid
         n_cloud = self.n_cloud if self.traffic_par is None else self.n_cloud_all   # (with traffic: the static points and the others' plans)
-        chain = self._shared_map_stages(B, P, c, m, p, origin, res, dims, n_cloud)
+        chain = self._shared_map_stages(B, P, c, m, p, origin, res, dims, n_cloud, d_active_begin)
         if self.check_par is not None:   # backup -> commit -> check -> revert (include/fasterhip_check.h)
             chain = chain[:-1] + [
                 ("backup", lambda: c.fleet_backup_device(p(self.d_vehicles), p(self.d_plans), B, self.max_states, p(self.d_backup_vehicles),
                                                          p(self.d_backup_plans))),
                 chain[-1],
                 ("check", lambda: c.fleet_check_device(self.check_par, p(self.d_vehicles), p(self.d_plans), p(self.d_backup_vehicles),
-                                                       p(self.d_backup_plans), B, self.max_states, self.check_cells, p(self.d_check))),
-                ("revert", lambda: c.fleet_revert_device(p(self.d_check), p(self.d_backup_vehicles), p(self.d_backup_plans), B, self.max_states,
+                                                       p(self.d_backup_plans), B, self.max_states, self.check_cells, p(d_check))),
+                ("revert", lambda: c.fleet_revert_device(p(d_check), p(self.d_backup_vehicles), p(self.d_backup_plans), B, self.max_states,
                                                          p(self.d_vehicles), p(self.d_plans))),
             ]
         if self.point_mask is None:
@@ -434,10 +560,10 @@ class Fleet:
         ]
         return chain[:1] + views + chain[2:]
 
-    def _shared_map_stages(self, B, P, c, m, p, origin, res, dims, n_cloud):
+    def _shared_map_stages(self, B, P, c, m, p, origin, res, dims, n_cloud, d_active_begin):
         return [
             ("begin", lambda: c.fleet_begin_device(P, p(self.d_vehicles), p(self.d_plans), B, self.max_states, p(self.d_whole), p(self.d_safe),
-                                                   p(self.d_starts), p(self.d_goals), p(self.d_radius), p(self.d_active))),
+                                                   p(self.d_starts), p(self.d_goals), p(self.d_radius), p(d_active_begin))),
             ("path_search", lambda: m.plan_batch_radius_device(p(self.d_starts), p(self.d_goals), p(self.d_radius), p(self.d_active), B, self.mp,
                                                                p(self.d_paths), p(self.d_np), p(self.d_ex), self.dist_max_vertexes, 0)),
             ("corridors", lambda: c.corridor_batch_device(p(self.cloud), n_cloud, p(self.d_paths), p(self.d_np), B, self.mp, self.max_poly, self.fpp,

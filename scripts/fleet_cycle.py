@@ -37,8 +37,14 @@ set per vehicle, which both reports carry.
 default cell grid), one cycle to warm up, then the stage table again with "backup", "check" and "revert" as stages of their own; per
 timed cycle how many vehicles were candidates and how many were withheld, and Fleet.separation_device with the same count, every state,
 fenced like a stage on the plans as they stand at the end.
+--rounds R [--round-reach M] [--retries T] adds "rounds": the fleet of --traffic-timed (or of --traffic, or without either the shared-grid
+fleet), with Fleet.enable_check when --check is given (which --retries needs), timed first as it is ("without_rounds": traffic ->
+replan -> 5 ticks) and then after Fleet.enable_rounds(R, reach = M, default Fleet's; retries = T): every stage of every round fenced
+like the others ("stages_ms", names suffixed @r), the same summed over the rounds per stage ("by_stage_ms"), "round_classes" and the
+mean of the gates on their own, and per timed cycle the vehicles per class, the flagged records and the commits withheld per round.
     usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
-                                         [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]"""
+                                         [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
+                                         [--rounds R [--round-reach M] [--retries T]]"""
 import json
 import os
 import sys
@@ -341,9 +347,88 @@ def traffic_cycles(B, cycles, p, world, samples, stride, reach, window=None):
     return {"traffic" if window is None else "traffic_timed": out}
 
 
+def rounds_cycles(B, cycles, p, world, rounds, reach, retries, traffic, window, check):
+    """The cycle before and after Fleet.enable_rounds: see the module docstring."""
+    cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims = world
+    out = {"rounds": rounds, "retries": retries, "check": bool(check)}
+    fl = Fleet(B, p, max_states=1024)
+    try:
+        fl.set_map(cloud, cells, res, center, zmax, infl)
+        with_traffic = traffic is not None or window is not None
+        if with_traffic:
+            samples, stride, rng = traffic or (8, 25, 6.0)
+            fl.set_unknown_views(torch.from_numpy(flags.reshape(1, -1)).to(fl.dev).repeat(B, 1), origin=origin, res=res, dims=dims)
+            fl.set_point_views(torch.full((B, abi.point_mask_words(len(cloud))), -1, dtype=torch.int32, device=fl.dev))
+            fl.init(states, goals)
+            fl.enable_traffic(samples, stride, rng, timed=window is not None, window=window or 0)
+            out["traffic"] = {"samples": samples, "stride": stride, "range": rng, "window": window}
+        else:
+            fl.set_unknown(flags, origin, res, dims)
+            fl.init(states, goals)
+        if check:
+            fl.enable_check()
+        for _ in range(2):
+            if with_traffic:
+                fl.traffic()
+            fl.replan()
+            fl.next_goals(5)
+        fl.sync()
+        med = timed_cycles(fl, cycles, traffic=with_traffic)
+        out["without_rounds"] = {"stages_ms": med, "cycle_fenced_ms": float(sum(med.values()))}
+        fl.enable_rounds(rounds, reach=reach, retries=retries)
+        out["reach"], out["passes"] = float(fl.round_par["reach"]), int(fl.round_par["passes"])
+        out["cells"], out["cell_res"] = list(fl.round_cells[2]), fl.round_cells[1]
+        fl.replan()
+        fl.next_goals(5)
+        fl.sync()
+        names = [n for n, _ in fl.stages()] + ["next_goals"]
+        per = {n: [] for n in names}
+        per_class, flagged, withheld = [], [], []
+        for _ in range(cycles):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+            ev[0].record(fl.stream)
+            for j, (n, launch) in enumerate(fl.stages()):
+                launch()
+                ev[j + 1].record(fl.stream)
+            fl.next_goals(5)
+            ev[-1].record(fl.stream)
+            fl.sync()
+            for j, n in enumerate(names):
+                per[n].append(ev[j].elapsed_time(ev[j + 1]))
+            rec = fl.round_records()
+            per_class.append(np.bincount(rec["round_class"], minlength=rounds).tolist())
+            flagged.append({"overflow": int(((rec["flags"] & abi.FH_ROUND_OVERFLOW) != 0).sum()),
+                            "unsettled": int(((rec["flags"] & abi.FH_ROUND_UNSETTLED) != 0).sum()), "n_lower_max": int(rec["n_lower"].max())})
+            if check:
+                withheld.append([int(((r["flags"] & abi.FH_CHECK_CONFLICT) != 0).sum()) for r in fl.check_records_by_round()])
+        med = {n: float(np.median(v)) for n, v in per.items()}
+        by_stage = {}
+        for n, v in med.items():
+            by_stage[n.split("@")[0]] = by_stage.get(n.split("@")[0], 0.0) + v
+        gates = [v for n, v in med.items() if n.startswith("gate")]
+        out["with_rounds"] = {"stages_ms": med, "by_stage_ms": by_stage, "cycle_fenced_ms": float(sum(med.values())),
+                              "round_classes_ms": med.get("round_classes"), "gate_mean_ms": float(np.mean(gates)), "gates": len(gates),
+                              "vehicles_per_class": per_class, "flagged": flagged, "withheld_per_round": withheld,
+                              "committed_last": int((fl.vehicles()["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum())}
+    finally:
+        fl.close()
+    return {"rounds": out}
+
+
 def main():
     argv = sys.argv[1:]
     r_sense, fov, teams, traffic, window = 3.0, None, 0, None, None
+    rounds, round_reach, retries = 0, None, 0
+    for opt in ("--rounds", "--round-reach", "--retries"):
+        if opt in argv:
+            k = argv.index(opt)
+            if opt == "--rounds":
+                rounds = int(argv[k + 1])
+            elif opt == "--retries":
+                retries = int(argv[k + 1])
+            else:
+                round_reach = float(argv[k + 1])
+            del argv[k:k + 2]
     if "--traffic-timed" in argv:
         k = argv.index("--traffic-timed")
         window = int(argv[k + 1])
@@ -469,6 +554,9 @@ def main():
     if window is not None:
         world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
         out.update(traffic_cycles(B, cycles, p, world, *(traffic or (8, 25, 6.0)), window=window))
+    if rounds:
+        world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
+        out.update(rounds_cycles(B, cycles, p, world, rounds, round_reach, retries, traffic, window, "--check" in sys.argv))
     print(json.dumps(out))
 
 
