@@ -224,12 +224,17 @@ traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", 
 assert traffic_params_dtype.itemsize == 48
 
 
+def _traffic_common(dtype, samples, stride, range, hull, rule, first_point):  # noqa: A002
+    """A zeroed record of `dtype` with the six fields both traffic records begin with."""
+    p = np.zeros((), dtype=dtype)
+    p["range"], p["hull"], p["samples"], p["stride"], p["rule"], p["first_point"] = range, hull, samples, stride, rule, first_point
+    return p
+
+
 def default_traffic_params(samples, stride, range, hull=0.0, rule=FH_TRAFFIC_ALL, first_point=0):  # noqa: A002  (the header's word)
     """fh_traffic_params: `samples` instants of every plan, `stride` states apart, shown to the vehicles nearer than `range`; hull > 0
     inflates every sample to seven points.  first_point: the cloud index of the first traffic point, a multiple of 32."""
-    p = np.zeros((), dtype=traffic_params_dtype)
-    p["range"], p["hull"], p["samples"], p["stride"], p["rule"], p["first_point"] = range, hull, samples, stride, rule, first_point
-    return p
+    return _traffic_common(traffic_params_dtype, samples, stride, range, hull, rule, first_point)
 
 
 # fh_traffic_timed_params: the same points, the bits matched instant by instant (include/fasterhip_traffic_timed.h)
@@ -242,8 +247,7 @@ assert traffic_timed_params_dtype.itemsize == 48
 def default_traffic_timed_params(samples, stride, range, hull=0.0, rule=FH_TRAFFIC_ALL, first_point=0, first_instant=0, window=0):  # noqa: A002
     """fh_traffic_timed_params: default_traffic_params' fields, and sample s is the instant first_instant + s stride; sample (k, s) is
     shown to vehicle i when a shown sample s' of i's own plan with |s - s'| <= window lies nearer than `range`."""
-    p = np.zeros((), dtype=traffic_timed_params_dtype)
-    p["range"], p["hull"], p["samples"], p["stride"], p["rule"], p["first_point"] = range, hull, samples, stride, rule, first_point
+    p = _traffic_common(traffic_timed_params_dtype, samples, stride, range, hull, rule, first_point)
     p["first_instant"], p["window"] = first_instant, window
     return p
 

@@ -36,7 +36,7 @@
 #include "fh_separation.hip.hpp"
 #include "fh_traffic.hip.hpp"
 #include "fh_check.hip.hpp"
-#include "fh_traffic_timed.hip.hpp"  // (after every other device header of before it: its kernels came last in the code object)
+#include "fh_traffic_timed.hip.hpp"  // (after fh_check: where its mask kernels have lain in the code object since they came)
 #include "fh_rounds.hip.hpp"         // (after every other device header: the functions of before keep their place and their bytes)
 #include "fh_host.hpp"
 
@@ -79,11 +79,11 @@ enum Buf {
   CELL_STARTS,   // cell_scan_kernel writes the first item of every cell (and the total behind the last); cell_fill_kernel and the narrow kernel read
   CELL_ITEMS,    // cell_fill_kernel writes the vehicle numbers sorted by cell; the narrow kernel reads them
   CELL_EXTENT,   // zeroed on the stream; the boxes kernel raises the largest half-extent per axis (three words), the narrow kernel reads it
-  // Shared by fh_fleet_traffic_device and fh_fleet_traffic_timed_device (the traffic_timed_* kernels): both run on the context's stream,
-  // in order, and each call writes all it reads.
+  // Shared by fh_fleet_traffic_device and fh_fleet_traffic_timed_device (traffic_stage below): both run on the context's stream, in order,
+  // and each call writes all it reads.
   TRAFFIC_SAMPLES,  // traffic_points{1,7}_kernel write centre, show word and vehicle of every sample (whole chunks of 64);
-                    // traffic_mask{1,7}_kernel read them
-  TRAFFIC_BOXES,    // traffic_points{1,7}_kernel write the grown box of the shown centres of every chunk; traffic_mask{1,7}_kernel read them
+                    // the rule's mask kernels (traffic_mask{1,7}_kernel, traffic_timed_mask{1,7}_kernel) read them
+  TRAFFIC_BOXES,    // traffic_points{1,7}_kernel write the grown box of the shown centres of every chunk; the rule's mask kernels read them
   // fh_fleet_round_classes_device (its box records live in CELL_BOXES, like those of the other two stages of the cell grid)
   ROUND_LISTS,      // rounds_narrow_kernel writes the lower neighbours of every vehicle (rows of FH_ROUNDS_LIST), rounds_pass_kernel reads them
   N_BUFS
@@ -1091,30 +1091,35 @@ int fh_fleet_separation_device(fh_ctx* ctx, const fh_separation_params* par, con
   return cell_broad_phase(ctx, *cells, n, a, fh::sep_boxes_kernel, fh::sep_narrow_kernel);
 }
 
-// ---- traffic (include/fasterhip_traffic.h): the other vehicles' plans as cloud points and mask bits; the points, then the words ----
-int fh_fleet_traffic_device(fh_ctx* ctx, const fh_traffic_params* par, const fh_vehicle* d_vehicles, const fh_state* d_plans, int n,
-                            int max_states, double* d_cloud_xyz, int n_cloud, uint32_t* d_point_mask, int mask_words) {
-  if (!ctx || !par) return FH_ERR_ARG;
-  if (!audit_radius_ok(par->range) || !(par->range > 0)) return FH_ERR_ARG;
-  if (!audit_radius_ok(par->hull)) return FH_ERR_ARG;
-  if (par->samples < 1 || par->stride < 1) return FH_ERR_ARG;
-  if (par->rule != FH_TRAFFIC_ALL && par->rule != FH_TRAFFIC_YIELD_TO_LOWER) return FH_ERR_ARG;
-  if (par->first_point < 0 || par->first_point % 32 != 0) return FH_ERR_ARG;
+// ---- traffic (include/fasterhip_traffic.h, include/fasterhip_traffic_timed.h): the other vehicles' plans as cloud points and mask bits ----
+// What the two rules share, after the checks of their own: the rest of the prologue, one TrafficArgs, the two working buffers, the points
+// and then the words.  The six fields the two records begin with come by value; `window` is already clipped; mask1 / mask7 are the rule's
+// mask kernels.
+typedef void (*traffic_kernel)(fh::TrafficArgs);
+static int traffic_stage(fh_ctx* ctx, double range, double hull, int samples, int stride, int rule, int first_point, int first_instant,
+                         int window, traffic_kernel mask1, traffic_kernel mask7, const fh_vehicle* d_vehicles, const fh_state* d_plans, int n,
+                         int max_states, double* d_cloud_xyz, int n_cloud, uint32_t* d_point_mask, int mask_words) {
+  if (!audit_radius_ok(range) || !(range > 0)) return FH_ERR_ARG;
+  if (!audit_radius_ok(hull)) return FH_ERR_ARG;
+  if (stride < 1) return FH_ERR_ARG;
+  if (rule != FH_TRAFFIC_ALL && rule != FH_TRAFFIC_YIELD_TO_LOWER) return FH_ERR_ARG;
+  if (first_point < 0 || first_point % 32 != 0) return FH_ERR_ARG;
   if (n < 0 || max_states < 1) return FH_ERR_ARG;
-  const int pps = par->hull > 0 ? 7 : 1;
-  const long long n_samples = (long long)n * (long long)par->samples;  // (below 2^62)
-  if (n_samples > (long long)INT32_MAX) return FH_ERR_ARG;             // (more than any n_cloud: n_samples * pps is then safe in 64 bits)
-  const long long end_point = (long long)par->first_point + n_samples * pps;
+  const int pps = hull > 0 ? 7 : 1;
+  const long long n_samples = (long long)n * (long long)samples;  // (below 2^62)
+  if (n_samples > (long long)INT32_MAX) return FH_ERR_ARG;        // (more than any n_cloud: n_samples * pps is then safe in 64 bits)
+  const long long end_point = (long long)first_point + n_samples * pps;
   if (end_point > (long long)n_cloud || end_point > (long long)mask_words * 32) return FH_ERR_ARG;
   if (ctx->device < 0) return FH_ERR_DEVICE;
   DeviceScope device_scope(ctx->device);
   if (n == 0) return FH_OK;
   if (!d_vehicles || !d_plans || !d_cloud_xyz || !d_point_mask) return FH_ERR_ARG;
   fh::TrafficArgs a;
-  a.range = par->range; a.range2 = par->range * par->range; a.hull = par->hull;
-  a.samples = par->samples; a.stride = par->stride; a.rule = par->rule; a.first_point = par->first_point;
+  a.range = range; a.range2 = range * range; a.hull = hull;
+  a.samples = samples; a.stride = stride; a.rule = rule; a.first_point = first_point;
   a.n = n; a.max_states = max_states; a.n_samples = (int)n_samples; a.n_chunks = (int)((n_samples + 63) / 64);
-  a.mask_words = mask_words; a.first_word = par->first_point / 32; a.n_words = (int)((end_point + 31) / 32) - a.first_word;
+  a.mask_words = mask_words; a.first_word = first_point / 32; a.n_words = (int)((end_point + 31) / 32) - a.first_word;
+  a.first_instant = first_instant; a.window = window; a.span = std::min(2 * window + 1, samples);
   a.vehicles = d_vehicles; a.plans = d_plans; a.cloud = d_cloud_xyz; a.mask = d_point_mask;
   int rc;
   if ((rc = ensure(ctx, TRAFFIC_SAMPLES, sizeof(fh::TrafficRec) * 64 * (size_t)a.n_chunks)) != FH_OK) return rc;
@@ -1122,68 +1127,31 @@ int fh_fleet_traffic_device(fh_ctx* ctx, const fh_traffic_params* par, const fh_
   a.recs = ctx->buf[TRAFFIC_SAMPLES].as<fh::TrafficRec>();
   a.boxes = ctx->buf[TRAFFIC_BOXES].as<fh::TrafficBox>();
   const dim3 chunks((unsigned)a.n_chunks), rows((unsigned)((a.n_chunks + 63) / 64), (unsigned)std::min(n, fh::TRAFFIC_GRID_ROWS));
-  if (pps == 7) {
-    hipLaunchKernelGGL(fh::traffic_points7_kernel, chunks, dim3(64), 0, ctx->stream, a);
-    FH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(fh::traffic_mask7_kernel, rows, dim3(64), 0, ctx->stream, a);
-  } else {
-    hipLaunchKernelGGL(fh::traffic_points1_kernel, chunks, dim3(64), 0, ctx->stream, a);
-    FH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(fh::traffic_mask1_kernel, rows, dim3(64), 0, ctx->stream, a);
-  }
+  hipLaunchKernelGGL(pps == 7 ? fh::traffic_points7_kernel : fh::traffic_points1_kernel, chunks, dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pps == 7 ? mask7 : mask1, rows, dim3(64), 0, ctx->stream, a);
   FH_HIP(hipGetLastError());
   return FH_OK;
 }
 
-// ---- time-aware traffic (include/fasterhip_traffic_timed.h): the same points, the bits matched instant by instant ----
+int fh_fleet_traffic_device(fh_ctx* ctx, const fh_traffic_params* par, const fh_vehicle* d_vehicles, const fh_state* d_plans, int n,
+                            int max_states, double* d_cloud_xyz, int n_cloud, uint32_t* d_point_mask, int mask_words) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (par->samples < 1) return FH_ERR_ARG;
+  return traffic_stage(ctx, par->range, par->hull, par->samples, par->stride, par->rule, par->first_point, 0, 0, fh::traffic_mask1_kernel,
+                       fh::traffic_mask7_kernel, d_vehicles, d_plans, n, max_states, d_cloud_xyz, n_cloud, d_point_mask, mask_words);
+}
+
+// time-aware: the same points, the bits matched instant by instant
 int fh_fleet_traffic_timed_device(fh_ctx* ctx, const fh_traffic_timed_params* par, const fh_vehicle* d_vehicles, const fh_state* d_plans,
                                   int n, int max_states, double* d_cloud_xyz, int n_cloud, uint32_t* d_point_mask, int mask_words) {
   if (!ctx || !par) return FH_ERR_ARG;
-  if (!audit_radius_ok(par->range) || !(par->range > 0)) return FH_ERR_ARG;
-  if (!audit_radius_ok(par->hull)) return FH_ERR_ARG;
   if (par->samples < 1 || par->samples > FH_TRAFFIC_TIMED_MAX_SAMPLES) return FH_ERR_ARG;
-  if (par->stride < 1) return FH_ERR_ARG;
-  if (par->rule != FH_TRAFFIC_ALL && par->rule != FH_TRAFFIC_YIELD_TO_LOWER) return FH_ERR_ARG;
-  if (par->first_point < 0 || par->first_point % 32 != 0) return FH_ERR_ARG;
-  if (par->first_instant < 0) return FH_ERR_ARG;
-  if (par->window < 0) return FH_ERR_ARG;
-  if (n < 0 || max_states < 1) return FH_ERR_ARG;
-  const int pps = par->hull > 0 ? 7 : 1;
-  const long long n_samples = (long long)n * (long long)par->samples;  // (below 2^41)
-  if (n_samples > (long long)INT32_MAX) return FH_ERR_ARG;             // (more than any n_cloud: n_samples * pps is then safe in 64 bits)
-  const long long end_point = (long long)par->first_point + n_samples * pps;
-  if (end_point > (long long)n_cloud || end_point > (long long)mask_words * 32) return FH_ERR_ARG;
-  if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx->device);
-  if (n == 0) return FH_OK;
-  if (!d_vehicles || !d_plans || !d_cloud_xyz || !d_point_mask) return FH_ERR_ARG;
-  fh::TrafficTimedArgs b;
-  fh::TrafficArgs& a = b.t;
-  a.range = par->range; a.range2 = par->range * par->range; a.hull = par->hull;
-  a.samples = par->samples; a.stride = par->stride; a.rule = par->rule; a.first_point = par->first_point;
-  a.n = n; a.max_states = max_states; a.n_samples = (int)n_samples; a.n_chunks = (int)((n_samples + 63) / 64);
-  a.mask_words = mask_words; a.first_word = par->first_point / 32; a.n_words = (int)((end_point + 31) / 32) - a.first_word;
-  a.vehicles = d_vehicles; a.plans = d_plans; a.cloud = d_cloud_xyz; a.mask = d_point_mask;
-  b.first_instant = par->first_instant;
-  b.window = std::min(par->window, par->samples - 1);  // (any window >= S - 1 is every sampled instant)
-  b.span = std::min(2 * b.window + 1, par->samples);
-  int rc;
-  if ((rc = ensure(ctx, TRAFFIC_SAMPLES, sizeof(fh::TrafficRec) * 64 * (size_t)a.n_chunks)) != FH_OK) return rc;
-  if ((rc = ensure(ctx, TRAFFIC_BOXES, sizeof(fh::TrafficBox) * (size_t)a.n_chunks)) != FH_OK) return rc;
-  a.recs = ctx->buf[TRAFFIC_SAMPLES].as<fh::TrafficRec>();
-  a.boxes = ctx->buf[TRAFFIC_BOXES].as<fh::TrafficBox>();
-  const dim3 chunks((unsigned)a.n_chunks), rows((unsigned)((a.n_chunks + 63) / 64), (unsigned)std::min(n, fh::TRAFFIC_GRID_ROWS));
-  if (pps == 7) {
-    hipLaunchKernelGGL(fh::traffic_timed_points7_kernel, chunks, dim3(64), 0, ctx->stream, b);
-    FH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(fh::traffic_timed_mask7_kernel, rows, dim3(64), 0, ctx->stream, b);
-  } else {
-    hipLaunchKernelGGL(fh::traffic_timed_points1_kernel, chunks, dim3(64), 0, ctx->stream, b);
-    FH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(fh::traffic_timed_mask1_kernel, rows, dim3(64), 0, ctx->stream, b);
-  }
-  FH_HIP(hipGetLastError());
-  return FH_OK;
+  if (par->first_instant < 0 || par->window < 0) return FH_ERR_ARG;
+  const int window = std::min(par->window, par->samples - 1);  // (any window >= S - 1 is every sampled instant)
+  return traffic_stage(ctx, par->range, par->hull, par->samples, par->stride, par->rule, par->first_point, par->first_instant, window,
+                       fh::traffic_timed_mask1_kernel, fh::traffic_timed_mask7_kernel, d_vehicles, d_plans, n, max_states, d_cloud_xyz,
+                       n_cloud, d_point_mask, mask_words);
 }
 
 // ---- the commit check (include/fasterhip_check.h): backup before the commit; the cell grid around check_boxes_kernel and

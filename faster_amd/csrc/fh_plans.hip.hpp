@@ -13,9 +13,8 @@ __device__ __forceinline__ double plan_pack(int lo, int hi) { return __hiloint2d
 
 // The BAD_PLAN rule of every stage, decided before any plan state is read.  A record that passes it indexes plans[k max_states + head
 // .. + size) inside the array: every later index of a stage comes from such a record.
-// (audit_kernel and traffic_points write this expression out, and audit_kernel the six lines of plan_box_take: through the functions
-// the compiler orders audit_kernel's box registers differently and no longer adds head and size of traffic_points in 32 bits, and
-// neither kernel was to move when these helpers were gathered: DESIGN.md, the cell grid.)
+// (audit_kernel writes this expression out, and the six lines of plan_box_take: through the functions the compiler orders its box
+// registers differently, and the kernel was not to move when these helpers were gathered: DESIGN.md, the cell grid.)
 __device__ __forceinline__ bool plan_bad_extent(int head, int size, int max_states) {
   return head < 0 || size < 0 || (long long)head + (long long)size > (long long)max_states;
 }

@@ -182,6 +182,42 @@ def test_one_sample_at_instant_0_is_the_untimed_entry_point(ctx, n, hull, rule):
     assert ttm.traffic_bits(par, n, timed[1]).any()
 
 
+# ---- 4b. one points kernel and one host prologue under both entry points -------------------------------------------------------------------
+ONE_STAGE_SHAPES = [(5, 3, 0.25), (3, 65, 0.0)]   # (the second: a chunk ends inside a vehicle's samples)
+
+
+@pytest.mark.parametrize("n,S,hull", ONE_STAGE_SHAPES)
+def test_both_entry_points_write_the_same_points(ctx, n, S, hull):
+    """first_instant = 0 and the same first six fields: the cloud from first_point on is the same in every byte after either call, and it
+    is the model's points.  The masks follow different rules and are not compared."""
+    v, pl = moving_fleet(np.random.default_rng(1000 * n + S), n, box=0.4)
+    par = ttm.params(S, 1 if S >= 10 else 3, 0.75, hull=hull, first_point=64, first_instant=0, window=1)
+    cloud, mask = gt.arrays(par, n, 40)
+    timed, _ = call(gt.Device(cloud, mask), ctx, par, v, pl)
+    untimed, _ = call(gt.Device(cloud, mask), ctx, ttm.untimed(par), v, pl)
+    first = int(par["first_point"])
+    assert timed[first:].tobytes() == untimed[first:].tobytes()
+    want = tm.points(par, *tm.samples(par, v, pl, pl.shape[1])).reshape(-1, 3)
+    assert want.any() and timed[first:first + len(want)].tobytes() == want.tobytes()
+    assert (timed[first + len(want):] == -3e3).all()
+
+
+@pytest.mark.parametrize("n,S,hull", ONE_STAGE_SHAPES)
+def test_untimed_entry_ignores_its_reserved_words(ctx, n, S, hull):
+    """reserved[0..1] of fh_traffic_params lie where fh_traffic_timed_params has first_instant and window: the untimed entry point reads
+    neither, so a record with (7, 3, -1, 1 << 30) there gives the cloud and the masks of one with zeros, which are the model's."""
+    v, pl = moving_fleet(np.random.default_rng(1000 * n + S), n, box=0.4)
+    zeros = tm.params(S, 1 if S >= 10 else 3, 0.75, hull=hull, first_point=64)
+    marked = zeros.copy()
+    marked["reserved"] = (7, 3, -1, 1 << 30)
+    cloud, mask = gt.arrays(zeros, n, 40)
+    got_zeros = call(gt.Device(cloud, mask), ctx, zeros, v, pl)
+    got_marked = call(gt.Device(cloud, mask), ctx, marked, v, pl)
+    assert got_marked[0].tobytes() == got_zeros[0].tobytes() and got_marked[1].tobytes() == got_zeros[1].tobytes()
+    tm.assert_equal(*got_marked, *tm.traffic(zeros, v, pl, pl.shape[1], cloud, mask), "reserved words set")
+    assert ttm.traffic_bits(zeros, n, got_marked[1]).any()
+
+
 # ---- 5. timed and untimed calls alternate on one context without a wait: they share TRAFFIC_SAMPLES and TRAFFIC_BOXES ---------------------
 def test_timed_and_untimed_calls_alternate_on_one_context(ctx):
     import torch

@@ -14,8 +14,8 @@ def _bad(head, size, max_states):
     return head < 0 or size < 0 or head + size > max_states
 
 
-def samples(par, vehicles, plans, max_states, variant=None):
-    """(show [n][S] bool, centres [n][S][3], zero where the sample does not show)."""
+def samples(par, vehicles, plans, max_states, variant=None, first_instant=0):
+    """(show [n][S] bool, centres [n][S][3], zero where the sample does not show).  Sample s is the instant first_instant + s stride."""
     n, S, stride = len(vehicles), int(par["samples"]), int(par["stride"])
     plans = np.asarray(plans).reshape(n, max_states)
     show, c = np.zeros((n, S), dtype=bool), np.zeros((n, S, 3))
@@ -24,7 +24,7 @@ def samples(par, vehicles, plans, max_states, variant=None):
         if _bad(head, size, max_states) or size < 1:   # (decided before any plan state is read)
             continue
         for s in range(S):
-            j = s * stride
+            j = first_instant + s * stride   # (python integers: no overflow)
             if variant == "no_clamp" and j >= size:
                 continue
             p = plans["pos"][k, head + min(j, size - 1)]   # a vehicle whose plan has ended stands at its last state

@@ -12,22 +12,9 @@ assert_equal, fleet, layout, bit = tm.assert_equal, tm.fleet, tm.layout, tm.bit
 
 
 def samples(par, vehicles, plans, max_states, variant=None):
-    """(show [n][S] bool, centres [n][S][3], zero where the sample does not show)."""
-    n, S, stride, first = len(vehicles), int(par["samples"]), int(par["stride"]), int(par["first_instant"])
-    plans = np.asarray(plans).reshape(n, max_states)
-    show, c = np.zeros((n, S), dtype=bool), np.zeros((n, S, 3))
-    for k in range(n):
-        head, size = int(vehicles["plan_head"][k]), int(vehicles["plan_size"][k])
-        if head < 0 or size < 0 or head + size > max_states or size < 1:   # (decided before any plan state is read)
-            continue
-        for s in range(S):
-            j = (0 if variant == "ignores_first_instant" else first) + s * stride   # (python integers: no overflow)
-            if variant == "no_clamp" and j >= size:
-                continue
-            p = plans["pos"][k, head + min(j, size - 1)]   # a plan that has ended stands at its last state
-            if np.isfinite(p).all():
-                show[k, s], c[k, s] = True, p
-    return show, c
+    """tests/traffic_model.py's samples from the record's first_instant on."""
+    first = 0 if variant == "ignores_first_instant" else int(par["first_instant"])
+    return tm.samples(par, vehicles, plans, max_states, variant, first)
 
 
 def decisions(par, vehicles, show, c, variant=None):
