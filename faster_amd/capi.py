@@ -46,6 +46,8 @@ TRAFFIC_TIMED_SYMBOLS = ["fh_fleet_traffic_timed_device"]
 CHECK_SYMBOLS = ["fh_fleet_backup_device", "fh_fleet_check_device", "fh_fleet_revert_device"]
 # include/fasterhip_rounds.h
 ROUNDS_SYMBOLS = ["fh_fleet_round_classes_device", "fh_fleet_round_gate_device"]
+# include/fasterhip_view_subset.h
+VIEW_SUBSET_SYMBOLS = ["fh_map_view_list_device", "fh_map_read_views_listed_device"]
 
 _LIB = None
 
@@ -307,6 +309,10 @@ def lib():
         L.fh_fleet_round_classes_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
         L.fh_fleet_round_gate_device.restype = i32
         L.fh_fleet_round_gate_device.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+        L.fh_map_view_list_device.restype = i32
+        L.fh_map_view_list_device.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+        L.fh_map_read_views_listed_device.restype = i32
+        L.fh_map_read_views_listed_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, f64, vp, f64, f64, f64, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -509,6 +515,21 @@ class Map:
         self._check(lib().fh_map_read_views_device(self._h, d_cloud, int(n_cloud), d_point_mask, int(mask_words), int(n_views), abi.ptr(cells),
                                                    float(res), abi.ptr(center), float(z_ground), float(z_max), float(inflation)),
                     "fh_map_read_views_device")
+
+    def view_list_device(self, d_active, d_view_of, n, n_views, d_list, d_count):
+        """fh_map_view_list_device (include/fasterhip_view_subset.h): the views that the active queries need (view d_view_of[q], None: q;
+        d_active None: every query) into d_list [n_views] int32, ascending, each once, -1 behind them, and their number into d_count [1]."""
+        self._check(lib().fh_map_view_list_device(self._h, d_active, d_view_of, int(n), int(n_views), d_list, d_count), "fh_map_view_list_device")
+
+    def read_views_listed_device(self, d_cloud, n_cloud, d_point_mask, mask_words, n_views, cells, res, center, z_ground, z_max, inflation, d_list,
+                                 d_count):
+        """fh_map_read_views_listed_device: read_views_device for the views d_list[0 .. *d_count) only, and their jump tables where the
+        views have valid ones; every other view keeps its grid and tables.  Needs a read_views_device with the same lattice before it."""
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        center = np.ascontiguousarray(center, dtype=np.float64)
+        self._check(lib().fh_map_read_views_listed_device(self._h, d_cloud, int(n_cloud), d_point_mask, int(mask_words), int(n_views),
+                                                          abi.ptr(cells), float(res), abi.ptr(center), float(z_ground), float(z_max),
+                                                          float(inflation), d_list, d_count), "fh_map_read_views_listed_device")
 
     def view_occupancy(self, view):
         """The grid of one view as occupancy() gives the map's."""

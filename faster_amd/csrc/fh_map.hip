@@ -13,8 +13,10 @@
 
 #include "../../include/fasterhip.h"
 #include "../../include/fasterhip_occupancy.h"
+#include "../../include/fasterhip_view_subset.h"
 #include "../host/jps_tables.hpp"
 #include "fh_path.hip.hpp"
+#include "fh_view_subset.hip.hpp"
 #include "fh_host.hpp"
 
 struct fh_map {
@@ -58,6 +60,7 @@ struct fh_map {
   double view_res = 0.0, view_origin[3] = {0, 0, 0}, view_inflation = 0.0;
   size_t words_per_view = 0;
   bool view_entries_valid = false;
+  fhh::DeviceBuffer view_need;  // fh_map_view_list_device: a flag per view
   // staging of the host-pointer entry points (synchronous: nothing in flight reads them once they have returned)
   enum Stage { CLOUD, QUERIES, PATHS, N_POINTS, EXPANSIONS, N_STAGE };
   fhh::DeviceBuffer stage[N_STAGE];
@@ -162,7 +165,7 @@ void fh_map_destroy(fh_map* m) {
   for (void* p : {(void*)m->ws.d_cells, (void*)m->ws.d_hkeys, (void*)m->ws.d_chunks, (void*)m->ws.d_serials, (void*)m->d_ticket, (void*)m->d_jps_tables,
                   (void*)m->parked.d_cells, (void*)m->parked.d_hkeys, (void*)m->parked.d_chunks, (void*)m->parked.d_serials})
     if (p) (void)hipFree(p);
-  for (fhh::DeviceBuffer* b : {&m->bits, &m->order, &m->jps_entries, &m->view_bits, &m->view_entries}) b->release();
+  for (fhh::DeviceBuffer* b : {&m->bits, &m->order, &m->jps_entries, &m->view_bits, &m->view_entries, &m->view_need}) b->release();
   for (fhh::DeviceBuffer& b : m->stage) b.release();
   if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
   delete m;
@@ -569,6 +572,78 @@ int fh_map_plan_batch(fh_map* m, const double* starts, const double* goals, int 
       }
     }
   }
+  return FH_OK;
+}
+
+// include/fasterhip_view_subset.h: the views that the active queries need, ascending, each once
+int fh_map_view_list_device(fh_map* m, const int32_t* d_active, const int32_t* d_view_of, int n, int n_views, int32_t* d_list, int32_t* d_count) {
+  if (!m || !d_list || !d_count || n < 0 || n_views <= 0 || n_views > (1 << 24) || (!d_view_of && n > n_views)) return FH_ERR_ARG;
+  fhh::DeviceScope scope(m->device);
+  FM_HIP(m->view_need.reserve(sizeof(int) * (size_t)n_views, m->stream));
+  int* d_need = m->view_need.as<int>();
+  FM_HIP(hipMemsetAsync(d_need, 0, sizeof(int) * (size_t)n_views, m->stream));
+  if (n > 0)
+    hipLaunchKernelGGL(fhp::view_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, (const int*)d_active, (const int*)d_view_of, n,
+                       n_views, d_need);
+  hipLaunchKernelGGL(fhp::view_compact_kernel, dim3(1), dim3(fhp::VIEW_COMPACT_THREADS), 0, m->stream, (const int*)d_need, n_views, (int*)d_list,
+                     (int*)d_count);
+  FM_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// fh_map_read_views_device for the listed views only; with valid jump tables, their three levels for the same views
+int fh_map_read_views_listed_device(fh_map* m, const double* d_cloud_xyz, int n_cloud, const uint32_t* d_point_mask, int mask_words, int n_views,
+                                    const int32_t cells[3], double res, const double center[3], double z_ground, double z_max, double inflation,
+                                    const int32_t* d_list, const int32_t* d_count) {
+  if (!m) return FH_ERR_ARG;
+  auto refuse = [&](const char* why) {
+    m->err = std::string("fh_map_read_views_listed_device: ") + why;
+    return FH_ERR_ARG;
+  };
+  if (!d_list || !d_count) return refuse("a null list or count");
+  if (n_views <= 0 || n_cloud < 0 || mask_words < 0 || (long long)mask_words * 32 < (long long)n_cloud) return refuse("n_views, n_cloud or mask_words");
+  if (!cells || !center || (n_cloud > 0 && (!d_cloud_xyz || !d_point_mask)) || !(res > 0.0) || !(inflation >= 0.0)) return refuse("a null or bad argument");
+  if (cells[0] <= 0 || cells[1] <= 0 || cells[2] <= 0) return refuse("cells");
+  if (m->n_views <= 0 || !m->view_bits.ptr) return refuse("no grids yet: fh_map_read_views_device first");
+  int dx = cells[0] + (int)(5 * inflation / res), dy = cells[1] + (int)(5 * inflation / res), dz = cells[2];
+  int down = (int)(dz / 2.0), up = (int)(dz / 2.0);
+  if (center[2] - res * dz / 2.0 < z_ground) down = std::max((int)((center[2] - z_ground) / res), 0);
+  if (center[2] + res * dz / 2.0 > z_max) {
+    up = (int)((z_max - center[2]) / res);
+    up = up > 0 ? up : 1;
+  }
+  dz = down + up;
+  const double ox = center[0] - res * dx / 2.0, oy = center[1] - res * dy / 2.0, oz = center[2] - res * down;
+  if (n_views != m->n_views || dx != m->view_nx || dy != m->view_ny || dz != m->view_nz || res != m->view_res || inflation != m->view_inflation ||
+      ox != m->view_origin[0] || oy != m->view_origin[1] || oz != m->view_origin[2])
+    return refuse("the lattice, n_views and inflation of the last fh_map_read_views_device are needed");
+  fhh::DeviceScope scope(m->device);
+  const long long total = (long long)dx * dy * dz, words = (long long)m->words_per_view;
+  const unsigned rows = (unsigned)std::min(n_views, fhp::VIEW_LIST_ROWS);
+  unsigned* d_bits = m->view_bits.as<unsigned>();
+  hipLaunchKernelGGL(fhp::clear_views_listed_kernel, dim3((unsigned)((words + 255) / 256), rows), dim3(256), 0, m->stream, d_bits, words, n_views,
+                     (const int*)d_list, (const int*)d_count);
+  if (n_cloud > 0) {
+    const int mcube = (int)std::floor(inflation / res);
+    hipLaunchKernelGGL(fhp::mark_views_listed_kernel, dim3((unsigned)((n_cloud + 255) / 256), rows), dim3(256), 0, m->stream, d_cloud_xyz, n_cloud, dx,
+                       dy, dz, res, ox, oy, oz, mcube, d_bits, words, (const unsigned*)d_point_mask, mask_words, n_views, (const int*)d_list,
+                       (const int*)d_count);
+  }
+  if (m->view_entries_valid) {  // (only a view search in mode 1 sets it: the neighbour tables and the entries are there, sized for this lattice)
+    fhp::MapView mv;
+    mv.nx = dx; mv.ny = dy; mv.nz = dz;
+    mv.total = (int)total;
+    mv.inv_nxy = fhu::inverse(dx * dy); mv.inv_nx = fhu::inverse(dx);
+    mv.m_free = (int)std::round((double)(float)inflation / res + 0.5);
+    mv.res = res; mv.ox = ox; mv.oy = oy; mv.oz = oz;
+    mv.bits = d_bits;
+    for (int level = 1; level <= 3; level++) {
+      const long long threads = total * (level == 1 ? 6 : (level == 2 ? 12 : 8));
+      hipLaunchKernelGGL(fhp::jps_table_views_listed_kernel, dim3((unsigned)((threads + 255) / 256), rows), dim3(256), 0, m->stream, mv,
+                         m->d_jps_tables, m->view_entries.as<short>(), level, words, n_views, (const int*)d_list, (const int*)d_count);
+    }
+  }
+  FM_HIP(hipGetLastError());
   return FH_OK;
 }
 

@@ -31,6 +31,9 @@ different rounds, and a later round sees, through traffic and check, what the ea
 
     begin -> round_classes -> for every round: gate -> [traffic] -> path search -> ... -> commit [-> check -> revert] -> gate_restore
 
+enable_listed_views() makes map_views cheap where few vehicles replan (include/fasterhip_view_subset.h): a view_list stage lists, on the
+device, the views of the vehicles that are switched on, and map_views rebuilds the grids and jump tables of those views only.
+
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
@@ -92,6 +95,7 @@ class Fleet:
         self.check_par = self.check_cells = self.d_backup_vehicles = self.d_backup_plans = self.d_check = None   # enable_check
         self.round_par = self.round_cells = self.d_rounds = self.d_active_begin = self.d_check_rounds = None      # enable_rounds
         self.round_retries, self.round_fixed = 0, False
+        self.listed_views, self._views_full, self.d_view_list, self.d_view_count = False, True, None, None   # enable_listed_views
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -150,6 +154,7 @@ class Fleet:
         self.cloud.record_stream(self.stream)  # (read by every later cycle's launches on the fleet's stream)
         self.map.read_device(self.cloud.data_ptr(), self.n_cloud, cells, res, center, self.z_ground, z_max, inflation)
         self.map_args = (tuple(int(c) for c in cells), float(res), tuple(float(c) for c in center), float(z_max), float(inflation))
+        self._views_changed()
         if self.point_mask is not None and self.point_mask.shape[1] * 32 < self.n_cloud:
             raise capi.FasterHipError("Fleet.set_map: the point masks hold fewer bits than the new cloud has points (set_point_views again)")
 
@@ -206,6 +211,7 @@ class Fleet:
                 raise capi.FasterHipError("Fleet.set_unknown_views: %d views, the point masks hold %d (set_point_views again)" % (self.n_views, self.point_mask.shape[0]))
             self.ctx.set_point_views_device(self.point_mask.data_ptr(), self.point_mask.shape[1], None if self.view_of is None else self.view_of.data_ptr(),
                                             self.n_views)
+        self._views_changed()
 
     def set_point_views(self, mask=None):
         """Occupied space per view: mask [n_views][ceil(n_cloud / 32)] uint32 (numpy or a device tensor, adopted as it is when it is on the
@@ -220,6 +226,7 @@ class Fleet:
             self.cloud = self.cloud[:self.n_cloud]
         if mask is False:
             self.point_mask = None
+            self.listed_views = False   # (no views to list)
             self.ctx.set_point_views_device(None)
             return
         if self.view_flags is None or self.cloud is None:
@@ -236,6 +243,7 @@ class Fleet:
         self.point_mask.record_stream(self.stream)
         self.ctx.set_point_views_device(self.point_mask.data_ptr(), self.point_mask.shape[1], None if self.view_of is None else self.view_of.data_ptr(),
                                         self.n_views)
+        self._views_changed()
 
     def observe(self):
         """Every view learns the cloud points that lie in voxels it knows (fh_fleet_observe_device): after sense(), before replan().  One
@@ -307,6 +315,7 @@ class Fleet:
         self.point_mask.record_stream(self.stream)
         self.ctx.set_point_views_device(self.point_mask.data_ptr(), self.point_mask.shape[1], None, self.n_views)
         self.traffic_par, self.n_cloud_all = par, total
+        self._views_changed()
 
     def traffic(self):
         """The committed plans of the other vehicles into the tail of the cloud and into every vehicle's mask row
@@ -379,8 +388,8 @@ class Fleet:
         separation_cells(reach); no field of a record depends on it.
         LIMITS.  results(), faces() and certify() describe every vehicle's buffers as the LAST round left them: a vehicle of an earlier
         round then shows an inactive query (its plan and record are what its own round committed).  With point views map_views runs once
-        per round for every view, so a cycle costs about `rounds + retries` times the path search and the views' maps; neither the
-        active vehicles of a round are compacted nor only their views rebuilt.  Rounds change nothing about who a vehicle sees unless
+        per round for every view, so a cycle costs about `rounds + retries` times the path search and the views' maps; the active
+        vehicles of a round are not compacted, and only enable_listed_views rebuilds the views of a round alone.  Rounds change nothing about who a vehicle sees unless
         traffic or the check is enabled: without them every round plans as if alone, and the result is that of one round.
         Memory: 16 bytes per vehicle, n ints, and with the check 32 bytes per vehicle and round."""
         t, B = self.torch, self.n
@@ -414,6 +423,48 @@ class Fleet:
         self.round_par, self.round_retries, self.round_fixed = par, retries, records is not None
         if self.check_par is not None:
             self._alloc_round_checks()
+        self._views_changed()
+
+    def enable_listed_views(self, on=True):
+        """map_views rebuilds only the views that somebody searches (include/fasterhip_view_subset.h): from now on stages() holds, in
+        place of map_views, `view_list` — the views of the vehicles that are switched on (d_active as begin or the round's gate left
+        it, through view_of), listed on the device, ascending — and a `map_views` that clears, marks and tables the listed views only;
+        with rounds one view_list@r and one listed map_views@r per round and retry.  The grid and the tables of a view that is not
+        listed stay as they were: the search of that round reads them for no query, and the round that does search the view lists it
+        and rebuilds it first, from the cloud and the masks as they stand then.  The lattice is the one thing the argument does not
+        cover, so the first map_views after this call, set_map, set_unknown_views, set_point_views, enable_traffic or enable_rounds
+        reads every view (Map.read_views_device); what a launch does is decided when it runs.  Needs point views (set_point_views or
+        enable_traffic).  on=False: today's chain.  view_lists() reads the lists back.  Memory: n_views + 1 ints per round."""
+        if not on:
+            self.listed_views = False
+            return
+        if self.point_mask is None:
+            raise capi.FasterHipError("Fleet.enable_listed_views: the fleet has no point views (set_point_views or enable_traffic first)")
+        self.listed_views = True
+        self._views_changed()
+
+    def _views_changed(self):
+        """The next map_views reads every view; the lists have a row per round and retry and an entry per view."""
+        self._views_full = True
+        if not self.listed_views:
+            return
+        t = self.torch
+        rows = 1 if self.round_par is None else int(self.round_par["rounds"]) + self.round_retries
+        if self.d_view_list is None or tuple(self.d_view_list.shape) != (rows, self.n_views):
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_view_list = t.full((rows, self.n_views), -1, dtype=t.int32, device=self.dev)
+                self.d_view_count = t.zeros(rows, dtype=t.int32, device=self.dev)
+            for d in (self.d_view_list, self.d_view_count):
+                d.record_stream(self.stream)
+
+    def view_lists(self):
+        """(lists [rows][n_views] int32, counts [rows] int32): the views every round (and retry) of the last replan() listed, ascending
+        with -1 behind them, and how many; without rounds one row (synchronises)."""
+        if not self.listed_views:
+            raise capi.FasterHipError("Fleet.view_lists: enable_listed_views first")
+        self.sync()
+        return self.d_view_list.cpu().numpy().copy(), self.d_view_count.cpu().numpy().copy()
 
     def _alloc_round_checks(self):
         """The check records of every round: [rounds + retries][n] fh_plan_check."""
@@ -506,7 +557,7 @@ class Fleet:
         if self.cloud is None or self.grid is None:
             raise capi.FasterHipError("Fleet.replan: set_map and set_unknown (or set_unknown_views) first")
         if self.round_par is None:
-            return self._cycle_stages(self.d_active, self.d_check)
+            return self._cycle_stages(self.d_active, self.d_check, 0)
         # priority rounds (include/fasterhip_rounds.h): begin once, into d_active_begin; the rest of the chain once per round, behind its gate
         B, c = self.n, self.ctx
         p = lambda t: t.data_ptr()  # noqa: E731
@@ -514,7 +565,7 @@ class Fleet:
         rounds += [(abi.FH_ROUND_RETRY, "@retry %d" % t) for t in range(self.round_retries)]
         out = []
         for row, (rnd, tag) in enumerate(rounds):
-            body = self._cycle_stages(self.d_active_begin, None if self.check_par is None else self.d_check_rounds[row])
+            body = self._cycle_stages(self.d_active_begin, None if self.check_par is None else self.d_check_rounds[row], row)
             if row == 0:
                 out.append(body[0])
                 if not self.round_fixed:
@@ -529,9 +580,9 @@ class Fleet:
                                                                       p(self.d_active))))
         return out
 
-    def _cycle_stages(self, d_active_begin, d_check):
+    def _cycle_stages(self, d_active_begin, d_check, row):
         """The chain of one replan: begin writes who replans into d_active_begin (without rounds: d_active, what the path search reads),
-        the check its records into d_check."""
+        the check its records into d_check, a listed map_views its list into row `row` of the view lists."""
         B, P, c, m = self.n, self.params, self.ctx, self.map
         p = lambda t: t.data_ptr()  # noqa: E731
         origin, res, dims = self.grid
@@ -558,6 +609,20 @@ class Fleet:
                                                                      p(self.d_paths), p(self.d_np), vo, self.n_views, p(self.d_ex),
                                                                      self.dist_max_vertexes, 0)),
         ]
+        if self.listed_views:
+            lst, cnt = self.d_view_list[row], self.d_view_count[row:row + 1]
+            full = views[0][1]
+
+            def map_views():   # (full or listed is decided when the launch runs: stages() may be called any number of times before)
+                if self._views_full:
+                    full()
+                    self._views_full = False
+                else:
+                    m.read_views_listed_device(p(self.cloud), n_cloud, p(self.point_mask), self.point_mask.shape[1], self.n_views, cells, mres,
+                                               center, self.z_ground, z_max, inflation, p(lst), p(cnt))
+
+            views = [("view_list", lambda: m.view_list_device(p(self.d_active), vo, B, self.n_views, p(lst), p(cnt))),
+                     ("map_views", map_views), views[1]]
         return chain[:1] + views + chain[2:]
 
     def _shared_map_stages(self, B, P, c, m, p, origin, res, dims, n_cloud, d_active_begin):

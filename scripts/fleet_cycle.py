@@ -42,9 +42,12 @@ fleet), with Fleet.enable_check when --check is given (which --retries needs), t
 replan -> 5 ticks) and then after Fleet.enable_rounds(R, reach = M, default Fleet's; retries = T): every stage of every round fenced
 like the others ("stages_ms", names suffixed @r), the same summed over the rounds per stage ("by_stage_ms"), "round_classes" and the
 mean of the gates on their own, and per timed cycle the vehicles per class, the flagged records and the commits withheld per round.
+--listed-views (with --rounds, --traffic, --traffic-timed or --occupancy) calls Fleet.enable_listed_views on the fleets that have point
+views: "view_list" becomes a stage of its own in front of every "map_views", which then rebuilds the listed views only; the rounds report
+carries the views listed per round and timed cycle ("views_listed_per_round").
     usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
-                                         [--rounds R [--round-reach M] [--retries T]]"""
+                                         [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
 import os
 import sys
@@ -60,6 +63,7 @@ from faster_amd.fleet import Fleet  # noqa: E402
 
 AUDIT = "--audit" in sys.argv
 SEPARATION = "--separation" in sys.argv
+LISTED_VIEWS = "--listed-views" in sys.argv
 
 
 def timed_audit(fl, cycles):
@@ -285,6 +289,9 @@ def occupancy_cycles(B, cycles, p, world, r_sense, teams):
         fl.set_map(cloud, cells, res, center, zmax, infl)
         fl.set_unknown_views(view_of=np.arange(B, dtype=np.int32) % teams, n_views=teams, origin=origin, res=res, dims=dims)
         fl.set_point_views()
+        if LISTED_VIEWS:
+            fl.enable_listed_views()
+            out["listed_views"] = True
         fl.init(states, goals)
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         e[0].record(fl.stream)
@@ -330,6 +337,9 @@ def traffic_cycles(B, cycles, p, world, samples, stride, reach, window=None):
         fl.enable_traffic(samples, stride, reach, timed=window is not None, window=window or 0)
         if window is not None:
             out.update({"window": int(window), "first_instant": int(fl.traffic_par["first_instant"])})
+        if LISTED_VIEWS:
+            fl.enable_listed_views()
+            out["listed_views"] = True
         out.update({"traffic_points": fl.n_cloud_all - int(fl.traffic_par["first_point"]), "cloud_points": fl.n_cloud_all,
                     "mask_bytes": int(fl.point_mask.numel()) * 4, "unknown_views_bytes": B * n_cells})
         fl.traffic()
@@ -367,6 +377,10 @@ def rounds_cycles(B, cycles, p, world, rounds, reach, retries, traffic, window, 
             fl.init(states, goals)
         if check:
             fl.enable_check()
+        listed = LISTED_VIEWS and fl.point_mask is not None
+        if listed:
+            fl.enable_listed_views()
+        out["listed_views"] = bool(listed)
         for _ in range(2):
             if with_traffic:
                 fl.traffic()
@@ -383,7 +397,7 @@ def rounds_cycles(B, cycles, p, world, rounds, reach, retries, traffic, window, 
         fl.sync()
         names = [n for n, _ in fl.stages()] + ["next_goals"]
         per = {n: [] for n in names}
-        per_class, flagged, withheld = [], [], []
+        per_class, flagged, withheld, views_listed = [], [], [], []
         for _ in range(cycles):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
             ev[0].record(fl.stream)
@@ -401,6 +415,8 @@ def rounds_cycles(B, cycles, p, world, rounds, reach, retries, traffic, window, 
                             "unsettled": int(((rec["flags"] & abi.FH_ROUND_UNSETTLED) != 0).sum()), "n_lower_max": int(rec["n_lower"].max())})
             if check:
                 withheld.append([int(((r["flags"] & abi.FH_CHECK_CONFLICT) != 0).sum()) for r in fl.check_records_by_round()])
+            if listed:
+                views_listed.append(fl.view_lists()[1].tolist())
         med = {n: float(np.median(v)) for n, v in per.items()}
         by_stage = {}
         for n, v in med.items():
@@ -409,6 +425,7 @@ def rounds_cycles(B, cycles, p, world, rounds, reach, retries, traffic, window, 
         out["with_rounds"] = {"stages_ms": med, "by_stage_ms": by_stage, "cycle_fenced_ms": float(sum(med.values())),
                               "round_classes_ms": med.get("round_classes"), "gate_mean_ms": float(np.mean(gates)), "gates": len(gates),
                               "vehicles_per_class": per_class, "flagged": flagged, "withheld_per_round": withheld,
+                              "views_listed_per_round": views_listed,
                               "committed_last": int((fl.vehicles()["stage"] == abi.FH_FLEET_STAGE_COMMITTED).sum())}
     finally:
         fl.close()
