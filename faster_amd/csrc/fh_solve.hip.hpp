@@ -113,6 +113,7 @@ __device__ __forceinline__ int mk_id(int kind, int t, int k, int f) { return (ki
 using fhw::dpp_f64; using fhw::first_lane; using fhw::halves_sum; using fhw::readlane_f64; using fhw::uniform_f64;
 using fhw::uniform_i32; using fhw::vmax_f64; using fhw::vmin_f64; using fhw::wave_any; using fhw::wave_max; using fhw::wave_max_nonneg;
 using fhw::wave_min; using fhw::wave_or; using fhw::wave_sum; using fhw::wave_sum_i32;
+using fhw::gather_f64; using fhw::group_max_nonneg; using fhw::half_min; using fhw::half_sum; using fhw::half_sum2; using fhw::rows3_sum_i32;
 
 // Scheduling fences.  in_flight(a): every element of `a` (just loaded) must be in its register here, so the loads are issued
 // back to back and their LDS latencies overlap (the scheduler of this register-tight kernel otherwise serialises
@@ -425,6 +426,21 @@ struct Solver {
   // 3 NSEG <= 32 (the N = 6 and N = 10 buckets): the rows of the jerks, of the states and of a reduced normal fit in half a wavefront,
   // and lanes l and l + 32 share the sum of row l (compute_states, moments) the way project() shares its sweeps
   static constexpr bool HALF = 3 * NSEG <= 32;
+  // Reductions of values that live in lanes < 32 and are the identity (+0, INFINITY) above them.  HALF: the reduced unknowns and a
+  // reduced normal (lanes < n <= 24), the jerks and a normal in jerk space (lanes < nx <= 30), the active rows (lanes < q <= n) — five
+  // stages instead of six, and two adjacent sums in one pass; the bits of the six-stage forms (fh_wave.hip.hpp).
+  static __device__ __forceinline__ double lo_sum(double v) {
+    if constexpr (HALF) return half_sum(v);
+    else return wave_sum(v);
+  }
+  static __device__ __forceinline__ double lo_min(double v) {
+    if constexpr (HALF) return half_min(v);
+    else return wave_min(v);
+  }
+  static __device__ __forceinline__ void lo_sum2(double a, double b, double& sa, double& sb) {
+    if constexpr (HALF) half_sum2(a, b, sa, sb);
+    else { sa = wave_sum(a); sb = wave_sum(b); }
+  }
   static constexpr int RPSZ = NVP * (NVP + 1) / 2;  // R is packed upper triangular, column major: R(r, c) = R[c(c+1)/2 + r]
   static __device__ __forceinline__ int rp(int r_, int c_) { return (c_ * (c_ + 1)) / 2 + r_; }
 
@@ -805,8 +821,13 @@ struct Solver {
       }
       xpr = xp;
       if (lane < NXP) xs[lane] = xp;
-      c0 = wave_sum(xp * xp);
-      l1 = may_end_early ? wave_sum(fabs(xp)) : 0.0;
+      if constexpr (HALF) {  // xp is +0 in lanes >= nx, nx <= 30: both sums in one pass
+        if (may_end_early) half_sum2(xp * xp, fabs(xp), c0, l1);
+        else { c0 = half_sum(xp * xp); l1 = 0.0; }
+      } else {
+        c0 = wave_sum(xp * xp);
+        l1 = may_end_early ? wave_sum(fabs(xp)) : 0.0;
+      }
     }
     FH_SYNC();
     // The cheapest trajectory that meets the final-state equalities already costs more than any trajectory inside the jerk box may
@@ -927,7 +948,9 @@ struct Solver {
     const int p = live ? assign[lane >> 2] : -1;
     scan_f0 = p >= 0 ? face_off[p] : 0;
     scan_F = p >= 0 ? face_off[p + 1] - scan_f0 : 0;
-    rows4 = wave_sum_i32(scan_F);  // flop accounting: rows x control points scanned per iteration of this run
+    // flop accounting: rows x control points scanned per iteration of this run (HALF: the lanes (t, k) < 4 N <= 40 lie in three rows)
+    if constexpr (HALF) rows4 = rows3_sum_i32(scan_F);
+    else rows4 = wave_sum_i32(scan_F);
     // (tried: the longest row list any lane scans in THIS run as the trip count, a wave maximum of scan_F — 19.4 M pairs/s on C4 with
     // and without it, the sweeps are not what a node waits for; not kept)
     scan_trip = maxF;
@@ -1030,7 +1053,7 @@ struct Solver {
         const int m = tt - 1 - kk;  // (here kk is the segment s of the x-space lane)
         const double gxv = (lane < nx && m >= 0) ? gi * wcoef(wk, m, h) : 0.0;
         if (lane < NXP) xs[lane] = gxv;
-        gx2 = wave_sum(gxv * gxv);
+        gx2 = lo_sum(gxv * gxv);  // (gxv: lanes < nx)
       }
       FH_SYNC();
       const bool on = lane < n;
@@ -1057,7 +1080,7 @@ struct Solver {
     }
     if (lane < NVP) g[lane] = gv;
     FH_SYNC();
-    return wave_sum(gv * gv);
+    return lo_sum(gv * gv);  // (gv: lanes < n)
   }
 
   // Q1 is stored COLUMN major, Q(i, c) = Q[c * S + i] (the live columns are a contiguous prefix: cheap node snapshots).
@@ -1158,7 +1181,7 @@ struct Solver {
       FH_SYNC();
       zi = g[ll] - col_dot2(Q, ll, d, q8);
       if (lane >= NVP) zi = 0.0;
-      double zz = wave_sum(zi * zi);
+      double zz = half_sum(zi * zi);  // (zi: lanes < NVP <= 32)
       if (zz < FH_REORTH_THRESHOLD * gg) {
         if (lane < NVP) z[lane] = zi;
         FH_SYNC();
@@ -1168,7 +1191,7 @@ struct Solver {
         FH_SYNC();
         zi -= col_dot2(Q, ll, r, q8);
         if (lane >= NVP) zi = 0.0;
-        zz = wave_sum(zi * zi);
+        zz = half_sum(zi * zi);
       }
       return zz;
     }
@@ -1325,12 +1348,14 @@ struct Solver {
            // test also ends the divergence of an infeasible node before a numerically dependent row (|z| ~ 1e-10 |g|) can be
            // mistaken for an independent one and answered with a step of 1e24.  (NaN-safe: !(cost <= ub).)
           const double xl = (lane < n) ? x[lane] : 0.0;
-          cost = c0 + wave_sum(xl * xl);
+          // (both sums below in one pass: xl lives in lanes < n, xj is +0 in lanes >= nx — compute_states)
           // [r5] The same certificate in the 1-norm (setup_trial has it for y = 0): the current point x* = xp + Z y* is the cheapest one that
           // satisfies the ACTIVE rows, x* = xp - sum mu_k a_k with mu >= 0 (the invariant of the dual method), so every feasible x has
           // x* . x >= |x*|^2 = cost; inside the jerk box x* . x <= |x*|_1 (j_max + tol).  cost > |x*|_1 (j_max + tol) is therefore
           // infeasible with the same conflict as the 2-norm bound, and never later (Cauchy-Schwarz): a refuted node ends iterations sooner.
-          const double l1x = wave_sum(fabs(xj));
+          double x2, l1x;
+          lo_sum2(xl * xl, fabs(xj), x2, l1x);
+          cost = c0 + x2;
           if (!(cost <= box_ub) || cost > l1x * (jmax + tol) * (1.0 + 1e-9)) {
             // Infeasible, with a certificate: the current point is the cheapest one that satisfies the ACTIVE rows (the invariant of
             // the dual method), so the active rows and the jerk box exclude each other — the conflict is the segments whose corridor
@@ -1359,7 +1384,7 @@ struct Solver {
         const bool dependent = zz <= dep2 * gx2;  // relative to the row's norm in JERK space: the rounding noise of z is eps |g_x|
         double ratio = INFINITY;
         if (lane < q && rc > 0) ratio = u[lane] / rc;
-        const double t1 = wave_any(ratio < INFINITY) ? wave_min(ratio) : INFINITY;  // (no blocking row in most iterations)
+        const double t1 = wave_any(ratio < INFINITY) ? lo_min(ratio) : INFINITY;  // (ratio: lanes < q)  // (no blocking row in most iterations)
         const int kb = (t1 < INFINITY) ? first_lane(ratio == t1) : -1;
         if (kb < 0 && dependent) {  // infeasible: row `id` is violated and a non-negative combination of active rows
           // The certificate: a_id = sum_c rc a_c over the active rows, and the remaining violation vp > 0.  Mathematically the
@@ -2551,6 +2576,43 @@ struct Solver {
                // control points of the segment bounds child p from below.  |n| in the reduced space is 1 / wcp of lane (segment,
                // control point) for a normalised row — the scaled violation of the row scan, squared.
               const int sb = uniform_i32(bseg);
+              double bmax = 0.0;  // lane p < P: the bound of polytope p
+              if constexpr (HALF) {
+                // lane = (polytope p, control point k, row slice r), r the low bits: S = 4 slices while 4 P <= 16, else 2 (P <= 8), so
+                // every lane of the wavefront sweeps a block of ceil(maxF / S) rows of its polytope, four rows loaded before their
+                // first use.  Each vt is the one of the sweep over all rows; x -> (x w)^2 does not decrease on x >= 0 (w >= 0), so the
+                // maximum of (m_r w)^2 over the slices and control points is the bound of before, bit for bit.
+                const int lane = opaque(this->lane);  // (recomputed: without it this block costs the kernel 16 B of scratch per lane)
+                const int sh = 4 * P <= 16 ? 2 : 1;
+                const int pk = lane >> sh, sr = lane & ((1 << sh) - 1);
+                const int lp = (pk >> 2) & 7, lk = pk & 3;
+                const bool on = lp < P && ((am >> lp) & 1u);
+                const int f0b = on ? face_off[lp] : 0, Fb = on ? face_off[lp + 1] - f0b : 0;
+                double cb[3];
+#pragma unroll
+                for (int i = 0; i < 3; i++) cb[i] = cp_of(lk, Pc[3 * sb + i], Vc[3 * sb + i], Ac[3 * sb + i], Pc[3 * sb + 3 + i]);
+                const int L = (maxF + (1 << sh) - 1) >> sh;  // rows per slice
+                const int flb = Fb > 0 ? Fb - 1 : 0;          // rows beyond the polytope re-read its last row and are masked
+                const fh_face* fp = faces + f0b;
+                const int r0 = sr * L;
+                double m = 0.0;
+                for (int fb = 0; fb < L; fb += 4) {
+                  fh_face fc[4];
+#pragma unroll
+                  for (int j = 0; j < 4; j++) fc[j] = fp[min(r0 + fb + j, flb)];  // the four loads in flight before the first use
+#pragma unroll
+                  for (int j = 0; j < 4; j++) {
+                    const double vt = fma(fc[j].a[0], cb[0], fma(fc[j].a[1], cb[1], fma(fc[j].a[2], cb[2], fc[j].b)));
+                    m = (r0 + fb + j < Fb && vt > m) ? vt : m;  // (a row past the block belongs to the next slice: the same maximum)
+                  }
+                }
+                const double w = gather_f64(this->wcp, 4 * sb + lk);  // the weight of (segment, control point) from the lane that keeps it
+                double bnd = m * w;
+                bnd = bnd * bnd;
+                bnd = sh == 2 ? group_max_nonneg<16>(bnd) : group_max_nonneg<8>(bnd);
+                const double bg = gather_f64(bnd, (lane << (sh + 2)) & 63);  // lane p reads the first lane of group p
+                bmax = lane < P ? bg : 0.0;
+              } else {
               const int lp = (lane >> 2) & 7, lk = lane & 3;
               const bool on = lane < 4 * FH_MAX_POLY && lp < P && ((am >> lp) & 1u);
               const int f0b = face_off[lp], Fb = on ? face_off[lp + 1] - f0b : 0;
@@ -2573,12 +2635,12 @@ struct Solver {
               }
               double bnd = m * w;
               bnd = bnd * bnd;
-              double bmax = 0.0;  // lane p < P: the bound of polytope p
               for (int p2 = 0; p2 < P; p2++) {
                 double b4 = 0.0;
 #pragma unroll
                 for (int k2 = 0; k2 < 4; k2++) b4 = fmax(b4, readlane_f64(bnd, 4 * p2 + k2));
                 bmax = (lane == p2) ? b4 : bmax;
+              }
               }
               // slack: 1e-9 of the increment (the rounding of the scaled violation) and 1e-12 of the bound itself — the leaf costs it is
               // compared with carry rounding noise relative to THEIR size, which the first term does not cover when bmax << cost

@@ -107,6 +107,47 @@ __device__ __forceinline__ double wave_max(double v) {
   v = fmax(v, dpp_f64<0x142, 0xa>(-INFINITY, v)); v = fmax(v, dpp_f64<0x143, 0xc>(-INFINITY, v));  // across the rows
   return readlane_f64(v, 63);
 }
+// Reductions over lanes 0..31 only, five stages: row_shr 1/2/4/8, row_bcast:15, the result in lane 31.  Where lanes 32..63 hold the
+// identity (+0, INFINITY) they return the bits of the six-stage forms above: lane 63 of wave_sum is (r3 + r2) + (r1 + r0) over the
+// four row totals, (0 + 0) + (r1 + r0) = r1 + r0 when no summand is -0; a maximum or minimum with its identity is the other operand.
+__device__ __forceinline__ double half_sum(double v) {
+  v += dpp0_f64<0x111>(v); v += dpp0_f64<0x112>(v); v += dpp0_f64<0x114>(v); v += dpp0_f64<0x118>(v);  // inside each row of 16 lanes
+  v += dpp0_f64<0x142>(v);  // row 0 into row 1
+  return readlane_f64(v, 31);
+}
+__device__ __forceinline__ double half_max_nonneg(double v) {
+  v = vmax_f64(v, dpp0_f64<0x111>(v)); v = vmax_f64(v, dpp0_f64<0x112>(v));  // inside each row of 16 lanes: row_shr 1, 2,
+  v = vmax_f64(v, dpp0_f64<0x114>(v)); v = vmax_f64(v, dpp0_f64<0x118>(v));  // 4, 8
+  v = vmax_f64(v, dpp0_f64<0x142>(v));  // row 0 into row 1
+  return readlane_f64(v, 31);
+}
+__device__ __forceinline__ double half_min(double v) {
+  v = vmin_f64(v, dpp_f64<0x111, 0xf>(INFINITY, v)); v = vmin_f64(v, dpp_f64<0x112, 0xf>(INFINITY, v));  // inside each row of 16 lanes: row_shr 1, 2,
+  v = vmin_f64(v, dpp_f64<0x114, 0xf>(INFINITY, v)); v = vmin_f64(v, dpp_f64<0x118, 0xf>(INFINITY, v));  // 4, 8
+  v = vmin_f64(v, dpp_f64<0x142, 0xa>(INFINITY, v));  // row 0 into row 1
+  return readlane_f64(v, 31);
+}
+// Two sums over lanes 0..31 in one pass: lanes 0..31 of b move to lanes 32..63 (v_permlane32_swap, gfx950), the five stages run once,
+// and the totals are read from lanes 31 and 63 (row_bcast:15 adds row 2 into row 3 the way it adds row 0 into row 1): sa and sb have
+// the bits of half_sum(a) and half_sum(b).  What a and b hold in lanes 32..63 is not read.
+__device__ __forceinline__ void half_sum2(double a, double b, double& sa, double& sb) {
+  // The first stage runs on a and b themselves, as in half_sum: where a is a product, the compiler contracts it with this addition
+  // (fma) as it does there, and the bits are those of the single sums.  A row_shr stays inside its row, so it commutes with the move.
+  a += dpp0_f64<0x111>(a);
+  b += dpp0_f64<0x111>(b);
+  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+  double v = __hiloint2double((int)hi[0], (int)lo[0]);  // lanes 0..31: a, lanes 32..63: b of the lane 32 below
+  v += dpp0_f64<0x112>(v); v += dpp0_f64<0x114>(v); v += dpp0_f64<0x118>(v);  // inside each row of 16 lanes
+  v += dpp0_f64<0x142>(v);  // row 0 into row 1, row 2 into row 3
+  sa = readlane_f64(v, 31);
+  sb = readlane_f64(v, 63);
+}
+// The sum of an int over lanes 0..47: the four stages inside the rows, then the three row totals added as scalars.
+__device__ __forceinline__ int rows3_sum_i32(int v) {
+  v += dpp0_i32<0x111>(v); v += dpp0_i32<0x112>(v); v += dpp0_i32<0x114>(v); v += dpp0_i32<0x118>(v);  // inside each row of 16 lanes
+  return __builtin_amdgcn_readlane(v, 15) + __builtin_amdgcn_readlane(v, 31) + __builtin_amdgcn_readlane(v, 47);
+}
 // max over each aligned group of four lanes, the result in all four of them (quad_perm [1,0,3,2], then [2,3,0,1]).  Written as the
 // comparison `o > v ? o : v`, not fmax: with no NaN among the inputs there is none in the result.  All 64 lanes must be active.
 __device__ __forceinline__ double quad_max(double v) {
@@ -114,6 +155,24 @@ __device__ __forceinline__ double quad_max(double v) {
   v = o > v ? o : v;
   o = dpp0_f64<0x4E>(v);
   return o > v ? o : v;
+}
+// max over each aligned group of 8 or 16 lanes of values that are >= +0 and no NaN, the result in every lane of the group: the two
+// quad_perm steps of quad_max, then row_half_mirror (the other quad of the eight) and row_mirror (the other eight of the row).
+// All 64 lanes must be active.
+template <int GROUP>
+__device__ __forceinline__ double group_max_nonneg(double v) {
+  static_assert(GROUP == 8 || GROUP == 16, "an aligned group inside a row of 16 lanes");
+  v = vmax_f64(v, dpp0_f64<0xB1>(v));
+  v = vmax_f64(v, dpp0_f64<0x4E>(v));
+  v = vmax_f64(v, dpp0_f64<0x141>(v));
+  if constexpr (GROUP == 16) v = vmax_f64(v, dpp0_f64<0x140>(v));
+  return v;
+}
+// every lane reads v of the lane it names (ds_bpermute_b32: the LDS crossbar, no LDS memory); src in 0..63, that lane active
+__device__ __forceinline__ double gather_f64(double v, int src) {
+  const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(v));
+  return __hiloint2double(hi, lo);
 }
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ int dpp_min_step(int v) {
