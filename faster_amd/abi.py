@@ -217,6 +217,21 @@ def default_round_params(reach, rounds):
     return p
 
 
+# fh_link_params: vehicles in radio range pool what their views know (include/fasterhip_link.h)
+FH_LINK_MAX_PASSES, FH_LINK_MAX_CELLS = 1024, 1 << 20
+FH_LINK_DEFAULT_PASSES = 32
+link_params_dtype = np.dtype([("range", "<f8"), ("passes", "<i4"), ("reserved", "<i4", (5,))], align=True)
+assert link_params_dtype.itemsize == 32
+
+
+def default_link_params(range):  # noqa: A002  (the header's word)
+    """fh_link_params: two speaking vehicles nearer than `range` are linked; FH_LINK_DEFAULT_PASSES passes of hook and jump (the header
+    states what the worst arrangements of 64 and 1024 views needed)."""
+    p = np.zeros((), dtype=link_params_dtype)
+    p["range"], p["passes"] = range, FH_LINK_DEFAULT_PASSES
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

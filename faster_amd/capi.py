@@ -48,6 +48,8 @@ CHECK_SYMBOLS = ["fh_fleet_backup_device", "fh_fleet_check_device", "fh_fleet_re
 ROUNDS_SYMBOLS = ["fh_fleet_round_classes_device", "fh_fleet_round_gate_device"]
 # include/fasterhip_view_subset.h
 VIEW_SUBSET_SYMBOLS = ["fh_map_view_list_device", "fh_map_read_views_listed_device"]
+# include/fasterhip_link.h
+LINK_SYMBOLS = ["fh_fleet_link_groups_device", "fh_fleet_link_merge_device"]
 
 _LIB = None
 
@@ -309,6 +311,10 @@ def lib():
         L.fh_fleet_round_classes_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
         L.fh_fleet_round_gate_device.restype = i32
         L.fh_fleet_round_gate_device.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+        L.fh_fleet_link_groups_device.restype = i32
+        L.fh_fleet_link_groups_device.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp]
+        L.fh_fleet_link_merge_device.restype = i32
+        L.fh_fleet_link_merge_device.argtypes = [vp, vp, i32, vp, ctypes.c_size_t, ctypes.c_size_t, vp, i32, i32]
         L.fh_map_view_list_device.restype = i32
         L.fh_map_view_list_device.argtypes = [vp, vp, vp, i32, i32, vp, vp]
         L.fh_map_read_views_listed_device.restype = i32
@@ -895,6 +901,24 @@ class Context:
         Asynchronous on the context's stream (include/fasterhip_rounds.h)."""
         self._check(lib().fh_fleet_round_gate_device(self._h, d_rounds, int(round), d_active_begin, int(n), d_vehicles, d_active),
                     "fh_fleet_round_gate_device")
+
+    def fleet_link_groups_device(self, par, d_vehicles, n, d_view_of, n_views, cells, d_labels, d_info):
+        """fh_fleet_link_groups_device: d_labels [n_views] int32, the label of every view after par["passes"] passes of hook and jump
+        over the vehicles nearer than par["range"] to each other (settled: the smallest view of its connected component), d_info [4]
+        int64: views changed by the last pass, roots, linked pairs, 0; par: one abi.link_params_dtype record; cells = (origin, res,
+        dims): the grid of the broad phase, on which no output byte depends.  A measurement.  Asynchronous on the context's stream
+        (include/fasterhip_link.h)."""
+        p = _one_record(par, "link", "fleet_link_groups_device")
+        g = _grid_record(cells)
+        self._check(lib().fh_fleet_link_groups_device(self._h, abi.ptr(p), d_vehicles, int(n), d_view_of, int(n_views),
+                                                      None if g is None else abi.ptr(g), d_labels, d_info), "fh_fleet_link_groups_device")
+
+    def fleet_link_merge_device(self, d_labels, n_views, d_flags, view_stride, view_bytes, d_point_mask, mask_words, shared_words):
+        """fh_fleet_link_merge_device: the views of every group (a root and the views whose label it is) become equal, in place: a flag
+        byte below view_bytes is cleared where any member has it clear, a mask word below shared_words becomes the OR of the members';
+        either table may be None.  Asynchronous on the context's stream (include/fasterhip_link.h)."""
+        self._check(lib().fh_fleet_link_merge_device(self._h, d_labels, int(n_views), d_flags, int(view_stride), int(view_bytes), d_point_mask,
+                                                     int(mask_words), int(shared_words)), "fh_fleet_link_merge_device")
 
     def sample_batch_device(self, d_problems, d_results, n, max_samples, d_states, d_counts):
         self._check(lib().fh_sample_batch_device(self._h, d_problems, d_results, n, max_samples, d_states, d_counts),

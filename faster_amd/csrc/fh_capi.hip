@@ -26,6 +26,7 @@
 #include "../../include/fasterhip_check.h"
 #include "../../include/fasterhip_traffic_timed.h"
 #include "../../include/fasterhip_rounds.h"
+#include "../../include/fasterhip_link.h"
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
 #include "fh_decomp.hip.hpp"
@@ -38,6 +39,7 @@
 #include "fh_check.hip.hpp"
 #include "fh_traffic_timed.hip.hpp"  // (after fh_check: where its mask kernels have lain in the code object since they came)
 #include "fh_rounds.hip.hpp"         // (after every other device header: the functions of before keep their place and their bytes)
+#include "fh_link.hip.hpp"           // (and this one after that one, for the same reason)
 #include "fh_host.hpp"
 
 using fhh::DeviceScope;
@@ -86,6 +88,10 @@ enum Buf {
   TRAFFIC_BOXES,    // traffic_points{1,7}_kernel write the grown box of the shown centres of every chunk; the rule's mask kernels read them
   // fh_fleet_round_classes_device (its box records live in CELL_BOXES, like those of the other two stages of the cell grid)
   ROUND_LISTS,      // rounds_narrow_kernel writes the lower neighbours of every vehicle (rows of FH_ROUNDS_LIST), rounds_pass_kernel reads them
+  // fh_fleet_link_groups_device (its box records live in CELL_BOXES as well)
+  LINK_LISTS,       // link_narrow_kernel writes the views of the linked of every vehicle (rows of FH_LINK_LIST), link_hook_kernel reads them
+  LINK_NBRS,        // link_narrow_kernel writes how many are linked to every vehicle, link_hook_kernel reads it
+  LINK_LABELS,      // the two copies of the labels ([2][n_views]) that link_hook_kernel lowers and link_jump_kernel reads and writes in turn
   N_BUFS
 };
 
@@ -1248,6 +1254,87 @@ int fh_fleet_round_gate_device(fh_ctx* ctx, const fh_plan_round* d_rounds, int r
   hipLaunchKernelGGL(fh::rounds_gate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_rounds, round, d_active_begin, n,
                      d_vehicles, d_active);
   FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// ---- the radio link (include/fasterhip_link.h): the cell grid around link_boxes_kernel and link_narrow_kernel, the passes; the merge ----
+int fh_fleet_link_groups_device(fh_ctx* ctx, const fh_link_params* par, const fh_vehicle* d_vehicles, int n, const int32_t* d_view_of,
+                                int n_views, const fh_voxel_grid* cells, int32_t* d_labels, int64_t* d_info) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->range) || !(par->range > 0)) return FH_ERR_ARG;
+  if (par->passes < 1 || par->passes > FH_LINK_MAX_PASSES) return FH_ERR_ARG;
+  if (n < 0 || n_views < 1) return FH_ERR_ARG;
+  if (!cell_grid_ok(cells, FH_LINK_MAX_CELLS)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n > 0 && (!d_vehicles || !d_labels || !d_info)) return FH_ERR_ARG;
+  int rc;
+  if ((rc = ensure(ctx, LINK_LABELS, sizeof(int) * 2 * (size_t)n_views)) != FH_OK) return rc;
+  int* copies[2] = {ctx->buf[LINK_LABELS].as<int>(), ctx->buf[LINK_LABELS].as<int>() + n_views};
+  unsigned long long* info = reinterpret_cast<unsigned long long*>(d_info);
+  const dim3 view_blocks((unsigned)((n_views + 255) / 256));
+  if (n == 0) {  // nobody speaks: the identity, every view a root
+    if (d_info) FH_HIP(hipMemsetAsync(d_info, 0, sizeof(int64_t) * 4, ctx->stream));
+    if (d_labels) {
+      hipLaunchKernelGGL(fh::link_init_kernel, view_blocks, dim3(256), 0, ctx->stream, d_labels, copies[0], n_views);
+      FH_HIP(hipGetLastError());
+      hipLaunchKernelGGL(fh::link_jump_kernel, view_blocks, dim3(256), 0, ctx->stream, copies[0], d_labels, copies[1], n_views, info);
+      FH_HIP(hipGetLastError());
+    }
+    return FH_OK;
+  }
+  if ((rc = ensure(ctx, LINK_LISTS, sizeof(int) * (size_t)FH_LINK_LIST * (size_t)n)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, LINK_NBRS, sizeof(int) * (size_t)n)) != FH_OK) return rc;
+  fh::LinkArgs a;
+  a.range = par->range; a.r2 = par->range * par->range;
+  a.n = n; a.n_views = n_views;
+  a.vehicles = d_vehicles; a.view_of = d_view_of;
+  a.lists = ctx->buf[LINK_LISTS].as<int>();
+  a.nbrs = ctx->buf[LINK_NBRS].as<int>();
+  a.info = info;
+  FH_HIP(hipMemsetAsync(d_info, 0, sizeof(int64_t) * 4, ctx->stream));
+  if ((rc = cell_broad_phase(ctx, *cells, n, a, fh::link_boxes_kernel, fh::link_narrow_kernel)) != FH_OK) return rc;
+  hipLaunchKernelGGL(fh::link_init_kernel, view_blocks, dim3(256), 0, ctx->stream, d_labels, copies[0], n_views);
+  FH_HIP(hipGetLastError());
+  for (int p = 1; p <= par->passes; p++) {
+    int* H = copies[(p - 1) & 1];
+    hipLaunchKernelGGL(fh::link_hook_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, d_labels, H);
+    FH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fh::link_jump_kernel, view_blocks, dim3(256), 0, ctx->stream, H, d_labels, copies[p & 1], n_views,
+                       p == par->passes ? info : nullptr);
+    FH_HIP(hipGetLastError());
+  }
+  return FH_OK;
+}
+
+int fh_fleet_link_merge_device(fh_ctx* ctx, const int32_t* d_labels, int n_views, unsigned char* d_flags, size_t view_stride, size_t view_bytes,
+                               uint32_t* d_point_mask, int mask_words, int shared_words) {
+  if (!ctx) return FH_ERR_ARG;
+  if (n_views < 1) return FH_ERR_ARG;
+  if (d_flags && view_stride < view_bytes) return FH_ERR_ARG;
+  if (d_point_mask && (mask_words < 0 || shared_words < 0 || shared_words > mask_words)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (!d_labels) return FH_ERR_ARG;
+  const unsigned rows = (unsigned)std::min(n_views, 65535);
+  if (d_flags && view_bytes > 0) {
+    const size_t chunks = view_bytes / 16 + 2;  // (at least as many as any row has)
+    const dim3 grid((unsigned)std::min<size_t>((chunks + 4 * fh::LINK_MERGE_THREADS - 1) / (4 * fh::LINK_MERGE_THREADS), 64), rows);
+    for (int take = 0; take < 2; take++) {
+      hipLaunchKernelGGL(fh::link_merge_flags_kernel, grid, dim3(fh::LINK_MERGE_THREADS), 0, ctx->stream, d_labels, n_views, d_flags, view_stride,
+                         view_bytes, take);
+      FH_HIP(hipGetLastError());
+    }
+  }
+  if (d_point_mask && shared_words > 0) {
+    const int per_block = 4 * fh::LINK_MERGE_THREADS;
+    const dim3 grid((unsigned)std::min((shared_words + per_block - 1) / per_block, 64), rows);
+    for (int take = 0; take < 2; take++) {
+      hipLaunchKernelGGL(fh::link_merge_mask_kernel, grid, dim3(fh::LINK_MERGE_THREADS), 0, ctx->stream, d_labels, n_views, d_point_mask, mask_words,
+                         shared_words, take);
+      FH_HIP(hipGetLastError());
+    }
+  }
   return FH_OK;
 }
 

@@ -34,6 +34,11 @@ different rounds, and a later round sees, through traffic and check, what the ea
 enable_listed_views() makes map_views cheap where few vehicles replan (include/fasterhip_view_subset.h): a view_list stage lists, on the
 device, the views of the vehicles that are switched on, and map_views rebuilds the grids and jump tables of those views only.
 
+link() lets the vehicles in radio range of each other pool what their views know (include/fasterhip_link.h): the views of every connected
+group become equal, unknown voxels and occupied points alike, and the group plans as a team does until it parts:
+
+    sense -> observe -> link -> replan -> next_goals
+
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
@@ -96,6 +101,7 @@ class Fleet:
         self.round_par = self.round_cells = self.d_rounds = self.d_active_begin = self.d_check_rounds = None      # enable_rounds
         self.round_retries, self.round_fixed = 0, False
         self.listed_views, self._views_full, self.d_view_list, self.d_view_count = False, True, None, None   # enable_listed_views
+        self.d_link_labels = self.d_link_info = None                                                           # link
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -489,6 +495,55 @@ class Fleet:
             raise capi.FasterHipError("Fleet.check_records_by_round: enable_rounds and enable_check first")
         self.sync()
         return self.d_check_rounds.cpu().numpy().view(abi.plan_check_dtype).copy()
+
+    def link(self, range, passes=None, cells=None):  # noqa: A002  (the header's word)
+        """The vehicles nearer than `range` to each other pool what their views know (include/fasterhip_link.h): link_groups labels
+        every view with the smallest view of its connected group (`passes` passes of hook and jump, None:
+        abi.FH_LINK_DEFAULT_PASSES; link_records() tells whether they settled), link_merge makes the views of a group equal: a voxel is
+        known to all when one of them knows it, and with point views so is a point of the static cloud.  The traffic words of the
+        masks are per observer and stay as they are.  After sense() and observe(), before replan(); needs set_unknown_views.  cells =
+        (origin, res, dims): the grid of the broad phase, by default separation_cells(range); no output byte depends on it.  Launches on
+        the fleet's stream.  Nothing is forgotten when the vehicles part.  Memory: n_views ints and four words."""
+        self._follow_current()
+        for _, launch in self.link_stages(range, passes, cells):
+            launch()
+
+    def link_stages(self, range, passes=None, cells=None):  # noqa: A002
+        """The two launches of link(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        t = self.torch
+        if self.view_flags is None:
+            raise capi.FasterHipError("Fleet.link: set_unknown_views first")
+        par = abi.default_link_params(range)
+        if passes is not None:
+            par["passes"] = passes
+        if cells is None:
+            cells = self.separation_cells(float(par["range"]))
+        if self.d_link_labels is None or self.d_link_labels.numel() != self.n_views:
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_link_labels = t.zeros(self.n_views, dtype=t.int32, device=self.dev)
+                self.d_link_info = t.zeros(4, dtype=t.int64, device=self.dev)
+            for d in (self.d_link_labels, self.d_link_info):
+                d.record_stream(self.stream)
+        c, p = self.ctx, (lambda t: t.data_ptr())
+        vo = None if self.view_of is None else p(self.view_of)
+        mask = None if self.point_mask is None else p(self.point_mask)
+        words = 0 if self.point_mask is None else int(self.point_mask.shape[1])
+        shared = words if self.traffic_par is None else int(self.traffic_par["first_point"]) // 32   # (below the traffic)
+        return [
+            ("link_groups", lambda: c.fleet_link_groups_device(par, p(self.d_vehicles), self.n, vo, self.n_views, cells, p(self.d_link_labels),
+                                                               p(self.d_link_info))),
+            ("link_merge", lambda: c.fleet_link_merge_device(p(self.d_link_labels), self.n_views, p(self.view_flags), self.view_flags.shape[1],
+                                                             self.view_flags.shape[1], mask, words, shared)),
+        ]
+
+    def link_records(self):
+        """(labels [n_views] int32, info [4] int64) of the last link(): the label of every view; the views whose label the last pass
+        changed (0: settled), the roots, the linked pairs of vehicles, 0 (synchronises)."""
+        if self.d_link_labels is None:
+            raise capi.FasterHipError("Fleet.link_records: link first")
+        self.sync()
+        return self.d_link_labels.cpu().numpy().copy(), self.d_link_info.cpu().numpy().copy()
 
     def point_masks(self):
         """[n_views][words] uint32 on the host (synchronises)."""

@@ -45,7 +45,11 @@ mean of the gates on their own, and per timed cycle the vehicles per class, the 
 --listed-views (with --rounds, --traffic, --traffic-timed or --occupancy) calls Fleet.enable_listed_views on the fleets that have point
 views: "view_list" becomes a stage of its own in front of every "map_views", which then rebuilds the listed views only; the rounds report
 carries the views listed per round and timed cycle ("views_listed_per_round").
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--link RANGE[,RANGE..] (with --views) adds "link": for every RANGE the closed loop of --views from views that are all unknown with
+Fleet.link(RANGE) between sensing and the replan (sense -> link -> replan -> 5 ticks), "link_groups" and "link_merge" fenced as stages of
+their own; the passes, the groups (roots), the linked pairs and whether the labels settled in the last timed cycle; and, fenced the same
+way in the same run, a device-to-device copy of the views' bytes ("views_copy_ms": the yardstick of the merge) with the ratio of the two.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -64,6 +68,7 @@ from faster_amd.fleet import Fleet  # noqa: E402
 AUDIT = "--audit" in sys.argv
 SEPARATION = "--separation" in sys.argv
 LISTED_VIEWS = "--listed-views" in sys.argv
+LINK = [float(r) for r in sys.argv[sys.argv.index("--link") + 1].split(",")] if "--link" in sys.argv else []
 
 
 def timed_audit(fl, cycles):
@@ -175,10 +180,12 @@ def check_cycles(fl, cycles):
             "first_kind_1_last": int((rec["first_kind"] == 1).sum()), "separation_count_0_ms": float(np.median(ms))}
 
 
-def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False, traffic=False):
+def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False, traffic=False, link=None):
     """`cycles` cycles, every stage fenced by events: {stage: [ms]} (with r_sense: sensing first, as a stage of its own; fov: forward;
-    observe: Fleet.observe after it, as another; traffic: Fleet.traffic after that)."""
-    names = (["sense"] if r_sense else []) + (["observe"] if observe else []) + (["traffic"] if traffic else []) + [n for n, _ in fl.stages()] + ["next_goals"]
+    observe: Fleet.observe after it, as another; traffic: Fleet.traffic after that; link: the two stages of Fleet.link(link) after those)."""
+    linked = fl.link_stages(link) if link else []
+    names = ((["sense"] if r_sense else []) + (["observe"] if observe else []) + (["traffic"] if traffic else []) + [n for n, _ in linked]
+             + [n for n, _ in fl.stages()] + ["next_goals"])
     per = {n: [] for n in names}
     for _ in range(cycles):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
@@ -196,6 +203,10 @@ def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False, traffic=Fals
             fl.traffic()
             k += 1
             ev[k].record(fl.stream)
+        for _, launch in linked:
+            launch()
+            k += 1
+            ev[k].record(fl.stream)
         for j, (n, launch) in enumerate(fl.stages()):
             launch()
             ev[k + j + 1].record(fl.stream)
@@ -207,8 +218,8 @@ def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False, traffic=Fals
     return {n: float(np.median(v)) for n, v in per.items()}
 
 
-def sensing_loop(fl, views, cycles, states, goals, r_sense, fov=None):
-    """The closed loop from views that are all unknown: the first look, then sense -> replan -> 5 ticks in steady state."""
+def sensing_loop(fl, views, cycles, states, goals, r_sense, fov=None, link=None):
+    """The closed loop from views that are all unknown: the first look, then sense -> [link ->] replan -> 5 ticks in steady state."""
     views.fill_(1)
     fl.init(states, goals)
     if fov is not None:
@@ -220,15 +231,19 @@ def sensing_loop(fl, views, cycles, states, goals, r_sense, fov=None):
     e1.record(fl.stream)
     fl.sync()
     first = e0.elapsed_time(e1)
+    if link:
+        fl.link(link)
     fl.replan()
     fl.next_goals(5)
     fl.sync()
-    med = timed_cycles(fl, cycles, r_sense, fov)
+    med = timed_cycles(fl, cycles, r_sense, fov, link=link)
     t = []
     for _ in range(cycles):
         fl.sync()
         t0 = time.perf_counter()
         fl.sense(r_sense, fov=fov)
+        if link:
+            fl.link(link)
         fl.replan()
         fl.next_goals(5)
         fl.sync()
@@ -267,6 +282,28 @@ def views_cycles(B, cycles, p, world, r_sense, staging, fov=None):
         if fov is not None:
             first, loop = sensing_loop(fl, views, cycles, states, goals, r_sense, fov)
             out["fov_sensing"] = dict(loop, sense_first_ms=first, tan_half_h=fov[0], tan_half_v=fov[1])
+        if LINK:
+            out["link"] = {"passes": abi.FH_LINK_DEFAULT_PASSES, "ranges": {}}
+            for r in LINK:
+                _, loop = sensing_loop(fl, views, cycles, states, goals, r_sense, link=r)
+                labels, info = fl.link_records()
+                loop.update({"changed_last_pass": int(info[0]), "groups": int(info[1]), "linked_pairs": int(info[2]),
+                             "largest_group": int(np.bincount(labels).max()), "link_ms": loop["stages_ms"]["link_groups"] + loop["stages_ms"]["link_merge"]})
+                out["link"]["ranges"]["%g" % r] = loop
+            # the yardstick of the merge: the views' bytes copied device to device on the fleet's stream, fenced the same way
+            other, ms = torch.empty_like(views), []
+            with torch.cuda.stream(fl.stream):
+                other.copy_(views)
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(fl.stream)
+                    other.copy_(views)
+                    e1.record(fl.stream)
+                    fl.sync()
+                    ms.append(e0.elapsed_time(e1))
+            out["link"]["views_copy_ms"] = float(np.median(ms))
+            for loop in out["link"]["ranges"].values():
+                loop["merge_over_copy"] = loop["stages_ms"]["link_merge"] / out["link"]["views_copy_ms"]
     finally:
         fl.close()
     return out
@@ -446,6 +483,9 @@ def main():
             else:
                 round_reach = float(argv[k + 1])
             del argv[k:k + 2]
+    if "--link" in argv:         # (read into LINK above)
+        k = argv.index("--link")
+        del argv[k:k + 2]
     if "--traffic-timed" in argv:
         k = argv.index("--traffic-timed")
         window = int(argv[k + 1])
