@@ -232,6 +232,26 @@ def default_link_params(range):  # noqa: A002  (the header's word)
     return p
 
 
+# fh_frontier_params, fh_frontier_record, fh_view_coverage: arrived vehicles take the nearest frontier voxel of their view as goal
+# (include/fasterhip_frontier.h)
+FH_FRONTIER_WANT_REACHED, FH_FRONTIER_WANT_NO_PATH, FH_FRONTIER_WANT_ALL = 1, 2, 4
+FH_FRONTIER_WANTED, FH_FRONTIER_FOUND, FH_FRONTIER_NO_VIEW, FH_FRONTIER_BAD_POS = 1, 2, 4, 8
+frontier_params_dtype = np.dtype([("r_max", "<f8"), ("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("want", "<i4"),
+                                  ("reserved", "<i4", (7,))], align=True)
+frontier_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("candidates", "<i4"), ("d2", "<f8"),
+                                  ("reserved", "<f8")], align=True)
+view_coverage_dtype = np.dtype([("known", "<i8"), ("frontier", "<i8")], align=True)
+assert (frontier_params_dtype.itemsize, frontier_record_dtype.itemsize, view_coverage_dtype.itemsize) == (64, 32, 16)
+
+
+def default_frontier_params(r_max):
+    """fh_frontier_params: the vehicles that have reached their goal look for the nearest frontier voxel nearer than r_max, at any
+    height, with no region around the old goal excluded."""
+    p = np.zeros((), dtype=frontier_params_dtype)
+    p["r_max"], p["r_avoid"], p["z_lo"], p["z_hi"], p["want"] = r_max, 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

@@ -50,6 +50,8 @@ ROUNDS_SYMBOLS = ["fh_fleet_round_classes_device", "fh_fleet_round_gate_device"]
 VIEW_SUBSET_SYMBOLS = ["fh_map_view_list_device", "fh_map_read_views_listed_device"]
 # include/fasterhip_link.h
 LINK_SYMBOLS = ["fh_fleet_link_groups_device", "fh_fleet_link_merge_device"]
+# include/fasterhip_frontier.h
+FRONTIER_SYMBOLS = ["fh_map_frontier_goals_device", "fh_map_view_coverage_device"]
 
 _LIB = None
 
@@ -319,6 +321,10 @@ def lib():
         L.fh_map_view_list_device.argtypes = [vp, vp, vp, i32, i32, vp, vp]
         L.fh_map_read_views_listed_device.restype = i32
         L.fh_map_read_views_listed_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, f64, vp, f64, f64, f64, vp, vp]
+        L.fh_map_frontier_goals_device.restype = i32
+        L.fh_map_frontier_goals_device.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, vp, vp]
+        L.fh_map_view_coverage_device.restype = i32
+        L.fh_map_view_coverage_device.argtypes = [vp, vp, vp, ctypes.c_size_t, i32, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -536,6 +542,23 @@ class Map:
         self._check(lib().fh_map_read_views_listed_device(self._h, d_cloud, int(n_cloud), d_point_mask, int(mask_words), int(n_views),
                                                           abi.ptr(cells), float(res), abi.ptr(center), float(z_ground), float(z_max),
                                                           float(inflation), d_list, d_count), "fh_map_read_views_listed_device")
+
+    def frontier_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_goals, d_mask, d_records):
+        """fh_map_frontier_goals_device (include/fasterhip_frontier.h): for every wanted vehicle the nearest voxel of its view that is
+        known, free in this map and next to unknown space, into d_goals [n][3] and d_mask [n] int32 — the shape
+        Context.fleet_set_goals_device takes — and d_records [n] abi.frontier_record_dtype.  par: one abi.frontier_params_dtype record;
+        grid = (origin, res, dims) of the views; d_view_of may be None.  Asynchronous on the map's stream."""
+        p = _one_record(par, "frontier", "frontier_goals_device")
+        g = _grid_record(grid)
+        self._check(lib().fh_map_frontier_goals_device(self._h, abi.ptr(p), None if g is None else abi.ptr(g), d_flags, int(view_stride), d_view_of,
+                                                       int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records), "fh_map_frontier_goals_device")
+
+    def view_coverage_device(self, grid, d_flags, view_stride, n_views, d_out):
+        """fh_map_view_coverage_device: d_out [n_views] abi.view_coverage_dtype, the known voxels (flag 0) of every view and those of
+        them that have an unknown face neighbour.  grid = (origin, res, dims); only the dims are read.  Asynchronous on the map's stream."""
+        g = _grid_record(grid)
+        self._check(lib().fh_map_view_coverage_device(self._h, None if g is None else abi.ptr(g), d_flags, int(view_stride), int(n_views), d_out),
+                    "fh_map_view_coverage_device")
 
     def view_occupancy(self, view):
         """The grid of one view as occupancy() gives the map's."""

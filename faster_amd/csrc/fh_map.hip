@@ -14,9 +14,11 @@
 #include "../../include/fasterhip.h"
 #include "../../include/fasterhip_occupancy.h"
 #include "../../include/fasterhip_view_subset.h"
+#include "../../include/fasterhip_frontier.h"
 #include "../host/jps_tables.hpp"
 #include "fh_path.hip.hpp"
 #include "fh_view_subset.hip.hpp"
+#include "fh_frontier.hip.hpp"
 #include "fh_host.hpp"
 
 struct fh_map {
@@ -642,6 +644,73 @@ int fh_map_read_views_listed_device(fh_map* m, const double* d_cloud_xyz, int n_
       hipLaunchKernelGGL(fhp::jps_table_views_listed_kernel, dim3((unsigned)((threads + 255) / 256), rows), dim3(256), 0, m->stream, mv,
                          m->d_jps_tables, m->view_entries.as<short>(), level, words, n_views, (const int*)d_list, (const int*)d_count);
     }
+  }
+  FM_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// include/fasterhip_frontier.h: the lattice of the views, judged the same way by both entry points (0: fine, cells filled in)
+static int frontier_lattice(const fh_voxel_grid* grid, bool with_res, size_t view_stride, int n_views, long long* cells) {
+  if (!grid || (with_res && !(grid->res > 0.0)) || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1) return FH_ERR_ARG;
+  // (each factor is below 2^31; the product of two fits 62 bits, and what is above the limit after two never comes back under it)
+  const long long xy = (long long)grid->dims[0] * grid->dims[1];
+  if (xy > 0x7fffffffll || xy * grid->dims[2] > 0x7fffffffll) return FH_ERR_ARG;
+  *cells = xy * grid->dims[2];
+  if (view_stride < (size_t)*cells) return FH_ERR_ARG;
+  if (n_views < 1) return FH_ERR_ARG;
+  return FH_OK;
+}
+
+// the nearest frontier voxel of its view for every vehicle that wants a goal, in the shape fh_fleet_set_goals_device takes
+int fh_map_frontier_goals_device(fh_map* m, const fh_frontier_params* par, const fh_voxel_grid* grid, const unsigned char* d_flags,
+                                 size_t view_stride, const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n,
+                                 double* d_goals, int32_t* d_mask, fh_frontier_record* d_records) {
+  if (!m || !m->have_map || !par) return FH_ERR_ARG;
+  if (!std::isfinite(par->r_max) || !(par->r_max > 0.0)) return FH_ERR_ARG;
+  if (!std::isfinite(par->r_avoid) || !(par->r_avoid >= 0.0)) return FH_ERR_ARG;
+  if (std::isnan(par->z_lo) || std::isnan(par->z_hi) || par->z_lo > par->z_hi) return FH_ERR_ARG;
+  const int all_wants = FH_FRONTIER_WANT_REACHED | FH_FRONTIER_WANT_NO_PATH | FH_FRONTIER_WANT_ALL;
+  if (par->want == 0 || (par->want & ~all_wants) != 0) return FH_ERR_ARG;
+  long long cells = 0;
+  if (frontier_lattice(grid, true, view_stride, n_views, &cells) != FH_OK) return FH_ERR_ARG;
+  if (n < 0) return FH_ERR_ARG;
+  if (n == 0) return FH_OK;
+  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  fhh::DeviceScope scope(m->device);
+  fhp::FrontierArgs a;
+  a.r_max = par->r_max;
+  a.r2 = par->r_max * par->r_max;
+  a.a2 = par->r_avoid * par->r_avoid;
+  a.z_lo = par->z_lo; a.z_hi = par->z_hi;
+  a.want = par->want;
+  a.nx = grid->dims[0]; a.ny = grid->dims[1]; a.nz = grid->dims[2];
+  a.res = grid->res; a.ox = grid->origin[0]; a.oy = grid->origin[1]; a.oz = grid->origin[2];
+  a.flags = d_flags; a.view_stride = view_stride; a.view_of = d_view_of; a.n_views = n_views;
+  a.vehicles = d_vehicles;
+  a.mx = m->nx; a.my = m->ny; a.mz = m->nz;
+  a.mres = m->res; a.mox = m->origin[0]; a.moy = m->origin[1]; a.moz = m->origin[2];
+  a.bits = m->bits.as<const unsigned>();
+  a.goals = d_goals; a.mask = d_mask; a.records = d_records;
+  hipLaunchKernelGGL(fhp::frontier_goals_kernel, dim3((unsigned)n), dim3(256), 0, m->stream, a);
+  FM_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// known and frontier voxels of every view: a memset and integer atomic adds
+int fh_map_view_coverage_device(fh_map* m, const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, int n_views,
+                                fh_view_coverage* d_out) {
+  if (!m) return FH_ERR_ARG;
+  long long cells = 0;
+  if (frontier_lattice(grid, false, view_stride, n_views, &cells) != FH_OK) return FH_ERR_ARG;
+  if (!d_flags || !d_out) return FH_ERR_ARG;
+  fhh::DeviceScope scope(m->device);
+  FM_HIP(hipMemsetAsync(d_out, 0, sizeof(fh_view_coverage) * (size_t)n_views, m->stream));
+  const long long chunks = (cells + 30) >> 4;  // (16-byte chunks aligned in memory: at most this many per row, wherever it begins)
+  const unsigned blocks = (unsigned)std::min<long long>((chunks + 255) / 256, fhp::VIEW_COVERAGE_BLOCKS);
+  for (int v0 = 0; v0 < n_views; v0 += 32768) {  // (the second grid dimension holds 65535 blocks)
+    const int nv = std::min(32768, n_views - v0);
+    hipLaunchKernelGGL(fhp::view_coverage_kernel, dim3(blocks, (unsigned)nv), dim3(256), 0, m->stream, d_flags, view_stride, grid->dims[0],
+                       grid->dims[1], grid->dims[2], v0, (unsigned long long*)d_out);
   }
   FM_HIP(hipGetLastError());
   return FH_OK;

@@ -39,6 +39,11 @@ group become equal, unknown voxels and occupied points alike, and the group plan
 
     sense -> observe -> link -> replan -> next_goals
 
+explore() closes the loop (include/fasterhip_frontier.h): a vehicle that has arrived takes the nearest voxel of its view that is known,
+free and next to unknown space as its new goal, on the device; coverage() counts what every view knows, so a loop can tell when it is done:
+
+    sense -> observe -> [link] -> explore -> replan -> next_goals
+
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
@@ -102,6 +107,7 @@ class Fleet:
         self.round_retries, self.round_fixed = 0, False
         self.listed_views, self._views_full, self.d_view_list, self.d_view_count = False, True, None, None   # enable_listed_views
         self.d_link_labels = self.d_link_info = None                                                           # link
+        self.d_explore_goals = self.d_explore_mask = self.d_explore_records = self.d_explore_view_of = self.d_coverage = None   # explore, coverage
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -544,6 +550,101 @@ class Fleet:
             raise capi.FasterHipError("Fleet.link_records: link first")
         self.sync()
         return self.d_link_labels.cpu().numpy().copy(), self.d_link_info.cpu().numpy().copy()
+
+    _EXPLORE_WANT = {"reached": abi.FH_FRONTIER_WANT_REACHED, "no_path": abi.FH_FRONTIER_WANT_NO_PATH, "all": abi.FH_FRONTIER_WANT_ALL}
+
+    def _explore_views(self):
+        """(flags tensor, view_stride, view_of pointer or None, n_views) of the frontier entry points: the views, or set_unknown's one
+        grid as a single view that every vehicle reads (an all-zero view_of)."""
+        if self.view_flags is not None:
+            return self.view_flags, int(self.view_flags.shape[1]), (None if self.view_of is None else self.view_of.data_ptr()), self.n_views
+        if self.flags is None:
+            raise capi.FasterHipError("Fleet.explore: set_unknown_views (or set_unknown) first")
+        t = self.torch
+        if self.d_explore_view_of is None:
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_explore_view_of = t.zeros(self.n, dtype=t.int32, device=self.dev)
+            self.d_explore_view_of.record_stream(self.stream)
+        return self.flags, int(self.flags.numel()), self.d_explore_view_of.data_ptr(), 1
+
+    def explore(self, r_max, r_avoid=None, z=None, want="reached"):
+        """The wanted vehicles take the nearest frontier voxel of their view as terminal goal (include/fasterhip_frontier.h): a voxel the
+        view knows, free in the map, nearer than r_max, with an unknown face neighbour.  want: "reached" (status GOAL_REACHED), "no_path"
+        (the last replan found no path), "all", or a tuple of them.  r_avoid: no voxel nearer than this to the goal the vehicle has (None:
+        params["goal_radius"]); z = (z_lo, z_hi) of the voxel centres, both inclusive (None: z_ground and the z_max of set_map).  Two
+        launches on the fleet's stream: frontier_goals into buffers of the fleet (explore_records()), then fh_fleet_set_goals_device with
+        that mask; a vehicle without a candidate keeps goal and status.  After sense(), observe() and link(), before replan(); needs
+        set_map and set_unknown_views (set_unknown's one grid counts as a single view of all vehicles), and, for "reached",
+        enable_heading: a vehicle that set_goals made YAWING leaves that status only in next_goals with headings."""
+        stages = self.explore_stages(r_max, r_avoid, z, want)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_stages(self, r_max, r_avoid=None, z=None, want="reached"):
+        """The two launches of explore(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        if self.cloud is None or self.map_args is None:
+            raise capi.FasterHipError("Fleet.explore: set_map first")
+        flags, stride, vo, n_views = self._explore_views()
+        wants = (want,) if isinstance(want, str) else tuple(want)
+        if not wants or any(w not in self._EXPLORE_WANT for w in wants):
+            raise capi.FasterHipError("Fleet.explore: want is \"reached\", \"no_path\", \"all\" or a tuple of them, got %r" % (want,))
+        if "reached" in wants and self.d_headings is None:
+            raise capi.FasterHipError("Fleet.explore: want=\"reached\" needs enable_heading first (a vehicle that takes a new goal after "
+                                      "GOAL_REACHED is YAWING until next_goals with headings has turned it)")
+        par = abi.default_frontier_params(r_max)
+        par["r_avoid"] = float(self.params["goal_radius"]) if r_avoid is None else r_avoid
+        par["z_lo"], par["z_hi"] = (self.z_ground, self.map_args[3]) if z is None else z
+        par["want"] = 0
+        for w in wants:
+            par["want"] |= self._EXPLORE_WANT[w]
+        if self.d_explore_goals is None:
+            t = self.torch
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_explore_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_explore_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_explore_records = t.zeros(self.n * abi.frontier_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            for d in (self.d_explore_goals, self.d_explore_mask, self.d_explore_records):
+                d.record_stream(self.stream)
+        c, m, p = self.ctx, self.map, (lambda t: t.data_ptr())
+        return [
+            ("frontier_goals", lambda: m.frontier_goals_device(par, self.grid, p(flags), stride, vo, n_views, p(self.d_vehicles), self.n,
+                                                               p(self.d_explore_goals), p(self.d_explore_mask), p(self.d_explore_records))),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_explore_goals), p(self.d_explore_mask),
+                                                           self.n)),
+        ]
+
+    def explore_records(self):
+        """(records [n] abi.frontier_record_dtype, goals [n][3], mask [n] int32) of the last explore() (synchronises)."""
+        if self.d_explore_goals is None:
+            raise capi.FasterHipError("Fleet.explore_records: explore first")
+        self.sync()
+        return (self.d_explore_records.cpu().numpy().view(abi.frontier_record_dtype).copy(), self.d_explore_goals.cpu().numpy().copy(),
+                self.d_explore_mask.cpu().numpy().copy())
+
+    def coverage_stages(self):
+        """The one launch of coverage(): [(name, callable)]."""
+        if self.grid is None:
+            raise capi.FasterHipError("Fleet.coverage: set_unknown_views (or set_unknown) first")
+        flags, stride, _, n_views = self._explore_views()
+        t = self.torch
+        if self.d_coverage is None or self.d_coverage.numel() != n_views * abi.view_coverage_dtype.itemsize:
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_coverage = t.zeros(n_views * abi.view_coverage_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            self.d_coverage.record_stream(self.stream)
+        return [("view_coverage", lambda: self.map.view_coverage_device(self.grid, flags.data_ptr(), stride, n_views, self.d_coverage.data_ptr()))]
+
+    def coverage(self):
+        """[n_views] abi.view_coverage_dtype: the known voxels of every view and its frontier voxels (fh_map_view_coverage_device; one
+        launch on the fleet's stream, then synchronises)."""
+        stages = self.coverage_stages()
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+        return self._host(self.d_coverage, abi.view_coverage_dtype)
 
     def point_masks(self):
         """[n_views][words] uint32 on the host (synchronises)."""

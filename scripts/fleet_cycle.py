@@ -49,7 +49,13 @@ carries the views listed per round and timed cycle ("views_listed_per_round").
 Fleet.link(RANGE) between sensing and the replan (sense -> link -> replan -> 5 ticks), "link_groups" and "link_merge" fenced as stages of
 their own; the passes, the groups (roots), the linked pairs and whether the labels settled in the last timed cycle; and, fenced the same
 way in the same run, a device-to-device copy of the views' bytes ("views_copy_ms": the yardstick of the merge) with the ratio of the two.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--explore R_MAX (with --views) adds "explore": the closed loop of --views from views that are all unknown, with headings, and
+Fleet.explore(R_MAX) between sensing and the replan (sense -> explore -> replan -> 5 ticks): "frontier_goals" (want = reached: the steady
+state, with the vehicles it wanted and found per timed cycle) and "set_goals" fenced as stages of their own; then, fenced the same way in
+the same run and applied to nobody, frontier_goals with every vehicle wanted ("frontier_goals_all_ms", with the vehicles that found a
+voxel and their candidates) and view_coverage ("view_coverage_ms"); and the known and the frontier voxels of the fleet after the first look
+and at the end.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -69,6 +75,7 @@ AUDIT = "--audit" in sys.argv
 SEPARATION = "--separation" in sys.argv
 LISTED_VIEWS = "--listed-views" in sys.argv
 LINK = [float(r) for r in sys.argv[sys.argv.index("--link") + 1].split(",")] if "--link" in sys.argv else []
+EXPLORE = float(sys.argv[sys.argv.index("--explore") + 1]) if "--explore" in sys.argv else None
 
 
 def timed_audit(fl, cycles):
@@ -257,6 +264,65 @@ def sensing_loop(fl, views, cycles, states, goals, r_sense, fov=None, link=None)
     return first, loop
 
 
+def fenced_ms(fl, launch, reps):
+    """`launch` `reps` times on the fleet's stream, each between two events: [ms]."""
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(fl.stream)
+        launch()
+        e1.record(fl.stream)
+        fl.sync()
+        ms.append(e0.elapsed_time(e1))
+    return ms
+
+
+def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
+    """The closed loop with Fleet.explore from views that are all unknown: see the module docstring."""
+    views.fill_(1)
+    fl.init(states, goals)
+    u = goals - states["pos"]
+    fl.enable_heading(yaw0=np.arctan2(u[:, 1], u[:, 0]))
+    fl.sense(r_sense)
+    first = fl.coverage()
+    fl.explore(r_max)
+    fl.replan()
+    fl.next_goals(5)
+    fl.sync()
+    explore = fl.explore_stages(r_max)
+    names = ["sense"] + [n for n, _ in explore] + [n for n, _ in fl.stages()] + ["next_goals"]
+    per, wanted, found = {n: [] for n in names}, [], []
+    for _ in range(cycles):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        ev[0].record(fl.stream)
+        fl.sense(r_sense)
+        ev[1].record(fl.stream)
+        for j, (_, launch) in enumerate(explore + fl.stages()):
+            launch()
+            ev[j + 2].record(fl.stream)
+        fl.next_goals(5)
+        ev[-1].record(fl.stream)
+        fl.sync()
+        for j, n in enumerate(names):
+            per[n].append(ev[j].elapsed_time(ev[j + 1]))
+        rec = fl.explore_records()[0]
+        wanted.append(int((rec["flags"] & abi.FH_FRONTIER_WANTED != 0).sum()))
+        found.append(int((rec["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()))
+    med = {n: float(np.median(v)) for n, v in per.items()}
+    # every vehicle wanted, applied to nobody: the one launch of frontier_goals; and the coverage
+    all_ms = fenced_ms(fl, fl.explore_stages(r_max, want="all")[0][1], max(cycles, 3))
+    rec = fl.explore_records()[0]
+    cov_ms = fenced_ms(fl, fl.coverage_stages()[0][1], max(cycles, 3))
+    last = fl.coverage()
+    return {"r_max": r_max, "stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "wanted_per_cycle": wanted, "found_per_cycle": found,
+            "frontier_goals_reached_ms": med["frontier_goals"], "frontier_goals_all_ms": float(np.median(all_ms)),
+            "frontier_goals_all_runs_ms": [float(x) for x in all_ms], "found_all": int((rec["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+            "candidates_all_mean": float(rec["candidates"].mean()), "view_coverage_ms": float(np.median(cov_ms)),
+            "view_coverage_runs_ms": [float(x) for x in cov_ms],
+            "known_first": int(first["known"].sum()), "frontier_first": int(first["frontier"].sum()),
+            "known_last": int(last["known"].sum()), "frontier_last": int(last["frontier"].sum())}
+
+
 def views_cycles(B, cycles, p, world, r_sense, staging, fov=None):
     """The cycle with a view per vehicle: see the module docstring."""
     cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims = world
@@ -304,6 +370,8 @@ def views_cycles(B, cycles, p, world, r_sense, staging, fov=None):
             out["link"]["views_copy_ms"] = float(np.median(ms))
             for loop in out["link"]["ranges"].values():
                 loop["merge_over_copy"] = loop["stages_ms"]["link_merge"] / out["link"]["views_copy_ms"]
+        if EXPLORE is not None:
+            out["explore"] = explore_loop(fl, views, cycles, states, goals, r_sense, EXPLORE)
     finally:
         fl.close()
     return out
@@ -485,6 +553,9 @@ def main():
             del argv[k:k + 2]
     if "--link" in argv:         # (read into LINK above)
         k = argv.index("--link")
+        del argv[k:k + 2]
+    if "--explore" in argv:      # (read into EXPLORE above)
+        k = argv.index("--explore")
         del argv[k:k + 2]
     if "--traffic-timed" in argv:
         k = argv.index("--traffic-timed")
