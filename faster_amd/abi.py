@@ -252,6 +252,24 @@ def default_frontier_params(r_max):
     return p
 
 
+# fh_reach_params, fh_reach_record: the frontier voxel that a flood of known free space reaches in the fewest steps
+# (include/fasterhip_reach.h); the record's flags are FH_FRONTIER_WANTED .. BAD_POS and these
+FH_REACH_START_OUTSIDE, FH_REACH_BOX_TOO_LARGE, FH_REACH_CUT = 16, 32, 64
+FH_REACH_MAX_WORDS = 1024
+reach_params_dtype = np.dtype([("r_max", "<f8"), ("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                               ("reserved", "<i4", (6,))], align=True)
+reach_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("hops", "<i4"), ("candidates", "<i4"),
+                               ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("d2", "<f8"), ("reserved", "<f8")], align=True)
+assert (reach_params_dtype.itemsize, reach_record_dtype.itemsize) == (64, 48)
+
+
+def default_reach_params(r_max):
+    """fh_reach_params: default_frontier_params with no limit on the levels of the flood."""
+    p = np.zeros((), dtype=reach_params_dtype)
+    p["r_max"], p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"] = r_max, 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SO = os.path.join(HERE, "libfasterhip.so")
 SOURCES = [os.path.join(HERE, "csrc", "fh_capi.hip"), os.path.join(HERE, "csrc", "fh_pool.hip"),
-           os.path.join(HERE, "csrc", "fh_map.hip")]
+           os.path.join(HERE, "csrc", "fh_map.hip"), os.path.join(HERE, "csrc", "fh_reach.hip")]
 import glob  # noqa: E402
 
 DEPS = SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + [os.path.join(ROOT, "include", "fasterhip.h"),
@@ -21,7 +21,8 @@ DEPS = SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + [os.pa
                                                                                     os.path.join(ROOT, "include", "fasterhip_rounds.h"),
                                                                                     os.path.join(ROOT, "include", "fasterhip_view_subset.h"),
                                                                                     os.path.join(ROOT, "include", "fasterhip_link.h"),
-                                                                                    os.path.join(ROOT, "include", "fasterhip_frontier.h")]
+                                                                                    os.path.join(ROOT, "include", "fasterhip_frontier.h"),
+                                                                                    os.path.join(ROOT, "include", "fasterhip_reach.h")]
 HOST_SO = os.path.join(HERE, "libsolverhip.so")
 HOST_SOURCES = [os.path.join(HERE, "host", "solver_hip.cpp"), os.path.join(HERE, "host", "decomp_hip.cpp"),
                 os.path.join(HERE, "host", "jps_hip.cpp"), os.path.join(HERE, "host", "corridor_frontend.cpp")]  # (JpsHip searches ONE query on the host)

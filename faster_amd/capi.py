@@ -52,6 +52,8 @@ VIEW_SUBSET_SYMBOLS = ["fh_map_view_list_device", "fh_map_read_views_listed_devi
 LINK_SYMBOLS = ["fh_fleet_link_groups_device", "fh_fleet_link_merge_device"]
 # include/fasterhip_frontier.h
 FRONTIER_SYMBOLS = ["fh_map_frontier_goals_device", "fh_map_view_coverage_device"]
+# include/fasterhip_reach.h
+REACH_SYMBOLS = ["fh_reach_goals_device"]
 
 _LIB = None
 
@@ -325,6 +327,8 @@ def lib():
         L.fh_map_frontier_goals_device.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, vp, vp]
         L.fh_map_view_coverage_device.restype = i32
         L.fh_map_view_coverage_device.argtypes = [vp, vp, vp, ctypes.c_size_t, i32, vp]
+        L.fh_reach_goals_device.restype = i32
+        L.fh_reach_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -552,6 +556,22 @@ class Map:
         g = _grid_record(grid)
         self._check(lib().fh_map_frontier_goals_device(self._h, abi.ptr(p), None if g is None else abi.ptr(g), d_flags, int(view_stride), d_view_of,
                                                        int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records), "fh_map_frontier_goals_device")
+
+    def reach_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_goals, d_mask, d_records, stream):
+        """fh_reach_goals_device (include/fasterhip_reach.h) with this map's lattice and bits (fh_map_dims,
+        fh_map_occupancy_bits_device): frontier_goals_device, but of the candidates the one that a flood of known free space from the
+        vehicle's voxel reaches in the fewest steps, and never one it does not reach.  d_records [n] abi.reach_record_dtype; par: one
+        abi.reach_params_dtype record; `stream`: the stream the map was filled on (an integer handle, 0 or None: the default stream)."""
+        p = _one_record(par, "reach", "reach_goals_device")
+        g = _grid_record(grid)
+        dims, origin = self.dims()
+        bits, res = ctypes.c_void_p(), ctypes.c_double()
+        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
+        mg = _grid_record((origin, res.value, dims))
+        rc = lib().fh_reach_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
+                                         d_view_of, int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records)
+        if rc != 0:
+            raise FasterHipError("fh_reach_goals_device: rc=%d" % rc)
 
     def view_coverage_device(self, grid, d_flags, view_stride, n_views, d_out):
         """fh_map_view_coverage_device: d_out [n_views] abi.view_coverage_dtype, the known voxels (flag 0) of every view and those of

@@ -44,6 +44,9 @@ free and next to unknown space as its new goal, on the device; coverage() counts
 
     sense -> observe -> [link] -> explore -> replan -> next_goals
 
+explore_reachable() stands in explore()'s place (include/fasterhip_reach.h): of those voxels the one that a flood of the space the view
+knows to be free reaches in the fewest steps, never one behind a wall or in a sealed pocket.
+
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
@@ -108,6 +111,7 @@ class Fleet:
         self.listed_views, self._views_full, self.d_view_list, self.d_view_count = False, True, None, None   # enable_listed_views
         self.d_link_labels = self.d_link_info = None                                                           # link
         self.d_explore_goals = self.d_explore_mask = self.d_explore_records = self.d_explore_view_of = self.d_coverage = None   # explore, coverage
+        self.d_reach_goals = self.d_reach_mask = self.d_reach_records = self.d_reach_view_of = None                            # explore_reachable
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -623,6 +627,70 @@ class Fleet:
         self.sync()
         return (self.d_explore_records.cpu().numpy().view(abi.frontier_record_dtype).copy(), self.d_explore_goals.cpu().numpy().copy(),
                 self.d_explore_mask.cpu().numpy().copy())
+
+    def explore_reachable(self, r_max, r_avoid=None, z=None, want="reached", max_hops=0):
+        """explore() with the choice of include/fasterhip_reach.h: of the frontier voxels of explore() the one that a flood of the space
+        the view knows to be free, from the voxel the vehicle stands in and over the box of its sphere, reaches in the fewest steps (six
+        neighbours; then the smallest distance), and never one the flood does not reach: a voxel behind a wall or in a sealed pocket is
+        not chosen, so the replan that follows is not spent on NO_PATH.  max_hops: the last level of the flood, 0 for no limit.  The
+        other arguments, the preconditions and the two launches are those of explore(); the buffers are its own (reach_records())."""
+        stages = self.explore_reachable_stages(r_max, r_avoid, z, want, max_hops)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_reachable_stages(self, r_max, r_avoid=None, z=None, want="reached", max_hops=0):
+        """The two launches of explore_reachable(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        if self.cloud is None or self.map_args is None:
+            raise capi.FasterHipError("Fleet.explore_reachable: set_map first")
+        if self.view_flags is not None:
+            flags, stride, vo, n_views = self.view_flags, int(self.view_flags.shape[1]), (None if self.view_of is None else self.view_of.data_ptr()), self.n_views
+        elif self.flags is None:
+            raise capi.FasterHipError("Fleet.explore_reachable: set_unknown_views (or set_unknown) first")
+        else:   # set_unknown's one grid: a single view that every vehicle reads (an all-zero view_of)
+            if self.d_reach_view_of is None:
+                t = self.torch
+                self._follow_current()
+                with t.cuda.stream(self.stream):
+                    self.d_reach_view_of = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_reach_view_of.record_stream(self.stream)
+            flags, stride, vo, n_views = self.flags, int(self.flags.numel()), self.d_reach_view_of.data_ptr(), 1
+        wants = (want,) if isinstance(want, str) else tuple(want)
+        if not wants or any(w not in self._EXPLORE_WANT for w in wants):
+            raise capi.FasterHipError("Fleet.explore_reachable: want is \"reached\", \"no_path\", \"all\" or a tuple of them, got %r" % (want,))
+        if "reached" in wants and self.d_headings is None:
+            raise capi.FasterHipError("Fleet.explore_reachable: want=\"reached\" needs enable_heading first (a vehicle that takes a new goal "
+                                      "after GOAL_REACHED is YAWING until next_goals with headings has turned it)")
+        par = abi.default_reach_params(r_max)
+        par["r_avoid"] = float(self.params["goal_radius"]) if r_avoid is None else r_avoid
+        par["z_lo"], par["z_hi"] = (self.z_ground, self.map_args[3]) if z is None else z
+        par["want"], par["max_hops"] = 0, max_hops
+        for w in wants:
+            par["want"] |= self._EXPLORE_WANT[w]
+        if self.d_reach_goals is None:
+            t = self.torch
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_reach_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_reach_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_reach_records = t.zeros(self.n * abi.reach_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            for d in (self.d_reach_goals, self.d_reach_mask, self.d_reach_records):
+                d.record_stream(self.stream)
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("reach_goals", lambda: m.reach_goals_device(par, self.grid, p(flags), stride, vo, n_views, p(self.d_vehicles), self.n,
+                                                         p(self.d_reach_goals), p(self.d_reach_mask), p(self.d_reach_records),
+                                                         self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_reach_goals), p(self.d_reach_mask), self.n)),
+        ]
+
+    def reach_records(self):
+        """(records [n] abi.reach_record_dtype, goals [n][3], mask [n] int32) of the last explore_reachable() (synchronises)."""
+        if self.d_reach_goals is None:
+            raise capi.FasterHipError("Fleet.reach_records: explore_reachable first")
+        self.sync()
+        return (self.d_reach_records.cpu().numpy().view(abi.reach_record_dtype).copy(), self.d_reach_goals.cpu().numpy().copy(),
+                self.d_reach_mask.cpu().numpy().copy())
 
     def coverage_stages(self):
         """The one launch of coverage(): [(name, callable)]."""

@@ -55,7 +55,11 @@ state, with the vehicles it wanted and found per timed cycle) and "set_goals" fe
 the same run and applied to nobody, frontier_goals with every vehicle wanted ("frontier_goals_all_ms", with the vehicles that found a
 voxel and their candidates) and view_coverage ("view_coverage_ms"); and the known and the frontier voxels of the fleet after the first look
 and at the end.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--reach (with --views --explore R_MAX) runs that loop with Fleet.explore_reachable in the place of Fleet.explore (include/fasterhip_reach.h):
+the stage is reported under its name, "reach_goals", and with every vehicle wanted as "reach_goals_all_ms", beside frontier_goals with
+every vehicle wanted in the same run; and, of that launch, the levels of the flood (mean, max), the voxels reached and the candidates
+reachable per searched vehicle, and the vehicles whose box was too large.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -76,6 +80,9 @@ SEPARATION = "--separation" in sys.argv
 LISTED_VIEWS = "--listed-views" in sys.argv
 LINK = [float(r) for r in sys.argv[sys.argv.index("--link") + 1].split(",")] if "--link" in sys.argv else []
 EXPLORE = float(sys.argv[sys.argv.index("--explore") + 1]) if "--explore" in sys.argv else None
+REACH = "--reach" in sys.argv
+if REACH and not ("--views" in sys.argv and EXPLORE is not None):
+    sys.exit("--reach needs --views --explore R_MAX")
 
 
 def timed_audit(fl, cycles):
@@ -285,11 +292,13 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     fl.enable_heading(yaw0=np.arctan2(u[:, 1], u[:, 0]))
     fl.sense(r_sense)
     first = fl.coverage()
-    fl.explore(r_max)
+    goal_stage = "reach_goals" if REACH else "frontier_goals"
+    explore_stages, explore_records = (fl.explore_reachable_stages, fl.reach_records) if REACH else (fl.explore_stages, fl.explore_records)
+    (fl.explore_reachable if REACH else fl.explore)(r_max)
     fl.replan()
     fl.next_goals(5)
     fl.sync()
-    explore = fl.explore_stages(r_max)
+    explore = explore_stages(r_max)
     names = ["sense"] + [n for n, _ in explore] + [n for n, _ in fl.stages()] + ["next_goals"]
     per, wanted, found = {n: [] for n in names}, [], []
     for _ in range(cycles):
@@ -305,7 +314,7 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
         fl.sync()
         for j, n in enumerate(names):
             per[n].append(ev[j].elapsed_time(ev[j + 1]))
-        rec = fl.explore_records()[0]
+        rec = explore_records()[0]
         wanted.append(int((rec["flags"] & abi.FH_FRONTIER_WANTED != 0).sum()))
         found.append(int((rec["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()))
     med = {n: float(np.median(v)) for n, v in per.items()}
@@ -314,8 +323,23 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     rec = fl.explore_records()[0]
     cov_ms = fenced_ms(fl, fl.coverage_stages()[0][1], max(cycles, 3))
     last = fl.coverage()
-    return {"r_max": r_max, "stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "wanted_per_cycle": wanted, "found_per_cycle": found,
-            "frontier_goals_reached_ms": med["frontier_goals"], "frontier_goals_all_ms": float(np.median(all_ms)),
+    reach = {}
+    if REACH:   # every vehicle wanted, applied to nobody, as frontier_goals above
+        reach_ms = fenced_ms(fl, explore_stages(r_max, want="all")[0][1], max(cycles, 3))
+        rr = explore_records()[0]
+        hit = (rr["flags"] & (abi.FH_REACH_START_OUTSIDE | abi.FH_REACH_BOX_TOO_LARGE | abi.FH_FRONTIER_NO_VIEW | abi.FH_FRONTIER_BAD_POS)) == 0
+        reach = {"reach_goals_reached_ms": med["reach_goals"], "reach_goals_all_ms": float(np.median(reach_ms)),
+                 "reach_goals_all_runs_ms": [float(x) for x in reach_ms], "reach_found_all": int((rr["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                 "reach_searched_all": int(hit.sum()), "reach_box_too_large": int((rr["flags"] & abi.FH_REACH_BOX_TOO_LARGE != 0).sum()),
+                 "reach_start_outside": int((rr["flags"] & abi.FH_REACH_START_OUTSIDE != 0).sum()),
+                 "levels_mean": float(rr["levels"][hit].mean()) if hit.any() else 0.0, "levels_max": int(rr["levels"].max()),
+                 "reached_mean": float(rr["reached"][hit].mean()) if hit.any() else 0.0, "reached_max": int(rr["reached"].max()),
+                 "hops_mean": float(rr["hops"][rr["hops"] >= 0].mean()) if (rr["hops"] >= 0).any() else -1.0,
+                 "candidates_mean": float(rr["candidates"][hit].mean()) if hit.any() else 0.0,
+                 "reachable_mean": float(rr["reachable"][hit].mean()) if hit.any() else 0.0,
+                 "same_cell_as_frontier_goals": int((rr["cell"] == rec["cell"]).sum())}
+    return {"r_max": r_max, "goal_stage": goal_stage, **reach, "stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "wanted_per_cycle": wanted, "found_per_cycle": found,
+            "frontier_goals_reached_ms": med.get("frontier_goals"), "frontier_goals_all_ms": float(np.median(all_ms)),
             "frontier_goals_all_runs_ms": [float(x) for x in all_ms], "found_all": int((rec["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
             "candidates_all_mean": float(rec["candidates"].mean()), "view_coverage_ms": float(np.median(cov_ms)),
             "view_coverage_runs_ms": [float(x) for x in cov_ms],
@@ -557,6 +581,8 @@ def main():
     if "--explore" in argv:      # (read into EXPLORE above)
         k = argv.index("--explore")
         del argv[k:k + 2]
+    if "--reach" in argv:        # (read into REACH above)
+        argv.remove("--reach")
     if "--traffic-timed" in argv:
         k = argv.index("--traffic-timed")
         window = int(argv[k + 1])
