@@ -270,6 +270,26 @@ def default_reach_params(r_max):
     return p
 
 
+# fh_spread_params, fh_spread_record: the chooser of fasterhip_reach.h for a team, goals claimed by peers avoided
+# (include/fasterhip_spread.h); the record's flags are those of fh_reach_record and these
+FH_SPREAD_OVERFLOW, FH_SPREAD_UNSETTLED, FH_SPREAD_CLAIMED = 128, 256, 512
+FH_SPREAD_LIST, FH_SPREAD_MAX_PASSES, FH_SPREAD_DEFAULT_PASSES = 32, 64, 8
+spread_params_dtype = np.dtype([("r_max", "<f8"), ("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                                ("r_spread", "<f8"), ("passes", "<i4"), ("reserved", "<i4", (7,))], align=True)
+spread_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("hops", "<i4"), ("candidates", "<i4"),
+                                ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("d2", "<f8"), ("group", "<i4"),
+                                ("decided_pass", "<i4"), ("lower", "<i4"), ("claims", "<i4"), ("claimed", "<i4"), ("reserved", "<i4")], align=True)
+assert (spread_params_dtype.itemsize, spread_record_dtype.itemsize) == (80, 64)
+
+
+def default_spread_params(r_max, r_spread):
+    """fh_spread_params: default_reach_params, no candidate nearer than r_spread to a peer's goal, FH_SPREAD_DEFAULT_PASSES passes."""
+    p = np.zeros((), dtype=spread_params_dtype)
+    p["r_max"], p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"] = r_max, 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0
+    p["r_spread"], p["passes"] = r_spread, FH_SPREAD_DEFAULT_PASSES
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

@@ -54,6 +54,8 @@ LINK_SYMBOLS = ["fh_fleet_link_groups_device", "fh_fleet_link_merge_device"]
 FRONTIER_SYMBOLS = ["fh_map_frontier_goals_device", "fh_map_view_coverage_device"]
 # include/fasterhip_reach.h
 REACH_SYMBOLS = ["fh_reach_goals_device"]
+# include/fasterhip_spread.h
+SPREAD_SYMBOLS = ["fh_spread_work_bytes", "fh_spread_goals_device"]
 
 _LIB = None
 
@@ -329,6 +331,10 @@ def lib():
         L.fh_map_view_coverage_device.argtypes = [vp, vp, vp, ctypes.c_size_t, i32, vp]
         L.fh_reach_goals_device.restype = i32
         L.fh_reach_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, vp, vp]
+        L.fh_spread_work_bytes.restype = ctypes.c_size_t
+        L.fh_spread_work_bytes.argtypes = [i32]
+        L.fh_spread_goals_device.restype = i32
+        L.fh_spread_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -572,6 +578,24 @@ class Map:
                                          d_view_of, int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records)
         if rc != 0:
             raise FasterHipError("fh_reach_goals_device: rc=%d" % rc)
+
+    def spread_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_group, d_vehicles, n, d_work, work_bytes, d_goals, d_mask,
+                            d_records, stream):
+        """fh_spread_goals_device (include/fasterhip_spread.h) with this map's lattice and bits: reach_goals_device for a team — a
+        candidate nearer than par["r_spread"] to the goal a peer holds, or that a peer with a lower index was given by an earlier pass,
+        is not chosen.  Peers: the vehicles with equal d_group[view] (d_group [n_views] int32, None: the view itself).  d_work:
+        work_bytes >= fh_spread_work_bytes(n) of device memory; d_records [n] abi.spread_record_dtype; par: one
+        abi.spread_params_dtype record; `stream` as for reach_goals_device."""
+        p = _one_record(par, "spread", "spread_goals_device")
+        g = _grid_record(grid)
+        dims, origin = self.dims()
+        bits, res = ctypes.c_void_p(), ctypes.c_double()
+        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
+        mg = _grid_record((origin, res.value, dims))
+        rc = lib().fh_spread_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
+                                          d_view_of, int(n_views), d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
+        if rc != 0:
+            raise FasterHipError("fh_spread_goals_device: rc=%d" % rc)
 
     def view_coverage_device(self, grid, d_flags, view_stride, n_views, d_out):
         """fh_map_view_coverage_device: d_out [n_views] abi.view_coverage_dtype, the known voxels (flag 0) of every view and those of

@@ -1,13 +1,16 @@
 // fh_reach.hip — host side of include/fasterhip_reach.h (fh_reach_goals_device): the frontier voxel that a flood of the space a vehicle
-// knows to be free reaches in the fewest steps (kernel: fh_reach.hip.hpp).  A translation unit of its own: fh_map.hip and fh_capi.hip,
-// their kernels and their code objects are what they were.  No CPU fallback.
+// knows to be free reaches in the fewest steps (kernel: fh_reach.hip.hpp), and of include/fasterhip_spread.h (fh_spread_goals_device):
+// that chooser for a team, goals claimed by peers avoided (kernels: fh_spread.hip.hpp).  A translation unit of its own: fh_map.hip and
+// fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/fasterhip.h"
 #include "../../include/fasterhip_reach.h"
+#include "../../include/fasterhip_spread.h"
 #include "fh_reach.hip.hpp"
+#include "fh_spread.hip.hpp"
 #include "fh_host.hpp"
 
 // the lattice of the views, judged as fh_map_frontier_goals_device judges it (0: fine, cells filled in)
@@ -22,18 +25,15 @@ static int reach_lattice(const fh_voxel_grid* grid, size_t view_stride, int n_vi
   return FH_OK;
 }
 
-extern "C" {
-
-int fh_reach_goals_device(void* stream, const fh_reach_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
-                          const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
-                          const fh_vehicle* d_vehicles, int n, double* d_goals, int32_t* d_mask, fh_reach_record* d_records) {
-  if (!par) return FH_ERR_ARG;
-  if (!std::isfinite(par->r_max) || !(par->r_max > 0.0)) return FH_ERR_ARG;
-  if (!std::isfinite(par->r_avoid) || !(par->r_avoid >= 0.0)) return FH_ERR_ARG;
-  if (std::isnan(par->z_lo) || std::isnan(par->z_hi) || par->z_lo > par->z_hi) return FH_ERR_ARG;
+// the clauses of fh_reach_goals_device from r_max to n < 0, in the header's order (both entry points; their params share these fields)
+static int reach_clauses(double r_max, double r_avoid, double z_lo, double z_hi, int want, int max_hops, const fh_voxel_grid* map_grid,
+                         const unsigned* d_map_bits, const fh_voxel_grid* grid, size_t view_stride, int n_views, int n) {
+  if (!std::isfinite(r_max) || !(r_max > 0.0)) return FH_ERR_ARG;
+  if (!std::isfinite(r_avoid) || !(r_avoid >= 0.0)) return FH_ERR_ARG;
+  if (std::isnan(z_lo) || std::isnan(z_hi) || z_lo > z_hi) return FH_ERR_ARG;
   const int all_wants = FH_FRONTIER_WANT_REACHED | FH_FRONTIER_WANT_NO_PATH | FH_FRONTIER_WANT_ALL;
-  if (par->want == 0 || (par->want & ~all_wants) != 0) return FH_ERR_ARG;
-  if (par->max_hops < 0) return FH_ERR_ARG;
+  if (want == 0 || (want & ~all_wants) != 0) return FH_ERR_ARG;
+  if (max_hops < 0) return FH_ERR_ARG;
   if (!fhh::voxel_grid_ok(map_grid)) return FH_ERR_ARG;
   const long long map_xy = (long long)map_grid->dims[0] * map_grid->dims[1];
   if (map_xy > 0x7fffffffll || map_xy * map_grid->dims[2] > 0x7fffffffll) return FH_ERR_ARG;
@@ -41,6 +41,39 @@ int fh_reach_goals_device(void* stream, const fh_reach_params* par, const fh_vox
   long long cells = 0;
   if (reach_lattice(grid, view_stride, n_views, &cells) != FH_OK) return FH_ERR_ARG;
   if (n < 0) return FH_ERR_ARG;
+  return FH_OK;
+}
+
+// the kernel's arguments from checked values (the outputs are the caller's to set)
+static void reach_args(fhp::ReachArgs& a, double r_max, double r_avoid, double z_lo, double z_hi, int want, int max_hops,
+                       const fh_voxel_grid* map_grid, const unsigned* d_map_bits, const fh_voxel_grid* grid, const unsigned char* d_flags,
+                       size_t view_stride, const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles) {
+  a.r_max = r_max;
+  a.r2 = r_max * r_max;
+  a.a2 = r_avoid * r_avoid;
+  a.z_lo = z_lo; a.z_hi = z_hi;
+  a.want = want;
+  a.max_hops = max_hops;
+  fhh::set_lattice(a, *grid);
+  a.flags = d_flags; a.view_stride = view_stride; a.view_of = d_view_of; a.n_views = n_views;
+  a.vehicles = d_vehicles;
+  a.mx = map_grid->dims[0]; a.my = map_grid->dims[1]; a.mz = map_grid->dims[2];
+  a.mres = map_grid->res; a.mox = map_grid->origin[0]; a.moy = map_grid->origin[1]; a.moz = map_grid->origin[2];
+  a.bits = d_map_bits;
+}
+
+// the class bytes, rounded up to a multiple of 64, before the rows
+static size_t spread_rows_offset(int n) { return ((size_t)n + 63) & ~(size_t)63; }
+
+extern "C" {
+
+int fh_reach_goals_device(void* stream, const fh_reach_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                          const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                          const fh_vehicle* d_vehicles, int n, double* d_goals, int32_t* d_mask, fh_reach_record* d_records) {
+  if (!par) return FH_ERR_ARG;
+  if (reach_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, view_stride, n_views,
+                    n) != FH_OK)
+    return FH_ERR_ARG;
   if (n == 0) return FH_OK;
   if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
   hipPointerAttribute_t where;
@@ -51,20 +84,56 @@ int fh_reach_goals_device(void* stream, const fh_reach_params* par, const fh_vox
   fhh::DeviceScope scope(where.device);
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::ReachArgs a;
-  a.r_max = par->r_max;
-  a.r2 = par->r_max * par->r_max;
-  a.a2 = par->r_avoid * par->r_avoid;
-  a.z_lo = par->z_lo; a.z_hi = par->z_hi;
-  a.want = par->want;
-  a.max_hops = par->max_hops;
-  fhh::set_lattice(a, *grid);
-  a.flags = d_flags; a.view_stride = view_stride; a.view_of = d_view_of; a.n_views = n_views;
-  a.vehicles = d_vehicles;
-  a.mx = map_grid->dims[0]; a.my = map_grid->dims[1]; a.mz = map_grid->dims[2];
-  a.mres = map_grid->res; a.mox = map_grid->origin[0]; a.moy = map_grid->origin[1]; a.moz = map_grid->origin[2];
-  a.bits = d_map_bits;
+  reach_args(a, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
+             d_view_of, n_views, d_vehicles);
   a.goals = d_goals; a.mask = d_mask; a.records = d_records;
   hipLaunchKernelGGL(fhp::reach_goals_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
+}
+
+size_t fh_spread_work_bytes(int n) { return n <= 0 ? 0 : spread_rows_offset(n) + (size_t)n * FH_SPREAD_LIST * sizeof(int32_t); }
+
+int fh_spread_goals_device(void* stream, const fh_spread_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                           const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                           const int32_t* d_group, const fh_vehicle* d_vehicles, int n, void* d_work, size_t work_bytes, double* d_goals,
+                           int32_t* d_mask, fh_spread_record* d_records) {
+  if (!par) return FH_ERR_ARG;
+  if (reach_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, view_stride, n_views,
+                    n) != FH_OK)
+    return FH_ERR_ARG;
+  if (!std::isfinite(par->r_spread) || !(par->r_spread > 0.0)) return FH_ERR_ARG;
+  if (par->passes < 1 || par->passes > FH_SPREAD_MAX_PASSES) return FH_ERR_ARG;
+  if (n == 0) return FH_OK;
+  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  if (!d_work) return FH_ERR_ARG;
+  if (work_bytes < fh_spread_work_bytes(n)) return FH_ERR_ARG;
+  hipPointerAttribute_t where;
+  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  fhh::DeviceScope scope(where.device);
+  if (!scope.ok) return FH_ERR_DEVICE;
+  fhp::SpreadArgs s;
+  reach_args(s.r, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
+             d_view_of, n_views, d_vehicles);
+  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
+  const double reach = (par->r_max + par->r_max) + par->r_spread, near = par->r_max + par->r_spread;
+  s.s2 = par->r_spread * par->r_spread;
+  s.reach2 = reach * reach;
+  s.near2 = near * near;
+  s.n = n; s.pass = 0;
+  s.group = d_group;
+  s.cls = static_cast<unsigned char*>(d_work);
+  s.rows = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(d_work) + spread_rows_offset(n));
+  s.records = d_records;
+  const hipStream_t q = (hipStream_t)stream;
+  hipLaunchKernelGGL(fhp::spread_class_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, s);
+  hipLaunchKernelGGL(fhp::spread_peers_kernel, dim3((unsigned)n), dim3(64), 0, q, s);
+  for (int p = 1; p <= par->passes; p++) {
+    s.pass = p;
+    hipLaunchKernelGGL(fhp::spread_goals_kernel, dim3((unsigned)n), dim3(256), 0, q, s);
+  }
   return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
 }
 

@@ -2,6 +2,8 @@
 // frontier voxel of its view that a flood of known free space reaches in the fewest steps.  Included by fh_reach.hip only.
 //   reach_goals_kernel : ONE workgroup of 256 per vehicle.  Status, stage, view and the six coordinates are read as uniform values; a
 //                        vehicle that is not searched has its three outputs written by thread 0 and the workgroup returns.
+//                        Its body is reach_body<CLAIMS>: reach_body<false> is this kernel, reach_body<true> the pass kernel of
+//                        fh_spread.hip.hpp, in which the build also leaves out the candidates near a peer's goal.
 //     build   A wavefront takes a row (iy, iz) of the box, lanes along x, one coalesced flag byte per lane; what depends on the row
 //             alone — the z test, dy dy, dz dz, the map's row — is computed once per row, with the float expressions of
 //             frontier_goals_kernel (fh_frontier.hip.hpp), so the candidates are its candidates.  The 64 predicates of a row segment
@@ -85,7 +87,14 @@ __device__ __forceinline__ void reach_store(const ReachArgs& a, int i, int flags
   a.records[i] = r;
 }
 
-__global__ void __launch_bounds__(256) reach_goals_kernel(ReachArgs a) {
+struct ReachNoClaims {};  // the X of reach_body<false>: nothing is read from it
+
+// The body of reach_goals_kernel, and with CLAIMS of the pass kernel of fh_spread.hip.hpp (include/fasterhip_spread.h): there x holds
+// x.count points x.pts[3 j ..] in LDS (uniform; written before a barrier that every thread has passed), x.s2, four LDS ints x.sum, and
+// x.store writes the outputs.  A candidate with s2 < x.s2 to one of the points is CLAIMED: counted, and left out of `cand`.
+// With CLAIMS false every `if constexpr` below is gone and the code is what the kernel held before it was a template.
+template <bool CLAIMS, class X>
+__device__ __forceinline__ void reach_body(const ReachArgs& a, const X& x) {
 #pragma clang fp contract(off)
   __shared__ unsigned long long s_pass[REACH_WORDS], s_cand[REACH_WORDS], s_a[REACH_WORDS], s_b[REACH_WORDS];
   __shared__ double s_d2[4];
@@ -103,13 +112,19 @@ __global__ void __launch_bounds__(256) reach_goals_kernel(ReachArgs a) {
   int flags = (wanted ? FH_FRONTIER_WANTED : 0) | (view >= 0 && view < a.n_views ? 0 : FH_FRONTIER_NO_VIEW) | (finite ? 0 : FH_FRONTIER_BAD_POS);
   const ReachCounts none = {-1, 0, 0, 0, 0};
   if (flags != FH_FRONTIER_WANTED) {  // not eligible (uniform over the workgroup)
-    if (t == 0) reach_store(a, i, flags, view, -1, INFINITY, none);
+    if (t == 0) {
+      if constexpr (CLAIMS) x.store(a, i, flags, view, -1, INFINITY, none, 0);
+      else reach_store(a, i, flags, view, -1, INFINITY, none);
+    }
     return;
   }
   // the start cell, tested as a double before it is an index
   const double sfx = floor((px - a.ox) / a.res), sfy = floor((py - a.oy) / a.res), sfz = floor((pz - a.oz) / a.res);
   if (!(sfx >= 0.0 && sfx < (double)a.nx && sfy >= 0.0 && sfy < (double)a.ny && sfz >= 0.0 && sfz < (double)a.nz)) {
-    if (t == 0) reach_store(a, i, flags | FH_REACH_START_OUTSIDE, view, -1, INFINITY, none);
+    if (t == 0) {
+      if constexpr (CLAIMS) x.store(a, i, flags | FH_REACH_START_OUTSIDE, view, -1, INFINITY, none, 0);
+      else reach_store(a, i, flags | FH_REACH_START_OUTSIDE, view, -1, INFINITY, none);
+    }
     return;
   }
   const int sx = (int)sfx, sy = (int)sfy, sz = (int)sfz;
@@ -123,7 +138,10 @@ __global__ void __launch_bounds__(256) reach_goals_kernel(ReachArgs a) {
   const int wx = holds ? (hi0 - lo0 + 64) >> 6 : 0;                     // (hi0 - lo0 + 1 <= nx: no overflow)
   const long long words = (long long)wx * rows_y * rows_z;            // (rows_y rows_z <= ny nz < 2^31, wx < 2^26)
   if (!holds || words > (long long)REACH_WORDS) {
-    if (t == 0) reach_store(a, i, flags | FH_REACH_BOX_TOO_LARGE, view, -1, INFINITY, none);
+    if (t == 0) {
+      if constexpr (CLAIMS) x.store(a, i, flags | FH_REACH_BOX_TOO_LARGE, view, -1, INFINITY, none, 0);
+      else reach_store(a, i, flags | FH_REACH_BOX_TOO_LARGE, view, -1, INFINITY, none);
+    }
     return;
   }
   const int W = (int)words, rows = rows_y * rows_z, slab = wx * rows_y;
@@ -131,6 +149,7 @@ __global__ void __launch_bounds__(256) reach_goals_kernel(ReachArgs a) {
 
   // ---- build: pass and cand, a wavefront per row ----
   int count = 0;  // candidates (uniform over the wavefront: sums of popcounts of ballots)
+  [[maybe_unused]] int claimed = 0;  // CLAIMS: those of them that are claimed
   for (int r = w; r < rows; r += 4) {  // (r, and all that follows from it alone, is uniform over the wavefront)
     const int iz = lo2 + r / rows_y, iy = lo1 + r % rows_y;
     const double qz = (iz + 0.5) * a.res + a.oz, qy = (iy + 0.5) * a.res + a.oy;
@@ -165,11 +184,29 @@ __global__ void __launch_bounds__(256) reach_goals_kernel(ReachArgs a) {
           cand = (ix > 0 && F[c - 1] != 0) || (ix < a.nx - 1 && F[c + 1] != 0) || (iy > 0 && F[c - a.nx] != 0) ||
                  (iy < a.ny - 1 && F[c + a.nx] != 0) || (iz > 0 && F[c - slice] != 0) || (iz < a.nz - 1 && F[c + slice] != 0);
       }
+      bool claim = false;
+      if constexpr (CLAIMS) {
+        if (cand) {  // (x.count is uniform; a point is read by every lane at once: a broadcast)
+          for (int j = 0; j < x.count; j++) {
+            const double sx = x.pts[3 * j] - qx, sy = x.pts[3 * j + 1] - qy, sz = x.pts[3 * j + 2] - qz;
+            const double s2 = sx * sx + sy * sy + sz * sz;
+            claim = claim || s2 < x.s2;
+          }
+        }
+      }
       // all 64 lanes are here again
-      const unsigned long long bp = __ballot(pass), bc = __ballot(cand);
+      unsigned long long bp = __ballot(pass), bc = __ballot(cand);
       count += __popcll(bc);
+      if constexpr (CLAIMS) {
+        const unsigned long long bk = __ballot(claim);
+        claimed += __popcll(bk);
+        bc &= ~bk;
+      }
       if (lane == 0) { s_pass[r * wx + k] = bp; s_cand[r * wx + k] = bc; }
     }
+  }
+  if constexpr (CLAIMS) {
+    if (lane == 0) x.sum[w] = claimed;  // (read after the barrier below)
   }
   // the start: level 0, whatever its flag and map bit are
   const int sw = ((sz - lo2) * rows_y + (sy - lo1)) * wx + ((sx - lo0) >> 6);  // (< W: s is in the box)
@@ -290,8 +327,11 @@ __global__ void __launch_bounds__(256) reach_goals_kernel(ReachArgs a) {
     n.reached = s_n[0] + s_n[1] + s_n[2] + s_n[3];
     n.levels = level;
     if (cut) flags |= FH_REACH_CUT;
-    reach_store(a, i, flags, view, hops >= 0 ? best_cell : -1, hops >= 0 ? best : INFINITY, n);
+    if constexpr (CLAIMS) x.store(a, i, flags, view, hops >= 0 ? best_cell : -1, hops >= 0 ? best : INFINITY, n, x.sum[0] + x.sum[1] + x.sum[2] + x.sum[3]);
+    else reach_store(a, i, flags, view, hops >= 0 ? best_cell : -1, hops >= 0 ? best : INFINITY, n);
   }
 }
+
+__global__ void __launch_bounds__(256) reach_goals_kernel(ReachArgs a) { reach_body<false>(a, ReachNoClaims()); }
 
 }  // namespace fhp

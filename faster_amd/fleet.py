@@ -45,7 +45,8 @@ free and next to unknown space as its new goal, on the device; coverage() counts
     sense -> observe -> [link] -> explore -> replan -> next_goals
 
 explore_reachable() stands in explore()'s place (include/fasterhip_reach.h): of those voxels the one that a flood of the space the view
-knows to be free reaches in the fewest steps, never one behind a wall or in a sealed pocket.
+knows to be free reaches in the fewest steps, never one behind a wall or in a sealed pocket.  explore_spread() is that chooser for a team
+(include/fasterhip_spread.h): a voxel nearer than r_spread to the goal a peer holds or has just been given is left to that peer.
 
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
@@ -112,6 +113,7 @@ class Fleet:
         self.d_link_labels = self.d_link_info = None                                                           # link
         self.d_explore_goals = self.d_explore_mask = self.d_explore_records = self.d_explore_view_of = self.d_coverage = None   # explore, coverage
         self.d_reach_goals = self.d_reach_mask = self.d_reach_records = self.d_reach_view_of = None                            # explore_reachable
+        self.d_spread_goals = self.d_spread_mask = self.d_spread_records = self.d_spread_work = None                           # explore_spread
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -639,14 +641,16 @@ class Fleet:
         for _, launch in stages:
             launch()
 
-    def explore_reachable_stages(self, r_max, r_avoid=None, z=None, want="reached", max_hops=0):
-        """The two launches of explore_reachable(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+    def _reach_inputs(self, who, par, r_avoid, z, want, max_hops):
+        """What explore_reachable() and explore_spread() share: the preconditions, raised in the name `who`; the views as (flags tensor,
+        view_stride, view_of pointer or None, n_views); and the fields that fh_reach_params and fh_spread_params have in common,
+        written into `par`."""
         if self.cloud is None or self.map_args is None:
-            raise capi.FasterHipError("Fleet.explore_reachable: set_map first")
+            raise capi.FasterHipError("Fleet.%s: set_map first" % who)
         if self.view_flags is not None:
-            flags, stride, vo, n_views = self.view_flags, int(self.view_flags.shape[1]), (None if self.view_of is None else self.view_of.data_ptr()), self.n_views
+            views = self.view_flags, int(self.view_flags.shape[1]), (None if self.view_of is None else self.view_of.data_ptr()), self.n_views
         elif self.flags is None:
-            raise capi.FasterHipError("Fleet.explore_reachable: set_unknown_views (or set_unknown) first")
+            raise capi.FasterHipError("Fleet.%s: set_unknown_views (or set_unknown) first" % who)
         else:   # set_unknown's one grid: a single view that every vehicle reads (an all-zero view_of)
             if self.d_reach_view_of is None:
                 t = self.torch
@@ -654,19 +658,24 @@ class Fleet:
                 with t.cuda.stream(self.stream):
                     self.d_reach_view_of = t.zeros(self.n, dtype=t.int32, device=self.dev)
                 self.d_reach_view_of.record_stream(self.stream)
-            flags, stride, vo, n_views = self.flags, int(self.flags.numel()), self.d_reach_view_of.data_ptr(), 1
+            views = self.flags, int(self.flags.numel()), self.d_reach_view_of.data_ptr(), 1
         wants = (want,) if isinstance(want, str) else tuple(want)
         if not wants or any(w not in self._EXPLORE_WANT for w in wants):
-            raise capi.FasterHipError("Fleet.explore_reachable: want is \"reached\", \"no_path\", \"all\" or a tuple of them, got %r" % (want,))
+            raise capi.FasterHipError("Fleet.%s: want is \"reached\", \"no_path\", \"all\" or a tuple of them, got %r" % (who, want))
         if "reached" in wants and self.d_headings is None:
-            raise capi.FasterHipError("Fleet.explore_reachable: want=\"reached\" needs enable_heading first (a vehicle that takes a new goal "
-                                      "after GOAL_REACHED is YAWING until next_goals with headings has turned it)")
-        par = abi.default_reach_params(r_max)
+            raise capi.FasterHipError("Fleet.%s: want=\"reached\" needs enable_heading first (a vehicle that takes a new goal "
+                                      "after GOAL_REACHED is YAWING until next_goals with headings has turned it)" % who)
         par["r_avoid"] = float(self.params["goal_radius"]) if r_avoid is None else r_avoid
         par["z_lo"], par["z_hi"] = (self.z_ground, self.map_args[3]) if z is None else z
         par["want"], par["max_hops"] = 0, max_hops
         for w in wants:
             par["want"] |= self._EXPLORE_WANT[w]
+        return views
+
+    def explore_reachable_stages(self, r_max, r_avoid=None, z=None, want="reached", max_hops=0):
+        """The two launches of explore_reachable(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        par = abi.default_reach_params(r_max)
+        flags, stride, vo, n_views = self._reach_inputs("explore_reachable", par, r_avoid, z, want, max_hops)
         if self.d_reach_goals is None:
             t = self.torch
             self._follow_current()
@@ -691,6 +700,57 @@ class Fleet:
         self.sync()
         return (self.d_reach_records.cpu().numpy().view(abi.reach_record_dtype).copy(), self.d_reach_goals.cpu().numpy().copy(),
                 self.d_reach_mask.cpu().numpy().copy())
+
+    def explore_spread(self, r_max, r_spread, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link"):
+        """explore_reachable() for a team (include/fasterhip_spread.h): a frontier voxel nearer than r_spread to the goal that a peer is
+        on its way to, or that a peer with a lower index has been given by an earlier pass of this call, is not chosen, so vehicles
+        with equal views that stand together fly to different places.  Peers are the vehicles of one group: groups="link" takes the
+        labels of the last link() if there was one, else the view; groups="view" always the view.  passes: how long a chain of
+        vehicles that wait for each other may be (None: abi.FH_SPREAD_DEFAULT_PASSES); a vehicle behind that gets no goal this period
+        (FH_SPREAD_UNSETTLED) and is wanted again in the next.  The other arguments, the preconditions and the errors are those of
+        explore_reachable(); the buffers and the workspace are its own (spread_records())."""
+        stages = self.explore_spread_stages(r_max, r_spread, r_avoid, z, want, max_hops, passes, groups)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_spread_stages(self, r_max, r_spread, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link"):
+        """The launches of explore_spread(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them one by one)."""
+        if groups not in ("link", "view"):
+            raise capi.FasterHipError("Fleet.explore_spread: groups is \"link\" or \"view\", got %r" % (groups,))
+        par = abi.default_spread_params(r_max, r_spread)
+        flags, stride, vo, n_views = self._reach_inputs("explore_spread", par, r_avoid, z, want, max_hops)   # (set_unknown's one grid: one team)
+        if passes is not None:
+            par["passes"] = passes
+        work_bytes = int(capi.lib().fh_spread_work_bytes(self.n))
+        if self.d_spread_goals is None:
+            t = self.torch
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_spread_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_spread_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_spread_records = t.zeros(self.n * abi.spread_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+                self.d_spread_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
+            for d in (self.d_spread_goals, self.d_spread_mask, self.d_spread_records, self.d_spread_work):
+                d.record_stream(self.stream)
+        # the labels are per view: with set_unknown's single view there is nothing to label
+        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
+            and self.d_link_labels.numel() == n_views else None
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("spread_goals", lambda: m.spread_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if labels is None else p(labels),
+                                                           p(self.d_vehicles), self.n, p(self.d_spread_work), work_bytes, p(self.d_spread_goals),
+                                                           p(self.d_spread_mask), p(self.d_spread_records), self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_spread_goals), p(self.d_spread_mask), self.n)),
+        ]
+
+    def spread_records(self):
+        """(records [n] abi.spread_record_dtype, goals [n][3], mask [n] int32) of the last explore_spread() (synchronises)."""
+        if self.d_spread_goals is None:
+            raise capi.FasterHipError("Fleet.spread_records: explore_spread first")
+        self.sync()
+        return (self.d_spread_records.cpu().numpy().view(abi.spread_record_dtype).copy(), self.d_spread_goals.cpu().numpy().copy(),
+                self.d_spread_mask.cpu().numpy().copy())
 
     def coverage_stages(self):
         """The one launch of coverage(): [(name, callable)]."""

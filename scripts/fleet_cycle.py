@@ -59,7 +59,13 @@ and at the end.
 the stage is reported under its name, "reach_goals", and with every vehicle wanted as "reach_goals_all_ms", beside frontier_goals with
 every vehicle wanted in the same run; and, of that launch, the levels of the flood (mean, max), the voxels reached and the candidates
 reachable per searched vehicle, and the vehicles whose box was too large.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--spread R_SPREAD (with --views --explore R_MAX --reach) runs that loop with Fleet.explore_spread in the place of Fleet.explore_reachable
+(include/fasterhip_spread.h): the stage is reported as "spread_goals"; with every vehicle wanted as "spread_goals_all_ms", and with one and
+two passes instead of the default eight (the difference is what the idle launches cost), beside reach_goals with every vehicle wanted
+before and after it in the same run; the vehicles decided per pass, those left UNSETTLED or in OVERFLOW, and the longest list of lower
+peers.  The peers are the vehicles of one view: with a view per vehicle nobody has one, unless --link RANGE is given too — then the
+vehicles are linked once after the first look, with the first RANGE, and the groups of that link are the teams.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD]]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -83,6 +89,9 @@ EXPLORE = float(sys.argv[sys.argv.index("--explore") + 1]) if "--explore" in sys
 REACH = "--reach" in sys.argv
 if REACH and not ("--views" in sys.argv and EXPLORE is not None):
     sys.exit("--reach needs --views --explore R_MAX")
+SPREAD = float(sys.argv[sys.argv.index("--spread") + 1]) if "--spread" in sys.argv else None
+if SPREAD is not None and not REACH:
+    sys.exit("--spread needs --views --explore R_MAX --reach")
 
 
 def timed_audit(fl, cycles):
@@ -292,9 +301,15 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     fl.enable_heading(yaw0=np.arctan2(u[:, 1], u[:, 0]))
     fl.sense(r_sense)
     first = fl.coverage()
-    goal_stage = "reach_goals" if REACH else "frontier_goals"
+    goal_stage = "spread_goals" if SPREAD is not None else "reach_goals" if REACH else "frontier_goals"
     explore_stages, explore_records = (fl.explore_reachable_stages, fl.reach_records) if REACH else (fl.explore_stages, fl.explore_records)
-    (fl.explore_reachable if REACH else fl.explore)(r_max)
+    if SPREAD is not None:
+        if LINK:   # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
+            fl.link(LINK[0])
+        explore_stages, explore_records = (lambda r, **kw: fl.explore_spread_stages(r, SPREAD, **kw)), fl.spread_records
+        fl.explore_spread(r_max, SPREAD)
+    else:
+        (fl.explore_reachable if REACH else fl.explore)(r_max)
     fl.replan()
     fl.next_goals(5)
     fl.sync()
@@ -325,10 +340,10 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     last = fl.coverage()
     reach = {}
     if REACH:   # every vehicle wanted, applied to nobody, as frontier_goals above
-        reach_ms = fenced_ms(fl, explore_stages(r_max, want="all")[0][1], max(cycles, 3))
-        rr = explore_records()[0]
+        reach_ms = fenced_ms(fl, fl.explore_reachable_stages(r_max, want="all")[0][1], max(cycles, 3))
+        rr = fl.reach_records()[0]
         hit = (rr["flags"] & (abi.FH_REACH_START_OUTSIDE | abi.FH_REACH_BOX_TOO_LARGE | abi.FH_FRONTIER_NO_VIEW | abi.FH_FRONTIER_BAD_POS)) == 0
-        reach = {"reach_goals_reached_ms": med["reach_goals"], "reach_goals_all_ms": float(np.median(reach_ms)),
+        reach = {"reach_goals_reached_ms": med.get("reach_goals"), "reach_goals_all_ms": float(np.median(reach_ms)),
                  "reach_goals_all_runs_ms": [float(x) for x in reach_ms], "reach_found_all": int((rr["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
                  "reach_searched_all": int(hit.sum()), "reach_box_too_large": int((rr["flags"] & abi.FH_REACH_BOX_TOO_LARGE != 0).sum()),
                  "reach_start_outside": int((rr["flags"] & abi.FH_REACH_START_OUTSIDE != 0).sum()),
@@ -338,6 +353,24 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                  "candidates_mean": float(rr["candidates"][hit].mean()) if hit.any() else 0.0,
                  "reachable_mean": float(rr["reachable"][hit].mean()) if hit.any() else 0.0,
                  "same_cell_as_frontier_goals": int((rr["cell"] == rec["cell"]).sum())}
+    if SPREAD is not None:   # every vehicle wanted, applied to nobody: all passes, and one pass (the difference: the idle launches)
+        reps = max(cycles, 3)
+        spread_ms = fenced_ms(fl, explore_stages(r_max, want="all")[0][1], reps)
+        sr = fl.spread_records()[0]
+        one_ms = fenced_ms(fl, explore_stages(r_max, want="all", passes=1)[0][1], reps)
+        two_ms = fenced_ms(fl, explore_stages(r_max, want="all", passes=2)[0][1], reps)
+        again_ms = fenced_ms(fl, fl.explore_reachable_stages(r_max, want="all")[0][1], reps)
+        passes = np.bincount(sr["decided_pass"][sr["decided_pass"] > 0], minlength=2)
+        reach.update({"r_spread": SPREAD, "passes": abi.FH_SPREAD_DEFAULT_PASSES, "spread_goals_reached_ms": med["spread_goals"],
+                      "spread_goals_all_ms": float(np.median(spread_ms)), "spread_goals_all_runs_ms": [float(x) for x in spread_ms],
+                      "spread_goals_all_one_pass_ms": float(np.median(one_ms)), "spread_goals_all_two_passes_ms": float(np.median(two_ms)),
+                      "reach_goals_all_after_ms": float(np.median(again_ms)), "reach_goals_all_after_runs_ms": [float(x) for x in again_ms],
+                      "decided_per_pass": passes[1:].tolist(), "passes_that_decided": int((passes[1:] > 0).sum()),
+                      "unsettled": int((sr["flags"] & abi.FH_SPREAD_UNSETTLED != 0).sum()),
+                      "overflow": int((sr["flags"] & abi.FH_SPREAD_OVERFLOW != 0).sum()),
+                      "claimed_vehicles": int((sr["claimed"] > 0).sum()), "lower_max": int(sr["lower"].max()), "claims_max": int(sr["claims"].max()),
+                      "groups": int(len(np.unique(sr["group"]))), "spread_found_all": int((sr["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                      "same_cell_as_reach_goals": int((sr["cell"] == rr["cell"]).sum())})
     return {"r_max": r_max, "goal_stage": goal_stage, **reach, "stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "wanted_per_cycle": wanted, "found_per_cycle": found,
             "frontier_goals_reached_ms": med.get("frontier_goals"), "frontier_goals_all_ms": float(np.median(all_ms)),
             "frontier_goals_all_runs_ms": [float(x) for x in all_ms], "found_all": int((rec["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
@@ -583,6 +616,9 @@ def main():
         del argv[k:k + 2]
     if "--reach" in argv:        # (read into REACH above)
         argv.remove("--reach")
+    if "--spread" in argv:       # (read into SPREAD above)
+        k = argv.index("--spread")
+        del argv[k:k + 2]
     if "--traffic-timed" in argv:
         k = argv.index("--traffic-timed")
         window = int(argv[k + 1])
