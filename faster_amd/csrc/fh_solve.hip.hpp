@@ -113,7 +113,7 @@ __device__ __forceinline__ int mk_id(int kind, int t, int k, int f) { return (ki
 using fhw::dpp_f64; using fhw::first_lane; using fhw::halves_sum; using fhw::readlane_f64; using fhw::uniform_f64;
 using fhw::uniform_i32; using fhw::vmax_f64; using fhw::vmin_f64; using fhw::wave_any; using fhw::wave_max; using fhw::wave_max_nonneg;
 using fhw::wave_min; using fhw::wave_or; using fhw::wave_sum; using fhw::wave_sum_i32;
-using fhw::gather_f64; using fhw::group_max_nonneg; using fhw::half_min; using fhw::half_sum; using fhw::half_sum2; using fhw::rows3_sum_i32;
+using fhw::gather_f64; using fhw::gather_i32; using fhw::quad_argmax; using fhw::slices_max; using fhw::group_max_nonneg; using fhw::half_min; using fhw::half_sum; using fhw::half_sum2; using fhw::rows3_sum_i32;
 
 // Scheduling fences.  in_flight(a): every element of `a` (just loaded) must be in its register here, so the loads are issued
 // back to back and their LDS latencies overlap (the scheduler of this register-tight kernel otherwise serialises
@@ -499,6 +499,10 @@ struct Solver {
   double* bestx_g;        // [NVP] incumbent y (lane < n) in the workgroup's workspace: written when a better leaf is found, read when the problem ends or is first shared
   double cp_r[3];         // lane = (t, k): control point k of segment t at the current x (compute_states -> scan)
   int scan_f0, scan_F;    // lane = (t, k): first row and row count of the polytope segment t is assigned to (0 rows: free) (per node)
+                          //   HALF: (t, k) and the rows are those of the lane map of the run (bind_assignment): scan_f0 the first
+                          //   row of the lane's slice; scan_F bits 0..6 the rows from there to the polytope's last, 7..12 the slice's first row
+                          //   within the polytope, 13..18 4 t + k, 19..24 the lane whose joined answer the HOME lane 4 t + k = lane reads,
+                          //   25: that home lane belongs to an assigned segment
   // ---- wave-uniform scalars ----
   int lane, N, n, q, P;   // n = 3 K: unknowns of the reduced QP
   int nx;                 // 3 N: jerks of the trajectory
@@ -509,7 +513,7 @@ struct Solver {
   double box_ub;          // 3N j_max^2 (1 + 1e-9): no feasible trajectory costs more
   double gx2;             // |normal in jerk space|^2 of the row build_g built last
   int maxF;  // max faces of one polytope of this problem (wave-uniform trip count of the face sweeps)
-  int scan_trip;  // the scan's trip count (bind_assignment: maxF)
+  int scan_trip;  // the scan's trip count (bind_assignment: maxF; HALF: the rows per slice, and from bit 8 the log2 of the slices)
   unsigned poly_ok;  // polytopes without a violated zero-normal face (such a polytope can never hold a segment)
 #ifdef FH_PROFILE
   unsigned long long prof[24];   // 0-15: see scripts/phase_profile.py; 16 look-around + donations, 17 result write, 18 hand-off of the pair (charged to
@@ -929,8 +933,10 @@ struct Solver {
       if (lane >= 3) { Pc[lane] = p0r + dp; Vc[lane] = v0r + dv; Ac[lane] = a0r + da; }
     }
     FH_SYNC();
-    if (lane < 4 * N) {  // lane = (segment, control point): three axes each, no integer divisions
-      const int t = lane >> 2, k = lane & 3;
+    if (HALF || lane < 4 * N) {  // lane = (segment, control point): three axes each, no integer divisions
+      // HALF: the (segment, control point) whose rows the lane scans in this run (bind_assignment; (0, 0) in a lane without rows)
+      const int tk = HALF ? (scan_F >> 13) & 63 : lane;
+      const int t = tk >> 2, k = tk & 3;
       const int o = t * 3;
       double st[12];
 #pragma unroll
@@ -944,16 +950,49 @@ struct Solver {
   // assign[] only changes between two active-set runs: the scan lanes look their rows up once per run
   __device__ void bind_assignment() {
     const int lane = opaque(this->lane);  // (lane-derived constants are recomputed here, not kept in registers across the whole solve)
-    const bool live = lane < 4 * N;
-    const int p = live ? assign[lane >> 2] : -1;
-    scan_f0 = p >= 0 ? face_off[p] : 0;
-    scan_F = p >= 0 ? face_off[p + 1] - scan_f0 : 0;
-    // flop accounting: rows x control points scanned per iteration of this run (HALF: the lanes (t, k) < 4 N <= 40 lie in three rows)
-    if constexpr (HALF) rows4 = rows3_sum_i32(scan_F);
-    else rows4 = wave_sum_i32(scan_F);
-    // (tried: the longest row list any lane scans in THIS run as the trip count, a wave maximum of scan_F — 19.4 M pairs/s on C4 with
-    // and without it, the sweeps are not what a node waits for; not kept)
-    scan_trip = maxF;
+    if constexpr (HALF) {
+      // The lane map of the coming run.  nb segments are assigned; their 4 nb (segment, control point) pairs take
+      // S = 1 << sh lanes each, S = 4 while nb <= 4, 2 while nb <= 8: the j-th assigned segment (ascending t), control point k and row
+      // slice r own lane (4 j + k) S + r, and slice r sweeps the rows from r L on, L = ceil(maxF / S).  S = 1: lane = 4 t + k, all rows.
+      const bool seg = lane < N;
+      const int pa = seg ? assign[lane] : -1;
+      const int f0t = pa >= 0 ? face_off[pa] : 0;
+      const int Ft = pa >= 0 ? face_off[pa + 1] - f0t : 0;  // lane t < N: the rows of the polytope of segment t
+      const unsigned m = (unsigned)__ballot(pa >= 0);
+      const int nb = __builtin_popcount(m);
+      const int sh = nb <= 4 ? 2 : (nb <= 8 ? 1 : 0);
+      // flop accounting: rows x control points scanned per iteration of this run, as the sum over the lanes (t, k) gave it
+      rows4 = 4 * rows3_sum_i32(Ft);
+      unsigned long long tab = 0;  // nibble j: the j-th assigned segment (wave-uniform: scalar work)
+      {
+        unsigned mm = m;
+        for (int j = 0; mm; j++, mm &= mm - 1) tab |= (unsigned long long)__builtin_ctz(mm) << (4 * j);
+      }
+      const int L = (maxF + (1 << sh) - 1) >> sh;  // rows per slice
+      const int g = lane >> sh, r0 = (lane & ((1 << sh) - 1)) * L;
+      const int j = g >> 2, k = g & 3;
+      const bool on = sh ? j < nb : lane < 4 * N;
+      const int t = on ? (sh ? (int)((tab >> (4 * j)) & 15u) : j) : 0;
+      const int f0s = gather_i32(f0t, t), Fs = gather_i32(Ft, t);
+      const bool live = on && r0 < Fs;  // (a slice wholly past its polytope would only re-read the last row, which another slice reads)
+      // the home lane 4 t + k of an assigned segment reads the answer of its group from that group's first lane
+      const int th = lane >> 2;
+      const bool mine = lane < 4 * N && ((m >> th) & 1u);
+      const int src = (mine && sh) ? ((4 * __builtin_popcount(m & ((1u << th) - 1u)) + (lane & 3)) << sh) : lane;
+      scan_f0 = live ? f0s + r0 : 0;
+      scan_F = (live ? Fs - r0 : 0) | (r0 << 7) | ((on ? 4 * t + k : 0) << 13) | (src << 19) | (mine ? 1 << 25 : 0);
+      scan_trip = L | (sh << 8);
+    } else {
+      const bool live = lane < 4 * N;
+      const int p = live ? assign[lane >> 2] : -1;
+      scan_f0 = p >= 0 ? face_off[p] : 0;
+      scan_F = p >= 0 ? face_off[p + 1] - scan_f0 : 0;
+      // flop accounting: rows x control points scanned per iteration of this run
+      rows4 = wave_sum_i32(scan_F);
+      // (tried: the longest row list any lane scans in THIS run as the trip count, a wave maximum of scan_F — 19.4 M pairs/s on C4 with
+      // and without it, the sweeps are not what a node waits for; not kept)
+      scan_trip = maxF;
+    }
   }
 
   // ---- most violated inactive inequality row; violation relative to the row norm. id<0: none. ----
@@ -989,14 +1028,18 @@ struct Solver {
        // All rows of a lane share the weight factor, so the lane maximises the normalised violation and scales once.
       const bool live = lane < 4 * N;
       const int t = live ? (lane >> 2) : 0, k = lane & 3;
-      const int f0 = scan_f0, F = scan_F;  // rows of the polytope this lane's segment is assigned to (bind_assignment)
+      // rows of the polytope this lane's segment is assigned to (bind_assignment).  HALF: the rows of the lane's slice, from its
+      // first row to the polytope's last, of the (segment, control point) the lane holds in this run
+      int f0 = scan_f0;
+      const int F = HALF ? scan_F & 127 : scan_F;
+      const int trip = HALF ? scan_trip & 255 : scan_trip;
       const double c0 = cp_r[0], c1 = cp_r[1], c2 = cp_r[2];  // this lane's control point (compute_states)
       const double wi = wcp;
       int bf = -1;
       double bvt = (F > 0) ? 0.0 : INFINITY;  // dead lanes never take
       const int fl = F > 0 ? F - 1 : 0;        // rows beyond the lane's polytope re-read its last row: never a strict improvement
       const fh_face* fp = faces + f0;
-      for (int fb = 0; fb < scan_trip; fb += 4) {
+      for (int fb = 0; fb < trip; fb += 4) {
         fh_face fc[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) fc[j] = fp[min(fb + j, fl)];  // the four loads in flight before the first use
@@ -1007,6 +1050,24 @@ struct Solver {
           bvt = take ? vt : bvt;
           bf = take ? fb + j : bf;
         }
+      }
+      if constexpr (HALF) {
+        // Join the slices of each (segment, control point): the largest vt, among equal vt the lowest row — the row the strict `>` of
+        // one lane over all rows keeps (a slice reports the first of its rows that attains its maximum, and every row lies in a
+        // slice).  The pair travels as (vt, row | (index of the row in faces[]) << 8); -1: no row of the slice is violated.
+        const int sm = scan_F, sh = scan_trip >> 8;
+        const int r0 = (sm >> 7) & 63;
+        int pk = bf >= 0 ? bf * 257 + ((f0 << 8) + r0) : -1;
+        bvt = bf >= 0 ? bvt : 0.0;
+        if (sh) {
+          quad_argmax(sh, bvt, pk);
+          const int src = (sm >> 19) & 63;  // the home lane (t, k) of an assigned segment reads the first lane of its group
+          bvt = gather_f64(bvt, src);
+          pk = gather_i32(pk, src);
+        }
+        pk = (sm >> 25) & 1 ? pk : -1;  // lanes that are the home of no assigned (t, k) drop what they swept for another lane
+        bf = pk >= 0 ? pk & 255 : -1;
+        f0 = (pk >> 8) - bf;  // first row of the polytope of the home lane's segment (read only where bf >= 0)
       }
       if (bf >= 0) {
         if (wi == 0.0) bad = true;  // a row that does not depend on y (segment 0: control points 0..2; whole trajectory: 1..3 of the last segment) violated
@@ -1502,12 +1563,20 @@ struct Solver {
       FH_SYNC();
       return -1;
     }
-    for (int pair0 = 0; pair0 < N * P; pair0 += 64) {
-      const int pair = pair0 + lane;
+    // HALF: while N P <= 32 a (segment, polytope) pair takes S = 2 lanes, 4 while N P <= 16 (the slice r in the low bits); slice r
+    // sweeps the rows from r L on, L = ceil(maxF / S), and a maximum over the S lanes joins them: the same values under the same
+    // maximum, and -INFINITY where nothing is needed
+    const int sh = HALF ? (N * P <= 16 ? 2 : (N * P <= 32 ? 1 : 0)) : 0;
+    const int trip = (maxF + (1 << sh) - 1) >> sh;
+    for (int pair0 = 0; pair0 < N * P; pair0 += 64 >> sh) {
+      const int pair = pair0 + (lane >> sh);
+      const int r0 = (lane & ((1 << sh) - 1)) * trip;
       const bool live = pair < N * P;
       const int t = live ? pair / P : 0, p = live ? pair - t * P : 0;
       const bool need = live && assign[t] < 0 && ((allowed_mask(t) >> p) & 1u);
-      const int f0 = face_off[p], F = need ? face_off[p + 1] - f0 : 0;
+      const int fp0 = face_off[p], Fp = need ? face_off[p + 1] - fp0 : 0;
+      const bool mine = r0 == 0 || r0 < Fp;  // (a slice wholly past its polytope has no row of its own)
+      const int f0 = fp0 + (mine ? r0 : 0), F = mine ? Fp - r0 : 0;
       // every face row is read once for the four control points of the segment; rows beyond the polytope re-read its last
       // row (harmless for a maximum), so that the trip count is wave-uniform and four rows are in flight
       double c[12];
@@ -1524,7 +1593,7 @@ struct Solver {
       const int fl = F > 0 ? F - 1 : 0;
       const fh_face* fp = faces + f0;
       double worst = -INFINITY;
-      for (int fb = 0; fb < maxF; fb += 4) {
+      for (int fb = 0; fb < trip; fb += 4) {
         fh_face fc[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) fc[j] = fp[min(fb + j, fl)];
@@ -1535,8 +1604,9 @@ struct Solver {
             worst = vmax_f64(worst, fma(fc[j].a[0], c[3 * k], fma(fc[j].a[1], c[3 * k + 1], fma(fc[j].a[2], c[3 * k + 2], fc[j].b))));
         }
       }
-      if (!need) worst = -INFINITY;
-      if (live) viol[t * FH_MAX_POLY + p] = (assign[t] < 0 && !need) ? INFINITY : worst;
+      if (!need || !mine) worst = -INFINITY;
+      if constexpr (HALF) worst = slices_max(sh, worst);
+      if (live && r0 == 0) viol[t * FH_MAX_POLY + p] = (assign[t] < 0 && !need) ? INFINITY : worst;
     }
     FH_SYNC();
     double score = -INFINITY;

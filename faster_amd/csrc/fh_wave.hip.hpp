@@ -174,6 +174,31 @@ __device__ __forceinline__ double gather_f64(double v, int src) {
   const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(v));
   return __hiloint2double(hi, lo);
 }
+__device__ __forceinline__ int gather_i32(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
+// One step of an arg-max over pairs (v, i): the lane takes the pair of the lane CTRL names when that one is larger in the order
+// "greater v first, among equal v the smaller i as an unsigned number" (so i = -1, no candidate, loses against every index).  A total
+// order: both lanes of an exchange keep the same pair.  No NaN among the v.  All 64 lanes must be active.
+template <int CTRL>
+__device__ __forceinline__ void argmax_step(double& v, int& i) {
+  const double ov = dpp0_f64<CTRL>(v);
+  const int oi = dpp0_i32<CTRL>(i);
+  const bool take = ov > v || (ov == v && (unsigned)oi < (unsigned)i);
+  v = take ? ov : v;
+  i = take ? oi : i;
+}
+// arg-max over each aligned group of 1 << sh lanes, sh in {0, 1, 2} (wave-uniform), the winning pair in every lane of the group:
+// the quad_perm steps of quad_max
+__device__ __forceinline__ void quad_argmax(int sh, double& v, int& i) {
+  if (sh >= 1) argmax_step<0xB1>(v, i);
+  if (sh >= 2) argmax_step<0x4E>(v, i);
+}
+// max over each aligned group of 1 << sh lanes, sh in {0, 1, 2} (wave-uniform), the result in every lane of the group: the quad_perm
+// steps of quad_max on v_max_f64.  Any sign and -INFINITY, no NaN.  All 64 lanes must be active.
+__device__ __forceinline__ double slices_max(int sh, double v) {
+  if (sh >= 1) v = vmax_f64(v, dpp0_f64<0xB1>(v));
+  if (sh >= 2) v = vmax_f64(v, dpp0_f64<0x4E>(v));
+  return v;
+}
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ int dpp_min_step(int v) {
   const int o = __builtin_amdgcn_update_dpp(0x7fffffff, v, CTRL, ROW_MASK, 0xf, false);
