@@ -290,6 +290,26 @@ def default_spread_params(r_max, r_spread):
     return p
 
 
+# fh_gain_params, fh_gain_record: the reachable frontier voxel with the most unknown space around it for its steps
+# (include/fasterhip_gain.h); the record's flags are those of fh_reach_record and FH_GAIN_ALL_POOR
+FH_GAIN_MAX_RADIUS, FH_GAIN_MAX_HOP_COST, FH_GAIN_ALL_POOR = 31, 16384, 128
+gain_params_dtype = np.dtype([("r_max", "<f8"), ("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                              ("gain_radius", "<i4"), ("hop_cost", "<i4"), ("min_gain", "<i4"), ("reserved", "<i4", (3,))], align=True)
+gain_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("hops", "<i4"), ("candidates", "<i4"),
+                              ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("d2", "<f8"), ("gain", "<i4"), ("utility", "<i4"),
+                              ("poor", "<i4"), ("best_gain", "<i4"), ("reserved", "<f8")], align=True)
+assert (gain_params_dtype.itemsize, gain_record_dtype.itemsize) == (64, 64)
+
+
+def default_gain_params(r_max, gain_radius):
+    """fh_gain_params: default_reach_params, the unknown voxels within gain_radius voxels of a candidate weighed against its steps one
+    for one (hop_cost 1), no candidate poor (min_gain 0)."""
+    p = np.zeros((), dtype=gain_params_dtype)
+    p["r_max"], p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"] = r_max, 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0
+    p["gain_radius"], p["hop_cost"], p["min_gain"] = gain_radius, 1, 0
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

@@ -1,7 +1,8 @@
 // fh_reach.hip — host side of include/fasterhip_reach.h (fh_reach_goals_device): the frontier voxel that a flood of the space a vehicle
 // knows to be free reaches in the fewest steps (kernel: fh_reach.hip.hpp), and of include/fasterhip_spread.h (fh_spread_goals_device):
-// that chooser for a team, goals claimed by peers avoided (kernels: fh_spread.hip.hpp).  A translation unit of its own: fh_map.hip and
-// fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
+// that chooser for a team, goals claimed by peers avoided (kernels: fh_spread.hip.hpp), and of include/fasterhip_gain.h
+// (fh_gain_goals_device): the reachable frontier voxel with the most unknown space around it for its steps (kernel: fh_gain.hip.hpp).
+// A translation unit of its own: fh_map.hip and fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -9,8 +10,10 @@
 #include "../../include/fasterhip.h"
 #include "../../include/fasterhip_reach.h"
 #include "../../include/fasterhip_spread.h"
+#include "../../include/fasterhip_gain.h"
 #include "fh_reach.hip.hpp"
 #include "fh_spread.hip.hpp"
+#include "fh_gain.hip.hpp"
 #include "fh_host.hpp"
 
 // the lattice of the views, judged as fh_map_frontier_goals_device judges it (0: fine, cells filled in)
@@ -25,15 +28,20 @@ static int reach_lattice(const fh_voxel_grid* grid, size_t view_stride, int n_vi
   return FH_OK;
 }
 
-// the clauses of fh_reach_goals_device from r_max to n < 0, in the header's order (both entry points; their params share these fields)
-static int reach_clauses(double r_max, double r_avoid, double z_lo, double z_hi, int want, int max_hops, const fh_voxel_grid* map_grid,
-                         const unsigned* d_map_bits, const fh_voxel_grid* grid, size_t view_stride, int n_views, int n) {
+// the clauses of fh_reach_goals_device from r_max to max_hops < 0, in the header's order (the fields that all three params share)
+static int reach_field_clauses(double r_max, double r_avoid, double z_lo, double z_hi, int want, int max_hops) {
   if (!std::isfinite(r_max) || !(r_max > 0.0)) return FH_ERR_ARG;
   if (!std::isfinite(r_avoid) || !(r_avoid >= 0.0)) return FH_ERR_ARG;
   if (std::isnan(z_lo) || std::isnan(z_hi) || z_lo > z_hi) return FH_ERR_ARG;
   const int all_wants = FH_FRONTIER_WANT_REACHED | FH_FRONTIER_WANT_NO_PATH | FH_FRONTIER_WANT_ALL;
   if (want == 0 || (want & ~all_wants) != 0) return FH_ERR_ARG;
   if (max_hops < 0) return FH_ERR_ARG;
+  return FH_OK;
+}
+
+// and its clauses from map_grid to n < 0 (fh_gain_goals_device has clauses of its own between the two)
+static int reach_table_clauses(const fh_voxel_grid* map_grid, const unsigned* d_map_bits, const fh_voxel_grid* grid, size_t view_stride, int n_views,
+                               int n) {
   if (!fhh::voxel_grid_ok(map_grid)) return FH_ERR_ARG;
   const long long map_xy = (long long)map_grid->dims[0] * map_grid->dims[1];
   if (map_xy > 0x7fffffffll || map_xy * map_grid->dims[2] > 0x7fffffffll) return FH_ERR_ARG;
@@ -42,6 +50,13 @@ static int reach_clauses(double r_max, double r_avoid, double z_lo, double z_hi,
   if (reach_lattice(grid, view_stride, n_views, &cells) != FH_OK) return FH_ERR_ARG;
   if (n < 0) return FH_ERR_ARG;
   return FH_OK;
+}
+
+// the clauses of fh_reach_goals_device from r_max to n < 0, in the header's order (it and fh_spread_goals_device)
+static int reach_clauses(double r_max, double r_avoid, double z_lo, double z_hi, int want, int max_hops, const fh_voxel_grid* map_grid,
+                         const unsigned* d_map_bits, const fh_voxel_grid* grid, size_t view_stride, int n_views, int n) {
+  if (reach_field_clauses(r_max, r_avoid, z_lo, z_hi, want, max_hops) != FH_OK) return FH_ERR_ARG;
+  return reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n);
 }
 
 // the kernel's arguments from checked values (the outputs are the caller's to set)
@@ -134,6 +149,37 @@ int fh_spread_goals_device(void* stream, const fh_spread_params* par, const fh_v
     s.pass = p;
     hipLaunchKernelGGL(fhp::spread_goals_kernel, dim3((unsigned)n), dim3(256), 0, q, s);
   }
+  return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
+}
+
+int fh_gain_goals_device(void* stream, const fh_gain_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                         const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                         const fh_vehicle* d_vehicles, int n, double* d_goals, int32_t* d_mask, fh_gain_record* d_records) {
+  if (!par) return FH_ERR_ARG;
+  if (reach_field_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
+  if (par->gain_radius < 0 || par->gain_radius > FH_GAIN_MAX_RADIUS) return FH_ERR_ARG;
+  if (par->hop_cost < 0 || par->hop_cost > FH_GAIN_MAX_HOP_COST) return FH_ERR_ARG;
+  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
+  if (n == 0) return FH_OK;
+  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  hipPointerAttribute_t where;
+  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  fhh::DeviceScope scope(where.device);
+  if (!scope.ok) return FH_ERR_DEVICE;
+  fhp::GainArgs s;
+  reach_args(s.r, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
+             d_view_of, n_views, d_vehicles);
+  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
+  s.g = par->gain_radius;
+  s.g2 = par->gain_radius * par->gain_radius;
+  s.hop_cost = par->hop_cost;
+  s.min_gain = par->min_gain;
+  s.records = d_records;
+  hipLaunchKernelGGL(fhp::gain_goals_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, s);
   return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
 }
 

@@ -47,6 +47,8 @@ free and next to unknown space as its new goal, on the device; coverage() counts
 explore_reachable() stands in explore()'s place (include/fasterhip_reach.h): of those voxels the one that a flood of the space the view
 knows to be free reaches in the fewest steps, never one behind a wall or in a sealed pocket.  explore_spread() is that chooser for a team
 (include/fasterhip_spread.h): a voxel nearer than r_spread to the goal a peer holds or has just been given is left to that peer.
+explore_gain() is explore_reachable() with a sense of what a goal is worth (include/fasterhip_gain.h): the unknown voxels near a
+candidate are weighed against the steps to it.
 
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
@@ -114,6 +116,7 @@ class Fleet:
         self.d_explore_goals = self.d_explore_mask = self.d_explore_records = self.d_explore_view_of = self.d_coverage = None   # explore, coverage
         self.d_reach_goals = self.d_reach_mask = self.d_reach_records = self.d_reach_view_of = None                            # explore_reachable
         self.d_spread_goals = self.d_spread_mask = self.d_spread_records = self.d_spread_work = None                           # explore_spread
+        self.d_gain_goals = self.d_gain_mask = self.d_gain_records = None                                                      # explore_gain
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -751,6 +754,49 @@ class Fleet:
         self.sync()
         return (self.d_spread_records.cpu().numpy().view(abi.spread_record_dtype).copy(), self.d_spread_goals.cpu().numpy().copy(),
                 self.d_spread_mask.cpu().numpy().copy())
+
+    def explore_gain(self, r_max, gain_radius, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0):
+        """explore_reachable() with the choice of include/fasterhip_gain.h: of the frontier voxels that the flood reaches the one with the
+        largest gain - hop_cost * hops, where the gain of a voxel is the number of unknown voxels of the view, inside the box of the
+        vehicle's sphere, within gain_radius voxels of it, and the hops are the steps of the flood; among equals the fewest hops, then
+        the smallest distance.  gain_radius is in voxels: sensor radius / res, rounded down, at most 31.  hop_cost: the unknown voxels
+        that one step is worth (0 .. 16384); min_gain: a voxel with a smaller gain is never chosen (gain_records() counts them as poor).
+        With gain_radius 0, hop_cost 1 and min_gain 0 it is explore_reachable().  The other arguments, the preconditions and the errors
+        are those of explore_reachable(); the buffers are its own (gain_records())."""
+        stages = self.explore_gain_stages(r_max, gain_radius, hop_cost, min_gain, r_avoid, z, want, max_hops)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_gain_stages(self, r_max, gain_radius, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0):
+        """The two launches of explore_gain(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        par = abi.default_gain_params(r_max, gain_radius)
+        par["hop_cost"], par["min_gain"] = hop_cost, min_gain
+        flags, stride, vo, n_views = self._reach_inputs("explore_gain", par, r_avoid, z, want, max_hops)
+        if self.d_gain_goals is None:
+            t = self.torch
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_gain_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_gain_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_gain_records = t.zeros(self.n * abi.gain_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            for d in (self.d_gain_goals, self.d_gain_mask, self.d_gain_records):
+                d.record_stream(self.stream)
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("gain_goals", lambda: m.gain_goals_device(par, self.grid, p(flags), stride, vo, n_views, p(self.d_vehicles), self.n,
+                                                       p(self.d_gain_goals), p(self.d_gain_mask), p(self.d_gain_records),
+                                                       self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_gain_goals), p(self.d_gain_mask), self.n)),
+        ]
+
+    def gain_records(self):
+        """(records [n] abi.gain_record_dtype, goals [n][3], mask [n] int32) of the last explore_gain() (synchronises)."""
+        if self.d_gain_goals is None:
+            raise capi.FasterHipError("Fleet.gain_records: explore_gain first")
+        self.sync()
+        return (self.d_gain_records.cpu().numpy().view(abi.gain_record_dtype).copy(), self.d_gain_goals.cpu().numpy().copy(),
+                self.d_gain_mask.cpu().numpy().copy())
 
     def coverage_stages(self):
         """The one launch of coverage(): [(name, callable)]."""

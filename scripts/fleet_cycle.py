@@ -65,7 +65,13 @@ two passes instead of the default eight (the difference is what the idle launche
 before and after it in the same run; the vehicles decided per pass, those left UNSETTLED or in OVERFLOW, and the longest list of lower
 peers.  The peers are the vehicles of one view: with a view per vehicle nobody has one, unless --link RANGE is given too — then the
 vehicles are linked once after the first look, with the first RANGE, and the groups of that link are the teams.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD]]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--gain G [--hop-cost K] [--min-gain M] (with --views --explore R_MAX --reach, not with --spread) runs that loop with Fleet.explore_gain in
+the place of Fleet.explore_reachable (include/fasterhip_gain.h; G in voxels, K default 1, M default 0): the stage is reported as
+"gain_goals"; with every vehicle wanted as "gain_goals_all_ms", beside reach_goals with every vehicle wanted before and after it in the same
+run; and, of that launch, the candidates evaluated per searched vehicle (the reachable ones), the levels of the flood (every level with a
+candidate costs a second barrier: at most min(levels + 1, reachable) of them), the gains, the poor candidates, and the vehicles whose
+choice is not the one of reach_goals.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD | --gain G [--hop-cost K] [--min-gain M]]]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -92,6 +98,11 @@ if REACH and not ("--views" in sys.argv and EXPLORE is not None):
 SPREAD = float(sys.argv[sys.argv.index("--spread") + 1]) if "--spread" in sys.argv else None
 if SPREAD is not None and not REACH:
     sys.exit("--spread needs --views --explore R_MAX --reach")
+GAIN = int(sys.argv[sys.argv.index("--gain") + 1]) if "--gain" in sys.argv else None
+HOP_COST = int(sys.argv[sys.argv.index("--hop-cost") + 1]) if "--hop-cost" in sys.argv else 1
+MIN_GAIN = int(sys.argv[sys.argv.index("--min-gain") + 1]) if "--min-gain" in sys.argv else 0
+if GAIN is not None and (not REACH or SPREAD is not None):
+    sys.exit("--gain needs --views --explore R_MAX --reach, without --spread")
 
 
 def timed_audit(fl, cycles):
@@ -301,13 +312,16 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     fl.enable_heading(yaw0=np.arctan2(u[:, 1], u[:, 0]))
     fl.sense(r_sense)
     first = fl.coverage()
-    goal_stage = "spread_goals" if SPREAD is not None else "reach_goals" if REACH else "frontier_goals"
+    goal_stage = "spread_goals" if SPREAD is not None else "gain_goals" if GAIN is not None else "reach_goals" if REACH else "frontier_goals"
     explore_stages, explore_records = (fl.explore_reachable_stages, fl.reach_records) if REACH else (fl.explore_stages, fl.explore_records)
     if SPREAD is not None:
         if LINK:   # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
             fl.link(LINK[0])
         explore_stages, explore_records = (lambda r, **kw: fl.explore_spread_stages(r, SPREAD, **kw)), fl.spread_records
         fl.explore_spread(r_max, SPREAD)
+    elif GAIN is not None:
+        explore_stages, explore_records = (lambda r, **kw: fl.explore_gain_stages(r, GAIN, HOP_COST, MIN_GAIN, **kw)), fl.gain_records
+        fl.explore_gain(r_max, GAIN, HOP_COST, MIN_GAIN)
     else:
         (fl.explore_reachable if REACH else fl.explore)(r_max)
     fl.replan()
@@ -371,6 +385,24 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                       "claimed_vehicles": int((sr["claimed"] > 0).sum()), "lower_max": int(sr["lower"].max()), "claims_max": int(sr["claims"].max()),
                       "groups": int(len(np.unique(sr["group"]))), "spread_found_all": int((sr["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
                       "same_cell_as_reach_goals": int((sr["cell"] == rr["cell"]).sum())})
+    if GAIN is not None:   # every vehicle wanted, applied to nobody, with reach_goals after it again
+        reps = max(cycles, 3)
+        gain_ms = fenced_ms(fl, explore_stages(r_max, want="all")[0][1], reps)
+        gr = fl.gain_records()[0]
+        again_ms = fenced_ms(fl, fl.explore_reachable_stages(r_max, want="all")[0][1], reps)
+        both = (gr["cell"] >= 0) & (rr["cell"] >= 0)
+        chosen = gr["cell"] >= 0
+        reach.update({"gain_radius": GAIN, "hop_cost": HOP_COST, "min_gain": MIN_GAIN, "gain_goals_reached_ms": med["gain_goals"],
+                      "gain_goals_all_ms": float(np.median(gain_ms)), "gain_goals_all_runs_ms": [float(x) for x in gain_ms],
+                      "reach_goals_all_after_ms": float(np.median(again_ms)), "reach_goals_all_after_runs_ms": [float(x) for x in again_ms],
+                      "gain_found_all": int(chosen.sum()), "evaluated_mean": float(gr["reachable"][hit].mean()) if hit.any() else 0.0,
+                      "evaluated_max": int(gr["reachable"].max()), "evaluated_total": int(gr["reachable"].sum()),
+                      "levels_with_candidates_bound_mean": float(np.minimum(gr["levels"] + 1, gr["reachable"])[hit].mean()) if hit.any() else 0.0,
+                      "gain_mean": float(gr["gain"][chosen].mean()) if chosen.any() else -1.0, "gain_max": int(gr["best_gain"].max()),
+                      "gain_hops_mean": float(gr["hops"][chosen].mean()) if chosen.any() else -1.0,
+                      "poor_total": int(gr["poor"].sum()), "all_poor": int((gr["flags"] & abi.FH_GAIN_ALL_POOR != 0).sum()),
+                      "same_first_40_bytes_counts": bool(all(np.array_equal(gr[k], rr[k]) for k in ("candidates", "reachable", "reached", "levels"))),
+                      "other_cell_than_reach_goals": int((gr["cell"][both] != rr["cell"][both]).sum()), "chosen_by_both": int(both.sum())})
     return {"r_max": r_max, "goal_stage": goal_stage, **reach, "stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "wanted_per_cycle": wanted, "found_per_cycle": found,
             "frontier_goals_reached_ms": med.get("frontier_goals"), "frontier_goals_all_ms": float(np.median(all_ms)),
             "frontier_goals_all_runs_ms": [float(x) for x in all_ms], "found_all": int((rec["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
@@ -619,6 +651,10 @@ def main():
     if "--spread" in argv:       # (read into SPREAD above)
         k = argv.index("--spread")
         del argv[k:k + 2]
+    for opt in ("--gain", "--hop-cost", "--min-gain"):   # (read into GAIN, HOP_COST, MIN_GAIN above)
+        if opt in argv:
+            k = argv.index(opt)
+            del argv[k:k + 2]
     if "--traffic-timed" in argv:
         k = argv.index("--traffic-timed")
         window = int(argv[k + 1])
