@@ -310,6 +310,33 @@ def default_gain_params(r_max, gain_radius):
     return p
 
 
+# fh_team_params, fh_team_record: the gain-aware chooser for a team, the space a peer's claim covers not counted twice
+# (include/fasterhip_team.h); the first 64 bytes of the record are fh_spread_record's, its flags those of that record and
+# FH_TEAM_ALL_POOR (FH_GAIN_ALL_POOR is FH_SPREAD_OVERFLOW's bit); the other constants are those two headers' under the header's names
+FH_TEAM_OVERFLOW, FH_TEAM_UNSETTLED, FH_TEAM_CLAIMED, FH_TEAM_ALL_POOR = 128, 256, 512, 1024
+FH_TEAM_LIST, FH_TEAM_MAX_PASSES, FH_TEAM_DEFAULT_PASSES, FH_TEAM_MAX_RADIUS, FH_TEAM_MAX_HOP_COST = 32, 64, 8, 31, 16384
+team_params_dtype = np.dtype([("r_max", "<f8"), ("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                              ("r_spread", "<f8"), ("passes", "<i4"), ("gain_radius", "<i4"), ("hop_cost", "<i4"), ("min_gain", "<i4"),
+                              ("claim_radius", "<i4"), ("reserved", "<i4", (3,))], align=True)
+team_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("hops", "<i4"), ("candidates", "<i4"),
+                              ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("d2", "<f8"), ("group", "<i4"),
+                              ("decided_pass", "<i4"), ("lower", "<i4"), ("claims", "<i4"), ("claimed", "<i4"), ("reserved0", "<i4"),
+                              ("gain", "<i4"), ("utility", "<i4"), ("poor", "<i4"), ("best_gain", "<i4"), ("covered", "<i4"),
+                              ("reserved", "<i4", (3,))], align=True)
+assert (team_params_dtype.itemsize, team_record_dtype.itemsize) == (80, 96)
+
+
+def default_team_params(r_max, r_spread, gain_radius, claim_radius=None):
+    """fh_team_params: default_spread_params and default_gain_params together, and a claim that covers the ball of claim_radius voxels
+    around it (None: gain_radius, what the peer's own gain counted; -1: claims cover nothing)."""
+    p = np.zeros((), dtype=team_params_dtype)
+    p["r_max"], p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"] = r_max, 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0
+    p["r_spread"], p["passes"] = r_spread, FH_TEAM_DEFAULT_PASSES
+    p["gain_radius"], p["hop_cost"], p["min_gain"] = gain_radius, 1, 0
+    p["claim_radius"] = gain_radius if claim_radius is None else claim_radius
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

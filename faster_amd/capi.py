@@ -58,6 +58,8 @@ REACH_SYMBOLS = ["fh_reach_goals_device"]
 SPREAD_SYMBOLS = ["fh_spread_work_bytes", "fh_spread_goals_device"]
 # include/fasterhip_gain.h
 GAIN_SYMBOLS = ["fh_gain_goals_device"]
+# include/fasterhip_team.h
+TEAM_SYMBOLS = ["fh_team_goals_device"]
 
 _LIB = None
 
@@ -339,6 +341,8 @@ def lib():
         L.fh_spread_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
         L.fh_gain_goals_device.restype = i32
         L.fh_gain_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, vp, vp]
+        L.fh_team_goals_device.restype = i32
+        L.fh_team_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -616,6 +620,23 @@ class Map:
                                         d_view_of, int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records)
         if rc != 0:
             raise FasterHipError("fh_gain_goals_device: rc=%d" % rc)
+
+    def team_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_group, d_vehicles, n, d_work, work_bytes, d_goals, d_mask,
+                          d_records, stream):
+        """fh_team_goals_device (include/fasterhip_team.h) with this map's lattice and bits: gain_goals_device's utility inside
+        spread_goals_device's passes — a candidate nearer than par["r_spread"] to a peer's claim is not chosen, and the unknown voxels
+        within par["claim_radius"] voxels of a claim's voxel are counted in no gain.  The arguments are spread_goals_device's, with
+        d_records [n] abi.team_record_dtype and par one abi.team_params_dtype record; d_work: work_bytes >= fh_spread_work_bytes(n)."""
+        p = _one_record(par, "team", "team_goals_device")
+        g = _grid_record(grid)
+        dims, origin = self.dims()
+        bits, res = ctypes.c_void_p(), ctypes.c_double()
+        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
+        mg = _grid_record((origin, res.value, dims))
+        rc = lib().fh_team_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
+                                        d_view_of, int(n_views), d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
+        if rc != 0:
+            raise FasterHipError("fh_team_goals_device: rc=%d" % rc)
 
     def view_coverage_device(self, grid, d_flags, view_stride, n_views, d_out):
         """fh_map_view_coverage_device: d_out [n_views] abi.view_coverage_dtype, the known voxels (flag 0) of every view and those of

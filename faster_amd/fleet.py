@@ -117,6 +117,7 @@ class Fleet:
         self.d_reach_goals = self.d_reach_mask = self.d_reach_records = self.d_reach_view_of = None                            # explore_reachable
         self.d_spread_goals = self.d_spread_mask = self.d_spread_records = self.d_spread_work = None                           # explore_spread
         self.d_gain_goals = self.d_gain_mask = self.d_gain_records = None                                                      # explore_gain
+        self.d_team_goals = self.d_team_mask = self.d_team_records = self.d_team_work = None                                   # explore_team
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -797,6 +798,61 @@ class Fleet:
         self.sync()
         return (self.d_gain_records.cpu().numpy().view(abi.gain_record_dtype).copy(), self.d_gain_goals.cpu().numpy().copy(),
                 self.d_gain_mask.cpu().numpy().copy())
+
+    def explore_team(self, r_max, r_spread, gain_radius, claim_radius=None, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached",
+                     max_hops=0, passes=None, groups="link"):
+        """explore_gain() for a team (include/fasterhip_team.h): explore_gain()'s utility inside explore_spread()'s passes.  The goal
+        that a peer is on its way to, or that a peer with a lower index has been given by an earlier pass, removes the candidates
+        nearer than r_spread to it and, from every gain, the unknown voxels within claim_radius voxels of its voxel, which that peer's
+        sensor will uncover anyway (None: gain_radius; -1: claims cover nothing; at most 31).  Two teammates before one hall get goals
+        whose balls do not count the same voxels twice.  gain_radius, hop_cost and min_gain are explore_gain()'s, passes and groups
+        explore_spread()'s; the other arguments, the preconditions and the errors are those of explore_reachable(); the buffers and
+        the workspace are its own (team_records())."""
+        stages = self.explore_team_stages(r_max, r_spread, gain_radius, claim_radius, hop_cost, min_gain, r_avoid, z, want, max_hops, passes,
+                                          groups)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_team_stages(self, r_max, r_spread, gain_radius, claim_radius=None, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached",
+                            max_hops=0, passes=None, groups="link"):
+        """The launches of explore_team(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them one by one)."""
+        if groups not in ("link", "view"):
+            raise capi.FasterHipError("Fleet.explore_team: groups is \"link\" or \"view\", got %r" % (groups,))
+        par = abi.default_team_params(r_max, r_spread, gain_radius, claim_radius)
+        par["hop_cost"], par["min_gain"] = hop_cost, min_gain
+        flags, stride, vo, n_views = self._reach_inputs("explore_team", par, r_avoid, z, want, max_hops)   # (set_unknown's one grid: one team)
+        if passes is not None:
+            par["passes"] = passes
+        work_bytes = int(capi.lib().fh_spread_work_bytes(self.n))
+        if self.d_team_goals is None:
+            t = self.torch
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_team_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_team_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_team_records = t.zeros(self.n * abi.team_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+                self.d_team_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
+            for d in (self.d_team_goals, self.d_team_mask, self.d_team_records, self.d_team_work):
+                d.record_stream(self.stream)
+        # the labels are per view: with set_unknown's single view there is nothing to label
+        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
+            and self.d_link_labels.numel() == n_views else None
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("team_goals", lambda: m.team_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if labels is None else p(labels),
+                                                       p(self.d_vehicles), self.n, p(self.d_team_work), work_bytes, p(self.d_team_goals),
+                                                       p(self.d_team_mask), p(self.d_team_records), self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_team_goals), p(self.d_team_mask), self.n)),
+        ]
+
+    def team_records(self):
+        """(records [n] abi.team_record_dtype, goals [n][3], mask [n] int32) of the last explore_team() (synchronises)."""
+        if self.d_team_goals is None:
+            raise capi.FasterHipError("Fleet.team_records: explore_team first")
+        self.sync()
+        return (self.d_team_records.cpu().numpy().view(abi.team_record_dtype).copy(), self.d_team_goals.cpu().numpy().copy(),
+                self.d_team_mask.cpu().numpy().copy())
 
     def coverage_stages(self):
         """The one launch of coverage(): [(name, callable)]."""

@@ -65,13 +65,17 @@ two passes instead of the default eight (the difference is what the idle launche
 before and after it in the same run; the vehicles decided per pass, those left UNSETTLED or in OVERFLOW, and the longest list of lower
 peers.  The peers are the vehicles of one view: with a view per vehicle nobody has one, unless --link RANGE is given too — then the
 vehicles are linked once after the first look, with the first RANGE, and the groups of that link are the teams.
---gain G [--hop-cost K] [--min-gain M] (with --views --explore R_MAX --reach, not with --spread) runs that loop with Fleet.explore_gain in
+--gain G [--hop-cost K] [--min-gain M] (with --views --explore R_MAX --reach) runs that loop with Fleet.explore_gain in
 the place of Fleet.explore_reachable (include/fasterhip_gain.h; G in voxels, K default 1, M default 0): the stage is reported as
 "gain_goals"; with every vehicle wanted as "gain_goals_all_ms", beside reach_goals with every vehicle wanted before and after it in the same
 run; and, of that launch, the candidates evaluated per searched vehicle (the reachable ones), the levels of the flood (every level with a
 candidate costs a second barrier: at most min(levels + 1, reachable) of them), the gains, the poor candidates, and the vehicles whose
 choice is not the one of reach_goals.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD | --gain G [--hop-cost K] [--min-gain M]]]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--spread R_SPREAD together with --gain G [--claim-radius R] runs that loop with Fleet.explore_team (include/fasterhip_team.h; R in voxels,
+default G): the stage is reported as "team_goals"; with every vehicle wanted as "team_goals_all_ms", beside gain_goals and spread_goals
+with every vehicle wanted in the same run, alternating; the vehicles decided per pass, those left UNSETTLED or in OVERFLOW, the mean of
+`covered` over the searched vehicles, and the teammates that hold the same goal voxel.  --link RANGE makes the teams, as for --spread.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R]]]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -101,8 +105,12 @@ if SPREAD is not None and not REACH:
 GAIN = int(sys.argv[sys.argv.index("--gain") + 1]) if "--gain" in sys.argv else None
 HOP_COST = int(sys.argv[sys.argv.index("--hop-cost") + 1]) if "--hop-cost" in sys.argv else 1
 MIN_GAIN = int(sys.argv[sys.argv.index("--min-gain") + 1]) if "--min-gain" in sys.argv else 0
-if GAIN is not None and (not REACH or SPREAD is not None):
-    sys.exit("--gain needs --views --explore R_MAX --reach, without --spread")
+if GAIN is not None and not REACH:
+    sys.exit("--gain needs --views --explore R_MAX --reach")
+TEAM = SPREAD is not None and GAIN is not None   # both: Fleet.explore_team
+CLAIM_RADIUS = int(sys.argv[sys.argv.index("--claim-radius") + 1]) if "--claim-radius" in sys.argv else None
+if CLAIM_RADIUS is not None and not TEAM:
+    sys.exit("--claim-radius needs --spread R_SPREAD and --gain G")
 
 
 def timed_audit(fl, cycles):
@@ -312,9 +320,16 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     fl.enable_heading(yaw0=np.arctan2(u[:, 1], u[:, 0]))
     fl.sense(r_sense)
     first = fl.coverage()
-    goal_stage = "spread_goals" if SPREAD is not None else "gain_goals" if GAIN is not None else "reach_goals" if REACH else "frontier_goals"
+    goal_stage = "team_goals" if TEAM else "spread_goals" if SPREAD is not None else "gain_goals" if GAIN is not None else "reach_goals" if REACH \
+        else "frontier_goals"
     explore_stages, explore_records = (fl.explore_reachable_stages, fl.reach_records) if REACH else (fl.explore_stages, fl.explore_records)
-    if SPREAD is not None:
+    if TEAM:
+        if LINK:   # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
+            fl.link(LINK[0])
+        explore_stages = lambda r, **kw: fl.explore_team_stages(r, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN, **kw)   # noqa: E731
+        explore_records = fl.team_records
+        fl.explore_team(r_max, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN)
+    elif SPREAD is not None:
         if LINK:   # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
             fl.link(LINK[0])
         explore_stages, explore_records = (lambda r, **kw: fl.explore_spread_stages(r, SPREAD, **kw)), fl.spread_records
@@ -367,7 +382,40 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                  "candidates_mean": float(rr["candidates"][hit].mean()) if hit.any() else 0.0,
                  "reachable_mean": float(rr["reachable"][hit].mean()) if hit.any() else 0.0,
                  "same_cell_as_frontier_goals": int((rr["cell"] == rec["cell"]).sum())}
-    if SPREAD is not None:   # every vehicle wanted, applied to nobody: all passes, and one pass (the difference: the idle launches)
+    if TEAM:   # every vehicle wanted, applied to nobody: team_goals, gain_goals and spread_goals in turn, a median each
+        reps = max(cycles, 5)
+        runs = {"team_goals": [], "gain_goals": [], "spread_goals": []}
+        launches = {"team_goals": explore_stages(r_max, want="all")[0][1],
+                    "gain_goals": fl.explore_gain_stages(r_max, GAIN, HOP_COST, MIN_GAIN, want="all")[0][1],
+                    "spread_goals": fl.explore_spread_stages(r_max, SPREAD, want="all")[0][1]}
+        for _ in range(reps):
+            for name, launch in launches.items():
+                runs[name] += fenced_ms(fl, launch, 1)
+        tr, t_goals, _ = fl.team_records()
+        gr, sr = fl.gain_records()[0], fl.spread_records()[0]
+        searched = tr["decided_pass"] > 0
+        passes = np.bincount(tr["decided_pass"][searched], minlength=2)
+
+        def shared_goals(r):   # teammates (one group) that hold the same goal voxel
+            held = r["cell"] >= 0
+            keys = np.stack([tr["group"][held].astype(np.int64), r["cell"][held].astype(np.int64)], axis=1)
+            _, counts = np.unique(keys, axis=0, return_counts=True) if len(keys) else (None, np.zeros(0, dtype=np.int64))
+            return int((counts - 1).sum())
+
+        reach.update({"r_spread": SPREAD, "gain_radius": GAIN, "claim_radius": GAIN if CLAIM_RADIUS is None else CLAIM_RADIUS, "hop_cost": HOP_COST,
+                      "min_gain": MIN_GAIN, "passes": abi.FH_TEAM_DEFAULT_PASSES, "team_goals_reached_ms": med["team_goals"],
+                      "team_goals_all_ms": float(np.median(runs["team_goals"])), "team_goals_all_runs_ms": [float(x) for x in runs["team_goals"]],
+                      "gain_goals_all_ms": float(np.median(runs["gain_goals"])), "gain_goals_all_runs_ms": [float(x) for x in runs["gain_goals"]],
+                      "spread_goals_all_ms": float(np.median(runs["spread_goals"])), "spread_goals_all_runs_ms": [float(x) for x in runs["spread_goals"]],
+                      "decided_per_pass": passes[1:].tolist(), "unsettled": int((tr["flags"] & abi.FH_TEAM_UNSETTLED != 0).sum()),
+                      "overflow": int((tr["flags"] & abi.FH_TEAM_OVERFLOW != 0).sum()), "spread_overflow": int((sr["flags"] & abi.FH_SPREAD_OVERFLOW != 0).sum()),
+                      "lower_max": int(tr["lower"].max()), "claims_max": int(tr["claims"].max()), "groups": int(len(np.unique(tr["group"]))),
+                      "covered_mean": float(tr["covered"][searched].mean()) if searched.any() else 0.0, "covered_max": int(tr["covered"].max()),
+                      "team_found_all": int((tr["cell"] >= 0).sum()), "gain_found_all": int((gr["cell"] >= 0).sum()),
+                      "team_gain_mean": float(tr["gain"][tr["cell"] >= 0].mean()) if (tr["cell"] >= 0).any() else -1.0,
+                      "all_poor": int((tr["flags"] & abi.FH_TEAM_ALL_POOR != 0).sum()),
+                      "same_goal_voxel_team": shared_goals(tr), "same_goal_voxel_gain": shared_goals(gr)})
+    elif SPREAD is not None:   # every vehicle wanted, applied to nobody: all passes, and one pass (the difference: the idle launches)
         reps = max(cycles, 3)
         spread_ms = fenced_ms(fl, explore_stages(r_max, want="all")[0][1], reps)
         sr = fl.spread_records()[0]
@@ -385,7 +433,7 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                       "claimed_vehicles": int((sr["claimed"] > 0).sum()), "lower_max": int(sr["lower"].max()), "claims_max": int(sr["claims"].max()),
                       "groups": int(len(np.unique(sr["group"]))), "spread_found_all": int((sr["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
                       "same_cell_as_reach_goals": int((sr["cell"] == rr["cell"]).sum())})
-    if GAIN is not None:   # every vehicle wanted, applied to nobody, with reach_goals after it again
+    if GAIN is not None and not TEAM:   # every vehicle wanted, applied to nobody, with reach_goals after it again
         reps = max(cycles, 3)
         gain_ms = fenced_ms(fl, explore_stages(r_max, want="all")[0][1], reps)
         gr = fl.gain_records()[0]
@@ -651,7 +699,7 @@ def main():
     if "--spread" in argv:       # (read into SPREAD above)
         k = argv.index("--spread")
         del argv[k:k + 2]
-    for opt in ("--gain", "--hop-cost", "--min-gain"):   # (read into GAIN, HOP_COST, MIN_GAIN above)
+    for opt in ("--gain", "--hop-cost", "--min-gain", "--claim-radius"):   # (read into GAIN, HOP_COST, MIN_GAIN, CLAIM_RADIUS above)
         if opt in argv:
             k = argv.index(opt)
             del argv[k:k + 2]
