@@ -337,6 +337,26 @@ def default_team_params(r_max, r_spread, gain_radius, claim_radius=None):
     return p
 
 
+# fh_sight_params, fh_sight_record: the gain chooser with a gain that counts only the unknown voxels a candidate has a line of sight to
+# (include/fasterhip_sight.h); the params are fh_gain_params field by field, the record is fh_gain_record through best_gain, then
+# ball_gain (the count without the test of sight) and walls; the constants are that header's under this header's names
+FH_SIGHT_MAX_RADIUS, FH_SIGHT_MAX_HOP_COST, FH_SIGHT_ALL_POOR = 31, 16384, 128
+sight_params_dtype = np.dtype([("r_max", "<f8"), ("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                               ("gain_radius", "<i4"), ("hop_cost", "<i4"), ("min_gain", "<i4"), ("reserved", "<i4", (3,))], align=True)
+sight_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("hops", "<i4"), ("candidates", "<i4"),
+                               ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("d2", "<f8"), ("gain", "<i4"), ("utility", "<i4"),
+                               ("poor", "<i4"), ("best_gain", "<i4"), ("ball_gain", "<i4"), ("walls", "<i4")], align=True)
+assert (sight_params_dtype.itemsize, sight_record_dtype.itemsize) == (64, 64)
+
+
+def default_sight_params(r_max, gain_radius):
+    """fh_sight_params: default_gain_params under this header's name (hop_cost 1, min_gain 0)."""
+    p = np.zeros((), dtype=sight_params_dtype)
+    p["r_max"], p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"] = r_max, 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0
+    p["gain_radius"], p["hop_cost"], p["min_gain"] = gain_radius, 1, 0
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

@@ -60,6 +60,8 @@ SPREAD_SYMBOLS = ["fh_spread_work_bytes", "fh_spread_goals_device"]
 GAIN_SYMBOLS = ["fh_gain_goals_device"]
 # include/fasterhip_team.h
 TEAM_SYMBOLS = ["fh_team_goals_device"]
+# include/fasterhip_sight.h
+SIGHT_SYMBOLS = ["fh_sight_goals_device"]
 
 _LIB = None
 
@@ -343,6 +345,8 @@ def lib():
         L.fh_gain_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, vp, vp]
         L.fh_team_goals_device.restype = i32
         L.fh_team_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
+        L.fh_sight_goals_device.restype = i32
+        L.fh_sight_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -637,6 +641,22 @@ class Map:
                                         d_view_of, int(n_views), d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
         if rc != 0:
             raise FasterHipError("fh_team_goals_device: rc=%d" % rc)
+
+    def sight_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_goals, d_mask, d_records, stream):
+        """fh_sight_goals_device (include/fasterhip_sight.h) with this map's lattice and bits: gain_goals_device with a gain that counts an
+        unknown voxel of the ball only if the straight line of voxels from the candidate to it crosses no voxel that is known and
+        occupied in this map (or outside it).  d_records [n] abi.sight_record_dtype; par: one abi.sight_params_dtype record; `stream` as
+        for reach_goals_device."""
+        p = _one_record(par, "sight", "sight_goals_device")
+        g = _grid_record(grid)
+        dims, origin = self.dims()
+        bits, res = ctypes.c_void_p(), ctypes.c_double()
+        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
+        mg = _grid_record((origin, res.value, dims))
+        rc = lib().fh_sight_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
+                                         d_view_of, int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records)
+        if rc != 0:
+            raise FasterHipError("fh_sight_goals_device: rc=%d" % rc)
 
     def view_coverage_device(self, grid, d_flags, view_stride, n_views, d_out):
         """fh_map_view_coverage_device: d_out [n_views] abi.view_coverage_dtype, the known voxels (flag 0) of every view and those of

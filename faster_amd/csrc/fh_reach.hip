@@ -3,21 +3,25 @@
 // that chooser for a team, goals claimed by peers avoided (kernels: fh_spread.hip.hpp), and of include/fasterhip_gain.h
 // (fh_gain_goals_device): the reachable frontier voxel with the most unknown space around it for its steps (kernel: fh_gain.hip.hpp),
 // and of include/fasterhip_team.h (fh_team_goals_device): that utility inside the passes of the chooser for a team, the space a peer's
-// claim covers not counted twice (kernels: fh_team.hip.hpp).
+// claim covers not counted twice (kernels: fh_team.hip.hpp), and of include/fasterhip_sight.h (fh_sight_goals_device): the gain chooser
+// with a gain that counts only the unknown voxels a candidate has a line of sight to (kernel: fh_sight.hip.hpp).
 // A translation unit of its own: fh_map.hip and fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 
 #include "../../include/fasterhip.h"
 #include "../../include/fasterhip_reach.h"
 #include "../../include/fasterhip_spread.h"
 #include "../../include/fasterhip_gain.h"
 #include "../../include/fasterhip_team.h"
+#include "../../include/fasterhip_sight.h"
 #include "fh_reach.hip.hpp"
 #include "fh_spread.hip.hpp"
 #include "fh_gain.hip.hpp"
 #include "fh_team.hip.hpp"
+#include "fh_sight.hip.hpp"
 #include "fh_host.hpp"
 
 // the lattice of the views, judged as fh_map_frontier_goals_device judges it (0: fine, cells filled in)
@@ -184,6 +188,45 @@ int fh_gain_goals_device(void* stream, const fh_gain_params* par, const fh_voxel
   s.min_gain = par->min_gain;
   s.records = d_records;
   hipLaunchKernelGGL(fhp::gain_goals_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, s);
+  return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
+}
+
+// (before fh_team_goals_device, whose three launches end this file)
+int fh_sight_goals_device(void* stream, const fh_sight_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                          const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                          const fh_vehicle* d_vehicles, int n, double* d_goals, int32_t* d_mask, fh_sight_record* d_records) {
+  static_assert(FH_SIGHT_MAX_RADIUS == FH_GAIN_MAX_RADIUS && FH_SIGHT_MAX_HOP_COST == FH_GAIN_MAX_HOP_COST && FH_SIGHT_ALL_POOR == FH_GAIN_ALL_POOR,
+                "the constants that include/fasterhip_sight.h shares with K17");
+  static_assert(sizeof(fh_sight_params) == sizeof(fh_gain_params) && offsetof(fh_sight_params, min_gain) == offsetof(fh_gain_params, min_gain) &&
+                    sizeof(fh_sight_record) == sizeof(fh_gain_record) && offsetof(fh_sight_record, best_gain) == offsetof(fh_gain_record, best_gain) &&
+                    offsetof(fh_sight_record, ball_gain) == 56 && offsetof(fh_sight_record, walls) == 60,
+                "include/fasterhip_sight.h: K17's params, and K17's record through best_gain");
+  if (!par) return FH_ERR_ARG;
+  if (reach_field_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
+  if (par->gain_radius < 0 || par->gain_radius > FH_SIGHT_MAX_RADIUS) return FH_ERR_ARG;
+  if (par->hop_cost < 0 || par->hop_cost > FH_SIGHT_MAX_HOP_COST) return FH_ERR_ARG;
+  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
+  if (n == 0) return FH_OK;
+  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  hipPointerAttribute_t where;
+  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  fhh::DeviceScope scope(where.device);
+  if (!scope.ok) return FH_ERR_DEVICE;
+  fhp::SightArgs s;
+  reach_args(s.gn.r, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
+             d_view_of, n_views, d_vehicles);
+  s.gn.r.goals = d_goals; s.gn.r.mask = d_mask; s.gn.r.records = nullptr;
+  s.gn.g = par->gain_radius;
+  s.gn.g2 = par->gain_radius * par->gain_radius;
+  s.gn.hop_cost = par->hop_cost;
+  s.gn.min_gain = par->min_gain;
+  s.gn.records = nullptr;
+  s.records = d_records;
+  hipLaunchKernelGGL(fhp::sight_goals_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, s);
   return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
 }
 

@@ -48,7 +48,8 @@ explore_reachable() stands in explore()'s place (include/fasterhip_reach.h): of 
 knows to be free reaches in the fewest steps, never one behind a wall or in a sealed pocket.  explore_spread() is that chooser for a team
 (include/fasterhip_spread.h): a voxel nearer than r_spread to the goal a peer holds or has just been given is left to that peer.
 explore_gain() is explore_reachable() with a sense of what a goal is worth (include/fasterhip_gain.h): the unknown voxels near a
-candidate are weighed against the steps to it.
+candidate are weighed against the steps to it.  explore_sight() is explore_gain() with the sensor's occlusion
+(include/fasterhip_sight.h): an unknown voxel counts only if no voxel known to be occupied lies on the line from the candidate to it.
 
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
@@ -118,6 +119,7 @@ class Fleet:
         self.d_spread_goals = self.d_spread_mask = self.d_spread_records = self.d_spread_work = None                           # explore_spread
         self.d_gain_goals = self.d_gain_mask = self.d_gain_records = None                                                      # explore_gain
         self.d_team_goals = self.d_team_mask = self.d_team_records = self.d_team_work = None                                   # explore_team
+        self.d_sight_goals = self.d_sight_mask = self.d_sight_records = None                                                   # explore_sight
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -798,6 +800,48 @@ class Fleet:
         self.sync()
         return (self.d_gain_records.cpu().numpy().view(abi.gain_record_dtype).copy(), self.d_gain_goals.cpu().numpy().copy(),
                 self.d_gain_mask.cpu().numpy().copy())
+
+    def explore_sight(self, r_max, gain_radius, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0):
+        """explore_gain() with a gain that the vehicle's sensor can deliver (include/fasterhip_sight.h): an unknown voxel of the ball
+        counts only if the straight line of voxels from the candidate to it crosses no voxel that the view knows and the map holds
+        occupied (or that lies outside the map); unknown voxels do not block.  A candidate beside a known wall is no longer promised
+        the hall behind it.  gain_radius is in voxels: sensor radius / res, rounded down, at most 31.  The arguments, the preconditions
+        and the errors are those of explore_gain(); the buffers are its own (sight_records()).  Where a vehicle's box holds no such
+        voxel the choice is explore_gain()'s."""
+        stages = self.explore_sight_stages(r_max, gain_radius, hop_cost, min_gain, r_avoid, z, want, max_hops)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_sight_stages(self, r_max, gain_radius, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0):
+        """The two launches of explore_sight(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        par = abi.default_sight_params(r_max, gain_radius)
+        par["hop_cost"], par["min_gain"] = hop_cost, min_gain
+        flags, stride, vo, n_views = self._reach_inputs("explore_sight", par, r_avoid, z, want, max_hops)
+        if self.d_sight_goals is None:
+            t = self.torch
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_sight_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_sight_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_sight_records = t.zeros(self.n * abi.sight_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            for d in (self.d_sight_goals, self.d_sight_mask, self.d_sight_records):
+                d.record_stream(self.stream)
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("sight_goals", lambda: m.sight_goals_device(par, self.grid, p(flags), stride, vo, n_views, p(self.d_vehicles), self.n,
+                                                         p(self.d_sight_goals), p(self.d_sight_mask), p(self.d_sight_records),
+                                                         self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_sight_goals), p(self.d_sight_mask), self.n)),
+        ]
+
+    def sight_records(self):
+        """(records [n] abi.sight_record_dtype, goals [n][3], mask [n] int32) of the last explore_sight() (synchronises)."""
+        if self.d_sight_goals is None:
+            raise capi.FasterHipError("Fleet.sight_records: explore_sight first")
+        self.sync()
+        return (self.d_sight_records.cpu().numpy().view(abi.sight_record_dtype).copy(), self.d_sight_goals.cpu().numpy().copy(),
+                self.d_sight_mask.cpu().numpy().copy())
 
     def explore_team(self, r_max, r_spread, gain_radius, claim_radius=None, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached",
                      max_hops=0, passes=None, groups="link"):

@@ -75,7 +75,12 @@ choice is not the one of reach_goals.
 default G): the stage is reported as "team_goals"; with every vehicle wanted as "team_goals_all_ms", beside gain_goals and spread_goals
 with every vehicle wanted in the same run, alternating; the vehicles decided per pass, those left UNSETTLED or in OVERFLOW, the mean of
 `covered` over the searched vehicles, and the teammates that hold the same goal voxel.  --link RANGE makes the teams, as for --spread.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R]]]]] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--sight together with --gain G (and without --spread) runs that loop with Fleet.explore_sight (include/fasterhip_sight.h): the stage is
+reported as "sight_goals"; with every vehicle wanted as "sight_goals_all_ms" beside "gain_goals_all_ms" in the same run, alternating;
+and, of that launch, the vehicles with a wall in their box, the walls per box, the chosen voxels that see less than their ball holds,
+and the vehicles whose choice is not the one of gain_goals.  --walls adds rooms to the world before anything reads it: planes of
+points every 5 m in x and in y, floor to ceiling, with a door of 1.2 m in every stretch of 5 m.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -111,6 +116,10 @@ TEAM = SPREAD is not None and GAIN is not None   # both: Fleet.explore_team
 CLAIM_RADIUS = int(sys.argv[sys.argv.index("--claim-radius") + 1]) if "--claim-radius" in sys.argv else None
 if CLAIM_RADIUS is not None and not TEAM:
     sys.exit("--claim-radius needs --spread R_SPREAD and --gain G")
+SIGHT = "--sight" in sys.argv
+if SIGHT and (GAIN is None or SPREAD is not None):
+    sys.exit("--sight needs --gain G and no --spread")
+WALLS = "--walls" in sys.argv
 
 
 def timed_audit(fl, cycles):
@@ -320,7 +329,7 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     fl.enable_heading(yaw0=np.arctan2(u[:, 1], u[:, 0]))
     fl.sense(r_sense)
     first = fl.coverage()
-    goal_stage = "team_goals" if TEAM else "spread_goals" if SPREAD is not None else "gain_goals" if GAIN is not None else "reach_goals" if REACH \
+    goal_stage = "team_goals" if TEAM else "spread_goals" if SPREAD is not None else "sight_goals" if SIGHT else "gain_goals" if GAIN is not None else "reach_goals" if REACH \
         else "frontier_goals"
     explore_stages, explore_records = (fl.explore_reachable_stages, fl.reach_records) if REACH else (fl.explore_stages, fl.explore_records)
     if TEAM:
@@ -334,6 +343,9 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
             fl.link(LINK[0])
         explore_stages, explore_records = (lambda r, **kw: fl.explore_spread_stages(r, SPREAD, **kw)), fl.spread_records
         fl.explore_spread(r_max, SPREAD)
+    elif SIGHT:
+        explore_stages, explore_records = (lambda r, **kw: fl.explore_sight_stages(r, GAIN, HOP_COST, MIN_GAIN, **kw)), fl.sight_records
+        fl.explore_sight(r_max, GAIN, HOP_COST, MIN_GAIN)
     elif GAIN is not None:
         explore_stages, explore_records = (lambda r, **kw: fl.explore_gain_stages(r, GAIN, HOP_COST, MIN_GAIN, **kw)), fl.gain_records
         fl.explore_gain(r_max, GAIN, HOP_COST, MIN_GAIN)
@@ -433,7 +445,30 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                       "claimed_vehicles": int((sr["claimed"] > 0).sum()), "lower_max": int(sr["lower"].max()), "claims_max": int(sr["claims"].max()),
                       "groups": int(len(np.unique(sr["group"]))), "spread_found_all": int((sr["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
                       "same_cell_as_reach_goals": int((sr["cell"] == rr["cell"]).sum())})
-    if GAIN is not None and not TEAM:   # every vehicle wanted, applied to nobody, with reach_goals after it again
+    if SIGHT:   # every vehicle wanted, applied to nobody: sight_goals and gain_goals in turn, a median each
+        reps = max(cycles, 5)
+        runs = {"sight_goals": [], "gain_goals": []}
+        launches = {"sight_goals": explore_stages(r_max, want="all")[0][1],
+                    "gain_goals": fl.explore_gain_stages(r_max, GAIN, HOP_COST, MIN_GAIN, want="all")[0][1]}
+        for _ in range(reps):
+            for name, launch in launches.items():
+                runs[name] += fenced_ms(fl, launch, 1)
+        sr, gr = fl.sight_records()[0], fl.gain_records()[0]
+        chosen, both = sr["cell"] >= 0, (sr["cell"] >= 0) & (gr["cell"] >= 0)
+        reach.update({"gain_radius": GAIN, "hop_cost": HOP_COST, "min_gain": MIN_GAIN, "sight_goals_reached_ms": med["sight_goals"],
+                      "sight_goals_all_ms": float(np.median(runs["sight_goals"])), "sight_goals_all_runs_ms": [float(x) for x in runs["sight_goals"]],
+                      "gain_goals_all_ms": float(np.median(runs["gain_goals"])), "gain_goals_all_runs_ms": [float(x) for x in runs["gain_goals"]],
+                      "sight_found_all": int(chosen.sum()), "gain_found_all": int((gr["cell"] >= 0).sum()),
+                      "evaluated_total": int(sr["reachable"].sum()), "evaluated_mean": float(sr["reachable"][hit].mean()) if hit.any() else 0.0,
+                      "vehicles_with_walls": int((sr["walls"] > 0).sum()), "walls_mean": float(sr["walls"][hit].mean()) if hit.any() else 0.0,
+                      "walls_max": int(sr["walls"].max()), "chosen_seeing_less_than_ball": int((sr["gain"][chosen] < sr["ball_gain"][chosen]).sum()),
+                      "sight_gain_mean": float(sr["gain"][chosen].mean()) if chosen.any() else -1.0,
+                      "sight_ball_gain_mean": float(sr["ball_gain"][chosen].mean()) if chosen.any() else -1.0,
+                      "gain_gain_mean": float(gr["gain"][gr["cell"] >= 0].mean()) if (gr["cell"] >= 0).any() else -1.0,
+                      "poor_total": int(sr["poor"].sum()), "all_poor": int((sr["flags"] & abi.FH_SIGHT_ALL_POOR != 0).sum()),
+                      "same_counts_as_gain_goals": bool(all(np.array_equal(sr[k], gr[k]) for k in ("candidates", "reachable", "reached", "levels"))),
+                      "other_cell_than_gain_goals": int((sr["cell"][both] != gr["cell"][both]).sum()), "chosen_by_both": int(both.sum())})
+    if GAIN is not None and not TEAM and not SIGHT:   # every vehicle wanted, applied to nobody, with reach_goals after it again
         reps = max(cycles, 3)
         gain_ms = fenced_ms(fl, explore_stages(r_max, want="all")[0][1], reps)
         gr = fl.gain_records()[0]
@@ -730,6 +765,18 @@ def main():
     cycles = int(args[1]) if len(args) > 1 else 3
     res, infl, zmax = 0.2, 0.3, 3.0
     cloud, cells, center, starts, goals, rng = frontend.forest_queries(B, 7, return_rng=True)
+    if WALLS:   # rooms: planes of points every 5 m in x and in y, floor to ceiling, a door of 1.2 m in every stretch of 5 m
+        lo, hi = cloud[:, :2].min(axis=0), cloud[:, :2].max(axis=0)
+        along = [np.arange(lo[k], hi[k], 0.1) for k in range(2)]
+        walls = []
+        for k in range(2):
+            run = along[1 - k][np.mod(along[1 - k] - lo[1 - k], 5.0) >= 1.2]
+            for at in np.arange(lo[k] + 5.0, hi[k] - 1.0, 5.0):
+                a, z = np.meshgrid(run, np.arange(0.05, 3.0, 0.1), indexing="ij")
+                pts = np.zeros((a.size, 3))
+                pts[:, k], pts[:, 1 - k], pts[:, 2] = at, a.ravel(), z.ravel()
+                walls.append(pts)
+        cloud = np.concatenate([cloud] + walls).astype(cloud.dtype)
     u = goals - starts
     u /= np.maximum(np.linalg.norm(u, axis=1, keepdims=True), 1e-9)
     states = np.zeros(B, dtype=abi.state_dtype)
