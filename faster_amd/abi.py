@@ -337,6 +337,32 @@ def default_team_params(r_max, r_spread, gain_radius, claim_radius=None):
     return p
 
 
+# fh_bid_params, fh_bid_record: team goals by bids, the best offer wins a contested frontier (include/fasterhip_bid.h); the params are
+# fh_team_params field by field, the record is fh_team_record with `lower` read as `rivals` and `reserved0` as `searches`; the constants
+# are that header's under this header's names, but for the list of 64
+FH_BID_OVERFLOW, FH_BID_UNSETTLED, FH_BID_CLAIMED, FH_BID_ALL_POOR = 128, 256, 512, 1024
+FH_BID_LIST, FH_BID_MAX_PASSES, FH_BID_DEFAULT_PASSES, FH_BID_MAX_RADIUS, FH_BID_MAX_HOP_COST = 64, 64, 8, 31, 16384
+bid_params_dtype = np.dtype([("r_max", "<f8"), ("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                             ("r_spread", "<f8"), ("passes", "<i4"), ("gain_radius", "<i4"), ("hop_cost", "<i4"), ("min_gain", "<i4"),
+                             ("claim_radius", "<i4"), ("reserved", "<i4", (3,))], align=True)
+bid_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("hops", "<i4"), ("candidates", "<i4"),
+                             ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("d2", "<f8"), ("group", "<i4"),
+                             ("decided_pass", "<i4"), ("rivals", "<i4"), ("claims", "<i4"), ("claimed", "<i4"), ("searches", "<i4"),
+                             ("gain", "<i4"), ("utility", "<i4"), ("poor", "<i4"), ("best_gain", "<i4"), ("covered", "<i4"),
+                             ("reserved", "<i4", (3,))], align=True)
+assert (bid_params_dtype.itemsize, bid_record_dtype.itemsize) == (80, 96)
+
+
+def default_bid_params(r_max, r_spread, gain_radius, claim_radius=None):
+    """fh_bid_params: default_team_params under this header's name (claim_radius None: gain_radius; -1: claims cover nothing)."""
+    p = np.zeros((), dtype=bid_params_dtype)
+    p["r_max"], p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"] = r_max, 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0
+    p["r_spread"], p["passes"] = r_spread, FH_BID_DEFAULT_PASSES
+    p["gain_radius"], p["hop_cost"], p["min_gain"] = gain_radius, 1, 0
+    p["claim_radius"] = gain_radius if claim_radius is None else claim_radius
+    return p
+
+
 # fh_sight_params, fh_sight_record: the gain chooser with a gain that counts only the unknown voxels a candidate has a line of sight to
 # (include/fasterhip_sight.h); the params are fh_gain_params field by field, the record is fh_gain_record through best_gain, then
 # ball_gain (the count without the test of sight) and walls; the constants are that header's under this header's names

@@ -62,6 +62,8 @@ GAIN_SYMBOLS = ["fh_gain_goals_device"]
 TEAM_SYMBOLS = ["fh_team_goals_device"]
 # include/fasterhip_sight.h
 SIGHT_SYMBOLS = ["fh_sight_goals_device"]
+# include/fasterhip_bid.h
+BID_SYMBOLS = ["fh_bid_work_bytes", "fh_bid_goals_device"]
 
 _LIB = None
 
@@ -347,6 +349,10 @@ def lib():
         L.fh_team_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
         L.fh_sight_goals_device.restype = i32
         L.fh_sight_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, i32, vp, vp, vp]
+        L.fh_bid_work_bytes.restype = ctypes.c_size_t
+        L.fh_bid_work_bytes.argtypes = [i32]
+        L.fh_bid_goals_device.restype = i32
+        L.fh_bid_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -641,6 +647,23 @@ class Map:
                                         d_view_of, int(n_views), d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
         if rc != 0:
             raise FasterHipError("fh_team_goals_device: rc=%d" % rc)
+
+    def bid_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_group, d_vehicles, n, d_work, work_bytes, d_goals, d_mask,
+                         d_records, stream):
+        """fh_bid_goals_device (include/fasterhip_bid.h) with this map's lattice and bits: team_goals_device's search inside rounds that
+        are ordered by bids — every undecided vehicle offers its best candidate under the claims so far, an offer that beats every
+        undecided rival's is final, the others search again.  The arguments are team_goals_device's, with d_records [n]
+        abi.bid_record_dtype and par one abi.bid_params_dtype record; d_work: work_bytes >= fh_bid_work_bytes(n)."""
+        p = _one_record(par, "bid", "bid_goals_device")
+        g = _grid_record(grid)
+        dims, origin = self.dims()
+        bits, res = ctypes.c_void_p(), ctypes.c_double()
+        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
+        mg = _grid_record((origin, res.value, dims))
+        rc = lib().fh_bid_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
+                                       d_view_of, int(n_views), d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
+        if rc != 0:
+            raise FasterHipError("fh_bid_goals_device: rc=%d" % rc)
 
     def sight_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_goals, d_mask, d_records, stream):
         """fh_sight_goals_device (include/fasterhip_sight.h) with this map's lattice and bits: gain_goals_device with a gain that counts an

@@ -4,7 +4,9 @@
 // (fh_gain_goals_device): the reachable frontier voxel with the most unknown space around it for its steps (kernel: fh_gain.hip.hpp),
 // and of include/fasterhip_team.h (fh_team_goals_device): that utility inside the passes of the chooser for a team, the space a peer's
 // claim covers not counted twice (kernels: fh_team.hip.hpp), and of include/fasterhip_sight.h (fh_sight_goals_device): the gain chooser
-// with a gain that counts only the unknown voxels a candidate has a line of sight to (kernel: fh_sight.hip.hpp).
+// with a gain that counts only the unknown voxels a candidate has a line of sight to (kernel: fh_sight.hip.hpp), and of
+// include/fasterhip_bid.h (fh_bid_goals_device): the search of the gain-aware chooser for a team inside rounds ordered by bids, the best
+// offer wins a contested frontier (kernels: fh_bid.hip.hpp).
 // A translation unit of its own: fh_map.hip and fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
@@ -17,11 +19,13 @@
 #include "../../include/fasterhip_gain.h"
 #include "../../include/fasterhip_team.h"
 #include "../../include/fasterhip_sight.h"
+#include "../../include/fasterhip_bid.h"
 #include "fh_reach.hip.hpp"
 #include "fh_spread.hip.hpp"
 #include "fh_gain.hip.hpp"
 #include "fh_team.hip.hpp"
 #include "fh_sight.hip.hpp"
+#include "fh_bid.hip.hpp"
 #include "fh_host.hpp"
 
 // the lattice of the views, judged as fh_map_frontier_goals_device judges it (0: fine, cells filled in)
@@ -188,6 +192,99 @@ int fh_gain_goals_device(void* stream, const fh_gain_params* par, const fh_voxel
   s.min_gain = par->min_gain;
   s.records = d_records;
   hipLaunchKernelGGL(fhp::gain_goals_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, s);
+  return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
+}
+
+// the offers (two words a vehicle) and the two buffers of decided words, after the rows of FH_BID_LIST
+static size_t bid_offers_offset(int n) { return spread_rows_offset(n) + (size_t)n * FH_BID_LIST * sizeof(int32_t); }
+
+size_t fh_bid_work_bytes(int n) { return n <= 0 ? 0 : bid_offers_offset(n) + (size_t)n * 2 * sizeof(int32_t) + (size_t)n * 2 * sizeof(int32_t); }
+
+// (K18's clauses in K18's order; it stands before fh_sight_goals_device, and fh_team_goals_device still ends this file)
+int fh_bid_goals_device(void* stream, const fh_bid_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                        const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                        const int32_t* d_group, const fh_vehicle* d_vehicles, int n, void* d_work, size_t work_bytes, double* d_goals,
+                        int32_t* d_mask, fh_bid_record* d_records) {
+  static_assert(FH_BID_OVERFLOW == FH_TEAM_OVERFLOW && FH_BID_UNSETTLED == FH_TEAM_UNSETTLED && FH_BID_CLAIMED == FH_TEAM_CLAIMED &&
+                    FH_BID_ALL_POOR == FH_TEAM_ALL_POOR && FH_BID_MAX_PASSES == FH_TEAM_MAX_PASSES && FH_BID_DEFAULT_PASSES == FH_TEAM_DEFAULT_PASSES &&
+                    FH_BID_MAX_RADIUS == FH_TEAM_MAX_RADIUS && FH_BID_MAX_HOP_COST == FH_TEAM_MAX_HOP_COST && FH_BID_LIST == 2 * FH_TEAM_LIST,
+                "the constants that include/fasterhip_bid.h shares with K18");
+  static_assert(sizeof(fh_bid_params) == sizeof(fh_team_params) && offsetof(fh_bid_params, r_spread) == offsetof(fh_team_params, r_spread) &&
+                    offsetof(fh_bid_params, passes) == offsetof(fh_team_params, passes) &&
+                    offsetof(fh_bid_params, gain_radius) == offsetof(fh_team_params, gain_radius) &&
+                    offsetof(fh_bid_params, hop_cost) == offsetof(fh_team_params, hop_cost) &&
+                    offsetof(fh_bid_params, min_gain) == offsetof(fh_team_params, min_gain) &&
+                    offsetof(fh_bid_params, claim_radius) == offsetof(fh_team_params, claim_radius),
+                "include/fasterhip_bid.h: K18's params");
+  static_assert(sizeof(fh_bid_record) == sizeof(fh_team_record) && offsetof(fh_bid_record, d2) == offsetof(fh_team_record, d2) &&
+                    offsetof(fh_bid_record, decided_pass) == offsetof(fh_team_record, decided_pass) &&
+                    offsetof(fh_bid_record, rivals) == offsetof(fh_team_record, lower) && offsetof(fh_bid_record, claims) == offsetof(fh_team_record, claims) &&
+                    offsetof(fh_bid_record, searches) == offsetof(fh_team_record, reserved0) && offsetof(fh_bid_record, gain) == offsetof(fh_team_record, gain) &&
+                    offsetof(fh_bid_record, covered) == offsetof(fh_team_record, covered),
+                "include/fasterhip_bid.h: K18's record, `lower` read as `rivals` and `reserved0` as `searches`");
+  if (!par) return FH_ERR_ARG;
+  if (reach_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, view_stride, n_views,
+                    n) != FH_OK)
+    return FH_ERR_ARG;
+  if (!std::isfinite(par->r_spread) || !(par->r_spread > 0.0)) return FH_ERR_ARG;
+  if (par->passes < 1 || par->passes > FH_BID_MAX_PASSES) return FH_ERR_ARG;
+  if (par->gain_radius < 0 || par->gain_radius > FH_BID_MAX_RADIUS) return FH_ERR_ARG;
+  if (par->hop_cost < 0 || par->hop_cost > FH_BID_MAX_HOP_COST) return FH_ERR_ARG;
+  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (par->claim_radius < -1 || par->claim_radius > FH_BID_MAX_RADIUS) return FH_ERR_ARG;
+  if (n == 0) return FH_OK;
+  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  if (!d_work) return FH_ERR_ARG;
+  if (work_bytes < fh_bid_work_bytes(n)) return FH_ERR_ARG;
+  hipPointerAttribute_t where;
+  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  fhh::DeviceScope scope(where.device);
+  if (!scope.ok) return FH_ERR_DEVICE;
+  fhp::BidArgs s;
+  reach_args(s.gn.r, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
+             d_view_of, n_views, d_vehicles);
+  s.gn.r.goals = d_goals; s.gn.r.mask = d_mask; s.gn.r.records = nullptr;
+  s.gn.g = par->gain_radius;
+  s.gn.g2 = par->gain_radius * par->gain_radius;
+  s.gn.hop_cost = par->hop_cost;
+  s.gn.min_gain = par->min_gain;
+  s.gn.records = nullptr;
+  // the interaction radius: a peer beyond it cannot touch the ball of a candidate
+  const double r_int = par->claim_radius < 0 ? par->r_spread : std::fmax(par->r_spread, (double)(par->gain_radius + par->claim_radius + 1) * grid->res);
+  const double reach = (par->r_max + par->r_max) + r_int, near = par->r_max + r_int;
+  s.s2 = par->r_spread * par->r_spread;
+  s.reach2 = reach * reach;
+  s.near2 = near * near;
+  s.n = n; s.pass = 0; s.last = 0;
+  s.cr = par->claim_radius;
+  s.cr2 = par->claim_radius * par->claim_radius;
+  s.group = d_group;
+  unsigned char* const work = static_cast<unsigned char*>(d_work);
+  s.cls = work;
+  s.rows = reinterpret_cast<int32_t*>(work + spread_rows_offset(n));
+  s.offers = reinterpret_cast<int32_t*>(work + bid_offers_offset(n));
+  s.decided = s.offers + 2 * (size_t)n;
+  s.records = d_records;
+  fhp::SpreadArgs c;  // the class kernel of fh_spread.hip.hpp as it is: it reads the vehicles and writes the class bytes
+  c.r = s.gn.r;
+  c.s2 = s.s2; c.reach2 = s.reach2; c.near2 = s.near2;
+  c.n = n; c.pass = 0;
+  c.group = d_group;
+  c.cls = work;
+  c.rows = s.rows;
+  c.records = nullptr;
+  const hipStream_t q = (hipStream_t)stream;
+  hipLaunchKernelGGL(fhp::spread_class_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, c);
+  hipLaunchKernelGGL(fhp::bid_peers_kernel, dim3((unsigned)n), dim3(64), 0, q, s);
+  for (int p = 1; p <= par->passes; p++) {
+    s.pass = p;
+    s.last = p == par->passes ? 1 : 0;
+    hipLaunchKernelGGL(fhp::bid_goals_kernel, dim3((unsigned)n), dim3(256), 0, q, s);
+    hipLaunchKernelGGL(fhp::bid_settle_kernel, dim3((unsigned)n), dim3(64), 0, q, s);
+  }
   return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
 }
 

@@ -50,6 +50,8 @@ knows to be free reaches in the fewest steps, never one behind a wall or in a se
 explore_gain() is explore_reachable() with a sense of what a goal is worth (include/fasterhip_gain.h): the unknown voxels near a
 candidate are weighed against the steps to it.  explore_sight() is explore_gain() with the sensor's occlusion
 (include/fasterhip_sight.h): an unknown voxel counts only if no voxel known to be occupied lies on the line from the candidate to it.
+explore_bid() is explore_team() with rounds ordered by bids (include/fasterhip_bid.h): of two teammates before one goal the one with the
+better offer gets it, whatever its index, and the other searches again under the winner's claim.
 
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
@@ -120,6 +122,7 @@ class Fleet:
         self.d_gain_goals = self.d_gain_mask = self.d_gain_records = None                                                      # explore_gain
         self.d_team_goals = self.d_team_mask = self.d_team_records = self.d_team_work = None                                   # explore_team
         self.d_sight_goals = self.d_sight_mask = self.d_sight_records = None                                                   # explore_sight
+        self.d_bid_goals = self.d_bid_mask = self.d_bid_records = self.d_bid_work = None                                       # explore_bid
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -897,6 +900,60 @@ class Fleet:
         self.sync()
         return (self.d_team_records.cpu().numpy().view(abi.team_record_dtype).copy(), self.d_team_goals.cpu().numpy().copy(),
                 self.d_team_mask.cpu().numpy().copy())
+
+    def explore_bid(self, r_max, r_spread, gain_radius, claim_radius=None, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached",
+                    max_hops=0, passes=None, groups="link"):
+        """explore_team() with rounds ordered by bids, not by the vehicle index (include/fasterhip_bid.h): every undecided vehicle offers
+        the best candidate of explore_team()'s search under the claims so far; an offer that beats the offer of every undecided rival
+        in reach (the larger utility, then the fewer hops, then the lower index) is final in that round, and the others search again
+        under the new claims.  Two teammates before one hall: the one beside it gets it, whatever its index.  The arguments (claim_radius
+        None: gain_radius; -1: claims cover nothing; at most 31), the preconditions and the errors are those of explore_team(); passes
+        counts the rounds; the buffers and the workspace are its own (bid_records())."""
+        stages = self.explore_bid_stages(r_max, r_spread, gain_radius, claim_radius, hop_cost, min_gain, r_avoid, z, want, max_hops, passes,
+                                         groups)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_bid_stages(self, r_max, r_spread, gain_radius, claim_radius=None, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached",
+                           max_hops=0, passes=None, groups="link"):
+        """The launches of explore_bid(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them one by one)."""
+        if groups not in ("link", "view"):
+            raise capi.FasterHipError("Fleet.explore_bid: groups is \"link\" or \"view\", got %r" % (groups,))
+        par = abi.default_bid_params(r_max, r_spread, gain_radius, claim_radius)
+        par["hop_cost"], par["min_gain"] = hop_cost, min_gain
+        flags, stride, vo, n_views = self._reach_inputs("explore_bid", par, r_avoid, z, want, max_hops)   # (set_unknown's one grid: one team)
+        if passes is not None:
+            par["passes"] = passes
+        work_bytes = int(capi.lib().fh_bid_work_bytes(self.n))
+        if self.d_bid_goals is None:
+            t = self.torch
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_bid_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_bid_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_bid_records = t.zeros(self.n * abi.bid_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+                self.d_bid_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
+            for d in (self.d_bid_goals, self.d_bid_mask, self.d_bid_records, self.d_bid_work):
+                d.record_stream(self.stream)
+        # the labels are per view: with set_unknown's single view there is nothing to label
+        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
+            and self.d_link_labels.numel() == n_views else None
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("bid_goals", lambda: m.bid_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if labels is None else p(labels),
+                                                     p(self.d_vehicles), self.n, p(self.d_bid_work), work_bytes, p(self.d_bid_goals),
+                                                     p(self.d_bid_mask), p(self.d_bid_records), self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_bid_goals), p(self.d_bid_mask), self.n)),
+        ]
+
+    def bid_records(self):
+        """(records [n] abi.bid_record_dtype, goals [n][3], mask [n] int32) of the last explore_bid() (synchronises)."""
+        if self.d_bid_goals is None:
+            raise capi.FasterHipError("Fleet.bid_records: explore_bid first")
+        self.sync()
+        return (self.d_bid_records.cpu().numpy().view(abi.bid_record_dtype).copy(), self.d_bid_goals.cpu().numpy().copy(),
+                self.d_bid_mask.cpu().numpy().copy())
 
     def coverage_stages(self):
         """The one launch of coverage(): [(name, callable)]."""

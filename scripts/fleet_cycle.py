@@ -75,12 +75,16 @@ choice is not the one of reach_goals.
 default G): the stage is reported as "team_goals"; with every vehicle wanted as "team_goals_all_ms", beside gain_goals and spread_goals
 with every vehicle wanted in the same run, alternating; the vehicles decided per pass, those left UNSETTLED or in OVERFLOW, the mean of
 `covered` over the searched vehicles, and the teammates that hold the same goal voxel.  --link RANGE makes the teams, as for --spread.
+--bid beside --spread R_SPREAD --gain G runs that loop with Fleet.explore_bid (include/fasterhip_bid.h): the stage is reported as
+"bid_goals"; with every vehicle wanted as "bid_goals_all_ms" beside "team_goals_all_ms" in the same run, alternating; the vehicles decided
+per round, those left UNSETTLED or in OVERFLOW, the mean of `searches` over the searched vehicles, the sum of `hops` and the mean gain of the
+goals given, each beside the figure of Fleet.explore_team on the same fleet.
 --sight together with --gain G (and without --spread) runs that loop with Fleet.explore_sight (include/fasterhip_sight.h): the stage is
 reported as "sight_goals"; with every vehicle wanted as "sight_goals_all_ms" beside "gain_goals_all_ms" in the same run, alternating;
 and, of that launch, the vehicles with a wall in their box, the walls per box, the chosen voxels that see less than their ball holds,
 and the vehicles whose choice is not the one of gain_goals.  --walls adds rooms to the world before anything reads it: planes of
 points every 5 m in x and in y, floor to ceiling, with a door of 1.2 m in every stretch of 5 m.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -116,6 +120,9 @@ TEAM = SPREAD is not None and GAIN is not None   # both: Fleet.explore_team
 CLAIM_RADIUS = int(sys.argv[sys.argv.index("--claim-radius") + 1]) if "--claim-radius" in sys.argv else None
 if CLAIM_RADIUS is not None and not TEAM:
     sys.exit("--claim-radius needs --spread R_SPREAD and --gain G")
+BID = "--bid" in sys.argv
+if BID and not TEAM:
+    sys.exit("--bid needs --spread R_SPREAD and --gain G")
 SIGHT = "--sight" in sys.argv
 if SIGHT and (GAIN is None or SPREAD is not None):
     sys.exit("--sight needs --gain G and no --spread")
@@ -329,10 +336,16 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     fl.enable_heading(yaw0=np.arctan2(u[:, 1], u[:, 0]))
     fl.sense(r_sense)
     first = fl.coverage()
-    goal_stage = "team_goals" if TEAM else "spread_goals" if SPREAD is not None else "sight_goals" if SIGHT else "gain_goals" if GAIN is not None else "reach_goals" if REACH \
+    goal_stage = "bid_goals" if BID else "team_goals" if TEAM else "spread_goals" if SPREAD is not None else "sight_goals" if SIGHT else "gain_goals" if GAIN is not None else "reach_goals" if REACH \
         else "frontier_goals"
     explore_stages, explore_records = (fl.explore_reachable_stages, fl.reach_records) if REACH else (fl.explore_stages, fl.explore_records)
-    if TEAM:
+    if BID:
+        if LINK:   # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
+            fl.link(LINK[0])
+        explore_stages = lambda r, **kw: fl.explore_bid_stages(r, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN, **kw)   # noqa: E731
+        explore_records = fl.bid_records
+        fl.explore_bid(r_max, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN)
+    elif TEAM:
         if LINK:   # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
             fl.link(LINK[0])
         explore_stages = lambda r, **kw: fl.explore_team_stages(r, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN, **kw)   # noqa: E731
@@ -394,7 +407,41 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                  "candidates_mean": float(rr["candidates"][hit].mean()) if hit.any() else 0.0,
                  "reachable_mean": float(rr["reachable"][hit].mean()) if hit.any() else 0.0,
                  "same_cell_as_frontier_goals": int((rr["cell"] == rec["cell"]).sum())}
-    if TEAM:   # every vehicle wanted, applied to nobody: team_goals, gain_goals and spread_goals in turn, a median each
+    if BID:   # every vehicle wanted, applied to nobody: bid_goals and team_goals in turn, a median each
+        reps = max(cycles, 5)
+        runs = {"bid_goals": [], "team_goals": []}
+        launches = {"bid_goals": explore_stages(r_max, want="all")[0][1],
+                    "team_goals": fl.explore_team_stages(r_max, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN, want="all")[0][1]}
+        for _ in range(reps):
+            for name, launch in launches.items():
+                runs[name] += fenced_ms(fl, launch, 1)
+        one_ms = fenced_ms(fl, explore_stages(r_max, want="all", passes=1)[0][1], reps)
+        launches["bid_goals"]()
+        br, tr = fl.bid_records()[0], fl.team_records()[0]
+
+        def figures(r, unsettled, overflow):
+            searched = r["decided_pass"] > 0
+            given = r["cell"] >= 0
+            keys = np.stack([r["group"][given].astype(np.int64), r["cell"][given].astype(np.int64)], axis=1)
+            _, counts = np.unique(keys, axis=0, return_counts=True) if len(keys) else (None, np.zeros(0, dtype=np.int64))
+            return {"decided_per_pass": np.bincount(r["decided_pass"][searched], minlength=2)[1:].tolist(), "decided": int(searched.sum()),
+                    "unsettled": int((r["flags"] & unsettled != 0).sum()), "overflow": int((r["flags"] & overflow != 0).sum()),
+                    "goals_given": int(given.sum()), "hops_sum": int(r["hops"][given].sum()),
+                    "gain_mean": float(r["gain"][given].mean()) if given.any() else -1.0,
+                    "utility_sum": int(r["utility"][given].sum()), "same_goal_voxel": int((counts - 1).sum())}
+
+        bid, team = figures(br, abi.FH_BID_UNSETTLED, abi.FH_BID_OVERFLOW), figures(tr, abi.FH_TEAM_UNSETTLED, abi.FH_TEAM_OVERFLOW)
+        took = br["searches"] > 0
+        bid.update({"searches_mean": float(br["searches"][took].mean()) if took.any() else 0.0, "searches_max": int(br["searches"].max()),
+                    "searches_sum": int(br["searches"].sum()), "rivals_max": int(br["rivals"].max()), "claims_max": int(br["claims"].max())})
+        team.update({"lower_max": int(tr["lower"].max()), "claims_max": int(tr["claims"].max())})
+        reach.update({"r_spread": SPREAD, "gain_radius": GAIN, "claim_radius": GAIN if CLAIM_RADIUS is None else CLAIM_RADIUS, "hop_cost": HOP_COST,
+                      "min_gain": MIN_GAIN, "passes": abi.FH_BID_DEFAULT_PASSES, "bid_goals_reached_ms": med["bid_goals"],
+                      "bid_goals_all_ms": float(np.median(runs["bid_goals"])), "bid_goals_all_runs_ms": [float(x) for x in runs["bid_goals"]],
+                      "bid_goals_all_one_pass_ms": float(np.median(one_ms)),
+                      "team_goals_all_ms": float(np.median(runs["team_goals"])), "team_goals_all_runs_ms": [float(x) for x in runs["team_goals"]],
+                      "groups": int(len(np.unique(br["group"]))), "bid": bid, "team": team})
+    elif TEAM:   # every vehicle wanted, applied to nobody: team_goals, gain_goals and spread_goals in turn, a median each
         reps = max(cycles, 5)
         runs = {"team_goals": [], "gain_goals": [], "spread_goals": []}
         launches = {"team_goals": explore_stages(r_max, want="all")[0][1],
