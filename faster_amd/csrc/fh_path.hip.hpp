@@ -154,7 +154,29 @@ struct Planner {
     const int m = mv.m_free;
     const bool a = x >= s[0] - m && x <= s[0] + m && y >= s[1] - m && y <= s[1] + m && z >= s[2] - m && z <= s[2] + m;
     const bool b = x >= t[0] - m && x <= t[0] + m && y >= t[1] - m && y <= t[1] + m && z >= t[2] - m && z <= t[2] + m;
+    if (wraps) {
+      const int id = index(x, y, z);
+      return in_cube_flat(id, s) || in_cube_flat(id, t);
+    }
     return a || b;
+  }
+  // MapUtil::setFree (map_util.h:244-252) tests the FLAT index of a cube cell only, as readMap does: a cube that sticks out of the lattice
+  // in x or y frees cells of the next row or layer.  `wraps` (uniform, per query): one of the two cubes does; then a cell is freed when
+  // some cube cell (ix, iy, iz), inside the lattice or not, has its flat index.
+  bool wraps = false;
+  __device__ __forceinline__ bool sticks_out(const int c[3]) const {
+    const int m = mv.m_free;
+    return c[0] - m < 0 || c[0] + m >= mv.nx || c[1] - m < 0 || c[1] + m >= mv.ny;
+  }
+  __device__ __forceinline__ bool in_cube_flat(int id, const int c[3]) const {
+    const int m = mv.m_free, nxy = mv.nx * mv.ny;
+    bool hit = false;
+    for (int iz = c[2] - m; iz <= c[2] + m; iz++)
+      for (int iy = c[1] - m; iy <= c[1] + m; iy++) {
+        const int ix = id - mv.nx * iy - nxy * iz;
+        hit = hit || (ix >= c[0] - m && ix <= c[0] + m);
+      }
+    return hit;
   }
   __device__ __forceinline__ bool occupied_in(int x, int y, int z) const {  // inside the grid is the caller's business
     if (freed(x, y, z)) return false;
@@ -277,6 +299,7 @@ struct Planner {
     for (int i = lane; i < NCHUNK; i += 64) fstack[i] = (short)(NCHUNK - 1 - i);  // chunk 0 on top
     ftop = NCHUNK;
     const int sid = index(s[0], s[1], s[2]), tid = index(t[0], t[1], t[2]);
+    wraps = sticks_out(s) || sticks_out(t);
     int limit = 0;
     // the sub-list records: all empty
     for (int i = lane; i < NS; i += 64) { r_key[i] = 0x7fffffff; r_h2[i] = 0x7fffffff; r_id[i] = 0x7fffffff; r_hc[i] = 0; }
@@ -1102,17 +1125,20 @@ struct Planner {
     }
   }
 
-  // the occupied cells inside the cube freed around centre c (they are free for this query): their bounding box
+  // the occupied cells that the cube around centre c frees (they are free for this query): their bounding box
   __device__ __forceinline__ void dirty_box(const int c[3], int q) {
     const int m = mv.m_free, w = 2 * m + 1, count = w * w * w;
     int lo0 = BIGK, lo1 = BIGK, lo2 = BIGK, hi0 = -BIGK, hi1 = -BIGK, hi2 = -BIGK;
     for (int i = lane; i < count; i += 64) {
       const int x = c[0] - m + i % w, y = c[1] - m + (i / w) % w, z = c[2] - m + i / (w * w);
-      if (!outside(x, y, z)) {
-        const int id = index(x, y, z);
+      const long long fid = (long long)x + (long long)mv.nx * y + (long long)mv.nx * mv.ny * z;  // (setFree's test: the flat index, see `wraps`)
+      if (fid >= 0 && fid < (long long)mv.total) {
+        const int id = (int)fid;
         if ((mv.bits[id >> 5] >> (id & 31)) & 1u) {
-          lo0 = min(lo0, x); lo1 = min(lo1, y); lo2 = min(lo2, z);
-          hi0 = max(hi0, x); hi1 = max(hi1, y); hi2 = max(hi2, z);
+          int gx, gy, gz;  // the cell that is freed: (x, y, z) itself unless the cube cell lies outside the lattice
+          decode(id, gx, gy, gz);
+          lo0 = min(lo0, gx); lo1 = min(lo1, gy); lo2 = min(lo2, gz);
+          hi0 = max(hi0, gx); hi1 = max(hi1, gy); hi2 = max(hi2, gz);
         }
       }
     }
@@ -1134,6 +1160,7 @@ struct Planner {
     const int sid = index(s[0], s[1], s[2]), tid = index(t[0], t[1], t[2]);
     const int nxy = mv.nx * mv.ny;
     boxes_matter = true;
+    wraps = sticks_out(s) || sticks_out(t);
     dirty_box(s, 0);
     dirty_box(t, 1);
     boxes_matter = dlo[0][0] <= dhi[0][0] || dlo[1][0] <= dhi[1][0];
@@ -1374,7 +1401,9 @@ __global__ void __launch_bounds__(64, JPS ? 5 : 3) plan_kernel(MapView mv, PlanA
     pl.prof_acc = 0;
     const long long q_t0 = (long long)__builtin_readcyclecounter();
 #endif
-    const bool live = !pa.active || uniform_i32(pa.active[q]) != 0;
+    // (a non-finite start or goal is outside the map: a NaN converts to cell 0 and fmax(NaN, 0) is 0, so the lattice test below would let it in)
+    const bool finite = isfinite(st[0]) && isfinite(st[1]) && isfinite(pa.starts[3 * q + 2]) && isfinite(gl[0]) && isfinite(gl[1]) && isfinite(pa.goals[3 * q + 2]);
+    const bool live = finite && (!pa.active || uniform_i32(pa.active[q]) != 0);
     if (live && !pl.outside(pl.s[0], pl.s[1], pl.s[2]) && !pl.outside(pl.t[0], pl.t[1], pl.t[2])) {
       serial++;
       if (serial >= (JPS ? JPS_SERIAL_LIMIT : 0x7fffffffu)) {  // 2^31 (2^26) queries of this wavefront: its stamps start over, so its cell states are cleared first
@@ -1418,7 +1447,9 @@ __global__ void __launch_bounds__(64, JPS ? 5 : 3) plan_kernel(MapView mv, PlanA
         double E[3] = {0, 0, 0};
         if (pa.radius || pa.sphere_ra > 0.0) {
           const double ra = pa.radius ? pa.radius[q] : fmin(Planner::dist(gl, st) - 0.001, pa.sphere_ra);
-          for (int i = 1; i < count; i++) {
+          // (a negative radius — goal and start less than 0.001 m apart — has the start itself outside: the path stays whole, as in the
+          // host restatement; the crossing of a zero-length leg would be 0 / 0)
+          for (int i = 1; i < count && !(0.0 > ra); i++) {
             double b[3];
             vertex(i, b);
             if (Planner::dist(b, st) > ra) {
@@ -1515,7 +1546,9 @@ __device__ __forceinline__ void plan_queries(const MapView& mv, MapView* own, co
       own->bits = pv.bits + v * pv.words_per_view;
       if (JPS) pl.jt = pv.entries + v * (long long)mv.total * 32;
     }
-    const bool live = has_view && (!pa.active || uniform_i32(pa.active[q]) != 0);
+    // (a non-finite start or goal is outside the map: a NaN converts to cell 0 and fmax(NaN, 0) is 0, so the lattice test below would let it in)
+    const bool finite = isfinite(st[0]) && isfinite(st[1]) && isfinite(pa.starts[3 * q + 2]) && isfinite(gl[0]) && isfinite(gl[1]) && isfinite(pa.goals[3 * q + 2]);
+    const bool live = finite && has_view && (!pa.active || uniform_i32(pa.active[q]) != 0);
     if (live && !pl.outside(pl.s[0], pl.s[1], pl.s[2]) && !pl.outside(pl.t[0], pl.t[1], pl.t[2])) {
       serial++;
       if (serial >= (JPS ? JPS_SERIAL_LIMIT : 0x7fffffffu)) {  // 2^31 (2^26) queries of this wavefront: its stamps start over, so its cell states are cleared first
@@ -1559,7 +1592,9 @@ __device__ __forceinline__ void plan_queries(const MapView& mv, MapView* own, co
         double E[3] = {0, 0, 0};
         if (pa.radius || pa.sphere_ra > 0.0) {
           const double ra = pa.radius ? pa.radius[q] : fmin(Planner::dist(gl, st) - 0.001, pa.sphere_ra);
-          for (int i = 1; i < count; i++) {
+          // (a negative radius — goal and start less than 0.001 m apart — has the start itself outside: the path stays whole, as in the
+          // host restatement; the crossing of a zero-length leg would be 0 / 0)
+          for (int i = 1; i < count && !(0.0 > ra); i++) {
             double b[3];
             vertex(i, b);
             if (Planner::dist(b, st) > ra) {

@@ -374,6 +374,12 @@ static int g_search_mode = 0;
 static double g_sphere_ra = 0.0;  // ff_set_sphere: clip every path to JPS_in (Faster::replan, faster.cpp:370-382) before the vertex refinement
 static bool run_search(fhfront::VoxelGrid& g, const fhfront::V3& s, const fhfront::V3& t, double inflation, std::vector<fhfront::V3>& path,
                        long long* expansions = nullptr) {
+  // a non-finite start or goal is outside the map (the device search says the same): its cell is not defined — the conversion of a
+  // NaN to int is not, and max(z, 0) would turn a z of -inf into 0
+  if (!std::isfinite(s.x) || !std::isfinite(s.y) || !std::isfinite(s.z) || !std::isfinite(t.x) || !std::isfinite(t.y) || !std::isfinite(t.z)) {
+    path.clear();
+    return false;
+  }
   return g_search_mode == 1 ? fhfront::plan_path_jps(g, s, t, inflation, path, expansions) : fhfront::plan_path(g, s, t, inflation, path, expansions);
 }
 

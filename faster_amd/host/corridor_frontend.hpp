@@ -329,11 +329,16 @@ struct VoxelGrid {
   // setFreeVoxelAndSurroundings(center, const float d) (jps3d map_util.h:248-263): n_voxels = round(d / res + 0.5) with d a FLOAT
   // (inflation 0.3, res 0.2: 2 cells — not the floor(inflation / res) = 1 of readMap's inflation)
   void set_free_around(const int c[3], double inflation) {
+    // setFree (map_util.h:244-252) tests the flat index only, as readMap does: a cube that sticks out of the lattice in x or y frees cells
+    // of the next row or layer
     const int m = (int)std::round((double)(float)inflation / res + 0.5);
+    const long long total = (long long)nx * ny * nz;
     for (int ix = c[0] - m; ix <= c[0] + m; ix++)
       for (int iy = c[1] - m; iy <= c[1] + m; iy++)
-        for (int iz = c[2] - m; iz <= c[2] + m; iz++)
-          if (!outside(ix, iy, iz)) occ[index(ix, iy, iz)] = 0;
+        for (int iz = c[2] - m; iz <= c[2] + m; iz++) {
+          const long long id = ix + (long long)nx * iy + (long long)nx * ny * iz;
+          if (id >= 0 && id < total) occ[(size_t)id] = 0;
+        }
   }
 
   // ray test of removeCornerPts: cells sampled every 0.8 cell along the ray (map_util.h:348-382)

@@ -523,8 +523,13 @@ int fh_pool_solve_pairs(fh_pool* pool, const fh_problem* whole, const fh_face* f
  *                            backwards), ends forced onto the requested points.  One query per wavefront.
  *   With max_vertex_dist > 0 the vertices additionally go through Faster::createMoreVertexes (faster/src/faster.cpp:80-97) and, with
  *   max_poly > 0, deleteVertexes (faster/src/utils.cpp:1117-1124): what Faster::replan hands to the convex decomposition.
- * paths: [n][max_points][3]; n_points[i]: number of vertices, 0 = no path (start/goal outside the map or not connected),
+ * paths: [n][max_points][3]; n_points[i]: number of vertices, 0 = no path (start/goal outside the map, not finite, or not connected),
  * -1 = more than max_points vertices, -2 = a search limit was hit (f >= 2040 cells, 131072 open entries, 4096 raw path cells).
+ * The limits as they act (tests/test_gpu_path_edges.py): f >= 2040 of ANY cell the A* search opens, the cells behind the start
+ * included; 4096 entries of the parent chain from the goal back to the start — a cell per move for A* (out of reach: the key range
+ * ends such a query first), a jump point per entry for the jump point search.  A query that answers 0 leaves its row of paths alone.
+ * max_points >= 2 (a path has two vertices at least; FH_ERR_ARG otherwise).  A negative clip radius (fh_map_set_sphere with goal and
+ * start less than 0.001 m apart, or a negative entry of d_radius) leaves the path whole.
  * expansions (may be NULL): cells expanded per query.  The CPU restatement the kernels are checked against vertex for vertex is
  * faster_amd/host/corridor_frontend.cpp (plan_path).  One stream per map; entry points of one map are not re-entrant.
  * No CPU fallback: FH_ERR_DEVICE without a device. */

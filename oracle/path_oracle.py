@@ -83,8 +83,9 @@ def plan(grid, start, goal):
         for ix in range(c[0] - grid.m_free, c[0] + grid.m_free + 1):
             for iy in range(c[1] - grid.m_free, c[1] + grid.m_free + 1):
                 for iz in range(c[2] - grid.m_free, c[2] + grid.m_free + 1):
-                    if not grid.outside(ix, iy, iz):
-                        freed.add(grid.index(ix, iy, iz))
+                    i = grid.index(ix, iy, iz)   # MapUtil::setFree tests the flat index only: a cube that sticks out in x or y
+                    if 0 <= i < grid.nx * grid.ny * grid.nz:   # frees cells of the next row or layer
+                        freed.add(i)
 
     def occupied(i):
         return grid.occ[i] != 0 and i not in freed

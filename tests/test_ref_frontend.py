@@ -335,3 +335,46 @@ def test_jps_vertex_lists_equal_jps3d_in_a_cubic_map_with_blobs(ref, inflation):
             assert len(p) == len(hp) and np.array_equal(p, hp), i
     m.close()
     assert found >= 120
+
+
+@pytest.mark.parametrize("name", ["empty/m1", "random/m1", "wall/m1", "empty/m2", "random/m2", "wall/m2"])
+def test_jps_vertex_lists_equal_jps3d_on_all_pairs_of_the_tiny_grids(ref, name):
+    """All 78 400 ordered pairs of cells of the 8 x 7 x 5 grids of tests/path_edge_cases.py (cubes clipped by every face, edge and corner
+    of the lattice, overlapping cubes, start = goal) through the reference's compiled jps3d, a fresh map for every query (solveJPS3D
+    frees the cubes in the map itself), and through plan_path_jps: the same vertex lists.
+
+    This is what found that MapUtil::setFree (map_util.h:244-252) tests the FLAT index of a cell only, as readMap does: a cube that sticks
+    out of the lattice frees cells on the next row or layer (a goal in the last row y = ny - 1 of layer 0 frees cells of row y = 0).
+    VoxelGrid::set_free_around and the device's Planner::freed used to clip the cube per axis — a mistake they shared, so their parity
+    tests passed; 30, 3108, 95 and 1234 of the 78 400 pairs of the four grids with obstacles differed from jps3d (the reference found
+    paths through wall cells freed by wrap-around), every one of them with a cube clipped by the border."""
+    import ctypes
+
+    import path_edge_cases as pe
+
+    sc = pe.tiny_scene(name)
+    with frontend.host_settings("jps", 0.0):
+        hp, hn, _ = frontend.plan_batch(*sc.map_args(), sc.starts, sc.goals, max_points=16)
+    cloud, cells, res, center, zg, zmax, infl = sc.map_args()
+    m = ref.Map(cloud, cells, res, center, zg, zmax, infl)
+    assert np.array_equal(m.occupancy(), sc.occ)
+    m.close()
+    c32 = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+    ce = np.ascontiguousarray(center, dtype=np.float64)
+    out, cost, nraw = np.zeros((64, 3)), ctypes.c_double(0.0), ctypes.c_int(0)
+    L = ref.lib()
+    differ = []
+    with ref._quiet_stdout():
+        for q in range(len(sc.starts)):
+            h = L.ref_map_create(ref._p(c32), len(c32), int(cells[0]), int(cells[1]), int(cells[2]), res, ref._p(ce), zg, zmax, infl)
+            k = L.ref_map_plan(h, ref._p(sc.starts[q]), ref._p(sc.goals[q]), 1, ref._p(out), 64, ctypes.byref(cost), ctypes.byref(nraw))
+            L.ref_map_destroy(h)
+            if k != hn[q] or (k > 0 and not np.array_equal(out[:k], hp[q, :k])):
+                differ.append(q)
+    c = sc.meta["cells_of"]
+    clipped = ((c < sc.m_free) | (c + sc.m_free >= np.array(pe.TINY_DIMS))).any(axis=1)
+    i, j = np.divmod(np.array(differ, dtype=np.int64), len(c))
+    print("%s: %d of %d pairs differ from jps3d; %d of them have no cube clipped by the border" % (name, len(differ), len(sc.starts),
+                                                                                                 int((~(clipped[i] | clipped[j])).sum())))
+    assert not (~(clipped[i] | clipped[j])).any()
+    assert not differ, (len(differ), differ[:8])
