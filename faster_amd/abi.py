@@ -383,6 +383,25 @@ def default_sight_params(r_max, gain_radius):
     return p
 
 
+# fh_far_params, fh_far_record: the fallback for the vehicles another chooser left without a goal, a flood of the whole view over blocks
+# of voxels (include/fasterhip_far.h); the record's flags are FH_FRONTIER_WANTED .. BAD_POS, FH_REACH_START_OUTSIDE, FH_REACH_CUT and this
+FH_FAR_SKIPPED = 128
+FH_FAR_MAX_WORDS = 512
+far_params_dtype = np.dtype([("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("reserved_d", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                             ("block", "<i4"), ("reserved", "<i4", (5,))], align=True)
+far_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("block_cell", "<i4"), ("hops", "<i4"), ("targets", "<i4"),
+                             ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("members", "<i4"), ("reserved", "<i4", (2,)),
+                             ("d2", "<f8"), ("block_d2", "<f8")], align=True)
+assert (far_params_dtype.itemsize, far_record_dtype.itemsize) == (64, 64)
+
+
+def default_far_params(block):
+    """fh_far_params: blocks of `block` voxels an edge, the vehicles that have reached their goal, at any height, no limit on the levels."""
+    p = np.zeros((), dtype=far_params_dtype)
+    p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"], p["block"] = 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0, block
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

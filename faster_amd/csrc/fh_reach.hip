@@ -6,7 +6,8 @@
 // claim covers not counted twice (kernels: fh_team.hip.hpp), and of include/fasterhip_sight.h (fh_sight_goals_device): the gain chooser
 // with a gain that counts only the unknown voxels a candidate has a line of sight to (kernel: fh_sight.hip.hpp), and of
 // include/fasterhip_bid.h (fh_bid_goals_device): the search of the gain-aware chooser for a team inside rounds ordered by bids, the best
-// offer wins a contested frontier (kernels: fh_bid.hip.hpp).
+// offer wins a contested frontier (kernels: fh_bid.hip.hpp), and of include/fasterhip_far.h (fh_far_goals_device): the fallback for the
+// vehicles those choosers left without a goal, a flood of the whole view over blocks of voxels (kernels: fh_far.hip.hpp).
 // A translation unit of its own: fh_map.hip and fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
@@ -20,12 +21,14 @@
 #include "../../include/fasterhip_team.h"
 #include "../../include/fasterhip_sight.h"
 #include "../../include/fasterhip_bid.h"
+#include "../../include/fasterhip_far.h"
 #include "fh_reach.hip.hpp"
 #include "fh_spread.hip.hpp"
 #include "fh_gain.hip.hpp"
 #include "fh_team.hip.hpp"
 #include "fh_sight.hip.hpp"
 #include "fh_bid.hip.hpp"
+#include "fh_far.hip.hpp"
 #include "fh_host.hpp"
 
 // the lattice of the views, judged as fh_map_frontier_goals_device judges it (0: fine, cells filled in)
@@ -192,6 +195,73 @@ int fh_gain_goals_device(void* stream, const fh_gain_params* par, const fh_voxel
   s.min_gain = par->min_gain;
   s.records = d_records;
   hipLaunchKernelGGL(fhp::gain_goals_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, s);
+  return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
+}
+
+// the words of a bitmap of blocks of edge `block` over the lattice; 0: a null grid, a dimension < 1 or a block outside 1..16;
+// FH_FAR_MAX_WORDS + 1: more than FH_FAR_MAX_WORDS (each partial product is tested, so nothing overflows)
+static int far_words(const fh_voxel_grid* grid, int block) {
+  if (!fhh::voxel_grid_ok(grid, false) || block < 1 || block > 16) return 0;
+  long long w = (((long long)grid->dims[0] + block - 1) / block + 63) / 64;
+  for (int k = 1; k < 3; k++) {
+    if (w > FH_FAR_MAX_WORDS) return FH_FAR_MAX_WORDS + 1;
+    w *= ((long long)grid->dims[k] + block - 1) / block;
+  }
+  return w > FH_FAR_MAX_WORDS ? FH_FAR_MAX_WORDS + 1 : (int)w;
+}
+
+size_t fh_far_work_bytes(const fh_voxel_grid* grid, int block, int n_views) {
+  const int W = far_words(grid, block);
+  if (W < 1 || W > FH_FAR_MAX_WORDS || n_views < 1) return 0;
+  return (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long) + (((size_t)n_views + 63) & ~(size_t)63);
+}
+
+int fh_far_goals_device(void* stream, const fh_far_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                        const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                        const int32_t* d_skip, const fh_vehicle* d_vehicles, int n, void* d_work, size_t work_bytes, double* d_goals,
+                        int32_t* d_mask, fh_far_record* d_records) {
+  static_assert(sizeof(fh_far_params) == 64 && sizeof(fh_far_record) == 64 && FH_FAR_MAX_WORDS % 256 == 0, "include/fasterhip_far.h");
+  if (!par) return FH_ERR_ARG;
+  // (K15's field clauses without r_max, which this chooser does not have: any r_max that passes stands in for it)
+  if (reach_field_clauses(1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
+  if (par->block < 1 || par->block > 16) return FH_ERR_ARG;
+  if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
+  const int W = far_words(grid, par->block);
+  if (W > FH_FAR_MAX_WORDS) return FH_ERR_ARG;
+  if (work_bytes < fh_far_work_bytes(grid, par->block, n_views)) return FH_ERR_ARG;
+  if (n == 0) return FH_OK;
+  if (!d_work || !d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  hipPointerAttribute_t where;
+  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  fhh::DeviceScope scope(where.device);
+  if (!scope.ok) return FH_ERR_DEVICE;
+  fhp::FarArgs s;
+  reach_args(s.r, 1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of,
+             n_views, d_vehicles);
+  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
+  s.B = par->block;
+  s.cx = (grid->dims[0] + s.B - 1) / s.B;  // (W <= FH_FAR_MAX_WORDS: the dims are far below 2^31 - 16)
+  s.cy = (grid->dims[1] + s.B - 1) / s.B;
+  s.cz = (grid->dims[2] + s.B - 1) / s.B;
+  s.wx = (s.cx + 63) / 64;
+  s.W = W;
+  s.n = n;
+  s.skip = d_skip;
+  s.sums = static_cast<unsigned long long*>(d_work);
+  const size_t need_bytes = ((size_t)n_views + 63) & ~(size_t)63;
+  s.need = static_cast<unsigned char*>(d_work) + (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long);
+  s.records = d_records;
+  const hipStream_t q = (hipStream_t)stream;
+  if (hipMemsetAsync(s.need, 0, need_bytes, q) != hipSuccess) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  hipLaunchKernelGGL(fhp::far_need_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, s);
+  hipLaunchKernelGGL(fhp::far_blocks_kernel, dim3((unsigned)W, (unsigned)(n_views < 65535 ? n_views : 65535)), dim3(256), 0, q, s);
+  hipLaunchKernelGGL(fhp::far_goals_kernel, dim3((unsigned)n), dim3(256), 0, q, s);
   return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
 }
 

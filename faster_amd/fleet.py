@@ -53,6 +53,13 @@ candidate are weighed against the steps to it.  explore_sight() is explore_gain(
 explore_bid() is explore_team() with rounds ordered by bids (include/fasterhip_bid.h): of two teammates before one goal the one with the
 better offer gets it, whatever its index, and the other searches again under the winner's claim.
 
+explore_far() is the fallback behind all of them (include/fasterhip_far.h).  Those choosers search the box of the vehicle's r_max sphere;
+a vehicle whose frontiers all lie beyond it gets no goal and stays where it is.  explore_far(after=<that chooser>) floods the WHOLE view
+at the resolution of blocks of voxels and gives every vehicle the chooser left without a goal the nearest frontier a chain of linked
+blocks reaches, however far away it is:
+
+    sense -> observe -> [link] -> explore_reachable -> explore_far(after="reachable") -> replan -> next_goals
+
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
@@ -123,6 +130,7 @@ class Fleet:
         self.d_team_goals = self.d_team_mask = self.d_team_records = self.d_team_work = None                                   # explore_team
         self.d_sight_goals = self.d_sight_mask = self.d_sight_records = None                                                   # explore_sight
         self.d_bid_goals = self.d_bid_mask = self.d_bid_records = self.d_bid_work = None                                       # explore_bid
+        self.d_far_goals = self.d_far_mask = self.d_far_records = self.d_far_work = self._far_work_key = None                  # explore_far
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -709,6 +717,70 @@ class Fleet:
         self.sync()
         return (self.d_reach_records.cpu().numpy().view(abi.reach_record_dtype).copy(), self.d_reach_goals.cpu().numpy().copy(),
                 self.d_reach_mask.cpu().numpy().copy())
+
+    _FAR_AFTER = {"explore": "d_explore_mask", "reachable": "d_reach_mask", "spread": "d_spread_mask", "gain": "d_gain_mask",
+                  "sight": "d_sight_mask", "team": "d_team_mask", "bid": "d_bid_mask"}
+
+    def explore_far(self, block=8, r_avoid=None, z=None, want="reached", max_hops=0, after=None):
+        """The fallback behind the other choosers (include/fasterhip_far.h): a wanted vehicle takes the nearest frontier voxel of its
+        WHOLE view that a flood over blocks of block x block x block voxels reaches from the block it stands in — two blocks are joined
+        where a pair of free voxels touches across the face they share — the fewest block steps first, then the nearest block, and in
+        it the nearest frontier voxel.  after: the chooser that ran earlier in this period, "explore", "reachable", "spread", "gain",
+        "sight", "team" or "bid"; the vehicles it gave a goal are skipped (None: nobody is).  block: 1 .. 16, and the blocks of the
+        lattice must fit abi.FH_FAR_MAX_WORDS words of 64.  max_hops: the last level of the flood, 0 for no limit.  The other arguments,
+        the preconditions and the errors are those of explore_reachable(); the buffers and the workspace are its own (far_records())."""
+        stages = self.explore_far_stages(block, r_avoid, z, want, max_hops, after)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_far_stages(self, block=8, r_avoid=None, z=None, want="reached", max_hops=0, after=None):
+        """The two launches of explore_far(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        par = abi.default_far_params(block)
+        flags, stride, vo, n_views = self._reach_inputs("explore_far", par, r_avoid, z, want, max_hops)
+        skip = None
+        if after is not None:
+            if after not in self._FAR_AFTER:
+                raise capi.FasterHipError("Fleet.explore_far: after is None or one of %s, got %r" % (", ".join(sorted(self._FAR_AFTER)), after))
+            skip = getattr(self, self._FAR_AFTER[after])
+            if skip is None:
+                raise capi.FasterHipError("Fleet.explore_far: after=%r, but that chooser has not run" % (after,))
+        g = capi._grid_record(self.grid)
+        work_bytes = int(capi.lib().fh_far_work_bytes(abi.ptr(g), int(block), int(n_views)))
+        if work_bytes == 0:
+            raise capi.FasterHipError("Fleet.explore_far: block must be 1 .. 16 and the blocks of the lattice must fit %d words of 64 "
+                                      "(got block %r on a lattice of %s)" % (abi.FH_FAR_MAX_WORDS, block, tuple(int(d) for d in self.grid[2])))
+        t = self.torch
+        if self.d_far_goals is None:
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_far_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_far_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_far_records = t.zeros(self.n * abi.far_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            for d in (self.d_far_goals, self.d_far_mask, self.d_far_records):
+                d.record_stream(self.stream)
+        key = (tuple(int(d) for d in self.grid[2]), int(block), int(n_views))
+        if self._far_work_key != key:   # (one workspace per lattice, block and number of views)
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_far_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
+            self.d_far_work.record_stream(self.stream)
+            self._far_work_key = key
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("far_goals", lambda: m.far_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if skip is None else p(skip),
+                                                     p(self.d_vehicles), self.n, p(self.d_far_work), work_bytes, p(self.d_far_goals),
+                                                     p(self.d_far_mask), p(self.d_far_records), self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_far_goals), p(self.d_far_mask), self.n)),
+        ]
+
+    def far_records(self):
+        """(records [n] abi.far_record_dtype, goals [n][3], mask [n] int32) of the last explore_far() (synchronises)."""
+        if self.d_far_goals is None:
+            raise capi.FasterHipError("Fleet.far_records: explore_far first")
+        self.sync()
+        return (self.d_far_records.cpu().numpy().view(abi.far_record_dtype).copy(), self.d_far_goals.cpu().numpy().copy(),
+                self.d_far_mask.cpu().numpy().copy())
 
     def explore_spread(self, r_max, r_spread, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link"):
         """explore_reachable() for a team (include/fasterhip_spread.h): a frontier voxel nearer than r_spread to the goal that a peer is

@@ -84,7 +84,11 @@ reported as "sight_goals"; with every vehicle wanted as "sight_goals_all_ms" bes
 and, of that launch, the vehicles with a wall in their box, the walls per box, the chosen voxels that see less than their ball holds,
 and the vehicles whose choice is not the one of gain_goals.  --walls adds rooms to the world before anything reads it: planes of
 points every 5 m in x and in y, floor to ceiling, with a door of 1.2 m in every stretch of 5 m.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--far BLOCK (with --views --explore R_MAX, beside any of the choosers above) runs Fleet.explore_far(BLOCK, after=<the chooser in use>)
+after that chooser in every period (include/fasterhip_far.h): its stages are reported as "far_goals" and "far_set_goals"; under "far" the
+launch with every vehicle wanted and nobody skipped as "far_goals_all_ms" beside "reach_goals_all_beside_ms" of the same call (medians of
+five, fenced by events), and the levels, blocks reached, target blocks, hops and members of that launch.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--far BLOCK] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -123,6 +127,9 @@ if CLAIM_RADIUS is not None and not TEAM:
 BID = "--bid" in sys.argv
 if BID and not TEAM:
     sys.exit("--bid needs --spread R_SPREAD and --gain G")
+FAR = int(sys.argv[sys.argv.index("--far") + 1]) if "--far" in sys.argv else None
+if FAR is not None and not ("--views" in sys.argv and EXPLORE is not None):
+    sys.exit("--far needs --views --explore R_MAX")
 SIGHT = "--sight" in sys.argv
 if SIGHT and (GAIN is None or SPREAD is not None):
     sys.exit("--sight needs --gain G and no --spread")
@@ -364,10 +371,16 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
         fl.explore_gain(r_max, GAIN, HOP_COST, MIN_GAIN)
     else:
         (fl.explore_reachable if REACH else fl.explore)(r_max)
+    far_after = "bid" if BID else "team" if TEAM else "spread" if SPREAD is not None else "sight" if SIGHT else "gain" if GAIN is not None else "reachable" if REACH \
+        else "explore"
+    if FAR is not None:
+        fl.explore_far(FAR, after=far_after)
     fl.replan()
     fl.next_goals(5)
     fl.sync()
     explore = explore_stages(r_max)
+    if FAR is not None:   # the fallback after the chooser in use, for the vehicles it left without a goal
+        explore = explore + [(n if n == "far_goals" else "far_set_goals", f) for n, f in fl.explore_far_stages(FAR, after=far_after)]
     names = ["sense"] + [n for n, _ in explore] + [n for n, _ in fl.stages()] + ["next_goals"]
     per, wanted, found = {n: [] for n in names}, [], []
     for _ in range(cycles):
@@ -407,6 +420,25 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                  "candidates_mean": float(rr["candidates"][hit].mean()) if hit.any() else 0.0,
                  "reachable_mean": float(rr["reachable"][hit].mean()) if hit.any() else 0.0,
                  "same_cell_as_frontier_goals": int((rr["cell"] == rec["cell"]).sum())}
+    far = {}
+    if FAR is not None:   # every vehicle wanted and nobody skipped, applied to nobody, beside reach_goals in the same call, a median of five each
+        fr = fl.far_records()[0]
+        far_ms = fenced_ms(fl, fl.explore_far_stages(FAR, want="all")[0][1], 5)
+        fa = fl.far_records()[0]
+        beside_ms = fenced_ms(fl, fl.explore_reachable_stages(r_max, want="all")[0][1], 5)
+        hit = (fa["flags"] & ~(abi.FH_FRONTIER_FOUND | abi.FH_REACH_CUT)) == abi.FH_FRONTIER_WANTED
+        far = {"far": {"block": FAR, "after": far_after, "work_bytes": int(fl.d_far_work.numel()),
+                       "far_goals_loop_ms": med.get("far_goals"), "far_searched_last_cycle": int(((fr["flags"] & ~(abi.FH_FRONTIER_FOUND | abi.FH_REACH_CUT))
+                                                                                                    == abi.FH_FRONTIER_WANTED).sum()),
+                       "far_skipped_last_cycle": int((fr["flags"] & abi.FH_FAR_SKIPPED != 0).sum()),
+                       "far_goals_all_ms": float(np.median(far_ms)), "far_goals_all_runs_ms": [float(x) for x in far_ms],
+                       "reach_goals_all_beside_ms": float(np.median(beside_ms)), "reach_goals_all_beside_runs_ms": [float(x) for x in beside_ms],
+                       "far_searched_all": int(hit.sum()), "far_found_all": int((fa["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                       "levels_mean": float(fa["levels"][hit].mean()) if hit.any() else 0.0, "levels_max": int(fa["levels"].max()),
+                       "reached_mean": float(fa["reached"][hit].mean()) if hit.any() else 0.0,
+                       "targets_mean": float(fa["targets"][hit].mean()) if hit.any() else 0.0,
+                       "hops_mean": float(fa["hops"][fa["hops"] >= 0].mean()) if (fa["hops"] >= 0).any() else -1.0,
+                       "members_mean": float(fa["members"][fa["hops"] >= 0].mean()) if (fa["hops"] >= 0).any() else 0.0}}
     if BID:   # every vehicle wanted, applied to nobody: bid_goals and team_goals in turn, a median each
         reps = max(cycles, 5)
         runs = {"bid_goals": [], "team_goals": []}
@@ -533,7 +565,7 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                       "poor_total": int(gr["poor"].sum()), "all_poor": int((gr["flags"] & abi.FH_GAIN_ALL_POOR != 0).sum()),
                       "same_first_40_bytes_counts": bool(all(np.array_equal(gr[k], rr[k]) for k in ("candidates", "reachable", "reached", "levels"))),
                       "other_cell_than_reach_goals": int((gr["cell"][both] != rr["cell"][both]).sum()), "chosen_by_both": int(both.sum())})
-    return {"r_max": r_max, "goal_stage": goal_stage, **reach, "stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "wanted_per_cycle": wanted, "found_per_cycle": found,
+    return {"r_max": r_max, "goal_stage": goal_stage, **reach, **far, "stages_ms": med, "cycle_fenced_ms": float(sum(med.values())), "wanted_per_cycle": wanted, "found_per_cycle": found,
             "frontier_goals_reached_ms": med.get("frontier_goals"), "frontier_goals_all_ms": float(np.median(all_ms)),
             "frontier_goals_all_runs_ms": [float(x) for x in all_ms], "found_all": int((rec["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
             "candidates_all_mean": float(rec["candidates"].mean()), "view_coverage_ms": float(np.median(cov_ms)),
@@ -775,6 +807,9 @@ def main():
         del argv[k:k + 2]
     if "--explore" in argv:      # (read into EXPLORE above)
         k = argv.index("--explore")
+        del argv[k:k + 2]
+    if "--far" in argv:          # (read into FAR above)
+        k = argv.index("--far")
         del argv[k:k + 2]
     if "--reach" in argv:        # (read into REACH above)
         argv.remove("--reach")
