@@ -143,7 +143,10 @@ int fh_set_params(fh_ctx* ctx, const fh_params* p);
 /* Kernels run on this stream (hipStream_t as void*); NULL => the context's own stream.
  * A context owns ONE work queue, ticket counter and branch-and-bound workspace: at most one of its launches may be in
  * flight at a time.  Launches issued through one context are ordered on its stream; switching streams synchronises with
- * the previous one.  Use one context per concurrent pipeline (as bench.py does). */
+ * the previous one.  Use one context per concurrent pipeline (as bench.py does).
+ * A context that is given a stream destroys its own one (NULL creates it again): the HIP runtime places the streams of a process on
+ * its hardware queues (GPU_MAX_HW_QUEUES, 4 by default) by how many streams each queue carries, and an idle stream per context would
+ * take the place of a pipeline's stream there. */
 int fh_set_stream(fh_ctx* ctx, void* hip_stream);
 
 /* Packed results: what crosses PCIe / xGMI.  An fh_result holds FH_MAX_SEG = 16 coefficient rows whatever n_seg is (1600 B; at
@@ -170,14 +173,25 @@ int fh_control_points(const fh_result* results, int n, int n_seg, double* cp);
 /* Scheduling of a solve launch: how the persistent workgroups order and share the work of a batch.  NO RESULT FIELD DEPENDS ON
  * ANY OF THESE (tests/test_gpu_round2.py solves 8192 pairs with each of them switched off and compares bit for bit); only
  * nodes / qp_iters / kflops, which count the work actually done, and the time a launch takes.  Defaults: fh_default_sched(). */
+/* launch_order, look_every and waiting_workgroups have automatic values that depend on what else the process has in flight on the device
+ * when the launch is issued (faster_amd/csrc/fh_policy.hpp is the one copy of the rule).  Three regimes, from `others` = the solve launches
+ * of OTHER contexts of this process in flight on the device and `queues` = the hardware queues of the HIP runtime (FASTERHIP_HW_QUEUES if
+ * set, else GPU_MAX_HW_QUEUES, else 4; clamped to 1..32; read once per context in fh_create, never set by the library):
+ *   alone          others == 0;
+ *   beside others  0 < others and others + 1 <= queues: every launch has a hardware queue of its own;
+ *   queued         others + 1 > queues: launches wait behind each other on the hardware queues (14 pipelines on the default 4 queues).
+ * Blind spots: launches of other PROCESSES on the device are not seen, and a runtime whose queue count differs from what the variables say
+ * is believed to have what they say (FASTERHIP_HW_QUEUES is there to state the real number). */
 typedef struct fh_sched {
-  int32_t launch_order;       /* 1 (default): batches of >= 2048 units start with the corridors that have most polytopes — unless another context
-                                 of this process has a solve launch in flight on the device (what the order is for, the END of a launch, is
-                                 hidden then, and the two small sorting launches queue behind the resident grids); 2: always; 0: never   */
+  int32_t launch_order;       /* 1 (default): batches of >= 2048 units start with the corridors that have most polytopes when the launch is
+                                 alone.  Beside others and queued it is not sorted: what the order is for, the END of a launch, is hidden
+                                 behind the other launches then, and the two small sorting launches queue behind the resident grids
+                                 (queued, four launches running at once: -0.9 % with the order); 2: always; 0: never                   */
   int32_t publish_factor;     /* a problem that has used this many times the running mean of active-set iterations may publish
                                  frames ahead of the idle workgroups (default 4; 0: never)                                      */
   int32_t backlog;            /* frames that may be published ahead of the takers (default 32; 0: none)                        */
-  int32_t waiting_workgroups; /* workgroups that keep waiting for frames when the fresh problems run out (0 = default: CUs / 64; CUs / 16 for batches of up to 8 problems per CU) */
+  int32_t waiting_workgroups; /* workgroups that keep waiting for frames when the fresh problems run out (0 = default: CUs / 64 in all three
+                                 regimes — queued, 8 or 16 of them are -0.2 / -1.8 %; CUs / 16 for batches of up to 8 problems per CU) */
   int32_t min_nodes;          /* a problem gives work to an IDLE workgroup only after this many nodes of its trees (default 2)  */
   int32_t cloud_blocks;       /* 1 (default): the decomposition skips blocks of 64 cloud points whose bounding box misses the
                                  local box of a segment                                                                         */
@@ -214,7 +228,8 @@ typedef struct fh_sched {
                                  such a launch is its tail: its long trees must find help early), 16 when another context of this process has a
                                  solve launch in flight on the same device when this one is issued (the tail of a launch is then hidden behind
                                  the others, and every frame that changes hands is overhead: C4, twelve launches in flight, +2.5 %; one launch
-                                 alone with 16: 2-5 % later).  fh_last_launch reports the value a launch ran with.                          */
+                                 alone with 16: 2-5 % later) — beside others and queued alike (queued, four launches running at once: 8 is
+                                 -4.6 %, 32 within the spread of 16).  fh_last_launch reports the value a launch ran with.                  */
   int32_t struct_size;        /* sizeof(fh_sched) as the CALLER was compiled (fh_default_sched sets it), or 0 = not stated.  fh_set_sched
                                  refuses any other value: the struct has changed between rounds (round 4's child_bound became
                                  no_child_bound with the opposite meaning at the same offset), and a binary built against an older
