@@ -402,6 +402,30 @@ def default_far_params(block):
     return p
 
 
+# fh_apart_params, fh_apart_record: that fallback for a team, the target blocks a peer's claim covers are no targets
+# (include/fasterhip_apart.h); the first 64 bytes of both are fh_far_params' and fh_far_record's, the record's flags that record's
+# and these; the pass limits are those of fh_spread_params under the header's names
+FH_APART_UNSETTLED, FH_APART_CLAIMED = 256, 512
+FH_APART_MAX_PASSES, FH_APART_DEFAULT_PASSES = 64, 8
+FH_APART_SKIPPED, FH_APART_MAX_WORDS = FH_FAR_SKIPPED, FH_FAR_MAX_WORDS   # (that header's own names for K21's two)
+far_spread_params_dtype = np.dtype([("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("reserved_d", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                                    ("block", "<i4"), ("reserved", "<i4", (5,)), ("r_spread", "<f8"), ("passes", "<i4"),
+                                    ("reserved_tail", "<i4", (5,))], align=True)
+far_spread_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("block_cell", "<i4"), ("hops", "<i4"), ("targets", "<i4"),
+                                    ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("members", "<i4"), ("reserved", "<i4", (2,)),
+                                    ("d2", "<f8"), ("block_d2", "<f8"), ("group", "<i4"), ("decided_pass", "<i4"), ("lower", "<i4"),
+                                    ("standing", "<i4"), ("claims", "<i4"), ("claimed", "<i4"), ("reserved_tail", "<i4", (2,))], align=True)
+assert (far_spread_params_dtype.itemsize, far_spread_record_dtype.itemsize) == (96, 96)
+
+
+def default_far_spread_params(block, r_spread):
+    """fh_apart_params: default_far_params, no target block nearer than r_spread to a peer's goal, FH_APART_DEFAULT_PASSES passes."""
+    p = np.zeros((), dtype=far_spread_params_dtype)
+    p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"], p["block"] = 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0, block
+    p["r_spread"], p["passes"] = r_spread, FH_APART_DEFAULT_PASSES
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

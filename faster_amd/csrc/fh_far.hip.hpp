@@ -19,6 +19,7 @@
 //                       the end of one row into the next.  In the first level that holds a target block every such bit computes D2; the
 //                       smallest (D2, b) by wave_min / wave_min_i32 and across the wavefronts through LDS; then the workgroup scans the
 //                       at most 16^3 voxels of that block for the smallest (d2, c) and counts them.  The flood runs on for the counts.
+//                       Its body is far_body<false>; the chooser for a team instantiates far_body<true>.
 // LDS of far_goals_kernel: 6 bitmaps of FH_FAR_MAX_WORDS words = 24 KB static, and the slots of the reductions.
 // Every address comes from a checked number: view in [0, n_views), the start cell tested against the dims before it is used, block
 // extents clipped to the lattice, neighbour bytes tested against the dims and neighbour words against the rows before they are loaded,
@@ -209,7 +210,13 @@ __device__ __forceinline__ double far_block_d2(const FarArgs& a, int bx, int by,
   return gx2 + gy2 + gz2;
 }
 
-__global__ void __launch_bounds__(256) far_goals_kernel(FarArgs a) {
+struct FarNoClaims {};
+
+// The body of far_goals_kernel, and with CLAIMS that of far_spread_goals_kernel (fh_apart.hpp): x.clear() takes the blocks that
+// the claims of peers cover out of T in LDS before the flood, x.store() writes the longer record.  With CLAIMS false every
+// `if constexpr` below is gone and the code is what the kernel held before it was a template.
+template <bool CLAIMS, class X>
+__device__ __forceinline__ void far_body(const FarArgs& a, const X& x) {
 #pragma clang fp contract(off)
   __shared__ unsigned long long s_t[FAR_WORDS], s_lx[FAR_WORDS], s_ly[FAR_WORDS], s_lz[FAR_WORDS], s_a[FAR_WORDS], s_b[FAR_WORDS];
   __shared__ double s_bd2[4], s_vd2[4];
@@ -227,7 +234,9 @@ __global__ void __launch_bounds__(256) far_goals_kernel(FarArgs a) {
   int flags = who.flags;
   const FarCounts none = {-1, -1, 0, 0, 0, 0, 0};
   if (!who.searched) {  // (uniform over the workgroup)
-    if (t == 0) far_store(a, i, flags, view, -1, INFINITY, INFINITY, none);
+    if constexpr (!CLAIMS) {  // (with CLAIMS the count kernel has written the outputs of a vehicle that is not searched)
+      if (t == 0) far_store(a, i, flags, view, -1, INFINITY, INFINITY, none);
+    }
     return;
   }
   const int W = a.W, wx = a.wx, slab = a.wx * a.cy;
@@ -269,6 +278,13 @@ __global__ void __launch_bounds__(256) far_goals_kernel(FarArgs a) {
       s_a[u] = u == sw ? sbit : 0ull;
       s_b[u] = 0ull;
     }
+  }
+  int n_claims = 0, n_standing = 0;  // (uniform)
+  if constexpr (CLAIMS) {
+    // every thread takes the claimed blocks out of the words of T it owns (and alone has written); the barriers inside are uniform
+    const int n_claimed = x.clear(a, i, t, s_t, n_claims, n_standing);
+    const int wave_claimed = fhw::wave_sum_i32(n_claimed);
+    if (lane == 0) x.sum[w] = wave_claimed;
   }
   const int wave_targets = fhw::wave_sum_i32(n_targets);
   if (lane == 0) s_k[w] = wave_targets;
@@ -392,8 +408,14 @@ __global__ void __launch_bounds__(256) far_goals_kernel(FarArgs a) {
     n.levels = level;
     n.members = hops >= 0 ? members : 0;
     if (cut) flags |= FH_REACH_CUT;
-    far_store(a, i, flags, view, hops >= 0 ? best_cell : -1, hops >= 0 ? best : INFINITY, hops >= 0 ? best_bd2 : INFINITY, n);
+    if constexpr (CLAIMS)
+      x.store(a, i, flags, view, hops >= 0 ? best_cell : -1, hops >= 0 ? best : INFINITY, hops >= 0 ? best_bd2 : INFINITY, n, n_claims, n_standing,
+              x.sum[0] + x.sum[1] + x.sum[2] + x.sum[3]);
+    else
+      far_store(a, i, flags, view, hops >= 0 ? best_cell : -1, hops >= 0 ? best : INFINITY, hops >= 0 ? best_bd2 : INFINITY, n);
   }
 }
+
+__global__ void __launch_bounds__(256) far_goals_kernel(FarArgs a) { far_body<false>(a, FarNoClaims()); }
 
 }  // namespace fhp

@@ -7,7 +7,9 @@
 // with a gain that counts only the unknown voxels a candidate has a line of sight to (kernel: fh_sight.hip.hpp), and of
 // include/fasterhip_bid.h (fh_bid_goals_device): the search of the gain-aware chooser for a team inside rounds ordered by bids, the best
 // offer wins a contested frontier (kernels: fh_bid.hip.hpp), and of include/fasterhip_far.h (fh_far_goals_device): the fallback for the
-// vehicles those choosers left without a goal, a flood of the whole view over blocks of voxels (kernels: fh_far.hip.hpp).
+// vehicles those choosers left without a goal, a flood of the whole view over blocks of voxels (kernels: fh_far.hip.hpp), and of
+// include/fasterhip_apart.h (fh_apart_goals_device): that fallback for a team, the target blocks that a peer's claim covers
+// taken out before the flood (kernels: fh_apart.hpp).
 // A translation unit of its own: fh_map.hip and fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
@@ -22,6 +24,7 @@
 #include "../../include/fasterhip_sight.h"
 #include "../../include/fasterhip_bid.h"
 #include "../../include/fasterhip_far.h"
+#include "../../include/fasterhip_apart.h"
 #include "fh_reach.hip.hpp"
 #include "fh_spread.hip.hpp"
 #include "fh_gain.hip.hpp"
@@ -30,6 +33,7 @@
 #include "fh_bid.hip.hpp"
 #include "fh_far.hip.hpp"
 #include "fh_host.hpp"
+#include "fh_apart.hpp"
 
 // the lattice of the views, judged as fh_map_frontier_goals_device judges it (0: fine, cells filled in)
 static int reach_lattice(const fh_voxel_grid* grid, size_t view_stride, int n_views, long long* cells) {
@@ -269,6 +273,87 @@ int fh_far_goals_device(void* stream, const fh_far_params* par, const fh_voxel_g
 static size_t bid_offers_offset(int n) { return spread_rows_offset(n) + (size_t)n * FH_BID_LIST * sizeof(int32_t); }
 
 size_t fh_bid_work_bytes(int n) { return n <= 0 ? 0 : bid_offers_offset(n) + (size_t)n * 2 * sizeof(int32_t) + (size_t)n * 2 * sizeof(int32_t); }
+
+size_t fh_apart_work_bytes(const fh_voxel_grid* grid, int block, int n_views, int n) {
+  const size_t far = fh_far_work_bytes(grid, block, n_views);
+  if (far == 0 || n < 0) return 0;
+  return far + spread_rows_offset(n) + (size_t)n * sizeof(int32_t) + (size_t)n * sizeof(int32_t);
+}
+
+// (behind K21's entry point and the bid chooser's workspace: K21's clauses in K21's order, then K16's two; the summary stage is K21's
+// three calls as they stand above)
+int fh_apart_goals_device(void* stream, const fh_apart_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                               const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                               const int32_t* d_skip, const int32_t* d_group, const fh_vehicle* d_vehicles, int n, void* d_work,
+                               size_t work_bytes, double* d_goals, int32_t* d_mask, fh_apart_record* d_records) {
+  static_assert(sizeof(fh_apart_params) == 96 && sizeof(fh_apart_record) == 96 && offsetof(fh_apart_params, r_spread) == 64 &&
+                    offsetof(fh_apart_params, block) == offsetof(fh_far_params, block) &&
+                    offsetof(fh_apart_record, d2) == offsetof(fh_far_record, d2) &&
+                    offsetof(fh_apart_record, block_d2) == offsetof(fh_far_record, block_d2) && offsetof(fh_apart_record, group) == 64 &&
+                    FH_APART_UNSETTLED == FH_SPREAD_UNSETTLED && FH_APART_CLAIMED == FH_SPREAD_CLAIMED &&
+                    FH_APART_MAX_PASSES == FH_SPREAD_MAX_PASSES && FH_APART_DEFAULT_PASSES == FH_SPREAD_DEFAULT_PASSES &&
+                    FH_APART_SKIPPED == FH_FAR_SKIPPED && FH_APART_MAX_WORDS == FH_FAR_MAX_WORDS &&
+                    offsetof(fh_apart_params, want) == offsetof(fh_far_params, want) && offsetof(fh_apart_params, max_hops) == offsetof(fh_far_params, max_hops) &&
+                    offsetof(fh_apart_record, members) == offsetof(fh_far_record, members) && offsetof(fh_apart_record, hops) == offsetof(fh_far_record, hops),
+                "include/fasterhip_apart.h: K21's params and record, K16's flags and pass limits under its own names");
+  if (!par) return FH_ERR_ARG;
+  if (reach_field_clauses(1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
+  if (par->block < 1 || par->block > 16) return FH_ERR_ARG;
+  if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
+  const int W = far_words(grid, par->block);
+  if (W > FH_FAR_MAX_WORDS) return FH_ERR_ARG;
+  if (!std::isfinite(par->r_spread) || !(par->r_spread > 0.0)) return FH_ERR_ARG;
+  if (par->passes < 1 || par->passes > FH_APART_MAX_PASSES) return FH_ERR_ARG;
+  if (work_bytes < fh_apart_work_bytes(grid, par->block, n_views, n)) return FH_ERR_ARG;
+  if (n == 0) return FH_OK;
+  if (!d_work || !d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  hipPointerAttribute_t where;
+  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  fhh::DeviceScope scope(where.device);
+  if (!scope.ok) return FH_ERR_DEVICE;
+  fhp::FarSpreadArgs x;
+  fhp::FarArgs& s = x.f;
+  reach_args(s.r, 1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of,
+             n_views, d_vehicles);
+  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
+  s.B = par->block;
+  s.cx = (grid->dims[0] + s.B - 1) / s.B;
+  s.cy = (grid->dims[1] + s.B - 1) / s.B;
+  s.cz = (grid->dims[2] + s.B - 1) / s.B;
+  s.wx = (s.cx + 63) / 64;
+  s.W = W;
+  s.n = n;
+  s.skip = d_skip;
+  unsigned char* const work = static_cast<unsigned char*>(d_work);
+  s.sums = static_cast<unsigned long long*>(d_work);
+  const size_t need_bytes = ((size_t)n_views + 63) & ~(size_t)63;
+  s.need = work + (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long);
+  s.records = nullptr;
+  x.s2 = par->r_spread * par->r_spread;
+  x.pass = 0; x.passes = par->passes;
+  x.group = d_group;
+  x.cls = s.need + need_bytes;  // (= work + fh_far_work_bytes: a multiple of 8)
+  x.grp = reinterpret_cast<int32_t*>(x.cls + spread_rows_offset(n));
+  x.lower = x.grp + n;
+  x.records = d_records;
+  const hipStream_t q = (hipStream_t)stream;
+  if (hipMemsetAsync(s.need, 0, need_bytes, q) != hipSuccess) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  hipLaunchKernelGGL(fhp::far_need_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, s);
+  hipLaunchKernelGGL(fhp::far_blocks_kernel, dim3((unsigned)W, (unsigned)(n_views < 65535 ? n_views : 65535)), dim3(256), 0, q, s);
+  hipLaunchKernelGGL(fhp::far_spread_class_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, x);
+  hipLaunchKernelGGL(fhp::far_spread_count_kernel, dim3((unsigned)n), dim3(64), 0, q, x);
+  for (int p = 1; p <= par->passes; p++) {
+    x.pass = p;
+    hipLaunchKernelGGL(fhp::far_spread_goals_kernel, dim3((unsigned)n), dim3(256), 0, q, x);
+  }
+  return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
+}
 
 // (K18's clauses in K18's order; it stands before fh_sight_goals_device, and fh_team_goals_device still ends this file)
 int fh_bid_goals_device(void* stream, const fh_bid_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,

@@ -60,6 +60,9 @@ blocks reaches, however far away it is:
 
     sense -> observe -> [link] -> explore_reachable -> explore_far(after="reachable") -> replan -> next_goals
 
+explore_far_spread() is explore_far() for a team (include/fasterhip_apart.h): a block within r_spread of the goal a peer holds or
+has just been given is no target, so stranded teammates with one view do not all fly the long way to one voxel.
+
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
@@ -131,6 +134,8 @@ class Fleet:
         self.d_sight_goals = self.d_sight_mask = self.d_sight_records = None                                                   # explore_sight
         self.d_bid_goals = self.d_bid_mask = self.d_bid_records = self.d_bid_work = None                                       # explore_bid
         self.d_far_goals = self.d_far_mask = self.d_far_records = self.d_far_work = self._far_work_key = None                  # explore_far
+        self.d_far_spread_goals = self.d_far_spread_mask = self.d_far_spread_records = None                                    # explore_far_spread
+        self.d_far_spread_work = self._far_spread_work_key = None
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -781,6 +786,77 @@ class Fleet:
         self.sync()
         return (self.d_far_records.cpu().numpy().view(abi.far_record_dtype).copy(), self.d_far_goals.cpu().numpy().copy(),
                 self.d_far_mask.cpu().numpy().copy())
+
+    def explore_far_spread(self, block=8, r_spread=2.0, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link", after=None):
+        """explore_far() for a team (include/fasterhip_apart.h): a block of the flood nearer than r_spread to the goal that a peer
+        is on its way to, or that a peer with a lower index has been given by an earlier pass of this call, is no target, so stranded
+        teammates with one view fly to different far frontiers.  A vehicle that `after`'s chooser gave a goal is skipped and claims
+        that goal.  groups and passes are explore_spread()'s (no list, so no overflow; a vehicle with `passes` searching peers below
+        it is FH_APART_UNSETTLED for a period); after, block and the other arguments are explore_far()'s; the buffers and the
+        workspace are its own (far_spread_records())."""
+        stages = self.explore_far_spread_stages(block, r_spread, r_avoid, z, want, max_hops, passes, groups, after)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_far_spread_stages(self, block=8, r_spread=2.0, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link",
+                                  after=None):
+        """The launches of explore_far_spread(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them)."""
+        if groups not in ("link", "view"):
+            raise capi.FasterHipError("Fleet.explore_far_spread: groups is \"link\" or \"view\", got %r" % (groups,))
+        par = abi.default_far_spread_params(block, r_spread)
+        flags, stride, vo, n_views = self._reach_inputs("explore_far_spread", par, r_avoid, z, want, max_hops)
+        if passes is not None:
+            par["passes"] = passes
+        skip = None
+        if after is not None:
+            if after not in self._FAR_AFTER:
+                raise capi.FasterHipError("Fleet.explore_far_spread: after is None or one of %s, got %r" % (", ".join(sorted(self._FAR_AFTER)), after))
+            skip = getattr(self, self._FAR_AFTER[after])
+            if skip is None:
+                raise capi.FasterHipError("Fleet.explore_far_spread: after=%r, but that chooser has not run" % (after,))
+        g = capi._grid_record(self.grid)
+        work_bytes = int(capi.lib().fh_apart_work_bytes(abi.ptr(g), int(block), int(n_views), int(self.n)))
+        if work_bytes == 0:
+            raise capi.FasterHipError("Fleet.explore_far_spread: block must be 1 .. 16 and the blocks of the lattice must fit %d words of 64 "
+                                      "(got block %r on a lattice of %s)" % (abi.FH_FAR_MAX_WORDS, block, tuple(int(d) for d in self.grid[2])))
+        t = self.torch
+        if self.d_far_spread_goals is None:
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_far_spread_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_far_spread_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_far_spread_records = t.zeros(self.n * abi.far_spread_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            for d in (self.d_far_spread_goals, self.d_far_spread_mask, self.d_far_spread_records):
+                d.record_stream(self.stream)
+        key = (tuple(int(d) for d in self.grid[2]), int(block), int(n_views), int(self.n))
+        if self._far_spread_work_key != key:   # (one workspace per lattice, block, number of views and vehicles)
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_far_spread_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
+            self.d_far_spread_work.record_stream(self.stream)
+            self._far_spread_work_key = key
+        # the labels are per view: with set_unknown's single view there is nothing to label
+        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
+            and self.d_link_labels.numel() == n_views else None
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("far_spread_goals", lambda: m.far_spread_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if skip is None else p(skip),
+                                                                   None if labels is None else p(labels), p(self.d_vehicles), self.n,
+                                                                   p(self.d_far_spread_work), work_bytes, p(self.d_far_spread_goals),
+                                                                   p(self.d_far_spread_mask), p(self.d_far_spread_records),
+                                                                   self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_far_spread_goals), p(self.d_far_spread_mask),
+                                                           self.n)),
+        ]
+
+    def far_spread_records(self):
+        """(records [n] abi.far_spread_record_dtype, goals [n][3], mask [n] int32) of the last explore_far_spread() (synchronises)."""
+        if self.d_far_spread_goals is None:
+            raise capi.FasterHipError("Fleet.far_spread_records: explore_far_spread first")
+        self.sync()
+        return (self.d_far_spread_records.cpu().numpy().view(abi.far_spread_record_dtype).copy(), self.d_far_spread_goals.cpu().numpy().copy(),
+                self.d_far_spread_mask.cpu().numpy().copy())
 
     def explore_spread(self, r_max, r_spread, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link"):
         """explore_reachable() for a team (include/fasterhip_spread.h): a frontier voxel nearer than r_spread to the goal that a peer is

@@ -88,7 +88,12 @@ points every 5 m in x and in y, floor to ceiling, with a door of 1.2 m in every 
 after that chooser in every period (include/fasterhip_far.h): its stages are reported as "far_goals" and "far_set_goals"; under "far" the
 launch with every vehicle wanted and nobody skipped as "far_goals_all_ms" beside "reach_goals_all_beside_ms" of the same call (medians of
 five, fenced by events), and the levels, blocks reached, target blocks, hops and members of that launch.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--far BLOCK] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--far BLOCK --far-spread R_SPREAD [--passes P] runs Fleet.explore_far_spread(BLOCK, R_SPREAD, passes=P, after=...) in its place
+(include/fasterhip_apart.h; with --link the groups are those of one link() after the first look): the stages are
+"far_spread_goals" and "far_spread_set_goals", and under "far_spread" the launch with every vehicle wanted and nobody skipped as
+"far_spread_goals_all_ms" beside "far_goals_all_beside_ms" of the same call, the same launch with 1 and with 64 passes, the cost of a
+pass from the two, the largest `lower`, and the vehicles left unsettled or with every target claimed.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--far BLOCK [--far-spread R_SPREAD [--passes P]]] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -130,6 +135,12 @@ if BID and not TEAM:
 FAR = int(sys.argv[sys.argv.index("--far") + 1]) if "--far" in sys.argv else None
 if FAR is not None and not ("--views" in sys.argv and EXPLORE is not None):
     sys.exit("--far needs --views --explore R_MAX")
+FAR_SPREAD = float(sys.argv[sys.argv.index("--far-spread") + 1]) if "--far-spread" in sys.argv else None
+if FAR_SPREAD is not None and FAR is None:
+    sys.exit("--far-spread needs --far BLOCK")
+PASSES = int(sys.argv[sys.argv.index("--passes") + 1]) if "--passes" in sys.argv else None
+if PASSES is not None and FAR_SPREAD is None:
+    sys.exit("--passes needs --far-spread R_SPREAD")
 SIGHT = "--sight" in sys.argv
 if SIGHT and (GAIN is None or SPREAD is not None):
     sys.exit("--sight needs --gain G and no --spread")
@@ -373,13 +384,20 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
         (fl.explore_reachable if REACH else fl.explore)(r_max)
     far_after = "bid" if BID else "team" if TEAM else "spread" if SPREAD is not None else "sight" if SIGHT else "gain" if GAIN is not None else "reachable" if REACH \
         else "explore"
-    if FAR is not None:
+    if FAR_SPREAD is not None:
+        if LINK and SPREAD is None:   # teams: the groups of one link() after the first look (the choosers for a team above have linked)
+            fl.link(LINK[0])
+        fl.explore_far_spread(FAR, FAR_SPREAD, passes=PASSES, after=far_after)
+    elif FAR is not None:
         fl.explore_far(FAR, after=far_after)
     fl.replan()
     fl.next_goals(5)
     fl.sync()
     explore = explore_stages(r_max)
-    if FAR is not None:   # the fallback after the chooser in use, for the vehicles it left without a goal
+    if FAR_SPREAD is not None:   # the fallback for a team after the chooser in use
+        explore = explore + [(n if n == "far_spread_goals" else "far_spread_set_goals", f)
+                             for n, f in fl.explore_far_spread_stages(FAR, FAR_SPREAD, passes=PASSES, after=far_after)]
+    elif FAR is not None:   # the fallback after the chooser in use, for the vehicles it left without a goal
         explore = explore + [(n if n == "far_goals" else "far_set_goals", f) for n, f in fl.explore_far_stages(FAR, after=far_after)]
     names = ["sense"] + [n for n, _ in explore] + [n for n, _ in fl.stages()] + ["next_goals"]
     per, wanted, found = {n: [] for n in names}, [], []
@@ -421,7 +439,35 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                  "reachable_mean": float(rr["reachable"][hit].mean()) if hit.any() else 0.0,
                  "same_cell_as_frontier_goals": int((rr["cell"] == rec["cell"]).sum())}
     far = {}
-    if FAR is not None:   # every vehicle wanted and nobody skipped, applied to nobody, beside reach_goals in the same call, a median of five each
+    if FAR_SPREAD is not None:   # every vehicle wanted and nobody skipped, applied to nobody, beside far_goals in the same call, medians of five
+        sr = fl.far_spread_records()[0]
+        searched = lambda r: (r["flags"] & ~(abi.FH_FRONTIER_FOUND | abi.FH_REACH_CUT | abi.FH_APART_UNSETTLED | abi.FH_APART_CLAIMED)) \
+            == abi.FH_FRONTIER_WANTED   # noqa: E731
+        runs = {}
+        for label, passes in (("set", PASSES), ("1", 1), ("64", abi.FH_APART_MAX_PASSES)):
+            runs[label] = fenced_ms(fl, fl.explore_far_spread_stages(FAR, FAR_SPREAD, want="all", passes=passes)[0][1], 5)
+            if label == "set":
+                sa = fl.far_spread_records()[0]
+        beside_ms = fenced_ms(fl, fl.explore_far_stages(FAR, want="all")[0][1], 5)
+        fb = fl.far_records()[0]
+        hit = searched(sa)
+        far = {"far_spread": {"block": FAR, "r_spread": FAR_SPREAD, "passes": int(PASSES or abi.FH_APART_DEFAULT_PASSES), "after": far_after,
+                              "linked": bool(LINK), "work_bytes": int(fl.d_far_spread_work.numel()),
+                              "far_spread_goals_loop_ms": med.get("far_spread_goals"), "searchers_last_cycle": int(searched(sr).sum()),
+                              "skipped_last_cycle": int((sr["flags"] & abi.FH_FAR_SKIPPED != 0).sum()),
+                              "far_spread_goals_all_ms": float(np.median(runs["set"])), "far_spread_goals_all_runs_ms": [float(x) for x in runs["set"]],
+                              "far_spread_goals_all_1_pass_ms": float(np.median(runs["1"])),
+                              "far_spread_goals_all_64_passes_ms": float(np.median(runs["64"])),
+                              "ms_per_pass": float((np.median(runs["64"]) - np.median(runs["1"])) / (abi.FH_APART_MAX_PASSES - 1)),
+                              "far_goals_all_beside_ms": float(np.median(beside_ms)), "far_goals_all_beside_runs_ms": [float(x) for x in beside_ms],
+                              "searchers_all": int(hit.sum()), "found_all": int((sa["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                              "far_found_all_beside": int((fb["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                              "lower_max": int(sa["lower"].max()), "standing_max": int(sa["standing"].max()), "claims_max": int(sa["claims"].max()),
+                              "unsettled_all": int((sa["flags"] & abi.FH_APART_UNSETTLED != 0).sum()),
+                              "all_claimed_all": int((sa["flags"] & abi.FH_APART_CLAIMED != 0).sum()),
+                              "claimed_mean": float(sa["claimed"][hit].mean()) if hit.any() else 0.0,
+                              "same_cell_as_far_goals": int((sa["cell"] == fb["cell"]).sum())}}
+    elif FAR is not None:   # every vehicle wanted and nobody skipped, applied to nobody, beside reach_goals in the same call, a median of five each
         fr = fl.far_records()[0]
         far_ms = fenced_ms(fl, fl.explore_far_stages(FAR, want="all")[0][1], 5)
         fa = fl.far_records()[0]
@@ -514,7 +560,7 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
         two_ms = fenced_ms(fl, explore_stages(r_max, want="all", passes=2)[0][1], reps)
         again_ms = fenced_ms(fl, fl.explore_reachable_stages(r_max, want="all")[0][1], reps)
         passes = np.bincount(sr["decided_pass"][sr["decided_pass"] > 0], minlength=2)
-        reach.update({"r_spread": SPREAD, "passes": abi.FH_SPREAD_DEFAULT_PASSES, "spread_goals_reached_ms": med["spread_goals"],
+        reach.update({"r_spread": SPREAD, "passes": abi.FH_APART_DEFAULT_PASSES, "spread_goals_reached_ms": med["spread_goals"],
                       "spread_goals_all_ms": float(np.median(spread_ms)), "spread_goals_all_runs_ms": [float(x) for x in spread_ms],
                       "spread_goals_all_one_pass_ms": float(np.median(one_ms)), "spread_goals_all_two_passes_ms": float(np.median(two_ms)),
                       "reach_goals_all_after_ms": float(np.median(again_ms)), "reach_goals_all_after_runs_ms": [float(x) for x in again_ms],
@@ -811,6 +857,10 @@ def main():
     if "--far" in argv:          # (read into FAR above)
         k = argv.index("--far")
         del argv[k:k + 2]
+    for opt in ("--far-spread", "--passes"):   # (read into FAR_SPREAD and PASSES above)
+        if opt in argv:
+            k = argv.index(opt)
+            del argv[k:k + 2]
     if "--reach" in argv:        # (read into REACH above)
         argv.remove("--reach")
     if "--spread" in argv:       # (read into SPREAD above)
