@@ -426,6 +426,31 @@ def default_far_spread_params(block, r_spread):
     return p
 
 
+# fh_prospect_params, fh_prospect_record: that fallback with a gain, the unknown voxels of a cube of blocks around a target block, chosen
+# by utility = gain - hop_cost * hops over all levels (include/fasterhip_prospect.h); the params are fh_far_params with three of its
+# reserved words in use, the first 64 bytes of the record are fh_far_record's
+FH_PROSPECT_SKIPPED, FH_PROSPECT_MAX_WORDS = FH_FAR_SKIPPED, FH_FAR_MAX_WORDS   # (that header's own names for K21's two)
+FH_PROSPECT_ALL_POOR = 1024
+FH_PROSPECT_MAX_BLOCKS, FH_PROSPECT_MAX_HOP_COST = 5, 16384
+far_gain_params_dtype = np.dtype([("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("reserved_d", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                                  ("block", "<i4"), ("gain_blocks", "<i4"), ("hop_cost", "<i4"), ("min_gain", "<i4"), ("reserved", "<i4", (2,))],
+                                 align=True)
+far_gain_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("block_cell", "<i4"), ("hops", "<i4"), ("targets", "<i4"),
+                                  ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("members", "<i4"), ("reserved", "<i4", (2,)),
+                                  ("d2", "<f8"), ("block_d2", "<f8"), ("gain", "<i4"), ("utility", "<i4"), ("poor", "<i4"), ("best_gain", "<i4")],
+                                 align=True)
+assert (far_gain_params_dtype.itemsize, far_gain_record_dtype.itemsize) == (64, 80)
+
+
+def default_far_gain_params(block, gain_blocks):
+    """fh_prospect_params: default_far_params, the gain of a block over a cube of 2 gain_blocks - 1 blocks an edge, a block step worth
+    the voxels of one face of a block (block * block; a judgement, not a measurement), no block is poor."""
+    p = np.zeros((), dtype=far_gain_params_dtype)
+    p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"], p["block"] = 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0, block
+    p["gain_blocks"], p["hop_cost"], p["min_gain"] = gain_blocks, int(block) * int(block), 0
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

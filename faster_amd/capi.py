@@ -68,6 +68,8 @@ BID_SYMBOLS = ["fh_bid_work_bytes", "fh_bid_goals_device"]
 FAR_SYMBOLS = ["fh_far_work_bytes", "fh_far_goals_device"]
 # include/fasterhip_apart.h
 FAR_SPREAD_SYMBOLS = ["fh_apart_work_bytes", "fh_apart_goals_device"]
+# include/fasterhip_prospect.h
+FAR_GAIN_SYMBOLS = ["fh_prospect_work_bytes", "fh_prospect_goals_device"]
 
 _LIB = None
 
@@ -365,6 +367,10 @@ def lib():
         L.fh_apart_work_bytes.argtypes = [vp, i32, i32, i32]
         L.fh_apart_goals_device.restype = i32
         L.fh_apart_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
+        L.fh_prospect_work_bytes.restype = ctypes.c_size_t
+        L.fh_prospect_work_bytes.argtypes = [vp, i32, i32]
+        L.fh_prospect_goals_device.restype = i32
+        L.fh_prospect_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -712,6 +718,25 @@ class Map:
                                               d_mask, d_records)
         if rc != 0:
             raise FasterHipError("fh_apart_goals_device: rc=%d" % rc)
+
+    def far_gain_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_vehicles, n, d_work, work_bytes, d_goals,
+                              d_mask, d_records, stream):
+        """fh_prospect_goals_device (include/fasterhip_prospect.h) with this map's lattice and bits: far_goals_device with a gain — a
+        target block is weighed by the unknown voxels of the cube of 2 par["gain_blocks"] - 1 blocks an edge around it, and of the
+        target blocks of ALL levels of the flood the one with the largest gain - par["hop_cost"] * hops is taken; a block whose gain is
+        below par["min_gain"] never is.  d_work: work_bytes >= fh_prospect_work_bytes(grid, block, n_views) of device memory; d_records
+        [n] abi.far_gain_record_dtype; par: one abi.far_gain_params_dtype record; `stream` as for reach_goals_device."""
+        p = _one_record(par, "far_gain", "far_gain_goals_device")
+        g = _grid_record(grid)
+        dims, origin = self.dims()
+        bits, res = ctypes.c_void_p(), ctypes.c_double()
+        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
+        mg = _grid_record((origin, res.value, dims))
+        rc = lib().fh_prospect_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
+                                            d_view_of, int(n_views), d_skip, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask,
+                                            d_records)
+        if rc != 0:
+            raise FasterHipError("fh_prospect_goals_device: rc=%d" % rc)
 
     def sight_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_goals, d_mask, d_records, stream):
         """fh_sight_goals_device (include/fasterhip_sight.h) with this map's lattice and bits: gain_goals_device with a gain that counts an

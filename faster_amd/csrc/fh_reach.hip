@@ -9,7 +9,8 @@
 // offer wins a contested frontier (kernels: fh_bid.hip.hpp), and of include/fasterhip_far.h (fh_far_goals_device): the fallback for the
 // vehicles those choosers left without a goal, a flood of the whole view over blocks of voxels (kernels: fh_far.hip.hpp), and of
 // include/fasterhip_apart.h (fh_apart_goals_device): that fallback for a team, the target blocks that a peer's claim covers
-// taken out before the flood (kernels: fh_apart.hpp).
+// taken out before the flood (kernels: fh_apart.hpp), and of include/fasterhip_prospect.h (fh_prospect_goals_device): that fallback
+// with a gain, the unknown voxels of the blocks around a target block, chosen by utility over all levels (kernels: fh_prospect.hpp).
 // A translation unit of its own: fh_map.hip and fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
@@ -25,6 +26,7 @@
 #include "../../include/fasterhip_bid.h"
 #include "../../include/fasterhip_far.h"
 #include "../../include/fasterhip_apart.h"
+#include "../../include/fasterhip_prospect.h"
 #include "fh_reach.hip.hpp"
 #include "fh_spread.hip.hpp"
 #include "fh_gain.hip.hpp"
@@ -33,6 +35,7 @@
 #include "fh_bid.hip.hpp"
 #include "fh_far.hip.hpp"
 #include "fh_host.hpp"
+#include "fh_prospect.hpp"
 #include "fh_apart.hpp"
 
 // the lattice of the views, judged as fh_map_frontier_goals_device judges it (0: fine, cells filled in)
@@ -278,6 +281,91 @@ size_t fh_apart_work_bytes(const fh_voxel_grid* grid, int block, int n_views, in
   const size_t far = fh_far_work_bytes(grid, block, n_views);
   if (far == 0 || n < 0) return 0;
   return far + spread_rows_offset(n) + (size_t)n * sizeof(int32_t) + (size_t)n * sizeof(int32_t);
+}
+
+size_t fh_prospect_work_bytes(const fh_voxel_grid* grid, int block, int n_views) {
+  const size_t far = fh_far_work_bytes(grid, block, n_views);  // (0: a null grid, a dimension < 1, a block outside 1..16, too many words, n_views < 1)
+  if (far == 0) return 0;
+  return far + (size_t)n_views * 64u * (size_t)far_words(grid, block) * sizeof(uint16_t);
+}
+
+// (K21's clauses in K21's order, the three new fields right behind `block`; K21's memset and need kernel as they stand above, then
+// one pass over the needed views for the four bitmaps and the counts, then a workgroup per vehicle)
+int fh_prospect_goals_device(void* stream, const fh_prospect_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                             const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                             const int32_t* d_skip, const fh_vehicle* d_vehicles, int n, void* d_work, size_t work_bytes, double* d_goals,
+                             int32_t* d_mask, fh_prospect_record* d_records) {
+  static_assert(sizeof(fh_prospect_params) == sizeof(fh_far_params) && sizeof(fh_prospect_record) == 80 && sizeof(fh_far_record) == 64 &&
+                    FH_PROSPECT_SKIPPED == FH_FAR_SKIPPED && FH_PROSPECT_MAX_WORDS == FH_FAR_MAX_WORDS &&
+                    offsetof(fh_prospect_params, r_avoid) == offsetof(fh_far_params, r_avoid) && offsetof(fh_prospect_params, z_lo) == offsetof(fh_far_params, z_lo) &&
+                    offsetof(fh_prospect_params, z_hi) == offsetof(fh_far_params, z_hi) &&
+                    offsetof(fh_prospect_params, reserved_d) == offsetof(fh_far_params, reserved_d) &&
+                    offsetof(fh_prospect_params, want) == offsetof(fh_far_params, want) && offsetof(fh_prospect_params, max_hops) == offsetof(fh_far_params, max_hops) &&
+                    offsetof(fh_prospect_params, block) == offsetof(fh_far_params, block) &&
+                    offsetof(fh_prospect_params, gain_blocks) == offsetof(fh_far_params, reserved) &&
+                    offsetof(fh_prospect_params, reserved) == offsetof(fh_far_params, reserved) + 3 * sizeof(int32_t) &&
+                    offsetof(fh_prospect_record, flags) == offsetof(fh_far_record, flags) && offsetof(fh_prospect_record, view) == offsetof(fh_far_record, view) &&
+                    offsetof(fh_prospect_record, cell) == offsetof(fh_far_record, cell) &&
+                    offsetof(fh_prospect_record, block_cell) == offsetof(fh_far_record, block_cell) &&
+                    offsetof(fh_prospect_record, hops) == offsetof(fh_far_record, hops) && offsetof(fh_prospect_record, targets) == offsetof(fh_far_record, targets) &&
+                    offsetof(fh_prospect_record, reachable) == offsetof(fh_far_record, reachable) &&
+                    offsetof(fh_prospect_record, reached) == offsetof(fh_far_record, reached) && offsetof(fh_prospect_record, levels) == offsetof(fh_far_record, levels) &&
+                    offsetof(fh_prospect_record, members) == offsetof(fh_far_record, members) &&
+                    offsetof(fh_prospect_record, reserved) == offsetof(fh_far_record, reserved) && offsetof(fh_prospect_record, d2) == offsetof(fh_far_record, d2) &&
+                    offsetof(fh_prospect_record, block_d2) == offsetof(fh_far_record, block_d2) && offsetof(fh_prospect_record, gain) == 64 &&
+                    (FH_PROSPECT_ALL_POOR & (FH_APART_UNSETTLED | FH_APART_CLAIMED | FH_FAR_SKIPPED)) == 0,
+                "include/fasterhip_prospect.h: K21's params, record, skip flag and word cap under its own names");
+  if (!par) return FH_ERR_ARG;
+  if (reach_field_clauses(1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
+  if (par->block < 1 || par->block > 16) return FH_ERR_ARG;
+  if (par->gain_blocks < 0 || par->gain_blocks > FH_PROSPECT_MAX_BLOCKS) return FH_ERR_ARG;
+  if (par->hop_cost < 0 || par->hop_cost > FH_PROSPECT_MAX_HOP_COST) return FH_ERR_ARG;
+  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
+  const int W = far_words(grid, par->block);
+  if (W > FH_PROSPECT_MAX_WORDS) return FH_ERR_ARG;
+  if (work_bytes < fh_prospect_work_bytes(grid, par->block, n_views)) return FH_ERR_ARG;
+  if (n == 0) return FH_OK;
+  if (!d_work || !d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  hipPointerAttribute_t where;
+  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  fhh::DeviceScope scope(where.device);
+  if (!scope.ok) return FH_ERR_DEVICE;
+  fhp::ProspectArgs x;
+  fhp::FarArgs& s = x.f;
+  reach_args(s.r, 1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of,
+             n_views, d_vehicles);
+  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
+  s.B = par->block;
+  s.cx = (grid->dims[0] + s.B - 1) / s.B;
+  s.cy = (grid->dims[1] + s.B - 1) / s.B;
+  s.cz = (grid->dims[2] + s.B - 1) / s.B;
+  s.wx = (s.cx + 63) / 64;
+  s.W = W;
+  s.n = n;
+  s.skip = d_skip;
+  unsigned char* const work = static_cast<unsigned char*>(d_work);
+  s.sums = static_cast<unsigned long long*>(d_work);
+  const size_t need_bytes = ((size_t)n_views + 63) & ~(size_t)63;
+  s.need = work + (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long);
+  s.records = nullptr;
+  x.g = par->gain_blocks;
+  x.hop_cost = par->hop_cost;
+  x.min_gain = par->min_gain;
+  x.counts = reinterpret_cast<uint16_t*>(s.need + need_bytes);  // (= work + K21's bytes: a multiple of 8)
+  x.records = d_records;
+  const hipStream_t q = (hipStream_t)stream;
+  if (hipMemsetAsync(s.need, 0, need_bytes, q) != hipSuccess) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  hipLaunchKernelGGL(fhp::far_need_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, s);
+  hipLaunchKernelGGL(fhp::prospect_blocks_kernel, dim3((unsigned)W, (unsigned)(n_views < 65535 ? n_views : 65535)), dim3(256), 0, q, x);
+  hipLaunchKernelGGL(fhp::prospect_goals_kernel, dim3((unsigned)n), dim3(256), 0, q, x);
+  return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
 }
 
 // (behind K21's entry point and the bid chooser's workspace: K21's clauses in K21's order, then K16's two; the summary stage is K21's

@@ -60,6 +60,9 @@ blocks reaches, however far away it is:
 
     sense -> observe -> [link] -> explore_reachable -> explore_far(after="reachable") -> replan -> next_goals
 
+explore_far_gain() is explore_far() with a gain (include/fasterhip_prospect.h): a target block is weighed by the unknown voxels of the
+blocks around it, and the best  gain - hop_cost * hops  of all levels of the flood is taken, not the first target block the flood meets.
+
 explore_far_spread() is explore_far() for a team (include/fasterhip_apart.h): a block within r_spread of the goal a peer holds or
 has just been given is no target, so stranded teammates with one view do not all fly the long way to one voxel.
 
@@ -136,6 +139,7 @@ class Fleet:
         self.d_far_goals = self.d_far_mask = self.d_far_records = self.d_far_work = self._far_work_key = None                  # explore_far
         self.d_far_spread_goals = self.d_far_spread_mask = self.d_far_spread_records = None                                    # explore_far_spread
         self.d_far_spread_work = self._far_spread_work_key = None
+        self.d_far_gain_goals = self.d_far_gain_mask = self.d_far_gain_records = self.d_far_gain_work = self._far_gain_work_key = None   # explore_far_gain
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -786,6 +790,80 @@ class Fleet:
         self.sync()
         return (self.d_far_records.cpu().numpy().view(abi.far_record_dtype).copy(), self.d_far_goals.cpu().numpy().copy(),
                 self.d_far_mask.cpu().numpy().copy())
+
+    def explore_far_gain(self, block=8, gain_blocks=2, hop_cost=None, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0, after=None):
+        """explore_far() with a gain (include/fasterhip_prospect.h): every block of the flood carries the number of its unknown voxels,
+        the gain of a target block is the sum of those numbers over the cube of 2 gain_blocks - 1 blocks an edge around it (0 .. 5
+        blocks; 0: every gain is 0), and of the target blocks of ALL levels the one with the largest  gain - hop_cost * hops  is taken
+        (then the fewest block steps, the nearest block, and in it explore_far()'s voxel), so the edge of an unexplored hall three
+        blocks on beats a one-voxel hole next door.  hop_cost: the unknown voxels a block step must be worth, 0 .. 16384; None means
+        block * block, the voxels of one face of a block — a judgement, not a measurement.  min_gain: a target block with a smaller
+        gain is poor and never taken (abi.FH_PROSPECT_ALL_POOR where every reachable one is).  after, block and the other arguments,
+        the preconditions and the errors are explore_far()'s; the buffers and the workspace are its own (far_gain_records())."""
+        stages = self.explore_far_gain_stages(block, gain_blocks, hop_cost, min_gain, r_avoid, z, want, max_hops, after)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_far_gain_stages(self, block=8, gain_blocks=2, hop_cost=None, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0,
+                                after=None):
+        """The two launches of explore_far_gain(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        par = abi.default_far_gain_params(block, gain_blocks)
+        flags, stride, vo, n_views = self._reach_inputs("explore_far_gain", par, r_avoid, z, want, max_hops)
+        skip = None
+        if after is not None:
+            if after not in self._FAR_AFTER:
+                raise capi.FasterHipError("Fleet.explore_far_gain: after is None or one of %s, got %r" % (", ".join(sorted(self._FAR_AFTER)), after))
+            skip = getattr(self, self._FAR_AFTER[after])
+            if skip is None:
+                raise capi.FasterHipError("Fleet.explore_far_gain: after=%r, but that chooser has not run" % (after,))
+        g = capi._grid_record(self.grid)
+        work_bytes = int(capi.lib().fh_prospect_work_bytes(abi.ptr(g), int(block), int(n_views)))
+        if work_bytes == 0:
+            raise capi.FasterHipError("Fleet.explore_far_gain: block must be 1 .. 16 and the blocks of the lattice must fit %d words of 64 "
+                                      "(got block %r on a lattice of %s)" % (abi.FH_PROSPECT_MAX_WORDS, block, tuple(int(d) for d in self.grid[2])))
+        if not 0 <= int(gain_blocks) <= abi.FH_PROSPECT_MAX_BLOCKS:
+            raise capi.FasterHipError("Fleet.explore_far_gain: gain_blocks must be 0 .. %d, got %r" % (abi.FH_PROSPECT_MAX_BLOCKS, gain_blocks))
+        if hop_cost is not None:
+            if not 0 <= int(hop_cost) <= abi.FH_PROSPECT_MAX_HOP_COST:
+                raise capi.FasterHipError("Fleet.explore_far_gain: hop_cost must be None or 0 .. %d, got %r" % (abi.FH_PROSPECT_MAX_HOP_COST, hop_cost))
+            par["hop_cost"] = int(hop_cost)
+        if int(min_gain) < 0:
+            raise capi.FasterHipError("Fleet.explore_far_gain: min_gain must be >= 0, got %r" % (min_gain,))
+        par["min_gain"] = int(min_gain)
+        t = self.torch
+        if self.d_far_gain_goals is None:
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_far_gain_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_far_gain_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_far_gain_records = t.zeros(self.n * abi.far_gain_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            for d in (self.d_far_gain_goals, self.d_far_gain_mask, self.d_far_gain_records):
+                d.record_stream(self.stream)
+        key = (tuple(int(d) for d in self.grid[2]), int(block), int(n_views))
+        if self._far_gain_work_key != key:   # (one workspace per lattice, block and number of views)
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_far_gain_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
+            self.d_far_gain_work.record_stream(self.stream)
+            self._far_gain_work_key = key
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("far_gain_goals", lambda: m.far_gain_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if skip is None else p(skip),
+                                                               p(self.d_vehicles), self.n, p(self.d_far_gain_work), work_bytes,
+                                                               p(self.d_far_gain_goals), p(self.d_far_gain_mask), p(self.d_far_gain_records),
+                                                               self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_far_gain_goals), p(self.d_far_gain_mask),
+                                                           self.n)),
+        ]
+
+    def far_gain_records(self):
+        """(records [n] abi.far_gain_record_dtype, goals [n][3], mask [n] int32) of the last explore_far_gain() (synchronises)."""
+        if self.d_far_gain_goals is None:
+            raise capi.FasterHipError("Fleet.far_gain_records: explore_far_gain first")
+        self.sync()
+        return (self.d_far_gain_records.cpu().numpy().view(abi.far_gain_record_dtype).copy(), self.d_far_gain_goals.cpu().numpy().copy(),
+                self.d_far_gain_mask.cpu().numpy().copy())
 
     def explore_far_spread(self, block=8, r_spread=2.0, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link", after=None):
         """explore_far() for a team (include/fasterhip_apart.h): a block of the flood nearer than r_spread to the goal that a peer

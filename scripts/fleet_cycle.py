@@ -93,7 +93,11 @@ five, fenced by events), and the levels, blocks reached, target blocks, hops and
 "far_spread_goals" and "far_spread_set_goals", and under "far_spread" the launch with every vehicle wanted and nobody skipped as
 "far_spread_goals_all_ms" beside "far_goals_all_beside_ms" of the same call, the same launch with 1 and with 64 passes, the cost of a
 pass from the two, the largest `lower`, and the vehicles left unsettled or with every target claimed.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--far BLOCK [--far-spread R_SPREAD [--passes P]]] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--far BLOCK --far-gain G [--far-hop-cost H] [--far-min-gain M] runs Fleet.explore_far_gain(BLOCK, G, H, M, after=...) in place of
+explore_far (include/fasterhip_prospect.h): its stages are reported as "far_gain_goals" and "far_gain_set_goals", and under "far_gain" the
+launch with every vehicle wanted and nobody skipped as "far_gain_goals_all_ms" beside "far_goals_all_beside_ms" of the same call (medians
+of five), and the same launch with gain_blocks 0, 1, 2 and 5.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--far BLOCK [--far-gain G [--far-hop-cost H] [--far-min-gain M]] [--far-spread R_SPREAD [--passes P]]] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -141,6 +145,13 @@ if FAR_SPREAD is not None and FAR is None:
 PASSES = int(sys.argv[sys.argv.index("--passes") + 1]) if "--passes" in sys.argv else None
 if PASSES is not None and FAR_SPREAD is None:
     sys.exit("--passes needs --far-spread R_SPREAD")
+FAR_GAIN = int(sys.argv[sys.argv.index("--far-gain") + 1]) if "--far-gain" in sys.argv else None
+if FAR_GAIN is not None and (FAR is None or FAR_SPREAD is not None):
+    sys.exit("--far-gain needs --far BLOCK and no --far-spread")
+FAR_HOP_COST = int(sys.argv[sys.argv.index("--far-hop-cost") + 1]) if "--far-hop-cost" in sys.argv else None
+FAR_MIN_GAIN = int(sys.argv[sys.argv.index("--far-min-gain") + 1]) if "--far-min-gain" in sys.argv else 0
+if ("--far-hop-cost" in sys.argv or "--far-min-gain" in sys.argv) and FAR_GAIN is None:
+    sys.exit("--far-hop-cost and --far-min-gain need --far-gain G")
 SIGHT = "--sight" in sys.argv
 if SIGHT and (GAIN is None or SPREAD is not None):
     sys.exit("--sight needs --gain G and no --spread")
@@ -388,6 +399,8 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
         if LINK and SPREAD is None:   # teams: the groups of one link() after the first look (the choosers for a team above have linked)
             fl.link(LINK[0])
         fl.explore_far_spread(FAR, FAR_SPREAD, passes=PASSES, after=far_after)
+    elif FAR_GAIN is not None:
+        fl.explore_far_gain(FAR, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, after=far_after)
     elif FAR is not None:
         fl.explore_far(FAR, after=far_after)
     fl.replan()
@@ -397,6 +410,9 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     if FAR_SPREAD is not None:   # the fallback for a team after the chooser in use
         explore = explore + [(n if n == "far_spread_goals" else "far_spread_set_goals", f)
                              for n, f in fl.explore_far_spread_stages(FAR, FAR_SPREAD, passes=PASSES, after=far_after)]
+    elif FAR_GAIN is not None:   # the fallback with a gain after the chooser in use
+        explore = explore + [(n if n == "far_gain_goals" else "far_gain_set_goals", f)
+                             for n, f in fl.explore_far_gain_stages(FAR, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, after=far_after)]
     elif FAR is not None:   # the fallback after the chooser in use, for the vehicles it left without a goal
         explore = explore + [(n if n == "far_goals" else "far_set_goals", f) for n, f in fl.explore_far_stages(FAR, after=far_after)]
     names = ["sense"] + [n for n, _ in explore] + [n for n, _ in fl.stages()] + ["next_goals"]
@@ -467,6 +483,37 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                               "all_claimed_all": int((sa["flags"] & abi.FH_APART_CLAIMED != 0).sum()),
                               "claimed_mean": float(sa["claimed"][hit].mean()) if hit.any() else 0.0,
                               "same_cell_as_far_goals": int((sa["cell"] == fb["cell"]).sum())}}
+    elif FAR_GAIN is not None:   # every vehicle wanted and nobody skipped, applied to nobody, beside far_goals in the same call, medians of five
+        gr = fl.far_gain_records()[0]
+        searched = lambda r: (r["flags"] & ~(abi.FH_FRONTIER_FOUND | abi.FH_REACH_CUT | abi.FH_PROSPECT_ALL_POOR)) == abi.FH_FRONTIER_WANTED   # noqa: E731
+        runs = {}
+        for g in (0, 1, 2, 5, FAR_GAIN):   # (the one asked for last: its records are read below)
+            runs[g] = fenced_ms(fl, fl.explore_far_gain_stages(FAR, g, FAR_HOP_COST, FAR_MIN_GAIN, want="all")[0][1], 5)
+        ga = fl.far_gain_records()[0]
+        beside_ms = fenced_ms(fl, fl.explore_far_stages(FAR, want="all")[0][1], 5)
+        fb = fl.far_records()[0]
+        hit = searched(ga)
+        chosen = ga["hops"] >= 0
+        _, _, dims_ = fl.grid
+        view_bytes = int(dims_[0]) * int(dims_[1]) * int(dims_[2])
+        far = {"far_gain": {"block": FAR, "gain_blocks": FAR_GAIN, "hop_cost": int(FAR * FAR if FAR_HOP_COST is None else FAR_HOP_COST),
+                            "min_gain": FAR_MIN_GAIN, "after": far_after, "work_bytes": int(fl.d_far_gain_work.numel()),
+                            "far_gain_goals_loop_ms": med.get("far_gain_goals"), "searched_last_cycle": int(searched(gr).sum()),
+                            "skipped_last_cycle": int((gr["flags"] & abi.FH_PROSPECT_SKIPPED != 0).sum()),
+                            "far_gain_goals_all_ms": float(np.median(runs[FAR_GAIN])), "far_gain_goals_all_runs_ms": [float(x) for x in runs[FAR_GAIN]],
+                            "far_gain_goals_all_by_gain_blocks_ms": {str(g): float(np.median(runs[g])) for g in (0, 1, 2, 5)},
+                            "far_goals_all_beside_ms": float(np.median(beside_ms)), "far_goals_all_beside_runs_ms": [float(x) for x in beside_ms],
+                            "view_bytes": view_bytes, "summary_bytes_all": view_bytes * int(fl.n_views),
+                            "searched_all": int(hit.sum()), "found_all": int((ga["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                            "all_poor_all": int((ga["flags"] & abi.FH_PROSPECT_ALL_POOR != 0).sum()),
+                            "far_found_all_beside": int((fb["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                            "same_cell_as_far_goals": int((ga["cell"] == fb["cell"]).sum()),
+                            "levels_mean": float(ga["levels"][hit].mean()) if hit.any() else 0.0,
+                            "reachable_mean": float(ga["reachable"][hit].mean()) if hit.any() else 0.0,
+                            "hops_mean": float(ga["hops"][chosen].mean()) if chosen.any() else -1.0,
+                            "far_hops_mean_beside": float(fb["hops"][fb["hops"] >= 0].mean()) if (fb["hops"] >= 0).any() else -1.0,
+                            "gain_mean": float(ga["gain"][chosen].mean()) if chosen.any() else -1.0,
+                            "best_gain_max": int(ga["best_gain"].max())}}
     elif FAR is not None:   # every vehicle wanted and nobody skipped, applied to nobody, beside reach_goals in the same call, a median of five each
         fr = fl.far_records()[0]
         far_ms = fenced_ms(fl, fl.explore_far_stages(FAR, want="all")[0][1], 5)
@@ -857,7 +904,7 @@ def main():
     if "--far" in argv:          # (read into FAR above)
         k = argv.index("--far")
         del argv[k:k + 2]
-    for opt in ("--far-spread", "--passes"):   # (read into FAR_SPREAD and PASSES above)
+    for opt in ("--far-spread", "--passes", "--far-gain", "--far-hop-cost", "--far-min-gain"):   # (read into FAR_SPREAD .. FAR_MIN_GAIN above)
         if opt in argv:
             k = argv.index(opt)
             del argv[k:k + 2]
