@@ -152,6 +152,24 @@ __device__ __forceinline__ int opaque(int v) {
   asm volatile("" : "+v"(v));
   return v;
 }
+// own_sreg(v): the scalar counterpart.  A kernel argument arrives as one word of an s_load_dwordx8 / x16 tuple, and the register
+// allocator keeps, spills and reloads the tuple as ONE value: a use of one field deep in the search then reloads up to sixteen lanes
+// of the spill register (one vector instruction each).  Behind this fence the field is a value of its own — a spill or a reload
+// costs the one or two lanes it has.  (A real move, once per launch: with an empty asm and a tied "+s" operand the coalescer joins
+// the operand with the tuple's sub-register again and the tuple stays one live range.)
+template <typename T>
+__device__ __forceinline__ void own_sreg(T& v) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two scalar registers");
+  if constexpr (sizeof(T) == 4) {
+    unsigned int o;
+    asm volatile("s_mov_b32 %0, %1" : "=s"(o) : "s"(__builtin_bit_cast(unsigned int, v)));
+    v = __builtin_bit_cast(T, o);
+  } else {
+    unsigned long long o;
+    asm volatile("s_mov_b64 %0, %1" : "=s"(o) : "s"(__builtin_bit_cast(unsigned long long, v)));
+    v = __builtin_bit_cast(T, o);
+  }
+}
 
 // coefficient of jerk j_s in functional `kind` of the state at the start of segment tt, m = tt-1-s >= 0
 __device__ __forceinline__ double wcoef(int kind, int m, double h) {
@@ -3131,6 +3149,27 @@ struct SolveArgs {  // (the problem / face / result arrays are separate `__restr
   const int* order;
 };
 
+// Every argument the kernel reads below its entry, made a scalar value of its own (own_sreg).  The order is of no consequence; a field
+// added to SolveArgs / ShareArgs that is read per node or per unit belongs here (scripts/lane_move_census.py shows what a tuple costs).
+template <bool PAIRS>
+__device__ __forceinline__ void split_args(SolveArgs& a) {
+  own_sreg(a.n); own_sreg(a.max_faces);
+  own_sreg(a.par.feas_tol); own_sreg(a.par.dep_tol); own_sreg(a.par.max_nodes); own_sreg(a.par.max_iters); own_sreg(a.par.max_work);
+  own_sreg(a.par.mip_gap);
+  own_sreg(a.workspace); own_sreg(a.basis);
+  ShareArgs& s = a.sa;
+  own_sreg(s.ctl); own_sreg(s.seqs); own_sreg(s.slots); own_sreg(s.slot_stride); own_sreg(s.recs); own_sreg(s.host_abort);
+  own_sreg(s.deadline_ticks); own_sreg(s.enabled); own_sreg(s.total_units); own_sreg(s.max_hungry); own_sreg(s.min_nodes);
+  own_sreg(s.backlog); own_sreg(s.giant_nodes); own_sreg(s.giant_factor); own_sreg(s.child_bound); own_sreg(s.compact_results);
+  own_sreg(s.look_mask); own_sreg(s.claims); own_sreg(a.order);
+  if constexpr (PAIRS) {  // (a plain launch has no use for these — sa.safe is null there; split all the same they cost <6, false, 3> 16 B of scratch)
+    own_sreg(s.pair_outputs); own_sreg(s.whole); own_sreg(s.wfaces); own_sreg(s.safe); own_sreg(s.sfaces); own_sreg(s.shrink);
+    own_sreg(s.r_margin);
+    own_sreg(a.safe); own_sreg(a.sfaces); own_sreg(a.sres); own_sreg(a.r_frac); own_sreg(a.shrink); own_sreg(a.r_margin);
+    own_sreg(a.max_safe_poly);
+  }
+}
+
 // Persistent workgroups (one wavefront each).  Every workgroup pulls fresh units from a device-scope ticket counter
 // until the batch is exhausted, so problems of very different difficulty balance across the 256 CUs and the snapshot
 // workspace is sized by the resident grid, not by the batch; then it takes over frames of the trees that are still
@@ -3148,7 +3187,10 @@ struct SolveArgs {  // (the problem / face / result arrays are separate `__restr
 // the lookup's registers are not the throughput build's problem; modes 0 and 1 run the same kernels as before.
 template <int NSEG, bool PAIRS, int WPS = FH_WAVES_PER_SIMD, bool UNK = false>
 __global__ void __launch_bounds__(64, WPS) solve_kernel(const fh_problem* __restrict__ problems, const fh_face* __restrict__ faces,
-                                                   fh_result* __restrict__ results, SolveArgs ka) {
+                                                   fh_result* __restrict__ results, SolveArgs ka_tuple) {
+  // every launch argument read below is a scalar value of its own, not a word of the tuple it was loaded in (own_sreg)
+  SolveArgs ka = ka_tuple;
+  split_args<PAIRS>(ka);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // [r6] The row norms stay in registers (Solver::wbj ..).  Round 5 re-read them from the basis table in the three-wavefront build to
   // save eight registers; with x0 in LDS and the safe problem built on chip the allocation was a different one: the table variant had 41
