@@ -451,6 +451,37 @@ def default_far_gain_params(block, gain_blocks):
     return p
 
 
+# fh_stake_params, fh_stake_record: the gain of fh_prospect_params inside the passes of fh_apart_params, a peer's claim covering a cube
+# of blocks whose unknown voxels no gain of the vehicle counts (include/fasterhip_stake.h); the params are fh_apart_params with three
+# reserved words of its first 64 bytes (fh_prospect_params' three) and the first of its tail in use, the first 96 bytes of the record
+# are fh_apart_record's, then fh_prospect_record's four, then covered and removed
+FH_STAKE_SKIPPED, FH_STAKE_MAX_WORDS = FH_FAR_SKIPPED, FH_FAR_MAX_WORDS   # (that header's own names for K21's two)
+FH_STAKE_UNSETTLED, FH_STAKE_CLAIMED, FH_STAKE_ALL_POOR = FH_APART_UNSETTLED, FH_APART_CLAIMED, FH_PROSPECT_ALL_POOR
+FH_STAKE_MAX_PASSES, FH_STAKE_DEFAULT_PASSES = FH_APART_MAX_PASSES, FH_APART_DEFAULT_PASSES
+FH_STAKE_MAX_BLOCKS, FH_STAKE_MAX_HOP_COST = FH_PROSPECT_MAX_BLOCKS, FH_PROSPECT_MAX_HOP_COST
+FH_STAKE_MAX_CLAIM_BLOCKS = 5
+far_team_params_dtype = np.dtype([("r_avoid", "<f8"), ("z_lo", "<f8"), ("z_hi", "<f8"), ("reserved_d", "<f8"), ("want", "<i4"), ("max_hops", "<i4"),
+                                  ("block", "<i4"), ("gain_blocks", "<i4"), ("hop_cost", "<i4"), ("min_gain", "<i4"), ("reserved", "<i4", (2,)),
+                                  ("r_spread", "<f8"), ("passes", "<i4"), ("claim_blocks", "<i4"), ("reserved_tail", "<i4", (4,))], align=True)
+far_team_record_dtype = np.dtype([("flags", "<i4"), ("view", "<i4"), ("cell", "<i4"), ("block_cell", "<i4"), ("hops", "<i4"), ("targets", "<i4"),
+                                  ("reachable", "<i4"), ("reached", "<i4"), ("levels", "<i4"), ("members", "<i4"), ("reserved", "<i4", (2,)),
+                                  ("d2", "<f8"), ("block_d2", "<f8"), ("group", "<i4"), ("decided_pass", "<i4"), ("lower", "<i4"),
+                                  ("standing", "<i4"), ("claims", "<i4"), ("claimed", "<i4"), ("reserved_tail", "<i4", (2,)), ("gain", "<i4"),
+                                  ("utility", "<i4"), ("poor", "<i4"), ("best_gain", "<i4"), ("covered", "<i4"), ("removed", "<i4"),
+                                  ("reserved_end", "<i4", (2,))], align=True)
+assert (far_team_params_dtype.itemsize, far_team_record_dtype.itemsize) == (96, 128)
+
+
+def default_far_team_params(block, r_spread, gain_blocks):
+    """fh_stake_params: default_far_spread_params and default_far_gain_params together; a claim covers the cube of a gain
+    (claim_blocks = gain_blocks: what a peer's goal is weighed by is what it is taken to uncover)."""
+    p = np.zeros((), dtype=far_team_params_dtype)
+    p["r_avoid"], p["z_lo"], p["z_hi"], p["want"], p["max_hops"], p["block"] = 0.0, -np.inf, np.inf, FH_FRONTIER_WANT_REACHED, 0, block
+    p["gain_blocks"], p["hop_cost"], p["min_gain"] = gain_blocks, int(block) * int(block), 0
+    p["r_spread"], p["passes"], p["claim_blocks"] = r_spread, FH_STAKE_DEFAULT_PASSES, gain_blocks
+    return p
+
+
 # fh_traffic_params: the other vehicles' committed plans as occupied points of a vehicle's view (include/fasterhip_traffic.h)
 FH_TRAFFIC_ALL, FH_TRAFFIC_YIELD_TO_LOWER = 0, 1
 traffic_params_dtype = np.dtype([("range", "<f8"), ("hull", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("rule", "<i4"), ("first_point", "<i4"),

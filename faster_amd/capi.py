@@ -70,6 +70,8 @@ FAR_SYMBOLS = ["fh_far_work_bytes", "fh_far_goals_device"]
 FAR_SPREAD_SYMBOLS = ["fh_apart_work_bytes", "fh_apart_goals_device"]
 # include/fasterhip_prospect.h
 FAR_GAIN_SYMBOLS = ["fh_prospect_work_bytes", "fh_prospect_goals_device"]
+# include/fasterhip_stake.h
+FAR_TEAM_SYMBOLS = ["fh_stake_work_bytes", "fh_stake_goals_device"]
 
 _LIB = None
 
@@ -371,6 +373,10 @@ def lib():
         L.fh_prospect_work_bytes.argtypes = [vp, i32, i32]
         L.fh_prospect_goals_device.restype = i32
         L.fh_prospect_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
+        L.fh_stake_work_bytes.restype = ctypes.c_size_t
+        L.fh_stake_work_bytes.argtypes = [vp, i32, i32, i32]
+        L.fh_stake_goals_device.restype = i32
+        L.fh_stake_goals_device.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, i32, vp, vp, vp, i32, vp, ctypes.c_size_t, vp, vp, vp]
         L.fh_map_occupancy_bits_device.restype = i32
         L.fh_map_occupancy_bits_device.argtypes = [vp, vp, vp]
         L.fh_timing_reset.restype = i32
@@ -737,6 +743,25 @@ class Map:
                                             d_records)
         if rc != 0:
             raise FasterHipError("fh_prospect_goals_device: rc=%d" % rc)
+
+    def far_team_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_group, d_vehicles, n, d_work, work_bytes,
+                              d_goals, d_mask, d_records, stream):
+        """fh_stake_goals_device (include/fasterhip_stake.h) with this map's lattice and bits: far_gain_goals_device inside the passes of
+        far_spread_goals_device — a peer's claim removes the target blocks within par["r_spread"] of it, and the unknown voxels of the
+        cube of 2 par["claim_blocks"] - 1 blocks an edge around its block from every gain of the vehicle.  d_work: work_bytes >=
+        fh_stake_work_bytes(grid, block, n_views, n) of device memory; d_records [n] abi.far_team_record_dtype; par: one
+        abi.far_team_params_dtype record; `stream` as for reach_goals_device."""
+        p = _one_record(par, "far_team", "far_team_goals_device")
+        g = _grid_record(grid)
+        dims, origin = self.dims()
+        bits, res = ctypes.c_void_p(), ctypes.c_double()
+        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
+        mg = _grid_record((origin, res.value, dims))
+        rc = lib().fh_stake_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
+                                         d_view_of, int(n_views), d_skip, d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals,
+                                         d_mask, d_records)
+        if rc != 0:
+            raise FasterHipError("fh_stake_goals_device: rc=%d" % rc)
 
     def sight_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_goals, d_mask, d_records, stream):
         """fh_sight_goals_device (include/fasterhip_sight.h) with this map's lattice and bits: gain_goals_device with a gain that counts an

@@ -10,7 +10,9 @@
 // vehicles those choosers left without a goal, a flood of the whole view over blocks of voxels (kernels: fh_far.hip.hpp), and of
 // include/fasterhip_apart.h (fh_apart_goals_device): that fallback for a team, the target blocks that a peer's claim covers
 // taken out before the flood (kernels: fh_apart.hpp), and of include/fasterhip_prospect.h (fh_prospect_goals_device): that fallback
-// with a gain, the unknown voxels of the blocks around a target block, chosen by utility over all levels (kernels: fh_prospect.hpp).
+// with a gain, the unknown voxels of the blocks around a target block, chosen by utility over all levels (kernels: fh_prospect.hpp), and
+// of include/fasterhip_stake.h (fh_stake_goals_device): that gain inside the passes of the fallback for a team, a peer's claim covering
+// a cube of blocks whose unknown voxels no gain of the vehicle counts (kernels: fh_stake.hpp).
 // A translation unit of its own: fh_map.hip and fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
@@ -27,6 +29,7 @@
 #include "../../include/fasterhip_far.h"
 #include "../../include/fasterhip_apart.h"
 #include "../../include/fasterhip_prospect.h"
+#include "../../include/fasterhip_stake.h"
 #include "fh_reach.hip.hpp"
 #include "fh_spread.hip.hpp"
 #include "fh_gain.hip.hpp"
@@ -36,6 +39,7 @@
 #include "fh_far.hip.hpp"
 #include "fh_host.hpp"
 #include "fh_prospect.hpp"
+#include "fh_stake.hpp"
 #include "fh_apart.hpp"
 
 // the lattice of the views, judged as fh_map_frontier_goals_device judges it (0: fine, cells filled in)
@@ -287,6 +291,136 @@ size_t fh_prospect_work_bytes(const fh_voxel_grid* grid, int block, int n_views)
   const size_t far = fh_far_work_bytes(grid, block, n_views);  // (0: a null grid, a dimension < 1, a block outside 1..16, too many words, n_views < 1)
   if (far == 0) return 0;
   return far + (size_t)n_views * 64u * (size_t)far_words(grid, block) * sizeof(uint16_t);
+}
+
+size_t fh_stake_work_bytes(const fh_voxel_grid* grid, int block, int n_views, int n) {
+  const size_t pro = fh_prospect_work_bytes(grid, block, n_views);
+  if (pro == 0 || n < 0) return 0;
+  return pro + spread_rows_offset(n) + (size_t)n * sizeof(int32_t) + (size_t)n * sizeof(int32_t);
+}
+
+// (K23's clauses through min_gain, K21's tables, then K22's two and claim_blocks; K21's memset and need kernel, K23's one pass for the
+// bitmaps and the counts and K22's class kernel as they stand, then this chooser's count kernel and its pass kernel once per pass)
+int fh_stake_goals_device(void* stream, const fh_stake_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                          const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                          const int32_t* d_skip, const int32_t* d_group, const fh_vehicle* d_vehicles, int n, void* d_work, size_t work_bytes,
+                          double* d_goals, int32_t* d_mask, fh_stake_record* d_records) {
+  static_assert(sizeof(fh_stake_params) == sizeof(fh_apart_params) && sizeof(fh_stake_record) == 128 && sizeof(fh_apart_record) == 96 &&
+                    sizeof(fh_prospect_record) == 80 && FH_STAKE_SKIPPED == FH_FAR_SKIPPED && FH_STAKE_MAX_WORDS == FH_FAR_MAX_WORDS &&
+                    FH_STAKE_UNSETTLED == FH_APART_UNSETTLED && FH_STAKE_CLAIMED == FH_APART_CLAIMED && FH_STAKE_ALL_POOR == FH_PROSPECT_ALL_POOR &&
+                    FH_STAKE_MAX_PASSES == FH_APART_MAX_PASSES && FH_STAKE_DEFAULT_PASSES == FH_APART_DEFAULT_PASSES &&
+                    FH_STAKE_MAX_BLOCKS == FH_PROSPECT_MAX_BLOCKS && FH_STAKE_MAX_HOP_COST == FH_PROSPECT_MAX_HOP_COST &&
+                    FH_STAKE_MAX_CLAIM_BLOCKS == 5 &&
+                    offsetof(fh_stake_params, r_avoid) == offsetof(fh_apart_params, r_avoid) && offsetof(fh_stake_params, z_lo) == offsetof(fh_apart_params, z_lo) &&
+                    offsetof(fh_stake_params, z_hi) == offsetof(fh_apart_params, z_hi) &&
+                    offsetof(fh_stake_params, reserved_d) == offsetof(fh_apart_params, reserved_d) &&
+                    offsetof(fh_stake_params, want) == offsetof(fh_apart_params, want) && offsetof(fh_stake_params, max_hops) == offsetof(fh_apart_params, max_hops) &&
+                    offsetof(fh_stake_params, block) == offsetof(fh_apart_params, block) &&
+                    offsetof(fh_stake_params, gain_blocks) == offsetof(fh_prospect_params, gain_blocks) &&
+                    offsetof(fh_stake_params, hop_cost) == offsetof(fh_prospect_params, hop_cost) &&
+                    offsetof(fh_stake_params, min_gain) == offsetof(fh_prospect_params, min_gain) &&
+                    offsetof(fh_stake_params, reserved) == offsetof(fh_prospect_params, reserved) &&
+                    offsetof(fh_stake_params, r_spread) == offsetof(fh_apart_params, r_spread) && offsetof(fh_stake_params, r_spread) == 64 &&
+                    offsetof(fh_stake_params, passes) == offsetof(fh_apart_params, passes) && offsetof(fh_stake_params, passes) == 72 &&
+                    offsetof(fh_stake_params, claim_blocks) == offsetof(fh_apart_params, reserved_tail) && offsetof(fh_stake_params, claim_blocks) == 76 &&
+                    offsetof(fh_stake_record, flags) == offsetof(fh_apart_record, flags) && offsetof(fh_stake_record, view) == offsetof(fh_apart_record, view) &&
+                    offsetof(fh_stake_record, cell) == offsetof(fh_apart_record, cell) &&
+                    offsetof(fh_stake_record, block_cell) == offsetof(fh_apart_record, block_cell) &&
+                    offsetof(fh_stake_record, hops) == offsetof(fh_apart_record, hops) && offsetof(fh_stake_record, targets) == offsetof(fh_apart_record, targets) &&
+                    offsetof(fh_stake_record, reachable) == offsetof(fh_apart_record, reachable) &&
+                    offsetof(fh_stake_record, reached) == offsetof(fh_apart_record, reached) && offsetof(fh_stake_record, levels) == offsetof(fh_apart_record, levels) &&
+                    offsetof(fh_stake_record, members) == offsetof(fh_apart_record, members) &&
+                    offsetof(fh_stake_record, reserved) == offsetof(fh_apart_record, reserved) && offsetof(fh_stake_record, d2) == offsetof(fh_apart_record, d2) &&
+                    offsetof(fh_stake_record, block_d2) == offsetof(fh_apart_record, block_d2) &&
+                    offsetof(fh_stake_record, group) == offsetof(fh_apart_record, group) &&
+                    offsetof(fh_stake_record, decided_pass) == offsetof(fh_apart_record, decided_pass) &&
+                    offsetof(fh_stake_record, lower) == offsetof(fh_apart_record, lower) &&
+                    offsetof(fh_stake_record, standing) == offsetof(fh_apart_record, standing) &&
+                    offsetof(fh_stake_record, claims) == offsetof(fh_apart_record, claims) &&
+                    offsetof(fh_stake_record, claimed) == offsetof(fh_apart_record, claimed) &&
+                    offsetof(fh_stake_record, reserved_tail) == offsetof(fh_apart_record, reserved_tail) &&
+                    offsetof(fh_stake_record, gain) == 96 && offsetof(fh_stake_record, gain) - 96 == offsetof(fh_prospect_record, gain) - 64 &&
+                    offsetof(fh_stake_record, utility) - 96 == offsetof(fh_prospect_record, utility) - 64 &&
+                    offsetof(fh_stake_record, poor) - 96 == offsetof(fh_prospect_record, poor) - 64 &&
+                    offsetof(fh_stake_record, best_gain) - 96 == offsetof(fh_prospect_record, best_gain) - 64 &&
+                    offsetof(fh_stake_record, covered) == 112 && offsetof(fh_stake_record, removed) == 116 &&
+                    fhp::STAKE_NONE == fhp::FAR_SPREAD_NONE && fhp::STAKE_SEARCHER == fhp::FAR_SPREAD_SEARCHER &&
+                    fhp::STAKE_STANDING == fhp::FAR_SPREAD_STANDING,
+                "include/fasterhip_stake.h: K21's, K22's and K23's params, records, flags, limits and class bytes under its own names");
+  if (!par) return FH_ERR_ARG;
+  if (reach_field_clauses(1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
+  if (par->block < 1 || par->block > 16) return FH_ERR_ARG;
+  if (par->gain_blocks < 0 || par->gain_blocks > FH_STAKE_MAX_BLOCKS) return FH_ERR_ARG;
+  if (par->hop_cost < 0 || par->hop_cost > FH_STAKE_MAX_HOP_COST) return FH_ERR_ARG;
+  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
+  const int W = far_words(grid, par->block);
+  if (W > FH_STAKE_MAX_WORDS) return FH_ERR_ARG;
+  if (!std::isfinite(par->r_spread) || !(par->r_spread > 0.0)) return FH_ERR_ARG;
+  if (par->passes < 1 || par->passes > FH_STAKE_MAX_PASSES) return FH_ERR_ARG;
+  if (par->claim_blocks < 0 || par->claim_blocks > FH_STAKE_MAX_CLAIM_BLOCKS) return FH_ERR_ARG;
+  if (work_bytes < fh_stake_work_bytes(grid, par->block, n_views, n)) return FH_ERR_ARG;
+  if (n == 0) return FH_OK;
+  if (!d_work || !d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  hipPointerAttribute_t where;
+  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  fhh::DeviceScope scope(where.device);
+  if (!scope.ok) return FH_ERR_DEVICE;
+  fhp::StakeArgs k;
+  fhp::ProspectArgs& x = k.p;
+  fhp::FarArgs& s = x.f;
+  reach_args(s.r, 1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of,
+             n_views, d_vehicles);
+  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
+  s.B = par->block;
+  s.cx = (grid->dims[0] + s.B - 1) / s.B;
+  s.cy = (grid->dims[1] + s.B - 1) / s.B;
+  s.cz = (grid->dims[2] + s.B - 1) / s.B;
+  s.wx = (s.cx + 63) / 64;
+  s.W = W;
+  s.n = n;
+  s.skip = d_skip;
+  unsigned char* const work = static_cast<unsigned char*>(d_work);
+  s.sums = static_cast<unsigned long long*>(d_work);
+  const size_t need_bytes = ((size_t)n_views + 63) & ~(size_t)63;
+  s.need = work + (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long);
+  s.records = nullptr;
+  x.g = par->gain_blocks;
+  x.hop_cost = par->hop_cost;
+  x.min_gain = par->min_gain;
+  x.counts = reinterpret_cast<uint16_t*>(s.need + need_bytes);  // (= work + K21's bytes: a multiple of 8)
+  x.records = nullptr;
+  fhp::FarSpreadArgs c;  // what K22's class kernel reads: the judge's values, the labels and the two tables it writes
+  c.f = s;
+  c.s2 = par->r_spread * par->r_spread;
+  c.pass = 0; c.passes = par->passes;
+  c.group = d_group;
+  c.cls = work + fh_prospect_work_bytes(grid, par->block, n_views);  // (K23's bytes: a multiple of 8)
+  c.grp = reinterpret_cast<int32_t*>(c.cls + spread_rows_offset(n));
+  c.lower = c.grp + n;
+  c.records = nullptr;
+  k.s2 = c.s2;
+  k.pass = 0; k.passes = par->passes;
+  k.k = par->claim_blocks;
+  k.cls = c.cls; k.grp = c.grp; k.lower = c.lower;
+  k.records = d_records;
+  const hipStream_t q = (hipStream_t)stream;
+  if (hipMemsetAsync(s.need, 0, need_bytes, q) != hipSuccess) {
+    (void)hipGetLastError();
+    return FH_ERR_DEVICE;
+  }
+  hipLaunchKernelGGL(fhp::far_need_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, s);
+  hipLaunchKernelGGL(fhp::prospect_blocks_kernel, dim3((unsigned)W, (unsigned)(n_views < 65535 ? n_views : 65535)), dim3(256), 0, q, x);
+  hipLaunchKernelGGL(fhp::far_spread_class_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, c);
+  hipLaunchKernelGGL(fhp::stake_count_kernel, dim3((unsigned)n), dim3(64), 0, q, k);
+  for (int p = 1; p <= par->passes; p++) {
+    k.pass = p;
+    hipLaunchKernelGGL(fhp::stake_goals_kernel, dim3((unsigned)n), dim3(256), 0, q, k);
+  }
+  return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
 }
 
 // (K21's clauses in K21's order, the three new fields right behind `block`; K21's memset and need kernel as they stand above, then

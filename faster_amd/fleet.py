@@ -66,6 +66,10 @@ blocks around it, and the best  gain - hop_cost * hops  of all levels of the flo
 explore_far_spread() is explore_far() for a team (include/fasterhip_apart.h): a block within r_spread of the goal a peer holds or
 has just been given is no target, so stranded teammates with one view do not all fly the long way to one voxel.
 
+explore_far_team() is both (include/fasterhip_stake.h): explore_far_gain()'s utility inside explore_far_spread()'s passes, and a peer's
+goal also takes the unknown voxels of the cube of blocks around it out of every gain of the vehicle, so the second of two stranded
+teammates flies to the next-best hall, not to another hole of the same one.
+
 enable_heading() adds the vehicle's yaw: next_goals then also gives yaw and dyaw (getDesiredYaw), a vehicle
 that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense(fov=...) looks forward only.
 
@@ -140,6 +144,7 @@ class Fleet:
         self.d_far_spread_goals = self.d_far_spread_mask = self.d_far_spread_records = None                                    # explore_far_spread
         self.d_far_spread_work = self._far_spread_work_key = None
         self.d_far_gain_goals = self.d_far_gain_mask = self.d_far_gain_records = self.d_far_gain_work = self._far_gain_work_key = None   # explore_far_gain
+        self.d_far_team_goals = self.d_far_team_mask = self.d_far_team_records = self.d_far_team_work = self._far_team_work_key = None   # explore_far_team
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -935,6 +940,98 @@ class Fleet:
         self.sync()
         return (self.d_far_spread_records.cpu().numpy().view(abi.far_spread_record_dtype).copy(), self.d_far_spread_goals.cpu().numpy().copy(),
                 self.d_far_spread_mask.cpu().numpy().copy())
+
+    def explore_far_team(self, block=8, r_spread=2.0, gain_blocks=2, hop_cost=None, min_gain=0, claim_blocks=None, r_avoid=None, z=None,
+                         want="reached", max_hops=0, passes=None, groups="link", after=None):
+        """explore_far_gain() inside the passes of explore_far_spread() (include/fasterhip_stake.h): a target block is weighed by the
+        unknown voxels of the cube of 2 gain_blocks - 1 blocks around it, the best  gain - hop_cost * hops  of all levels is taken,
+        and the goal a peer is on its way to, or that a peer with a lower index has been given by an earlier pass of this call, removes
+        the target blocks within r_spread of it AND, from every gain of the vehicle, the unknown voxels of the cube of
+        2 claim_blocks - 1 blocks around its block (0 .. 5; None means gain_blocks; 0: nothing is covered): that peer uncovers them
+        anyway.  gain_blocks, hop_cost and min_gain are explore_far_gain()'s, r_spread, passes, groups and after
+        explore_far_spread()'s, whose errors are raised before anything is launched; the buffers and the workspace are its own
+        (far_team_records())."""
+        stages = self.explore_far_team_stages(block, r_spread, gain_blocks, hop_cost, min_gain, claim_blocks, r_avoid, z, want, max_hops, passes,
+                                              groups, after)   # (raises before anything is launched)
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def explore_far_team_stages(self, block=8, r_spread=2.0, gain_blocks=2, hop_cost=None, min_gain=0, claim_blocks=None, r_avoid=None, z=None,
+                                want="reached", max_hops=0, passes=None, groups="link", after=None):
+        """The launches of explore_far_team(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them)."""
+        if groups not in ("link", "view"):
+            raise capi.FasterHipError("Fleet.explore_far_team: groups is \"link\" or \"view\", got %r" % (groups,))
+        par = abi.default_far_team_params(block, r_spread, gain_blocks)
+        flags, stride, vo, n_views = self._reach_inputs("explore_far_team", par, r_avoid, z, want, max_hops)
+        if not (np.isfinite(float(r_spread)) and float(r_spread) > 0.0):
+            raise capi.FasterHipError("Fleet.explore_far_team: r_spread must be finite and > 0, got %r" % (r_spread,))
+        if passes is not None:
+            if not 1 <= int(passes) <= abi.FH_STAKE_MAX_PASSES:
+                raise capi.FasterHipError("Fleet.explore_far_team: passes must be None or 1 .. %d, got %r" % (abi.FH_STAKE_MAX_PASSES, passes))
+            par["passes"] = int(passes)
+        skip = None
+        if after is not None:
+            if after not in self._FAR_AFTER:
+                raise capi.FasterHipError("Fleet.explore_far_team: after is None or one of %s, got %r" % (", ".join(sorted(self._FAR_AFTER)), after))
+            skip = getattr(self, self._FAR_AFTER[after])
+            if skip is None:
+                raise capi.FasterHipError("Fleet.explore_far_team: after=%r, but that chooser has not run" % (after,))
+        g = capi._grid_record(self.grid)
+        work_bytes = int(capi.lib().fh_stake_work_bytes(abi.ptr(g), int(block), int(n_views), int(self.n)))
+        if work_bytes == 0:
+            raise capi.FasterHipError("Fleet.explore_far_team: block must be 1 .. 16 and the blocks of the lattice must fit %d words of 64 "
+                                      "(got block %r on a lattice of %s)" % (abi.FH_STAKE_MAX_WORDS, block, tuple(int(d) for d in self.grid[2])))
+        if not 0 <= int(gain_blocks) <= abi.FH_STAKE_MAX_BLOCKS:
+            raise capi.FasterHipError("Fleet.explore_far_team: gain_blocks must be 0 .. %d, got %r" % (abi.FH_STAKE_MAX_BLOCKS, gain_blocks))
+        if hop_cost is not None:
+            if not 0 <= int(hop_cost) <= abi.FH_STAKE_MAX_HOP_COST:
+                raise capi.FasterHipError("Fleet.explore_far_team: hop_cost must be None or 0 .. %d, got %r" % (abi.FH_STAKE_MAX_HOP_COST, hop_cost))
+            par["hop_cost"] = int(hop_cost)
+        if int(min_gain) < 0:
+            raise capi.FasterHipError("Fleet.explore_far_team: min_gain must be >= 0, got %r" % (min_gain,))
+        par["min_gain"] = int(min_gain)
+        if claim_blocks is not None:
+            if not 0 <= int(claim_blocks) <= abi.FH_STAKE_MAX_CLAIM_BLOCKS:
+                raise capi.FasterHipError("Fleet.explore_far_team: claim_blocks must be None or 0 .. %d, got %r"
+                                          % (abi.FH_STAKE_MAX_CLAIM_BLOCKS, claim_blocks))
+            par["claim_blocks"] = int(claim_blocks)
+        t = self.torch
+        if self.d_far_team_goals is None:
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_far_team_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
+                self.d_far_team_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
+                self.d_far_team_records = t.zeros(self.n * abi.far_team_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            for d in (self.d_far_team_goals, self.d_far_team_mask, self.d_far_team_records):
+                d.record_stream(self.stream)
+        key = (tuple(int(d) for d in self.grid[2]), int(block), int(n_views), int(self.n))
+        if self._far_team_work_key != key:   # (one workspace per lattice, block, number of views and vehicles)
+            self._follow_current()
+            with t.cuda.stream(self.stream):
+                self.d_far_team_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
+            self.d_far_team_work.record_stream(self.stream)
+            self._far_team_work_key = key
+        # the labels are per view: with set_unknown's single view there is nothing to label
+        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
+            and self.d_link_labels.numel() == n_views else None
+        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
+        return [
+            ("far_team_goals", lambda: m.far_team_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if skip is None else p(skip),
+                                                               None if labels is None else p(labels), p(self.d_vehicles), self.n,
+                                                               p(self.d_far_team_work), work_bytes, p(self.d_far_team_goals),
+                                                               p(self.d_far_team_mask), p(self.d_far_team_records), self.stream.cuda_stream)),
+            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_far_team_goals), p(self.d_far_team_mask),
+                                                           self.n)),
+        ]
+
+    def far_team_records(self):
+        """(records [n] abi.far_team_record_dtype, goals [n][3], mask [n] int32) of the last explore_far_team() (synchronises)."""
+        if self.d_far_team_goals is None:
+            raise capi.FasterHipError("Fleet.far_team_records: explore_far_team first")
+        self.sync()
+        return (self.d_far_team_records.cpu().numpy().view(abi.far_team_record_dtype).copy(), self.d_far_team_goals.cpu().numpy().copy(),
+                self.d_far_team_mask.cpu().numpy().copy())
 
     def explore_spread(self, r_max, r_spread, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link"):
         """explore_reachable() for a team (include/fasterhip_spread.h): a frontier voxel nearer than r_spread to the goal that a peer is

@@ -97,7 +97,12 @@ pass from the two, the largest `lower`, and the vehicles left unsettled or with 
 explore_far (include/fasterhip_prospect.h): its stages are reported as "far_gain_goals" and "far_gain_set_goals", and under "far_gain" the
 launch with every vehicle wanted and nobody skipped as "far_gain_goals_all_ms" beside "far_goals_all_beside_ms" of the same call (medians
 of five), and the same launch with gain_blocks 0, 1, 2 and 5.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--far BLOCK [--far-gain G [--far-hop-cost H] [--far-min-gain M]] [--far-spread R_SPREAD [--passes P]]] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+--far BLOCK --far-spread R_SPREAD --far-gain G [--far-claim-blocks C] [--passes P] [--far-hop-cost H] [--far-min-gain M] runs
+Fleet.explore_far_team(BLOCK, R_SPREAD, G, H, M, C, passes=P, after=...) in their place (include/fasterhip_stake.h): the stages are
+"far_team_goals" and "far_team_set_goals", and under "far_team" the launch with every vehicle wanted and nobody skipped as
+"far_team_goals_all_ms" beside "far_spread_goals_all_beside_ms" and "far_gain_goals_all_beside_ms" of the same call (medians of five), the
+same launch with 1, 8 and 64 passes, the cost of an idle pass from the last two, and what the claims covered and removed.
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--far BLOCK [--far-gain G [--far-hop-cost H] [--far-min-gain M]] [--far-spread R_SPREAD [--passes P]] [--far-claim-blocks C]] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -146,8 +151,12 @@ PASSES = int(sys.argv[sys.argv.index("--passes") + 1]) if "--passes" in sys.argv
 if PASSES is not None and FAR_SPREAD is None:
     sys.exit("--passes needs --far-spread R_SPREAD")
 FAR_GAIN = int(sys.argv[sys.argv.index("--far-gain") + 1]) if "--far-gain" in sys.argv else None
-if FAR_GAIN is not None and (FAR is None or FAR_SPREAD is not None):
-    sys.exit("--far-gain needs --far BLOCK and no --far-spread")
+if FAR_GAIN is not None and FAR is None:
+    sys.exit("--far-gain needs --far BLOCK")
+FAR_TEAM = FAR_SPREAD is not None and FAR_GAIN is not None   # both: Fleet.explore_far_team
+FAR_CLAIM_BLOCKS = int(sys.argv[sys.argv.index("--far-claim-blocks") + 1]) if "--far-claim-blocks" in sys.argv else None
+if FAR_CLAIM_BLOCKS is not None and not FAR_TEAM:
+    sys.exit("--far-claim-blocks needs --far-spread R_SPREAD and --far-gain G")
 FAR_HOP_COST = int(sys.argv[sys.argv.index("--far-hop-cost") + 1]) if "--far-hop-cost" in sys.argv else None
 FAR_MIN_GAIN = int(sys.argv[sys.argv.index("--far-min-gain") + 1]) if "--far-min-gain" in sys.argv else 0
 if ("--far-hop-cost" in sys.argv or "--far-min-gain" in sys.argv) and FAR_GAIN is None:
@@ -395,9 +404,11 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
         (fl.explore_reachable if REACH else fl.explore)(r_max)
     far_after = "bid" if BID else "team" if TEAM else "spread" if SPREAD is not None else "sight" if SIGHT else "gain" if GAIN is not None else "reachable" if REACH \
         else "explore"
-    if FAR_SPREAD is not None:
-        if LINK and SPREAD is None:   # teams: the groups of one link() after the first look (the choosers for a team above have linked)
-            fl.link(LINK[0])
+    if FAR_SPREAD is not None and LINK and SPREAD is None:   # teams: the groups of one link() after the first look (the choosers for a team above have linked)
+        fl.link(LINK[0])
+    if FAR_TEAM:
+        fl.explore_far_team(FAR, FAR_SPREAD, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, FAR_CLAIM_BLOCKS, passes=PASSES, after=far_after)
+    elif FAR_SPREAD is not None:
         fl.explore_far_spread(FAR, FAR_SPREAD, passes=PASSES, after=far_after)
     elif FAR_GAIN is not None:
         fl.explore_far_gain(FAR, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, after=far_after)
@@ -407,7 +418,11 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     fl.next_goals(5)
     fl.sync()
     explore = explore_stages(r_max)
-    if FAR_SPREAD is not None:   # the fallback for a team after the chooser in use
+    if FAR_TEAM:   # the fallback by gain for a team after the chooser in use
+        explore = explore + [(n if n == "far_team_goals" else "far_team_set_goals", f)
+                             for n, f in fl.explore_far_team_stages(FAR, FAR_SPREAD, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, FAR_CLAIM_BLOCKS,
+                                                                    passes=PASSES, after=far_after)]
+    elif FAR_SPREAD is not None:   # the fallback for a team after the chooser in use
         explore = explore + [(n if n == "far_spread_goals" else "far_spread_set_goals", f)
                              for n, f in fl.explore_far_spread_stages(FAR, FAR_SPREAD, passes=PASSES, after=far_after)]
     elif FAR_GAIN is not None:   # the fallback with a gain after the chooser in use
@@ -455,7 +470,53 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
                  "reachable_mean": float(rr["reachable"][hit].mean()) if hit.any() else 0.0,
                  "same_cell_as_frontier_goals": int((rr["cell"] == rec["cell"]).sum())}
     far = {}
-    if FAR_SPREAD is not None:   # every vehicle wanted and nobody skipped, applied to nobody, beside far_goals in the same call, medians of five
+    if FAR_TEAM:   # every vehicle wanted and nobody skipped, applied to nobody, beside far_spread_goals and far_gain_goals in the same call, medians of five
+        tr = fl.far_team_records()[0]
+        searched = lambda r: (r["flags"] & ~(abi.FH_FRONTIER_FOUND | abi.FH_REACH_CUT | abi.FH_STAKE_UNSETTLED | abi.FH_STAKE_CLAIMED |
+                                             abi.FH_STAKE_ALL_POOR)) == abi.FH_FRONTIER_WANTED   # noqa: E731
+        team_all = lambda passes: fl.explore_far_team_stages(FAR, FAR_SPREAD, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, FAR_CLAIM_BLOCKS, want="all",
+                                                             passes=passes)[0][1]   # noqa: E731
+        runs = {}
+        for label, passes in (("1", 1), ("8", 8), ("64", abi.FH_STAKE_MAX_PASSES), ("set", PASSES)):   # (the one asked for last: its records are read below)
+            runs[label] = fenced_ms(fl, team_all(passes), 5)
+        ta = fl.far_team_records()[0]
+        spread_ms = fenced_ms(fl, fl.explore_far_spread_stages(FAR, FAR_SPREAD, want="all", passes=PASSES)[0][1], 5)
+        sb = fl.far_spread_records()[0]
+        gain_ms = fenced_ms(fl, fl.explore_far_gain_stages(FAR, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, want="all")[0][1], 5)
+        gb = fl.far_gain_records()[0]
+        hit = searched(ta)
+        chosen = ta["hops"] >= 0
+        far = {"far_team": {"block": FAR, "r_spread": FAR_SPREAD, "gain_blocks": FAR_GAIN,
+                            "hop_cost": int(FAR * FAR if FAR_HOP_COST is None else FAR_HOP_COST), "min_gain": FAR_MIN_GAIN,
+                            "claim_blocks": int(FAR_GAIN if FAR_CLAIM_BLOCKS is None else FAR_CLAIM_BLOCKS),
+                            "passes": int(PASSES or abi.FH_STAKE_DEFAULT_PASSES), "after": far_after, "linked": bool(LINK),
+                            "work_bytes": int(fl.d_far_team_work.numel()),
+                            "far_team_goals_loop_ms": med.get("far_team_goals"), "searchers_last_cycle": int(searched(tr).sum()),
+                            "skipped_last_cycle": int((tr["flags"] & abi.FH_STAKE_SKIPPED != 0).sum()),
+                            "far_team_goals_all_ms": float(np.median(runs["set"])), "far_team_goals_all_runs_ms": [float(x) for x in runs["set"]],
+                            "far_team_goals_all_1_pass_ms": float(np.median(runs["1"])),
+                            "far_team_goals_all_8_passes_ms": float(np.median(runs["8"])),
+                            "far_team_goals_all_64_passes_ms": float(np.median(runs["64"])),
+                            "idle_pass_ms": float((np.median(runs["64"]) - np.median(runs["8"])) / (abi.FH_STAKE_MAX_PASSES - 8)),
+                            "far_spread_goals_all_beside_ms": float(np.median(spread_ms)),
+                            "far_spread_goals_all_beside_runs_ms": [float(x) for x in spread_ms],
+                            "far_gain_goals_all_beside_ms": float(np.median(gain_ms)), "far_gain_goals_all_beside_runs_ms": [float(x) for x in gain_ms],
+                            "searchers_all": int(hit.sum()), "found_all": int((ta["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                            "far_spread_found_all_beside": int((sb["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                            "far_gain_found_all_beside": int((gb["flags"] & abi.FH_FRONTIER_FOUND != 0).sum()),
+                            "lower_max": int(ta["lower"].max()), "standing_max": int(ta["standing"].max()), "claims_max": int(ta["claims"].max()),
+                            "unsettled_all": int((ta["flags"] & abi.FH_STAKE_UNSETTLED != 0).sum()),
+                            "all_claimed_all": int((ta["flags"] & abi.FH_STAKE_CLAIMED != 0).sum()),
+                            "all_poor_all": int((ta["flags"] & abi.FH_STAKE_ALL_POOR != 0).sum()),
+                            "claimed_mean": float(ta["claimed"][hit].mean()) if hit.any() else 0.0,
+                            "covered_mean": float(ta["covered"][hit].mean()) if hit.any() else 0.0,
+                            "removed_mean": float(ta["removed"][hit].mean()) if hit.any() else 0.0,
+                            "gain_mean": float(ta["gain"][chosen].mean()) if chosen.any() else -1.0,
+                            "far_gain_gain_mean_beside": float(gb["gain"][gb["hops"] >= 0].mean()) if (gb["hops"] >= 0).any() else -1.0,
+                            "hops_mean": float(ta["hops"][chosen].mean()) if chosen.any() else -1.0,
+                            "same_cell_as_far_spread_goals": int((ta["cell"] == sb["cell"]).sum()),
+                            "same_cell_as_far_gain_goals": int((ta["cell"] == gb["cell"]).sum())}}
+    elif FAR_SPREAD is not None:   # every vehicle wanted and nobody skipped, applied to nobody, beside far_goals in the same call, medians of five
         sr = fl.far_spread_records()[0]
         searched = lambda r: (r["flags"] & ~(abi.FH_FRONTIER_FOUND | abi.FH_REACH_CUT | abi.FH_APART_UNSETTLED | abi.FH_APART_CLAIMED)) \
             == abi.FH_FRONTIER_WANTED   # noqa: E731
@@ -904,7 +965,7 @@ def main():
     if "--far" in argv:          # (read into FAR above)
         k = argv.index("--far")
         del argv[k:k + 2]
-    for opt in ("--far-spread", "--passes", "--far-gain", "--far-hop-cost", "--far-min-gain"):   # (read into FAR_SPREAD .. FAR_MIN_GAIN above)
+    for opt in ("--far-spread", "--passes", "--far-gain", "--far-hop-cost", "--far-min-gain", "--far-claim-blocks"):   # (read into FAR_SPREAD .. FAR_MIN_GAIN above)
         if opt in argv:
             k = argv.index(opt)
             del argv[k:k + 2]
