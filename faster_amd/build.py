@@ -98,10 +98,28 @@ def build_frontend(force=False, verbose=False):
     return FRONT_SO
 
 
+PROBE_SO = os.path.join(ROOT, "tests", "hip", "libwaveprobe.so")
+PROBE_SOURCES = [os.path.join(ROOT, "tests", "hip", "wave_probe.hip")]
+PROBE_DEPS = PROBE_SOURCES + [os.path.join(HERE, "csrc", "fh_wave.hip.hpp"), os.path.join(HERE, "csrc", "fh_udiv.hpp")]
+
+
+def build_wave_probe(force=False, verbose=False):
+    """Test-only device code: every primitive of fh_wave.hip.hpp and fhu::div on one wavefront (tests/test_gpu_wave.py).  The compiler
+    and the options of build_device, so that the primitives are compiled as the kernels that inline them are."""
+    if force or _stale(PROBE_SO, PROBE_DEPS):
+        cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-mllvm", "-sink-insts-to-avoid-spills",
+               "-mllvm", "-disable-machine-licm", "-o", PROBE_SO] + PROBE_SOURCES
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
+    return PROBE_SO
+
+
 def build_all(force=False, verbose=False):
     build_device(force, verbose)
     build_host(force, verbose)
     build_frontend(force, verbose)
+    build_wave_probe(force, verbose)
 
 
 if __name__ == "__main__":

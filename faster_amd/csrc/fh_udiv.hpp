@@ -8,7 +8,8 @@
 // quotient exactly.  d = 1: inv = 2^32 - 1 gives q' = n - 1 (n >= 1), corrected to n.
 // inverse_fp computes the same inv with one double division (the device has no cheap 64-bit integer division): the fraction of
 // 2^32 / d is 0 or at least 1/d >= 2^-20 for d <= 2^20, far above the rounding error of the quotient (< 2^-21), so the truncation of
-// the rounded quotient is the floor.  Plain C++ (host and device); tests/cpp/test_udiv.cpp checks both claims.
+// the rounded quotient is the floor.  Plain C++ (host and device); tests/cpp/test_udiv.cpp checks both claims on the host branch, and
+// tests/test_gpu_wave.py the device branch (__umulhi, the device's double division) against n // d and 2^32 // d.
 #pragma once
 #include <stdint.h>
 

@@ -71,6 +71,9 @@ __device__ __forceinline__ double halves_sum(double v) {
   const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
   return __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
 }
+// The summation tree is pairwise summation in lane order (`while (n > 1) v = v[0::2] + v[1::2]`): after row_shr 1/2/4/8 lane 15 of a
+// row holds the balanced tree of its 16 lanes, row_bcast:15 makes lanes 31 and 63 r1 + r0 and r3 + r2, row_bcast:31 makes lane 63
+// (r3 + r2) + (r1 + r0).  The device returns these bits in every lane (tests/test_gpu_wave.py), depth 6: |error| <= 6 u sum |v|.
 __device__ __forceinline__ double wave_sum(double v) {
   v += dpp0_f64<0x111>(v); v += dpp0_f64<0x112>(v); v += dpp0_f64<0x114>(v); v += dpp0_f64<0x118>(v);  // inside each row of 16 lanes
   v += dpp0_f64<0x142>(v); v += dpp0_f64<0x143>(v);  // across the rows
@@ -87,7 +90,10 @@ __device__ __forceinline__ unsigned wave_or(unsigned v) {
   v |= (unsigned)dpp0_i32<0x142>((int)v); v |= (unsigned)dpp0_i32<0x143>((int)v);  // across the rows
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
-// max(0, max over the lanes): every caller only asks whether the maximum is positive and where it sits
+// The maximum over the lanes, for callers that only ask whether it is positive and where it sits: positive iff some lane is positive,
+// and the maximum itself when that is >= +0.  NOT max(0, ...): the zero fill goes to lanes without a source, and lane 63 and the lanes
+// it depends on all have one, so all-negative input returns the negative maximum (measured, tests/test_gpu_wave.py; half_max_nonneg
+// likewise).  No NaN.
 __device__ __forceinline__ double wave_max_nonneg(double v) {
   v = vmax_f64(v, dpp0_f64<0x111>(v)); v = vmax_f64(v, dpp0_f64<0x112>(v));  // inside each row of 16 lanes: row_shr 1, 2,
   v = vmax_f64(v, dpp0_f64<0x114>(v)); v = vmax_f64(v, dpp0_f64<0x118>(v));  // 4, 8
@@ -109,7 +115,9 @@ __device__ __forceinline__ double wave_max(double v) {
 }
 // Reductions over lanes 0..31 only, five stages: row_shr 1/2/4/8, row_bcast:15, the result in lane 31.  Where lanes 32..63 hold the
 // identity (+0, INFINITY) they return the bits of the six-stage forms above: lane 63 of wave_sum is (r3 + r2) + (r1 + r0) over the
-// four row totals, (0 + 0) + (r1 + r0) = r1 + r0 when no summand is -0; a maximum or minimum with its identity is the other operand.
+// four row totals, (0 + 0) + (r1 + r0) = r1 + r0 when no summand is -0; a maximum or minimum with its identity is the other operand
+// (+0 is the identity of half_max_nonneg only while lanes 0..31 hold a value >= +0: see wave_max_nonneg).  half_sum is pairwise
+// summation in lane order over lanes 0..31, depth 5.  What lanes 32..63 hold is not read (NaN there changes nothing).
 __device__ __forceinline__ double half_sum(double v) {
   v += dpp0_f64<0x111>(v); v += dpp0_f64<0x112>(v); v += dpp0_f64<0x114>(v); v += dpp0_f64<0x118>(v);  // inside each row of 16 lanes
   v += dpp0_f64<0x142>(v);  // row 0 into row 1
