@@ -280,7 +280,7 @@ int fh_map_read_device(fh_map* m, const double* d_cloud_xyz, int n_cloud, const 
   if (n_cloud > 0) {
     const int mcube = (int)std::floor(inflation / res);
     hipLaunchKernelGGL(fhp::mark_kernel, dim3((unsigned)((n_cloud + 255) / 256)), dim3(256), 0, m->stream, d_cloud_xyz, n_cloud, dx, dy, dz, res,
-                       m->origin[0], m->origin[1], m->origin[2], mcube, m->bits.as<unsigned>());
+                       m->origin[0], m->origin[1], m->origin[2], mcube, fhp::mark_limits(dx, dy, dz, mcube), m->bits.as<unsigned>());
     FM_HIP(hipGetLastError());
   }
   m->have_map = true;
@@ -324,7 +324,8 @@ int fh_map_read_views_device(fh_map* m, const double* d_cloud_xyz, int n_cloud, 
     for (int v0 = 0; v0 < n_views; v0 += 32768) {  // (the second grid dimension holds 65535 blocks)
       const int nv = std::min(32768, n_views - v0);
       hipLaunchKernelGGL(fhp::mark_views_kernel, dim3((unsigned)((n_cloud + 255) / 256), (unsigned)nv), dim3(256), 0, m->stream, d_cloud_xyz, n_cloud,
-                         dx, dy, dz, res, m->view_origin[0], m->view_origin[1], m->view_origin[2], mcube, m->view_bits.as<unsigned>(),
+                         dx, dy, dz, res, m->view_origin[0], m->view_origin[1], m->view_origin[2], mcube, fhp::mark_limits(dx, dy, dz, mcube),
+                         m->view_bits.as<unsigned>(),
                          (long long)words, (const unsigned*)d_point_mask, mask_words, v0);
     }
     FM_HIP(hipGetLastError());
@@ -628,7 +629,7 @@ int fh_map_read_views_listed_device(fh_map* m, const double* d_cloud_xyz, int n_
   if (n_cloud > 0) {
     const int mcube = (int)std::floor(inflation / res);
     hipLaunchKernelGGL(fhp::mark_views_listed_kernel, dim3((unsigned)((n_cloud + 255) / 256), rows), dim3(256), 0, m->stream, d_cloud_xyz, n_cloud, dx,
-                       dy, dz, res, ox, oy, oz, mcube, d_bits, words, (const unsigned*)d_point_mask, mask_words, n_views, (const int*)d_list,
+                       dy, dz, res, ox, oy, oz, mcube, fhp::mark_limits(dx, dy, dz, mcube), d_bits, words, (const unsigned*)d_point_mask, mask_words, n_views, (const int*)d_list,
                        (const int*)d_count);
   }
   if (m->view_entries_valid) {  // (only a view search in mode 1 sets it: the neighbour tables and the entries are there, sized for this lattice)

@@ -1812,46 +1812,68 @@ __global__ void __launch_bounds__(256) jps_table_kernel(MapView mv, const unsign
 }
 
 // MapUtil::readMap (read_map.hpp:100-185): every point marks its cell and the cube of +-m cells around it; the flat index test is
-// the reference's (no per-axis clipping).
-__global__ void mark_kernel(const double* cloud, int n, int nx, int ny, int nz, double res, double ox, double oy, double oz, int m,
-                            unsigned* bits) {
-  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (i >= n) return;
-  int c[3];
-  c[0] = (int)round((cloud[3 * i] - ox) / res - 0.5);
-  c[1] = (int)round((cloud[3 * i + 1] - oy) / res - 0.5);
-  c[2] = (int)round((cloud[3 * i + 2] - oz) / res - 0.5);
-  for (int k = 0; k < 3; k++) c[k] = c[k] > 0 ? c[k] : 0;
-  const long long total = (long long)nx * ny * nz;
-  for (int ix = c[0] - m; ix <= c[0] + m; ix++)
-    for (int iy = c[1] - m; iy <= c[1] + m; iy++)
-      for (int iz = c[2] - m; iz <= c[2] + m; iz++) {
-        const long long id = ix + (long long)nx * iy + (long long)nx * ny * iz;
+// the reference's (no per-axis clipping).  The contract is written down at fh_map_read_device in include/fasterhip.h; the arithmetic of
+// the three mark kernels (here and in fh_view_subset.hip.hpp) is mark_cell and mark_cube and exists once.
+//
+// mark_cell: per axis v = round((p - origin) / res - 0.5) in double; a v that is not finite: false, the point marks nothing; else c =
+// max(v, 0).  Whether v is finite and fits is decided in double BEFORE any conversion (as fh_cells.hip.hpp does): no NaN, infinity or
+// 1e300 is ever converted to an integer.  The guard loses no cell: a cell id is sx (cx + i) + sy (cy + j) + sz (cz + k) with strides sx = 1,
+// sy = nx, sz = nx ny, every c >= 0 and every offset >= -m, so id >= s_a c_a - m (sx + sy + sz) for each axis a.  With G = total + m (sx +
+// sy + sz), s_a c_a >= G gives id >= total for the whole cube.  The guard is v >= 2 (G / s_a + 1) — twice the bound, so that its rounding
+// to double cannot stop a v with s_a c_a <= G — and what passes has s_a c_a < 2 G + 4 s_a: with total <= 2^27 (fh_map_read_device refuses
+// more) and m < 2^31, G < 2^60 and the three products and their sum stay inside 64 bits.  The three limits depend on the lattice alone:
+// the host computes them once per read (mark_limits, the expression of VoxelGrid::build) and the kernels take them as an argument.
+struct MarkLimits {
+  double v[3];  // per axis: a point with v >= this marks nothing
+};
+inline MarkLimits mark_limits(int nx, int ny, int nz, int m) {
+  const long long stride[3] = {1, (long long)nx, (long long)nx * ny};
+  const long long G = stride[2] * nz + (long long)m * (stride[0] + stride[1] + stride[2]);
+  MarkLimits lim;
+  for (int a = 0; a < 3; a++) lim.v[a] = 2.0 * (double)(G / stride[a] + 1);
+  return lim;
+}
+__device__ __forceinline__ bool mark_coord(double p, double o, double res, double limit, long long& c) {
+  const double v = round((p - o) / res - 0.5);
+  if (!isfinite(v) || v >= limit) return false;
+  c = v > 0.0 ? (long long)v : 0;
+  return true;
+}
+__device__ __forceinline__ bool mark_cell(const double* cloud, int i, double res, double ox, double oy, double oz, const MarkLimits& lim,
+                                          long long c[3]) {
+  return mark_coord(cloud[3 * (size_t)i], ox, res, lim.v[0], c[0]) && mark_coord(cloud[3 * (size_t)i + 1], oy, res, lim.v[1], c[1]) &&
+         mark_coord(cloud[3 * (size_t)i + 2], oz, res, lim.v[2], c[2]);
+}
+// mark_cube: every cell of the cube by its flat index in 64 bits; every store is behind 0 <= id < total.  Bits are only ORed.
+__device__ __forceinline__ void mark_cube(const long long c[3], int nx, int ny, int nz, int m, unsigned* bits) {
+  const long long sy = nx, sz = (long long)nx * ny, total = sz * nz;
+  for (long long ix = c[0] - m; ix <= c[0] + m; ix++)
+    for (long long iy = c[1] - m; iy <= c[1] + m; iy++)
+      for (long long iz = c[2] - m; iz <= c[2] + m; iz++) {
+        const long long id = ix + sy * iy + sz * iz;
         if (id >= 0 && id < total) atomicOr(&bits[id >> 5], 1u << (id & 31));
       }
+}
+
+__global__ void mark_kernel(const double* cloud, int n, int nx, int ny, int nz, double res, double ox, double oy, double oz, int m,
+                            MarkLimits lim, unsigned* bits) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  long long c[3];
+  if (mark_cell(cloud, i, res, ox, oy, oz, lim, c)) mark_cube(c, nx, ny, nz, m, bits);
 }
 
 // mark_kernel for n_views grids at once (fh_map_read_views_device): point i marks, with the same arithmetic, the grid of every view
 // whose row of `mask` ([n_views][mask_words], bit i & 31 of word i >> 5) has its bit.  blockIdx.y = the view.  Bits are only ORed.
 __global__ void mark_views_kernel(const double* cloud, int n, int nx, int ny, int nz, double res, double ox, double oy, double oz, int m,
-                                  unsigned* bits, long long words_per_view, const unsigned* mask, int mask_words, int first_view) {
+                                  MarkLimits lim, unsigned* bits, long long words_per_view, const unsigned* mask, int mask_words,
+                                  int first_view) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= n) return;
   const long long v = (long long)first_view + blockIdx.y;
   if (!((mask[v * mask_words + (i >> 5)] >> (i & 31)) & 1u)) return;
-  unsigned* mine = bits + v * words_per_view;
-  int c[3];
-  c[0] = (int)round((cloud[3 * i] - ox) / res - 0.5);
-  c[1] = (int)round((cloud[3 * i + 1] - oy) / res - 0.5);
-  c[2] = (int)round((cloud[3 * i + 2] - oz) / res - 0.5);
-  for (int k = 0; k < 3; k++) c[k] = c[k] > 0 ? c[k] : 0;
-  const long long total = (long long)nx * ny * nz;
-  for (int ix = c[0] - m; ix <= c[0] + m; ix++)
-    for (int iy = c[1] - m; iy <= c[1] + m; iy++)
-      for (int iz = c[2] - m; iz <= c[2] + m; iz++) {
-        const long long id = ix + (long long)nx * iy + (long long)nx * ny * iz;
-        if (id >= 0 && id < total) atomicOr(&mine[id >> 5], 1u << (id & 31));
-      }
+  long long c[3];
+  if (mark_cell(cloud, i, res, ox, oy, oz, lim, c)) mark_cube(c, nx, ny, nz, m, bits + v * words_per_view);
 }
 
 }  // namespace fhp

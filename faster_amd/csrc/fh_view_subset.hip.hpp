@@ -75,32 +75,22 @@ __global__ void __launch_bounds__(256) clear_views_listed_kernel(unsigned* bits,
   }
 }
 
-// mark_views_kernel for the listed views: the same arithmetic, the view from the list instead of from blockIdx.y
+// mark_views_kernel for the listed views: the same arithmetic (mark_cell, mark_cube), the view from the list instead of from blockIdx.y
 __global__ void __launch_bounds__(256) mark_views_listed_kernel(const double* cloud, int n, int nx, int ny, int nz, double res, double ox, double oy,
-                                                                double oz, int m, unsigned* bits, long long words_per_view, const unsigned* mask,
-                                                                int mask_words, int n_views, const int* __restrict__ list,
+                                                                double oz, int m, MarkLimits lim, unsigned* bits, long long words_per_view,
+                                                                const unsigned* mask, int mask_words, int n_views, const int* __restrict__ list,
                                                                 const int* __restrict__ count) {
   const int cnt = view_list_count(count, n_views);
   if ((int)blockIdx.y >= cnt) return;
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= n) return;
-  int c[3];
-  c[0] = (int)round((cloud[3 * i] - ox) / res - 0.5);
-  c[1] = (int)round((cloud[3 * i + 1] - oy) / res - 0.5);
-  c[2] = (int)round((cloud[3 * i + 2] - oz) / res - 0.5);
-  for (int k = 0; k < 3; k++) c[k] = c[k] > 0 ? c[k] : 0;
-  const long long total = (long long)nx * ny * nz;
+  long long c[3];
+  if (!mark_cell(cloud, i, res, ox, oy, oz, lim, c)) return;
   for (int e = (int)blockIdx.y; e < cnt; e += (int)gridDim.y) {
     const long long v = uniform_i32(list[e]);
     if (v < 0 || v >= n_views) continue;
     if (!((mask[v * mask_words + (i >> 5)] >> (i & 31)) & 1u)) continue;
-    unsigned* mine = bits + v * words_per_view;
-    for (int ix = c[0] - m; ix <= c[0] + m; ix++)
-      for (int iy = c[1] - m; iy <= c[1] + m; iy++)
-        for (int iz = c[2] - m; iz <= c[2] + m; iz++) {
-          const long long id = ix + (long long)nx * iy + (long long)nx * ny * iz;
-          if (id >= 0 && id < total) atomicOr(&mine[id >> 5], 1u << (id & 31));
-        }
+    mark_cube(c, nx, ny, nz, m, bits + v * words_per_view);
   }
 }
 

@@ -293,8 +293,21 @@ struct VoxelGrid {
     return V3((x + 0.5) * res + origin[0], (y + 0.5) * res + origin[1], (z + 0.5) * res + origin[2]);
   }
 
+  // One axis of readMap's cell arithmetic under the contract of fh_map_read_device (include/fasterhip.h): v = round((p - origin) / res -
+  // 0.5) in double; not finite: false, the point marks nothing; else c = max(v, 0) as an exact integer.  `limit` is a bound past which the
+  // point marks nothing whatever the other two axes hold (see build); v is compared with it in double, before any conversion, so that
+  // no value that an integer cannot hold is ever converted.
+  static bool mark_coord(double p, double o, double res, double limit, long long* c) {
+    const double v = std::round((p - o) / res - 0.5);
+    if (!std::isfinite(v) || v >= limit) return false;
+    *c = v > 0.0 ? (long long)v : 0;
+    return true;
+  }
+
   // FASTER's readMap (map_util.h:30-185): grid of cells_* cells (x,y widened by 5*inflation/res) centred on `center`, clipped
-  // to [z_ground, z_max]; every point marks its cell and the cube of +-floor(inflation/res) cells around it.
+  // to [z_ground, z_max]; every point marks its cell and the cube of +-floor(inflation/res) cells around it.  Where the reference's
+  // 32-bit arithmetic does not overflow this is the reference; beyond it (and for coordinates that are not finite) the contract of
+  // fh_map_read_device holds: exact integers, and a point with a coordinate that is not finite marks nothing.
   void build(const std::vector<V3>& cloud, int cells_x, int cells_y, int cells_z, double res_, const V3& center, double z_ground,
              double z_max, double inflation) {
     res = res_;
@@ -311,17 +324,27 @@ struct VoxelGrid {
     origin[1] = center.y - res * dy / 2.0;
     origin[2] = center.z - res * down;
     occ.assign((size_t)nx * ny * nz, 0);
-    const int total = nx * ny * nz;
-    const int m = (int)std::floor(inflation / res);
+    const long long total = (long long)nx * ny * nz;
+    const long long m = (long long)std::floor(inflation / res);
+    // A cell id is sx * (cx + i) + sy * (cy + j) + sz * (cz + k) with strides sx = 1, sy = nx, sz = nx * ny, every c >= 0 and every
+    // offset >= -m, so id >= s_a * c_a - m * (sx + sy + sz) for each axis a.  With G = total + m * (sx + sy + sz): s_a * c_a >= G gives
+    // id >= total for every cell of the cube, the point marks nothing.  The guard is v >= 2 * (G / s_a + 1): twice the bound, so that
+    // its rounding to double cannot let a smaller v through (no cell is lost: whatever the guard stops has s_a * c_a > G), and what
+    // passes has s_a * c_a < 2 G + 4 s_a, so that the sums below stay inside 64 bits (G < 2^60 for every lattice the device entry points
+    // accept: total <= 2^27, m < 2^31).
+    const long long stride[3] = {1, (long long)nx, (long long)nx * ny};
+    const long long G = total + m * (stride[0] + stride[1] + stride[2]);
     for (const V3& p : cloud) {
-      int c[3];
-      to_cell(p, c);
-      for (int k = 0; k < 3; k++) c[k] = c[k] > 0 ? c[k] : 0;
-      for (int ix = c[0] - m; ix <= c[0] + m; ix++)
-        for (int iy = c[1] - m; iy <= c[1] + m; iy++)
-          for (int iz = c[2] - m; iz <= c[2] + m; iz++) {
-            const int id = ix + nx * iy + nx * ny * iz;  // flat index test only, as in the reference
-            if (id >= 0 && id < total) occ[id] = 100;
+      long long c[3];
+      if (!mark_coord(p.x, origin[0], res, 2.0 * (double)(G / stride[0] + 1), &c[0]) ||
+          !mark_coord(p.y, origin[1], res, 2.0 * (double)(G / stride[1] + 1), &c[1]) ||
+          !mark_coord(p.z, origin[2], res, 2.0 * (double)(G / stride[2] + 1), &c[2]))
+        continue;
+      for (long long ix = c[0] - m; ix <= c[0] + m; ix++)
+        for (long long iy = c[1] - m; iy <= c[1] + m; iy++)
+          for (long long iz = c[2] - m; iz <= c[2] + m; iz++) {
+            const long long id = ix + stride[1] * iy + stride[2] * iz;  // flat index test only, as in the reference
+            if (id >= 0 && id < total) occ[(size_t)id] = 100;
           }
     }
   }

@@ -587,6 +587,23 @@ long long fh_map_workspace_bytes(const fh_map* map);
  * reference's single-precision crossing), the crossing point E appended, BEFORE createMoreVertexes / deleteVertexes.  0 (default): off. */
 int fh_map_set_sphere(fh_map* map, double ra);
 int fh_map_sync(fh_map* map);
+/* The map read: MapUtil::readMap (jps3d, jps_collision/map_util.h:30-185).  The lattice (dims, origin) is that function's arithmetic.
+ * What a point p of the cloud marks — the contract of every entry point that turns points into a grid (fh_map_read,
+ * fh_map_read_device, fh_map_read_views_device, fh_map_read_views_listed_device), of the host restatement VoxelGrid::build and of the
+ * model tests/map_read_model.py:
+ *   1. per axis v = round((p - origin) / res - 0.5), evaluated in IEEE double with no contraction; round() rounds halves away from zero.
+ *   2. if any v is not finite (p is NaN or infinite, or the quotient overflows) the point marks nothing — the rule of
+ *      fleet_observe_kernel: "outside the lattice or not finite: never observed".
+ *   3. otherwise c = max(v, 0) per axis (the reference's "force them to be positive", map_util.h:143-145): a finite point left of or
+ *      below the window, however far, marks the low face.
+ *   4. every offset (i, j, k) in [-m, m]^3, m = floor(inflation / res), gives id = (cx + i) + nx (cy + j) + nx ny (cz + k), in exact
+ *      integers.
+ *   5. the cell is marked iff 0 <= id < nx ny nz.  There is no per-axis clipping (map_util.h:175-176): a cube that sticks out in x comes
+ *      back on the next row, one that sticks out in y on the next layer; beyond the high z face nothing is marked.
+ * Where the reference's own 32-bit arithmetic does not overflow this is the reference, cell for cell, and stays pinned to it
+ * (tests/test_ref_frontend.py, tests/test_map_read_edge_cases.py).  Beyond that range the reference is undefined (a conversion of an
+ * out-of-range double, a signed overflow of the flat index: 410 m above a 1024 x 1024 window); there exact integers are the rule, so a
+ * far point marks nothing instead of coming back into the map.  Edge suite: tests/map_read_edge_cases.py. */
 int fh_map_read(fh_map* map, const double* cloud_xyz, int n_cloud, const int32_t cells[3], double res, const double center[3],
                 double z_ground, double z_max, double inflation);
 int fh_map_read_device(fh_map* map, const double* d_cloud_xyz, int n_cloud, const int32_t cells[3], double res, const double center[3],

@@ -65,21 +65,13 @@ def inside(c, dims):
 
 
 def occupancy(cloud, cells, res, center, z_ground, z_max, inflation):
-    """MapUtil::readMap as the comment on mark_kernel describes it: every point marks its cell (negative cell coordinates clamped to 0) and
-    the cube of +-floor(inflation / res) cells around it; a cube cell is taken by its FLAT index (no per-axis clipping: a cube that sticks
-    out in x comes back in on the next row).  -> (occ [nz][ny][nx] int8, dims, origin)"""
-    (nx, ny, nz), origin = geometry(cells, res, center, z_ground, z_max, inflation)
-    total = nx * ny * nz
-    occ = np.zeros(total, dtype=np.int8)
-    cloud = np.asarray(cloud, dtype=np.float64).reshape(-1, 3)
-    if len(cloud):
-        c = np.maximum(c_round((cloud - origin) / res - 0.5).astype(np.int64), 0)
-        m = int(math.floor(inflation / res))
-        r = np.arange(-m, m + 1)
-        ox, oy, oz = np.meshgrid(r, r, r, indexing="ij")
-        ids = ((c[:, 0, None] + ox.ravel()[None]) + nx * (c[:, 1, None] + oy.ravel()[None]) + nx * ny * (c[:, 2, None] + oz.ravel()[None])).ravel()
-        occ[ids[(ids >= 0) & (ids < total)]] = 100
-    return occ.reshape(nz, ny, nx), (nx, ny, nz), origin
+    """MapUtil::readMap: every point marks its cell (negative cell coordinates clamped to 0) and the cube of +-floor(inflation / res)
+    cells around it; a cube cell is taken by its FLAT index (no per-axis clipping: a cube that sticks out in x comes back in on the next
+    row); a point with a coordinate that is not finite marks nothing.  The one model of that contract is tests/map_read_model.py.
+    -> (occ [nz][ny][nx] int8, dims, origin)"""
+    import map_read_model
+
+    return map_read_model.occupancy(cloud, cells, res, center, z_ground, z_max, inflation)
 
 
 def m_free(inflation, res):
