@@ -50,6 +50,8 @@ ROUNDS_SYMBOLS = ["fh_fleet_round_classes_device", "fh_fleet_round_gate_device"]
 VIEW_SUBSET_SYMBOLS = ["fh_map_view_list_device", "fh_map_read_views_listed_device"]
 # include/fasterhip_link.h
 LINK_SYMBOLS = ["fh_fleet_link_groups_device", "fh_fleet_link_merge_device"]
+# include/fasterhip_link_los.h
+LINK_LOS_SYMBOLS = ["fh_fleet_link_groups_los_device"]
 # include/fasterhip_frontier.h
 FRONTIER_SYMBOLS = ["fh_map_frontier_goals_device", "fh_map_view_coverage_device"]
 # include/fasterhip_reach.h
@@ -335,6 +337,8 @@ def lib():
         L.fh_fleet_round_gate_device.argtypes = [vp, vp, i32, vp, i32, vp, vp]
         L.fh_fleet_link_groups_device.restype = i32
         L.fh_fleet_link_groups_device.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp]
+        L.fh_fleet_link_groups_los_device.restype = i32
+        L.fh_fleet_link_groups_los_device.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp]
         L.fh_fleet_link_merge_device.restype = i32
         L.fh_fleet_link_merge_device.argtypes = [vp, vp, i32, vp, ctypes.c_size_t, ctypes.c_size_t, vp, i32, i32]
         L.fh_map_view_list_device.restype = i32
@@ -1161,6 +1165,18 @@ class Context:
         g = _grid_record(cells)
         self._check(lib().fh_fleet_link_groups_device(self._h, abi.ptr(p), d_vehicles, int(n), d_view_of, int(n_views),
                                                       None if g is None else abi.ptr(g), d_labels, d_info), "fh_fleet_link_groups_device")
+
+    def fleet_link_groups_los_device(self, vmap, par, d_vehicles, n, d_view_of, n_views, cells, d_labels, d_info):
+        """fh_fleet_link_groups_los_device: fleet_link_groups_device where a linked pair also needs a line of sight through `vmap` (a
+        Map that holds a grid, filled on this context's stream): the pair is blocked when a half-cell sample of the ray from the vehicle
+        with the smaller index to the other lies in an occupied cell that is not the cell of either end.  d_info [4] int64: views changed
+        by the last pass, roots, linked pairs, pairs in range that are blocked; par["range"] is at most 4096 cells of the map.  No output
+        byte depends on cells.  A measurement.  Asynchronous on the context's stream (include/fasterhip_link_los.h)."""
+        p = _one_record(par, "link", "fleet_link_groups_los_device")
+        g = _grid_record(cells)
+        self._check(lib().fh_fleet_link_groups_los_device(self._h, None if vmap is None else vmap._h, abi.ptr(p), d_vehicles, int(n), d_view_of,
+                                                          int(n_views), None if g is None else abi.ptr(g), d_labels, d_info),
+                    "fh_fleet_link_groups_los_device")
 
     def fleet_link_merge_device(self, d_labels, n_views, d_flags, view_stride, view_bytes, d_point_mask, mask_words, shared_words):
         """fh_fleet_link_merge_device: the views of every group (a root and the views whose label it is) become equal, in place: a flag

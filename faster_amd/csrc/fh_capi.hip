@@ -27,6 +27,7 @@
 #include "../../include/fasterhip_traffic_timed.h"
 #include "../../include/fasterhip_rounds.h"
 #include "../../include/fasterhip_link.h"
+#include "../../include/fasterhip_link_los.h"
 #include "fh_policy.hpp"  // (host only; before fh_solve: the look periods are named there)
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
@@ -89,10 +90,13 @@ enum Buf {
   TRAFFIC_BOXES,    // traffic_points{1,7}_kernel write the grown box of the shown centres of every chunk; the rule's mask kernels read them
   // fh_fleet_round_classes_device (its box records live in CELL_BOXES, like those of the other two stages of the cell grid)
   ROUND_LISTS,      // rounds_narrow_kernel writes the lower neighbours of every vehicle (rows of FH_ROUNDS_LIST), rounds_pass_kernel reads them
-  // fh_fleet_link_groups_device (its box records live in CELL_BOXES as well)
+  // fh_fleet_link_groups_device (its box records live in CELL_BOXES as well) and fh_fleet_link_groups_los_device, whose narrow and hook
+  // kernels are link_los_narrow_kernel and link_los_hook_kernel
   LINK_LISTS,       // link_narrow_kernel writes the views of the linked of every vehicle (rows of FH_LINK_LIST), link_hook_kernel reads them
   LINK_NBRS,        // link_narrow_kernel writes how many are linked to every vehicle, link_hook_kernel reads it
   LINK_LABELS,      // the two copies of the labels ([2][n_views]) that link_hook_kernel lowers and link_jump_kernel reads and writes in turn
+  LINK_LOS_KEPT,    // link_los_narrow_kernel writes, per vehicle and turn of its walk, the ballot of the candidates in line of sight
+                    // (rows of fh::LINK_LOS_TURNS words); link_los_hook_kernel reads them where a vehicle has more than a row of LINK_LISTS
   N_BUFS
 };
 
@@ -385,9 +389,10 @@ static bool cell_grid_ok(const fh_voxel_grid* cells, long long max_cells) {
   return fhh::voxel_grid_ok(cells) && fhh::voxel_grid_cells(*cells) <= max_cells;
 }
 
-// The working buffers, a.g and a.boxes, and the four launches: the stage's boxes kernel, scan, fill, the stage's narrow kernel.
+// The working buffers, a.g and a.boxes, and the first three launches: the stage's boxes kernel, scan, fill.  (A stage whose narrow kernel
+// takes more than these arguments launches it itself: fh_fleet_link_groups_los_device.)
 template <class Args>
-static int cell_broad_phase(fh_ctx* ctx, const fh_voxel_grid& cells, int n, Args& a, void (*boxes_kernel)(Args), void (*narrow_kernel)(Args)) {
+static int cell_grid_build(fh_ctx* ctx, const fh_voxel_grid& cells, int n, Args& a, void (*boxes_kernel)(Args)) {
   using Box = typename std::remove_pointer<decltype(a.boxes)>::type;
   static_assert(offsetof(Box, c) == 0, "cell_fill_kernel reads the CellBox at the head of a box record");
   const int n_cells = (int)fhh::voxel_grid_cells(cells);
@@ -412,6 +417,14 @@ static int cell_broad_phase(fh_ctx* ctx, const fh_voxel_grid& cells, int n, Args
   hipLaunchKernelGGL(fh::cell_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a.g,
                      reinterpret_cast<const unsigned char*>(a.boxes), (int)sizeof(Box), n);
   FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+// cell_grid_build and the fourth launch, the stage's narrow kernel.
+template <class Args>
+static int cell_broad_phase(fh_ctx* ctx, const fh_voxel_grid& cells, int n, Args& a, void (*boxes_kernel)(Args), void (*narrow_kernel)(Args)) {
+  int rc;
+  if ((rc = cell_grid_build(ctx, cells, n, a, boxes_kernel)) != FH_OK) return rc;
   hipLaunchKernelGGL(narrow_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
   FH_HIP(hipGetLastError());
   return FH_OK;
@@ -1274,15 +1287,11 @@ int fh_fleet_round_gate_device(fh_ctx* ctx, const fh_plan_round* d_rounds, int r
 }
 
 // ---- the radio link (include/fasterhip_link.h): the cell grid around link_boxes_kernel and link_narrow_kernel, the passes; the merge ----
-int fh_fleet_link_groups_device(fh_ctx* ctx, const fh_link_params* par, const fh_vehicle* d_vehicles, int n, const int32_t* d_view_of,
-                                int n_views, const fh_voxel_grid* cells, int32_t* d_labels, int64_t* d_info) {
-  if (!ctx || !par) return FH_ERR_ARG;
-  if (!audit_radius_ok(par->range) || !(par->range > 0)) return FH_ERR_ARG;
-  if (par->passes < 1 || par->passes > FH_LINK_MAX_PASSES) return FH_ERR_ARG;
-  if (n < 0 || n_views < 1) return FH_ERR_ARG;
-  if (!cell_grid_ok(cells, FH_LINK_MAX_CELLS)) return FH_ERR_ARG;
-  if (ctx->device < 0) return FH_ERR_DEVICE;
-  DeviceScope device_scope(ctx->device);
+// What both entry points of the groups do after their prologues (the device is current): n == 0, the pointers, the launches.  los: the
+// map a link needs a line of sight through (include/fasterhip_link_los.h), or null.  Without it the launches are those of
+// fh_fleet_link_groups_device as they have always been.
+static int link_groups_launch(fh_ctx* ctx, const fh_link_params* par, const fh_vehicle* d_vehicles, int n, const int32_t* d_view_of, int n_views,
+                              const fh_voxel_grid* cells, int32_t* d_labels, int64_t* d_info, const fh::LinkLosMap* los) {
   if (n > 0 && (!d_vehicles || !d_labels || !d_info)) return FH_ERR_ARG;
   int rc;
   if ((rc = ensure(ctx, LINK_LABELS, sizeof(int) * 2 * (size_t)n_views)) != FH_OK) return rc;
@@ -1309,18 +1318,69 @@ int fh_fleet_link_groups_device(fh_ctx* ctx, const fh_link_params* par, const fh
   a.nbrs = ctx->buf[LINK_NBRS].as<int>();
   a.info = info;
   FH_HIP(hipMemsetAsync(d_info, 0, sizeof(int64_t) * 4, ctx->stream));
-  if ((rc = cell_broad_phase(ctx, *cells, n, a, fh::link_boxes_kernel, fh::link_narrow_kernel)) != FH_OK) return rc;
+  fh::LinkLosArgs al;  // (read only with los)
+  if (los) {
+    if ((rc = ensure(ctx, LINK_LOS_KEPT, sizeof(unsigned long long) * (size_t)fh::LINK_LOS_TURNS * (size_t)n)) != FH_OK) return rc;
+    if ((rc = cell_grid_build(ctx, *cells, n, a, fh::link_boxes_kernel)) != FH_OK) return rc;
+    al.l = a; al.m = *los;
+    al.turns = ctx->buf[LINK_LOS_KEPT].as<unsigned long long>();
+    hipLaunchKernelGGL(fh::link_los_narrow_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, al);
+    FH_HIP(hipGetLastError());
+  } else if ((rc = cell_broad_phase(ctx, *cells, n, a, fh::link_boxes_kernel, fh::link_narrow_kernel)) != FH_OK) {
+    return rc;
+  }
   hipLaunchKernelGGL(fh::link_init_kernel, view_blocks, dim3(256), 0, ctx->stream, d_labels, copies[0], n_views);
   FH_HIP(hipGetLastError());
   for (int p = 1; p <= par->passes; p++) {
     int* H = copies[(p - 1) & 1];
-    hipLaunchKernelGGL(fh::link_hook_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, d_labels, H);
+    if (los)
+      hipLaunchKernelGGL(fh::link_los_hook_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, al, d_labels, H);
+    else
+      hipLaunchKernelGGL(fh::link_hook_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a, d_labels, H);
     FH_HIP(hipGetLastError());
     hipLaunchKernelGGL(fh::link_jump_kernel, view_blocks, dim3(256), 0, ctx->stream, H, d_labels, copies[p & 1], n_views,
                        p == par->passes ? info : nullptr);
     FH_HIP(hipGetLastError());
   }
   return FH_OK;
+}
+
+int fh_fleet_link_groups_device(fh_ctx* ctx, const fh_link_params* par, const fh_vehicle* d_vehicles, int n, const int32_t* d_view_of,
+                                int n_views, const fh_voxel_grid* cells, int32_t* d_labels, int64_t* d_info) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->range) || !(par->range > 0)) return FH_ERR_ARG;
+  if (par->passes < 1 || par->passes > FH_LINK_MAX_PASSES) return FH_ERR_ARG;
+  if (n < 0 || n_views < 1) return FH_ERR_ARG;
+  if (!cell_grid_ok(cells, FH_LINK_MAX_CELLS)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  return link_groups_launch(ctx, par, d_vehicles, n, d_view_of, n_views, cells, d_labels, d_info, nullptr);
+}
+
+// (include/fasterhip_link_los.h: the same groups, a linked pair also needs a line of sight through the map's occupied cells)
+int fh_fleet_link_groups_los_device(fh_ctx* ctx, fh_map* map, const fh_link_params* par, const fh_vehicle* d_vehicles, int n,
+                                    const int32_t* d_view_of, int n_views, const fh_voxel_grid* cells, int32_t* d_labels, int64_t* d_info) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->range) || !(par->range > 0)) return FH_ERR_ARG;
+  if (par->passes < 1 || par->passes > FH_LINK_MAX_PASSES) return FH_ERR_ARG;
+  if (n < 0 || n_views < 1) return FH_ERR_ARG;
+  if (!cell_grid_ok(cells, FH_LINK_MAX_CELLS)) return FH_ERR_ARG;
+  fh::LinkLosMap los;
+  int32_t mdims[3];
+  double morigin[3], mres = 0;
+  if (!map || fh_map_dims(map, mdims, morigin) != FH_OK || fh_map_occupancy_bits_device(map, &los.occ, &mres) != FH_OK) {
+    ctx->err = "fh_fleet_link_groups_los_device: the map holds no grid (fh_map_read_device first)";
+    return FH_ERR_ARG;
+  }
+  if (!(par->range / mres <= 4096.0)) {  // (a ray has ceil(|q - p| / (0.5 res_map)) - 1 sample points)
+    ctx->err = "fh_fleet_link_groups_los_device: range is more than 4096 cells of the map";
+    return FH_ERR_ARG;
+  }
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  los.ox = morigin[0]; los.oy = morigin[1]; los.oz = morigin[2]; los.res = mres;
+  los.mx = mdims[0]; los.my = mdims[1]; los.mz = mdims[2]; los.pad = 0;
+  return link_groups_launch(ctx, par, d_vehicles, n, d_view_of, n_views, cells, d_labels, d_info, &los);
 }
 
 int fh_fleet_link_merge_device(fh_ctx* ctx, const int32_t* d_labels, int n_views, unsigned char* d_flags, size_t view_stride, size_t view_bytes,

@@ -255,3 +255,7 @@ __global__ void __launch_bounds__(LINK_MERGE_THREADS) link_merge_mask_kernel(con
 }
 
 }  // namespace fh
+
+// The link with a line of sight (include/fasterhip_link_los.h) comes in here, behind the last kernel of this file: its two kernels lie
+// after every kernel of before in the code object of fh_capi.hip, and this header stays the last device header that fh_capi.hip names.
+#include "fh_link_los.hip.hpp"

@@ -35,7 +35,8 @@ enable_listed_views() makes map_views cheap where few vehicles replan (include/f
 device, the views of the vehicles that are switched on, and map_views rebuilds the grids and jump tables of those views only.
 
 link() lets the vehicles in radio range of each other pool what their views know (include/fasterhip_link.h): the views of every connected
-group become equal, unknown voxels and occupied points alike, and the group plans as a team does until it parts:
+group become equal, unknown voxels and occupied points alike, and the group plans as a team does until it parts; link(range, los=True) is
+the same where walls block a link (include/fasterhip_link_los.h: a pair needs a line of sight through the fleet's map):
 
     sense -> observe -> link -> replan -> next_goals
 
@@ -539,23 +540,29 @@ class Fleet:
         self.sync()
         return self.d_check_rounds.cpu().numpy().view(abi.plan_check_dtype).copy()
 
-    def link(self, range, passes=None, cells=None):  # noqa: A002  (the header's word)
+    def link(self, range, passes=None, cells=None, los=False):  # noqa: A002  (the header's word)
         """The vehicles nearer than `range` to each other pool what their views know (include/fasterhip_link.h): link_groups labels
         every view with the smallest view of its connected group (`passes` passes of hook and jump, None:
         abi.FH_LINK_DEFAULT_PASSES; link_records() tells whether they settled), link_merge makes the views of a group equal: a voxel is
         known to all when one of them knows it, and with point views so is a point of the static cloud.  The traffic words of the
         masks are per observer and stay as they are.  After sense() and observe(), before replan(); needs set_unknown_views.  cells =
         (origin, res, dims): the grid of the broad phase, by default separation_cells(range); no output byte depends on it.  Launches on
-        the fleet's stream.  Nothing is forgotten when the vehicles part.  Memory: n_views ints and four words."""
+        the fleet's stream.  Nothing is forgotten when the vehicles part.  Memory: n_views ints and four words.
+        los=True: walls block a link (include/fasterhip_link_los.h): a pair in range is linked only when no half-cell sample of the ray
+        between the two vehicles lies in an occupied cell of the fleet's map other than the cells they stand in; a blocked pair can still
+        be one group through a vehicle that sees both.  Needs set_map.  los=False launches exactly what it always has."""
         self._follow_current()
-        for _, launch in self.link_stages(range, passes, cells):
+        for _, launch in self.link_stages(range, passes, cells, los):
             launch()
 
-    def link_stages(self, range, passes=None, cells=None):  # noqa: A002
-        """The two launches of link(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+    def link_stages(self, range, passes=None, cells=None, los=False):  # noqa: A002
+        """The two launches of link(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one); with los=True the
+        first is ("link_groups_los", ...) on the fleet's map."""
         t = self.torch
         if self.view_flags is None:
             raise capi.FasterHipError("Fleet.link: set_unknown_views first")
+        if los and self.cloud is None:
+            raise capi.FasterHipError("Fleet.link: los=True needs set_map")
         par = abi.default_link_params(range)
         if passes is not None:
             par["passes"] = passes
@@ -573,16 +580,21 @@ class Fleet:
         mask = None if self.point_mask is None else p(self.point_mask)
         words = 0 if self.point_mask is None else int(self.point_mask.shape[1])
         shared = words if self.traffic_par is None else int(self.traffic_par["first_point"]) // 32   # (below the traffic)
+        groups = ("link_groups", lambda: c.fleet_link_groups_device(par, p(self.d_vehicles), self.n, vo, self.n_views, cells,
+                                                                    p(self.d_link_labels), p(self.d_link_info)))
+        if los:
+            groups = ("link_groups_los", lambda: c.fleet_link_groups_los_device(self.map, par, p(self.d_vehicles), self.n, vo, self.n_views, cells,
+                                                                                p(self.d_link_labels), p(self.d_link_info)))
         return [
-            ("link_groups", lambda: c.fleet_link_groups_device(par, p(self.d_vehicles), self.n, vo, self.n_views, cells, p(self.d_link_labels),
-                                                               p(self.d_link_info))),
+            groups,
             ("link_merge", lambda: c.fleet_link_merge_device(p(self.d_link_labels), self.n_views, p(self.view_flags), self.view_flags.shape[1],
                                                              self.view_flags.shape[1], mask, words, shared)),
         ]
 
     def link_records(self):
         """(labels [n_views] int32, info [4] int64) of the last link(): the label of every view; the views whose label the last pass
-        changed (0: settled), the roots, the linked pairs of vehicles, 0 (synchronises)."""
+        changed (0: settled), the roots, the linked pairs of vehicles, and info[3]: 0 after link(), after link(los=True) the pairs in
+        range that a wall blocks (synchronises)."""
         if self.d_link_labels is None:
             raise capi.FasterHipError("Fleet.link_records: link first")
         self.sync()

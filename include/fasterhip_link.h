@@ -50,7 +50,7 @@
  *   bytes between view_bytes and view_stride are not touched.
  * The OR of observed rows is the observation of the AND of the views, so a linked group plans as one team does.
  *
- * KNOWN LIMITS.  Walls do not block a link.  There is no bandwidth or latency model: a call is one period in which a connected group
+ * KNOWN LIMITS.  Walls do not block a link (fasterhip_link_los.h adds the entry point where they do).  There is no bandwidth or latency model: a call is one period in which a connected group
  * floods everything.  Nothing is forgotten when vehicles part.  Jump tables and grids are not touched: they are rebuilt by the map's
  * view stage as before, and views that are not listed keep old grids (include/fasterhip_view_subset.h). */
 #ifndef FASTERHIP_LINK_H

@@ -47,7 +47,10 @@ views: "view_list" becomes a stage of its own in front of every "map_views", whi
 carries the views listed per round and timed cycle ("views_listed_per_round").
 --link RANGE[,RANGE..] (with --views) adds "link": for every RANGE the closed loop of --views from views that are all unknown with
 Fleet.link(RANGE) between sensing and the replan (sense -> link -> replan -> 5 ticks), "link_groups" and "link_merge" fenced as stages of
-their own; the passes, the groups (roots), the linked pairs and whether the labels settled in the last timed cycle; and, fenced the same
+their own; the passes, the groups (roots), the linked pairs and whether the labels settled in the last timed cycle (--link-los: the link
+stage of that loop is Fleet.link(RANGE, los=True), walls block a link, and "los" records side by side, on the fleet as the last timed cycle
+left it, the groups stage of the plain link and of the link with a line of sight in ms with their spread, and the groups, linked pairs
+and blocked pairs of both); and, fenced the same
 way in the same run, a device-to-device copy of the views' bytes ("views_copy_ms": the yardstick of the merge) with the ratio of the two.
 --explore R_MAX (with --views) adds "explore": the closed loop of --views from views that are all unknown, with headings, and
 Fleet.explore(R_MAX) between sensing and the replan (sense -> explore -> replan -> 5 ticks): "frontier_goals" (want = reached: the steady
@@ -102,7 +105,7 @@ Fleet.explore_far_team(BLOCK, R_SPREAD, G, H, M, C, passes=P, after=...) in thei
 "far_team_goals" and "far_team_set_goals", and under "far_team" the launch with every vehicle wanted and nobody skipped as
 "far_team_goals_all_ms" beside "far_spread_goals_all_beside_ms" and "far_gain_goals_all_beside_ms" of the same call (medians of five), the
 same launch with 1, 8 and 64 passes, the cost of an idle pass from the last two, and what the claims covered and removed.
-    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..]] [--explore R_MAX [--far BLOCK [--far-gain G [--far-hop-cost H] [--far-min-gain M]] [--far-spread R_SPREAD [--passes P]] [--far-claim-blocks C]] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
+    usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..] [--link-los]] [--explore R_MAX [--far BLOCK [--far-gain G [--far-hop-cost H] [--far-min-gain M]] [--far-spread R_SPREAD [--passes P]] [--far-claim-blocks C]] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
                                          [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
 import json
@@ -122,6 +125,7 @@ AUDIT = "--audit" in sys.argv
 SEPARATION = "--separation" in sys.argv
 LISTED_VIEWS = "--listed-views" in sys.argv
 LINK = [float(r) for r in sys.argv[sys.argv.index("--link") + 1].split(",")] if "--link" in sys.argv else []
+LINK_LOS = "--link-los" in sys.argv   # with --views --link: walls block a link (include/fasterhip_link_los.h)
 EXPLORE = float(sys.argv[sys.argv.index("--explore") + 1]) if "--explore" in sys.argv else None
 REACH = "--reach" in sys.argv
 if REACH and not ("--views" in sys.argv and EXPLORE is not None):
@@ -276,10 +280,10 @@ def check_cycles(fl, cycles):
             "first_kind_1_last": int((rec["first_kind"] == 1).sum()), "separation_count_0_ms": float(np.median(ms))}
 
 
-def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False, traffic=False, link=None):
+def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False, traffic=False, link=None, los=False):
     """`cycles` cycles, every stage fenced by events: {stage: [ms]} (with r_sense: sensing first, as a stage of its own; fov: forward;
     observe: Fleet.observe after it, as another; traffic: Fleet.traffic after that; link: the two stages of Fleet.link(link) after those)."""
-    linked = fl.link_stages(link) if link else []
+    linked = fl.link_stages(link, los=los) if link else []
     names = ((["sense"] if r_sense else []) + (["observe"] if observe else []) + (["traffic"] if traffic else []) + [n for n, _ in linked]
              + [n for n, _ in fl.stages()] + ["next_goals"])
     per = {n: [] for n in names}
@@ -314,8 +318,32 @@ def timed_cycles(fl, cycles, r_sense=None, fov=None, observe=False, traffic=Fals
     return {n: float(np.median(v)) for n, v in per.items()}
 
 
-def sensing_loop(fl, views, cycles, states, goals, r_sense, fov=None, link=None):
-    """The closed loop from views that are all unknown: the first look, then sense -> [link ->] replan -> 5 ticks in steady state."""
+def link_side_by_side(fl, r, cycles):
+    """On the fleet as the last timed cycle left it: the groups stage of Fleet.link(r) and of Fleet.link(r, los=True), one after the other
+    `cycles` times (at least 5), each fenced by events: the medians and the spread of both in ms, and what each found."""
+    stages = [fl.link_stages(r)[0], fl.link_stages(r, los=True)[0]]
+    ms, info = {n: [] for n, _ in stages}, {}
+    for _ in range(max(cycles, 5)):
+        for name, launch in stages:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(fl.stream)
+            launch()
+            e1.record(fl.stream)
+            fl.sync()
+            ms[name].append(e0.elapsed_time(e1))
+            info[name] = fl.link_records()[1]
+    plain, los = info["link_groups"], info["link_groups_los"]
+    out = {"groups": int(plain[1]), "groups_los": int(los[1]), "linked_pairs": int(plain[2]), "linked_pairs_los": int(los[2]),
+           "blocked_pairs": int(los[3]), "changed_last_pass_los": int(los[0])}
+    for name, v in ms.items():
+        out[name + "_ms"] = float(np.median(v))
+        out[name + "_ms_min_max"] = [float(min(v)), float(max(v))]
+    return out
+
+
+def sensing_loop(fl, views, cycles, states, goals, r_sense, fov=None, link=None, los=False):
+    """The closed loop from views that are all unknown: the first look, then sense -> [link ->] replan -> 5 ticks in steady state
+    (los: walls block a link, Fleet.link(link, los=True))."""
     views.fill_(1)
     fl.init(states, goals)
     if fov is not None:
@@ -328,18 +356,18 @@ def sensing_loop(fl, views, cycles, states, goals, r_sense, fov=None, link=None)
     fl.sync()
     first = e0.elapsed_time(e1)
     if link:
-        fl.link(link)
+        fl.link(link, los=los)
     fl.replan()
     fl.next_goals(5)
     fl.sync()
-    med = timed_cycles(fl, cycles, r_sense, fov, link=link)
+    med = timed_cycles(fl, cycles, r_sense, fov, link=link, los=los)
     t = []
     for _ in range(cycles):
         fl.sync()
         t0 = time.perf_counter()
         fl.sense(r_sense, fov=fov)
         if link:
-            fl.link(link)
+            fl.link(link, los=los)
         fl.replan()
         fl.next_goals(5)
         fl.sync()
@@ -756,10 +784,14 @@ def views_cycles(B, cycles, p, world, r_sense, staging, fov=None):
         if LINK:
             out["link"] = {"passes": abi.FH_LINK_DEFAULT_PASSES, "ranges": {}}
             for r in LINK:
-                _, loop = sensing_loop(fl, views, cycles, states, goals, r_sense, link=r)
+                _, loop = sensing_loop(fl, views, cycles, states, goals, r_sense, link=r, los=LINK_LOS)
                 labels, info = fl.link_records()
+                groups_stage = "link_groups_los" if LINK_LOS else "link_groups"
                 loop.update({"changed_last_pass": int(info[0]), "groups": int(info[1]), "linked_pairs": int(info[2]),
-                             "largest_group": int(np.bincount(labels).max()), "link_ms": loop["stages_ms"]["link_groups"] + loop["stages_ms"]["link_merge"]})
+                             "largest_group": int(np.bincount(labels).max()), "link_ms": loop["stages_ms"][groups_stage] + loop["stages_ms"]["link_merge"]})
+                if LINK_LOS:
+                    loop["blocked_pairs"] = int(info[3])
+                    loop["los"] = link_side_by_side(fl, r, cycles)
                 out["link"]["ranges"]["%g" % r] = loop
             # the yardstick of the merge: the views' bytes copied device to device on the fleet's stream, fenced the same way
             other, ms = torch.empty_like(views), []
@@ -959,6 +991,8 @@ def main():
     if "--link" in argv:         # (read into LINK above)
         k = argv.index("--link")
         del argv[k:k + 2]
+    if "--link-los" in argv:     # (read into LINK_LOS above)
+        argv.remove("--link-los")
     if "--explore" in argv:      # (read into EXPLORE above)
         k = argv.index("--explore")
         del argv[k:k + 2]
