@@ -609,21 +609,29 @@ class Map:
         self._check(lib().fh_map_frontier_goals_device(self._h, abi.ptr(p), None if g is None else abi.ptr(g), d_flags, int(view_stride), d_view_of,
                                                        int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records), "fh_map_frontier_goals_device")
 
+    def _goals(self, symbol, name, par, grid, stream, *middle):
+        """What the ten *_goals_device below share: `par` as one abi.<name>_params_dtype record, `grid` (the views') as a record or a null
+        pointer, this map's lattice (fh_map_dims) and bits (fh_map_occupancy_bits_device) as the record and the pointer the entry point
+        takes, the call of `symbol` with `middle` behind them, and its error.  Called through the class: a `par` of the wrong dtype is
+        refused before anything of `self` is looked at."""
+        p = _one_record(par, name, name + "_goals_device")
+        g = _grid_record(grid)
+        dims, origin = self.dims()
+        bits, res = ctypes.c_void_p(), ctypes.c_double()
+        L = lib()
+        self._check(L.fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
+        mg = _grid_record((origin, res.value, dims))
+        rc = getattr(L, symbol)(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), *middle)
+        if rc != 0:
+            raise FasterHipError("%s: rc=%d" % (symbol, rc))
+
     def reach_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_goals, d_mask, d_records, stream):
         """fh_reach_goals_device (include/fasterhip_reach.h) with this map's lattice and bits (fh_map_dims,
         fh_map_occupancy_bits_device): frontier_goals_device, but of the candidates the one that a flood of known free space from the
         vehicle's voxel reaches in the fewest steps, and never one it does not reach.  d_records [n] abi.reach_record_dtype; par: one
         abi.reach_params_dtype record; `stream`: the stream the map was filled on (an integer handle, 0 or None: the default stream)."""
-        p = _one_record(par, "reach", "reach_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_reach_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                         d_view_of, int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records)
-        if rc != 0:
-            raise FasterHipError("fh_reach_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_reach_goals_device", "reach", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_vehicles, int(n),
+                         d_goals, d_mask, d_records)
 
     def spread_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_group, d_vehicles, n, d_work, work_bytes, d_goals, d_mask,
                             d_records, stream):
@@ -632,32 +640,16 @@ class Map:
         is not chosen.  Peers: the vehicles with equal d_group[view] (d_group [n_views] int32, None: the view itself).  d_work:
         work_bytes >= fh_spread_work_bytes(n) of device memory; d_records [n] abi.spread_record_dtype; par: one
         abi.spread_params_dtype record; `stream` as for reach_goals_device."""
-        p = _one_record(par, "spread", "spread_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_spread_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                          d_view_of, int(n_views), d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
-        if rc != 0:
-            raise FasterHipError("fh_spread_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_spread_goals_device", "spread", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_group, d_vehicles,
+                         int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
 
     def gain_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_goals, d_mask, d_records, stream):
         """fh_gain_goals_device (include/fasterhip_gain.h) with this map's lattice and bits: reach_goals_device, but of the candidates
         the flood reaches the one with the largest gain - hop_cost * hops, the gain being the unknown voxels of the vehicle's box within
         par["gain_radius"] voxels of the candidate; a candidate with a gain below par["min_gain"] is never chosen.  d_records [n]
         abi.gain_record_dtype; par: one abi.gain_params_dtype record; `stream` as for reach_goals_device."""
-        p = _one_record(par, "gain", "gain_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_gain_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                        d_view_of, int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records)
-        if rc != 0:
-            raise FasterHipError("fh_gain_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_gain_goals_device", "gain", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_vehicles, int(n),
+                         d_goals, d_mask, d_records)
 
     def team_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_group, d_vehicles, n, d_work, work_bytes, d_goals, d_mask,
                           d_records, stream):
@@ -665,16 +657,8 @@ class Map:
         spread_goals_device's passes — a candidate nearer than par["r_spread"] to a peer's claim is not chosen, and the unknown voxels
         within par["claim_radius"] voxels of a claim's voxel are counted in no gain.  The arguments are spread_goals_device's, with
         d_records [n] abi.team_record_dtype and par one abi.team_params_dtype record; d_work: work_bytes >= fh_spread_work_bytes(n)."""
-        p = _one_record(par, "team", "team_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_team_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                        d_view_of, int(n_views), d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
-        if rc != 0:
-            raise FasterHipError("fh_team_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_team_goals_device", "team", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_group, d_vehicles,
+                         int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
 
     def bid_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_group, d_vehicles, n, d_work, work_bytes, d_goals, d_mask,
                          d_records, stream):
@@ -682,16 +666,8 @@ class Map:
         are ordered by bids — every undecided vehicle offers its best candidate under the claims so far, an offer that beats every
         undecided rival's is final, the others search again.  The arguments are team_goals_device's, with d_records [n]
         abi.bid_record_dtype and par one abi.bid_params_dtype record; d_work: work_bytes >= fh_bid_work_bytes(n)."""
-        p = _one_record(par, "bid", "bid_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_bid_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                       d_view_of, int(n_views), d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
-        if rc != 0:
-            raise FasterHipError("fh_bid_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_bid_goals_device", "bid", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_group, d_vehicles, int(n),
+                         d_work, int(work_bytes), d_goals, d_mask, d_records)
 
     def far_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_vehicles, n, d_work, work_bytes, d_goals, d_mask,
                          d_records, stream):
@@ -699,16 +675,8 @@ class Map:
         (d_skip [n] int32, the mask another chooser wrote; None: nobody is skipped) the nearest frontier of its WHOLE view that a flood
         over blocks of par["block"] voxels an edge reaches.  d_work: work_bytes >= fh_far_work_bytes(grid, block, n_views) of device
         memory; d_records [n] abi.far_record_dtype; par: one abi.far_params_dtype record; `stream` as for reach_goals_device."""
-        p = _one_record(par, "far", "far_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_far_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                       d_view_of, int(n_views), d_skip, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
-        if rc != 0:
-            raise FasterHipError("fh_far_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_far_goals_device", "far", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_skip, d_vehicles, int(n),
+                         d_work, int(work_bytes), d_goals, d_mask, d_records)
 
     def far_spread_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_group, d_vehicles, n, d_work, work_bytes,
                                 d_goals, d_mask, d_records, stream):
@@ -717,17 +685,8 @@ class Map:
         is no target.  Peers: the vehicles with equal d_group[view] (d_group [n_views] int32, None: the view itself).  d_work: work_bytes
         >= fh_apart_work_bytes(grid, block, n_views, n) of device memory; d_records [n] abi.far_spread_record_dtype; par: one
         abi.far_spread_params_dtype record; `stream` as for reach_goals_device."""
-        p = _one_record(par, "far_spread", "far_spread_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_apart_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                              d_view_of, int(n_views), d_skip, d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals,
-                                              d_mask, d_records)
-        if rc != 0:
-            raise FasterHipError("fh_apart_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_apart_goals_device", "far_spread", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_skip, d_group,
+                         d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
 
     def far_gain_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_vehicles, n, d_work, work_bytes, d_goals,
                               d_mask, d_records, stream):
@@ -736,17 +695,8 @@ class Map:
         target blocks of ALL levels of the flood the one with the largest gain - par["hop_cost"] * hops is taken; a block whose gain is
         below par["min_gain"] never is.  d_work: work_bytes >= fh_prospect_work_bytes(grid, block, n_views) of device memory; d_records
         [n] abi.far_gain_record_dtype; par: one abi.far_gain_params_dtype record; `stream` as for reach_goals_device."""
-        p = _one_record(par, "far_gain", "far_gain_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_prospect_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                            d_view_of, int(n_views), d_skip, d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask,
-                                            d_records)
-        if rc != 0:
-            raise FasterHipError("fh_prospect_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_prospect_goals_device", "far_gain", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_skip,
+                         d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
 
     def far_team_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_group, d_vehicles, n, d_work, work_bytes,
                               d_goals, d_mask, d_records, stream):
@@ -755,33 +705,16 @@ class Map:
         cube of 2 par["claim_blocks"] - 1 blocks an edge around its block from every gain of the vehicle.  d_work: work_bytes >=
         fh_stake_work_bytes(grid, block, n_views, n) of device memory; d_records [n] abi.far_team_record_dtype; par: one
         abi.far_team_params_dtype record; `stream` as for reach_goals_device."""
-        p = _one_record(par, "far_team", "far_team_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_stake_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                         d_view_of, int(n_views), d_skip, d_group, d_vehicles, int(n), d_work, int(work_bytes), d_goals,
-                                         d_mask, d_records)
-        if rc != 0:
-            raise FasterHipError("fh_stake_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_stake_goals_device", "far_team", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_skip, d_group,
+                         d_vehicles, int(n), d_work, int(work_bytes), d_goals, d_mask, d_records)
 
     def sight_goals_device(self, par, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, n, d_goals, d_mask, d_records, stream):
         """fh_sight_goals_device (include/fasterhip_sight.h) with this map's lattice and bits: gain_goals_device with a gain that counts an
         unknown voxel of the ball only if the straight line of voxels from the candidate to it crosses no voxel that is known and
         occupied in this map (or outside it).  d_records [n] abi.sight_record_dtype; par: one abi.sight_params_dtype record; `stream` as
         for reach_goals_device."""
-        p = _one_record(par, "sight", "sight_goals_device")
-        g = _grid_record(grid)
-        dims, origin = self.dims()
-        bits, res = ctypes.c_void_p(), ctypes.c_double()
-        self._check(lib().fh_map_occupancy_bits_device(self._h, ctypes.byref(bits), ctypes.byref(res)), "fh_map_occupancy_bits_device")
-        mg = _grid_record((origin, res.value, dims))
-        rc = lib().fh_sight_goals_device(stream, abi.ptr(p), abi.ptr(mg), bits, None if g is None else abi.ptr(g), d_flags, int(view_stride),
-                                         d_view_of, int(n_views), d_vehicles, int(n), d_goals, d_mask, d_records)
-        if rc != 0:
-            raise FasterHipError("fh_sight_goals_device: rc=%d" % rc)
+        Map._goals(self, "fh_sight_goals_device", "sight", par, grid, stream, d_flags, int(view_stride), d_view_of, int(n_views), d_vehicles, int(n),
+                         d_goals, d_mask, d_records)
 
     def view_coverage_device(self, grid, d_flags, view_stride, n_views, d_out):
         """fh_map_view_coverage_device: d_out [n_views] abi.view_coverage_dtype, the known voxels (flag 0) of every view and those of

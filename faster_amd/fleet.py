@@ -77,13 +77,50 @@ that has arrived takes a new goal (set_goals: YAWING, then TRAVELING), and sense
 The host restatement every cycle is checked against is fhreplan::Planner (faster_amd/host/replan_stub.hpp);
 tests/test_gpu_fleet.py and tests/test_gpu_fleet_views.py compare the two cycle by cycle.
 """
+from collections import namedtuple
+from operator import attrgetter
+
 import numpy as np
 
 from . import abi, capi
 
 
+# A frontier chooser, as far as the host layer can tell it from the others (DESIGN.md 1a).  name: in d_<name>_goals, _mask, _records, _work,
+# _<name>_work_key and <name>_records(); method: the public method, in messages; dtype: a record; call: the Map method; stage: the name of
+# its launch; view_of: the attribute that holds the all-zero view_of of set_unknown's one grid; stream: whether `call` takes the stream;
+# work: the library's workspace-bytes function (None: no workspace) and key: what a workspace is reallocated for (None: its size depends
+# on n alone, it is allocated once, with the outputs); skip, labels: whether `call` takes the mask of an earlier chooser and group labels.
+_Chooser = namedtuple("_Chooser", "name method dtype call stage view_of stream work key skip labels")
+_LATTICE = ("dims", "block", "n_views")
+
+
 class Fleet:
     """N vehicles, one map, one context.  Buffers are torch tensors on `device`; everything runs on the fleet's own stream."""
+
+    CHOOSERS = {c.name: c for c in (
+        _Chooser("explore", "explore", abi.frontier_record_dtype, "frontier_goals_device", "frontier_goals", "d_explore_view_of", False,
+                 None, None, False, False),
+        _Chooser("reach", "explore_reachable", abi.reach_record_dtype, "reach_goals_device", "reach_goals", "d_reach_view_of", True,
+                 None, None, False, False),
+        _Chooser("spread", "explore_spread", abi.spread_record_dtype, "spread_goals_device", "spread_goals", "d_reach_view_of", True,
+                 "fh_spread_work_bytes", None, False, True),
+        _Chooser("gain", "explore_gain", abi.gain_record_dtype, "gain_goals_device", "gain_goals", "d_reach_view_of", True,
+                 None, None, False, False),
+        _Chooser("team", "explore_team", abi.team_record_dtype, "team_goals_device", "team_goals", "d_reach_view_of", True,
+                 "fh_spread_work_bytes", None, False, True),
+        _Chooser("sight", "explore_sight", abi.sight_record_dtype, "sight_goals_device", "sight_goals", "d_reach_view_of", True,
+                 None, None, False, False),
+        _Chooser("bid", "explore_bid", abi.bid_record_dtype, "bid_goals_device", "bid_goals", "d_reach_view_of", True,
+                 "fh_bid_work_bytes", None, False, True),
+        _Chooser("far", "explore_far", abi.far_record_dtype, "far_goals_device", "far_goals", "d_reach_view_of", True,
+                 "fh_far_work_bytes", _LATTICE, True, False),
+        _Chooser("far_spread", "explore_far_spread", abi.far_spread_record_dtype, "far_spread_goals_device", "far_spread_goals",
+                 "d_reach_view_of", True, "fh_apart_work_bytes", _LATTICE + ("n",), True, True),
+        _Chooser("far_gain", "explore_far_gain", abi.far_gain_record_dtype, "far_gain_goals_device", "far_gain_goals", "d_reach_view_of", True,
+                 "fh_prospect_work_bytes", _LATTICE, True, False),
+        _Chooser("far_team", "explore_far_team", abi.far_team_record_dtype, "far_team_goals_device", "far_team_goals", "d_reach_view_of", True,
+                 "fh_stake_work_bytes", _LATTICE + ("n",), True, True),
+    )}
 
     def __init__(self, n, params=None, device=0, n_seg=6, max_poly=3, max_points=32, faces_per_problem=192, max_states=1024, dc=0.01,
                  v_max=5.0, a_max=5.0, j_max=8.0, decomp_radius=0.05, dist_max_vertexes=1.5, local_bbox=(2.0, 2.0, 1.0), z_ground=0.0,
@@ -134,18 +171,10 @@ class Fleet:
         self.round_retries, self.round_fixed = 0, False
         self.listed_views, self._views_full, self.d_view_list, self.d_view_count = False, True, None, None   # enable_listed_views
         self.d_link_labels = self.d_link_info = None                                                           # link
-        self.d_explore_goals = self.d_explore_mask = self.d_explore_records = self.d_explore_view_of = self.d_coverage = None   # explore, coverage
-        self.d_reach_goals = self.d_reach_mask = self.d_reach_records = self.d_reach_view_of = None                            # explore_reachable
-        self.d_spread_goals = self.d_spread_mask = self.d_spread_records = self.d_spread_work = None                           # explore_spread
-        self.d_gain_goals = self.d_gain_mask = self.d_gain_records = None                                                      # explore_gain
-        self.d_team_goals = self.d_team_mask = self.d_team_records = self.d_team_work = None                                   # explore_team
-        self.d_sight_goals = self.d_sight_mask = self.d_sight_records = None                                                   # explore_sight
-        self.d_bid_goals = self.d_bid_mask = self.d_bid_records = self.d_bid_work = None                                       # explore_bid
-        self.d_far_goals = self.d_far_mask = self.d_far_records = self.d_far_work = self._far_work_key = None                  # explore_far
-        self.d_far_spread_goals = self.d_far_spread_mask = self.d_far_spread_records = None                                    # explore_far_spread
-        self.d_far_spread_work = self._far_spread_work_key = None
-        self.d_far_gain_goals = self.d_far_gain_mask = self.d_far_gain_records = self.d_far_gain_work = self._far_gain_work_key = None   # explore_far_gain
-        self.d_far_team_goals = self.d_far_team_mask = self.d_far_team_records = self.d_far_team_work = self._far_team_work_key = None   # explore_far_team
+        self.d_coverage = self.d_explore_view_of = self.d_reach_view_of = None   # coverage; set_unknown's one grid as a view: explore, the others
+        for ch in self.CHOOSERS.values():   # explore .. explore_far_team: d_<name>_goals, _mask, _records, _work and _<name>_work_key
+            for attr in ("d_%s_goals", "d_%s_mask", "d_%s_records") + (("d_%s_work",) if ch.work else ()) + (("_%s_work_key",) if ch.key else ()):
+                setattr(self, attr % ch.name, None)
         torch.cuda.synchronize(self.dev)
 
     def close(self):
@@ -601,21 +630,146 @@ class Fleet:
         return self.d_link_labels.cpu().numpy().copy(), self.d_link_info.cpu().numpy().copy()
 
     _EXPLORE_WANT = {"reached": abi.FH_FRONTIER_WANT_REACHED, "no_path": abi.FH_FRONTIER_WANT_NO_PATH, "all": abi.FH_FRONTIER_WANT_ALL}
+    _FAR_AFTER = {"explore": "d_explore_mask", "reachable": "d_reach_mask", "spread": "d_spread_mask", "gain": "d_gain_mask",
+                  "sight": "d_sight_mask", "team": "d_team_mask", "bid": "d_bid_mask"}
 
-    def _explore_views(self):
-        """(flags tensor, view_stride, view_of pointer or None, n_views) of the frontier entry points: the views, or set_unknown's one
-        grid as a single view that every vehicle reads (an all-zero view_of)."""
+    # ---- what the frontier choosers share (CHOOSERS above says where they differ) ----
+    def _zeros(self, specs):
+        """A zeroed device tensor per (shape, name of the dtype), allocated on the fleet's stream, which is then recorded on each."""
+        t = self.torch
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            made = [t.zeros(shape, dtype=getattr(t, dtype), device=self.dev) for shape, dtype in specs]
+        for d in made:
+            d.record_stream(self.stream)
+        return made
+
+    def _chooser_views(self, who, view_of):
+        """(flags tensor, view_stride, view_of pointer or None, n_views) of the choosers' entry points: the views, or set_unknown's one
+        grid as a single view that every vehicle reads (an all-zero view_of, kept in the attribute `view_of` names)."""
         if self.view_flags is not None:
             return self.view_flags, int(self.view_flags.shape[1]), (None if self.view_of is None else self.view_of.data_ptr()), self.n_views
         if self.flags is None:
-            raise capi.FasterHipError("Fleet.explore: set_unknown_views (or set_unknown) first")
-        t = self.torch
-        if self.d_explore_view_of is None:
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_explore_view_of = t.zeros(self.n, dtype=t.int32, device=self.dev)
-            self.d_explore_view_of.record_stream(self.stream)
-        return self.flags, int(self.flags.numel()), self.d_explore_view_of.data_ptr(), 1
+            raise capi.FasterHipError("Fleet.%s: set_unknown_views (or set_unknown) first" % who)
+        if getattr(self, view_of) is None:
+            setattr(self, view_of, self._zeros([(self.n, "int32")])[0])
+        return self.flags, int(self.flags.numel()), getattr(self, view_of).data_ptr(), 1
+
+    def _explore_views(self):
+        return self._chooser_views("explore", "d_explore_view_of")
+
+    def _chooser_inputs(self, ch, par, r_avoid, z, want, max_hops=None):
+        """What the choosers share before anything is allocated: the preconditions, raised in the name of the chooser's method; the
+        views (_chooser_views); and the fields that all their params have in common, written into `par` (max_hops: but for
+        fh_frontier_params)."""
+        if self.cloud is None or self.map_args is None:
+            raise capi.FasterHipError("Fleet.%s: set_map first" % ch.method)
+        views = self._chooser_views(ch.method, ch.view_of)
+        wants = (want,) if isinstance(want, str) else tuple(want)
+        if not wants or any(w not in self._EXPLORE_WANT for w in wants):
+            raise capi.FasterHipError("Fleet.%s: want is \"reached\", \"no_path\", \"all\" or a tuple of them, got %r" % (ch.method, want))
+        if "reached" in wants and self.d_headings is None:
+            raise capi.FasterHipError("Fleet.%s: want=\"reached\" needs enable_heading first (a vehicle that takes a new goal "
+                                      "after GOAL_REACHED is YAWING until next_goals with headings has turned it)" % ch.method)
+        par["r_avoid"] = float(self.params["goal_radius"]) if r_avoid is None else r_avoid
+        par["z_lo"], par["z_hi"] = (self.z_ground, self.map_args[3]) if z is None else z
+        par["want"] = 0
+        for w in wants:
+            par["want"] |= self._EXPLORE_WANT[w]
+        if max_hops is not None:
+            par["max_hops"] = max_hops
+        return views
+
+    def _check_groups(self, ch, groups):
+        if groups not in ("link", "view"):
+            raise capi.FasterHipError("Fleet.%s: groups is \"link\" or \"view\", got %r" % (ch.method, groups))
+
+    def _far_skip(self, ch, after):
+        """The mask of the chooser `after` names (None: nobody is skipped)."""
+        if after is None:
+            return None
+        if after not in self._FAR_AFTER:
+            raise capi.FasterHipError("Fleet.%s: after is None or one of %s, got %r" % (ch.method, ", ".join(sorted(self._FAR_AFTER)), after))
+        skip = getattr(self, self._FAR_AFTER[after])
+        if skip is None:
+            raise capi.FasterHipError("Fleet.%s: after=%r, but that chooser has not run" % (ch.method, after))
+        return skip
+
+    def _far_work_bytes(self, ch, block, n_views, max_words):
+        """The bytes of a far chooser's workspace on the fleet's lattice; 0 from the library is a block it refuses."""
+        g = capi._grid_record(self.grid)
+        args = (abi.ptr(g), int(block), int(n_views)) + ((int(self.n),) if "n" in ch.key else ())
+        work_bytes = int(getattr(capi.lib(), ch.work)(*args))
+        if work_bytes == 0:
+            raise capi.FasterHipError("Fleet.%s: block must be 1 .. 16 and the blocks of the lattice must fit %d words of 64 "
+                                      "(got block %r on a lattice of %s)" % (ch.method, max_words, block, tuple(int(d) for d in self.grid[2])))
+        return work_bytes
+
+    def _chooser_buffers(self, ch, n_views, work_bytes, block):
+        """Goals, mask and records of a chooser, allocated once; a workspace without a key with them; a workspace with a key whenever
+        the key (the lattice, the block, the number of views and, for a team, of vehicles) is not the one it was allocated for."""
+        goals, mask, records, work = ("d_%s_%s" % (ch.name, w) for w in ("goals", "mask", "records", "work"))
+        if getattr(self, goals) is None:
+            names = [goals, mask, records] + ([work] if ch.work and not ch.key else [])
+            specs = [((self.n, 3), "float64"), (self.n, "int32"), (self.n * ch.dtype.itemsize, "uint8"), (work_bytes, "uint8")]
+            for name, d in zip(names, self._zeros(specs[:len(names)])):
+                setattr(self, name, d)
+        if ch.key:
+            key = (tuple(int(d) for d in self.grid[2]), int(block), int(n_views)) + ((int(self.n),) if "n" in ch.key else ())
+            if getattr(self, "_%s_work_key" % ch.name) != key:
+                setattr(self, work, self._zeros([(work_bytes, "uint8")])[0])
+                setattr(self, "_%s_work_key" % ch.name, key)
+
+    def _chooser_stages(self, ch, par, views, work_bytes=None, block=None, skip=None, groups=None):
+        """The two launches of a chooser, in order: [(stage, callable), ("set_goals", callable)].  Allocates what is missing; the
+        launches read the fleet's buffers when they run."""
+        flags, stride, vo, n_views = views
+        if ch.work and not ch.key:
+            work_bytes = int(getattr(capi.lib(), ch.work)(self.n))
+        self._chooser_buffers(ch, n_views, work_bytes, block)
+        # the labels are per view: with set_unknown's single view there is nothing to label
+        labels = self.d_link_labels if ch.labels and groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
+            and self.d_link_labels.numel() == n_views else None
+        goals, mask, records, work = ("d_%s_%s" % (ch.name, w) for w in ("goals", "mask", "records", "work"))
+        # what a launch does is what the host pays per period: the methods are bound here, the fleet's own buffers are fetched in one
+        # attrgetter when the launch runs, and the pointers of `skip` and `labels` (None: a null pointer) are asked for then, too
+        call, set_goals = getattr(self.map, ch.call), self.ctx.fleet_set_goals_device
+        fetch, chosen = attrgetter("d_vehicles", *([work] if ch.work else []), goals, mask, records), attrgetter("d_vehicles", goals, mask)
+        if ch.work:   # (a workspace comes with skip, labels or both, and with the stream)
+            takes_skip, takes_labels = ch.skip, ch.labels
+            skip_ptr, labels_ptr = (x if x is None else x.data_ptr for x in (skip, labels))
+
+            def choose():
+                v, w, g, k, r = fetch(self)
+                call(par, self.grid, flags.data_ptr(), stride, vo, n_views, *((skip_ptr and skip_ptr(),) if takes_skip else ()),
+                     *((labels_ptr and labels_ptr(),) if takes_labels else ()), v.data_ptr(), self.n, w.data_ptr(), work_bytes, g.data_ptr(),
+                     k.data_ptr(), r.data_ptr(), self.stream.cuda_stream)
+        else:
+            stream = (lambda: (self.stream.cuda_stream,)) if ch.stream else tuple   # (frontier_goals_device: the map's own stream)
+
+            def choose():
+                v, g, k, r = fetch(self)
+                call(par, self.grid, flags.data_ptr(), stride, vo, n_views, v.data_ptr(), self.n, g.data_ptr(), k.data_ptr(), r.data_ptr(), *stream())
+
+        def apply():
+            v, g, k = chosen(self)
+            set_goals(self.params, v.data_ptr(), g.data_ptr(), k.data_ptr(), self.n)
+
+        return [(ch.stage, choose), ("set_goals", apply)]
+
+    def _run(self, stages):
+        self._follow_current()
+        for _, launch in stages:
+            launch()
+
+    def _chooser_records(self, ch):
+        """(records [n] ch.dtype, goals [n][3], mask [n] int32) of the chooser's last run (synchronises)."""
+        goals = getattr(self, "d_%s_goals" % ch.name)
+        if goals is None:
+            raise capi.FasterHipError("Fleet.%s_records: %s first" % (ch.name, ch.method))
+        self.sync()
+        return (getattr(self, "d_%s_records" % ch.name).cpu().numpy().view(ch.dtype).copy(), goals.cpu().numpy().copy(),
+                getattr(self, "d_%s_mask" % ch.name).cpu().numpy().copy())
 
     def explore(self, r_max, r_avoid=None, z=None, want="reached"):
         """The wanted vehicles take the nearest frontier voxel of their view as terminal goal (include/fasterhip_frontier.h): a voxel the
@@ -626,52 +780,17 @@ class Fleet:
         that mask; a vehicle without a candidate keeps goal and status.  After sense(), observe() and link(), before replan(); needs
         set_map and set_unknown_views (set_unknown's one grid counts as a single view of all vehicles), and, for "reached",
         enable_heading: a vehicle that set_goals made YAWING leaves that status only in next_goals with headings."""
-        stages = self.explore_stages(r_max, r_avoid, z, want)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_stages(r_max, r_avoid, z, want))   # (raises before anything is launched)
 
     def explore_stages(self, r_max, r_avoid=None, z=None, want="reached"):
         """The two launches of explore(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
-        if self.cloud is None or self.map_args is None:
-            raise capi.FasterHipError("Fleet.explore: set_map first")
-        flags, stride, vo, n_views = self._explore_views()
-        wants = (want,) if isinstance(want, str) else tuple(want)
-        if not wants or any(w not in self._EXPLORE_WANT for w in wants):
-            raise capi.FasterHipError("Fleet.explore: want is \"reached\", \"no_path\", \"all\" or a tuple of them, got %r" % (want,))
-        if "reached" in wants and self.d_headings is None:
-            raise capi.FasterHipError("Fleet.explore: want=\"reached\" needs enable_heading first (a vehicle that takes a new goal after "
-                                      "GOAL_REACHED is YAWING until next_goals with headings has turned it)")
+        ch = self.CHOOSERS["explore"]
         par = abi.default_frontier_params(r_max)
-        par["r_avoid"] = float(self.params["goal_radius"]) if r_avoid is None else r_avoid
-        par["z_lo"], par["z_hi"] = (self.z_ground, self.map_args[3]) if z is None else z
-        par["want"] = 0
-        for w in wants:
-            par["want"] |= self._EXPLORE_WANT[w]
-        if self.d_explore_goals is None:
-            t = self.torch
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_explore_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_explore_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_explore_records = t.zeros(self.n * abi.frontier_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-            for d in (self.d_explore_goals, self.d_explore_mask, self.d_explore_records):
-                d.record_stream(self.stream)
-        c, m, p = self.ctx, self.map, (lambda t: t.data_ptr())
-        return [
-            ("frontier_goals", lambda: m.frontier_goals_device(par, self.grid, p(flags), stride, vo, n_views, p(self.d_vehicles), self.n,
-                                                               p(self.d_explore_goals), p(self.d_explore_mask), p(self.d_explore_records))),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_explore_goals), p(self.d_explore_mask),
-                                                           self.n)),
-        ]
+        return self._chooser_stages(ch, par, self._chooser_inputs(ch, par, r_avoid, z, want))
 
     def explore_records(self):
         """(records [n] abi.frontier_record_dtype, goals [n][3], mask [n] int32) of the last explore() (synchronises)."""
-        if self.d_explore_goals is None:
-            raise capi.FasterHipError("Fleet.explore_records: explore first")
-        self.sync()
-        return (self.d_explore_records.cpu().numpy().view(abi.frontier_record_dtype).copy(), self.d_explore_goals.cpu().numpy().copy(),
-                self.d_explore_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["explore"])
 
     def explore_reachable(self, r_max, r_avoid=None, z=None, want="reached", max_hops=0):
         """explore() with the choice of include/fasterhip_reach.h: of the frontier voxels of explore() the one that a flood of the space
@@ -679,73 +798,17 @@ class Fleet:
         neighbours; then the smallest distance), and never one the flood does not reach: a voxel behind a wall or in a sealed pocket is
         not chosen, so the replan that follows is not spent on NO_PATH.  max_hops: the last level of the flood, 0 for no limit.  The
         other arguments, the preconditions and the two launches are those of explore(); the buffers are its own (reach_records())."""
-        stages = self.explore_reachable_stages(r_max, r_avoid, z, want, max_hops)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
-
-    def _reach_inputs(self, who, par, r_avoid, z, want, max_hops):
-        """What explore_reachable() and explore_spread() share: the preconditions, raised in the name `who`; the views as (flags tensor,
-        view_stride, view_of pointer or None, n_views); and the fields that fh_reach_params and fh_spread_params have in common,
-        written into `par`."""
-        if self.cloud is None or self.map_args is None:
-            raise capi.FasterHipError("Fleet.%s: set_map first" % who)
-        if self.view_flags is not None:
-            views = self.view_flags, int(self.view_flags.shape[1]), (None if self.view_of is None else self.view_of.data_ptr()), self.n_views
-        elif self.flags is None:
-            raise capi.FasterHipError("Fleet.%s: set_unknown_views (or set_unknown) first" % who)
-        else:   # set_unknown's one grid: a single view that every vehicle reads (an all-zero view_of)
-            if self.d_reach_view_of is None:
-                t = self.torch
-                self._follow_current()
-                with t.cuda.stream(self.stream):
-                    self.d_reach_view_of = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_reach_view_of.record_stream(self.stream)
-            views = self.flags, int(self.flags.numel()), self.d_reach_view_of.data_ptr(), 1
-        wants = (want,) if isinstance(want, str) else tuple(want)
-        if not wants or any(w not in self._EXPLORE_WANT for w in wants):
-            raise capi.FasterHipError("Fleet.%s: want is \"reached\", \"no_path\", \"all\" or a tuple of them, got %r" % (who, want))
-        if "reached" in wants and self.d_headings is None:
-            raise capi.FasterHipError("Fleet.%s: want=\"reached\" needs enable_heading first (a vehicle that takes a new goal "
-                                      "after GOAL_REACHED is YAWING until next_goals with headings has turned it)" % who)
-        par["r_avoid"] = float(self.params["goal_radius"]) if r_avoid is None else r_avoid
-        par["z_lo"], par["z_hi"] = (self.z_ground, self.map_args[3]) if z is None else z
-        par["want"], par["max_hops"] = 0, max_hops
-        for w in wants:
-            par["want"] |= self._EXPLORE_WANT[w]
-        return views
+        self._run(self.explore_reachable_stages(r_max, r_avoid, z, want, max_hops))   # (raises before anything is launched)
 
     def explore_reachable_stages(self, r_max, r_avoid=None, z=None, want="reached", max_hops=0):
         """The two launches of explore_reachable(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        ch = self.CHOOSERS["reach"]
         par = abi.default_reach_params(r_max)
-        flags, stride, vo, n_views = self._reach_inputs("explore_reachable", par, r_avoid, z, want, max_hops)
-        if self.d_reach_goals is None:
-            t = self.torch
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_reach_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_reach_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_reach_records = t.zeros(self.n * abi.reach_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-            for d in (self.d_reach_goals, self.d_reach_mask, self.d_reach_records):
-                d.record_stream(self.stream)
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("reach_goals", lambda: m.reach_goals_device(par, self.grid, p(flags), stride, vo, n_views, p(self.d_vehicles), self.n,
-                                                         p(self.d_reach_goals), p(self.d_reach_mask), p(self.d_reach_records),
-                                                         self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_reach_goals), p(self.d_reach_mask), self.n)),
-        ]
+        return self._chooser_stages(ch, par, self._chooser_inputs(ch, par, r_avoid, z, want, max_hops))
 
     def reach_records(self):
         """(records [n] abi.reach_record_dtype, goals [n][3], mask [n] int32) of the last explore_reachable() (synchronises)."""
-        if self.d_reach_goals is None:
-            raise capi.FasterHipError("Fleet.reach_records: explore_reachable first")
-        self.sync()
-        return (self.d_reach_records.cpu().numpy().view(abi.reach_record_dtype).copy(), self.d_reach_goals.cpu().numpy().copy(),
-                self.d_reach_mask.cpu().numpy().copy())
-
-    _FAR_AFTER = {"explore": "d_explore_mask", "reachable": "d_reach_mask", "spread": "d_spread_mask", "gain": "d_gain_mask",
-                  "sight": "d_sight_mask", "team": "d_team_mask", "bid": "d_bid_mask"}
+        return self._chooser_records(self.CHOOSERS["reach"])
 
     def explore_far(self, block=8, r_avoid=None, z=None, want="reached", max_hops=0, after=None):
         """The fallback behind the other choosers (include/fasterhip_far.h): a wanted vehicle takes the nearest frontier voxel of its
@@ -755,58 +818,20 @@ class Fleet:
         "sight", "team" or "bid"; the vehicles it gave a goal are skipped (None: nobody is).  block: 1 .. 16, and the blocks of the
         lattice must fit abi.FH_FAR_MAX_WORDS words of 64.  max_hops: the last level of the flood, 0 for no limit.  The other arguments,
         the preconditions and the errors are those of explore_reachable(); the buffers and the workspace are its own (far_records())."""
-        stages = self.explore_far_stages(block, r_avoid, z, want, max_hops, after)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_far_stages(block, r_avoid, z, want, max_hops, after))   # (raises before anything is launched)
 
     def explore_far_stages(self, block=8, r_avoid=None, z=None, want="reached", max_hops=0, after=None):
         """The two launches of explore_far(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        ch = self.CHOOSERS["far"]
         par = abi.default_far_params(block)
-        flags, stride, vo, n_views = self._reach_inputs("explore_far", par, r_avoid, z, want, max_hops)
-        skip = None
-        if after is not None:
-            if after not in self._FAR_AFTER:
-                raise capi.FasterHipError("Fleet.explore_far: after is None or one of %s, got %r" % (", ".join(sorted(self._FAR_AFTER)), after))
-            skip = getattr(self, self._FAR_AFTER[after])
-            if skip is None:
-                raise capi.FasterHipError("Fleet.explore_far: after=%r, but that chooser has not run" % (after,))
-        g = capi._grid_record(self.grid)
-        work_bytes = int(capi.lib().fh_far_work_bytes(abi.ptr(g), int(block), int(n_views)))
-        if work_bytes == 0:
-            raise capi.FasterHipError("Fleet.explore_far: block must be 1 .. 16 and the blocks of the lattice must fit %d words of 64 "
-                                      "(got block %r on a lattice of %s)" % (abi.FH_FAR_MAX_WORDS, block, tuple(int(d) for d in self.grid[2])))
-        t = self.torch
-        if self.d_far_goals is None:
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_far_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_far_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_far_records = t.zeros(self.n * abi.far_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-            for d in (self.d_far_goals, self.d_far_mask, self.d_far_records):
-                d.record_stream(self.stream)
-        key = (tuple(int(d) for d in self.grid[2]), int(block), int(n_views))
-        if self._far_work_key != key:   # (one workspace per lattice, block and number of views)
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_far_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
-            self.d_far_work.record_stream(self.stream)
-            self._far_work_key = key
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("far_goals", lambda: m.far_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if skip is None else p(skip),
-                                                     p(self.d_vehicles), self.n, p(self.d_far_work), work_bytes, p(self.d_far_goals),
-                                                     p(self.d_far_mask), p(self.d_far_records), self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_far_goals), p(self.d_far_mask), self.n)),
-        ]
+        views = self._chooser_inputs(ch, par, r_avoid, z, want, max_hops)
+        skip = self._far_skip(ch, after)
+        work_bytes = self._far_work_bytes(ch, block, views[3], abi.FH_FAR_MAX_WORDS)
+        return self._chooser_stages(ch, par, views, work_bytes, block, skip)
 
     def far_records(self):
         """(records [n] abi.far_record_dtype, goals [n][3], mask [n] int32) of the last explore_far() (synchronises)."""
-        if self.d_far_goals is None:
-            raise capi.FasterHipError("Fleet.far_records: explore_far first")
-        self.sync()
-        return (self.d_far_records.cpu().numpy().view(abi.far_record_dtype).copy(), self.d_far_goals.cpu().numpy().copy(),
-                self.d_far_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["far"])
 
     def explore_far_gain(self, block=8, gain_blocks=2, hop_cost=None, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0, after=None):
         """explore_far() with a gain (include/fasterhip_prospect.h): every block of the flood carries the number of its unknown voxels,
@@ -817,28 +842,16 @@ class Fleet:
         block * block, the voxels of one face of a block — a judgement, not a measurement.  min_gain: a target block with a smaller
         gain is poor and never taken (abi.FH_PROSPECT_ALL_POOR where every reachable one is).  after, block and the other arguments,
         the preconditions and the errors are explore_far()'s; the buffers and the workspace are its own (far_gain_records())."""
-        stages = self.explore_far_gain_stages(block, gain_blocks, hop_cost, min_gain, r_avoid, z, want, max_hops, after)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_far_gain_stages(block, gain_blocks, hop_cost, min_gain, r_avoid, z, want, max_hops, after))   # (raises before anything is launched)
 
     def explore_far_gain_stages(self, block=8, gain_blocks=2, hop_cost=None, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0,
                                 after=None):
         """The two launches of explore_far_gain(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        ch = self.CHOOSERS["far_gain"]
         par = abi.default_far_gain_params(block, gain_blocks)
-        flags, stride, vo, n_views = self._reach_inputs("explore_far_gain", par, r_avoid, z, want, max_hops)
-        skip = None
-        if after is not None:
-            if after not in self._FAR_AFTER:
-                raise capi.FasterHipError("Fleet.explore_far_gain: after is None or one of %s, got %r" % (", ".join(sorted(self._FAR_AFTER)), after))
-            skip = getattr(self, self._FAR_AFTER[after])
-            if skip is None:
-                raise capi.FasterHipError("Fleet.explore_far_gain: after=%r, but that chooser has not run" % (after,))
-        g = capi._grid_record(self.grid)
-        work_bytes = int(capi.lib().fh_prospect_work_bytes(abi.ptr(g), int(block), int(n_views)))
-        if work_bytes == 0:
-            raise capi.FasterHipError("Fleet.explore_far_gain: block must be 1 .. 16 and the blocks of the lattice must fit %d words of 64 "
-                                      "(got block %r on a lattice of %s)" % (abi.FH_PROSPECT_MAX_WORDS, block, tuple(int(d) for d in self.grid[2])))
+        views = self._chooser_inputs(ch, par, r_avoid, z, want, max_hops)
+        skip = self._far_skip(ch, after)
+        work_bytes = self._far_work_bytes(ch, block, views[3], abi.FH_PROSPECT_MAX_WORDS)
         if not 0 <= int(gain_blocks) <= abi.FH_PROSPECT_MAX_BLOCKS:
             raise capi.FasterHipError("Fleet.explore_far_gain: gain_blocks must be 0 .. %d, got %r" % (abi.FH_PROSPECT_MAX_BLOCKS, gain_blocks))
         if hop_cost is not None:
@@ -848,39 +861,11 @@ class Fleet:
         if int(min_gain) < 0:
             raise capi.FasterHipError("Fleet.explore_far_gain: min_gain must be >= 0, got %r" % (min_gain,))
         par["min_gain"] = int(min_gain)
-        t = self.torch
-        if self.d_far_gain_goals is None:
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_far_gain_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_far_gain_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_far_gain_records = t.zeros(self.n * abi.far_gain_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-            for d in (self.d_far_gain_goals, self.d_far_gain_mask, self.d_far_gain_records):
-                d.record_stream(self.stream)
-        key = (tuple(int(d) for d in self.grid[2]), int(block), int(n_views))
-        if self._far_gain_work_key != key:   # (one workspace per lattice, block and number of views)
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_far_gain_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
-            self.d_far_gain_work.record_stream(self.stream)
-            self._far_gain_work_key = key
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("far_gain_goals", lambda: m.far_gain_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if skip is None else p(skip),
-                                                               p(self.d_vehicles), self.n, p(self.d_far_gain_work), work_bytes,
-                                                               p(self.d_far_gain_goals), p(self.d_far_gain_mask), p(self.d_far_gain_records),
-                                                               self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_far_gain_goals), p(self.d_far_gain_mask),
-                                                           self.n)),
-        ]
+        return self._chooser_stages(ch, par, views, work_bytes, block, skip)
 
     def far_gain_records(self):
         """(records [n] abi.far_gain_record_dtype, goals [n][3], mask [n] int32) of the last explore_far_gain() (synchronises)."""
-        if self.d_far_gain_goals is None:
-            raise capi.FasterHipError("Fleet.far_gain_records: explore_far_gain first")
-        self.sync()
-        return (self.d_far_gain_records.cpu().numpy().view(abi.far_gain_record_dtype).copy(), self.d_far_gain_goals.cpu().numpy().copy(),
-                self.d_far_gain_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["far_gain"])
 
     def explore_far_spread(self, block=8, r_spread=2.0, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link", after=None):
         """explore_far() for a team (include/fasterhip_apart.h): a block of the flood nearer than r_spread to the goal that a peer
@@ -889,69 +874,24 @@ class Fleet:
         that goal.  groups and passes are explore_spread()'s (no list, so no overflow; a vehicle with `passes` searching peers below
         it is FH_APART_UNSETTLED for a period); after, block and the other arguments are explore_far()'s; the buffers and the
         workspace are its own (far_spread_records())."""
-        stages = self.explore_far_spread_stages(block, r_spread, r_avoid, z, want, max_hops, passes, groups, after)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_far_spread_stages(block, r_spread, r_avoid, z, want, max_hops, passes, groups, after))   # (raises before anything is launched)
 
     def explore_far_spread_stages(self, block=8, r_spread=2.0, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link",
                                   after=None):
         """The launches of explore_far_spread(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them)."""
-        if groups not in ("link", "view"):
-            raise capi.FasterHipError("Fleet.explore_far_spread: groups is \"link\" or \"view\", got %r" % (groups,))
+        ch = self.CHOOSERS["far_spread"]
+        self._check_groups(ch, groups)
         par = abi.default_far_spread_params(block, r_spread)
-        flags, stride, vo, n_views = self._reach_inputs("explore_far_spread", par, r_avoid, z, want, max_hops)
+        views = self._chooser_inputs(ch, par, r_avoid, z, want, max_hops)
         if passes is not None:
             par["passes"] = passes
-        skip = None
-        if after is not None:
-            if after not in self._FAR_AFTER:
-                raise capi.FasterHipError("Fleet.explore_far_spread: after is None or one of %s, got %r" % (", ".join(sorted(self._FAR_AFTER)), after))
-            skip = getattr(self, self._FAR_AFTER[after])
-            if skip is None:
-                raise capi.FasterHipError("Fleet.explore_far_spread: after=%r, but that chooser has not run" % (after,))
-        g = capi._grid_record(self.grid)
-        work_bytes = int(capi.lib().fh_apart_work_bytes(abi.ptr(g), int(block), int(n_views), int(self.n)))
-        if work_bytes == 0:
-            raise capi.FasterHipError("Fleet.explore_far_spread: block must be 1 .. 16 and the blocks of the lattice must fit %d words of 64 "
-                                      "(got block %r on a lattice of %s)" % (abi.FH_FAR_MAX_WORDS, block, tuple(int(d) for d in self.grid[2])))
-        t = self.torch
-        if self.d_far_spread_goals is None:
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_far_spread_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_far_spread_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_far_spread_records = t.zeros(self.n * abi.far_spread_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-            for d in (self.d_far_spread_goals, self.d_far_spread_mask, self.d_far_spread_records):
-                d.record_stream(self.stream)
-        key = (tuple(int(d) for d in self.grid[2]), int(block), int(n_views), int(self.n))
-        if self._far_spread_work_key != key:   # (one workspace per lattice, block, number of views and vehicles)
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_far_spread_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
-            self.d_far_spread_work.record_stream(self.stream)
-            self._far_spread_work_key = key
-        # the labels are per view: with set_unknown's single view there is nothing to label
-        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
-            and self.d_link_labels.numel() == n_views else None
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("far_spread_goals", lambda: m.far_spread_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if skip is None else p(skip),
-                                                                   None if labels is None else p(labels), p(self.d_vehicles), self.n,
-                                                                   p(self.d_far_spread_work), work_bytes, p(self.d_far_spread_goals),
-                                                                   p(self.d_far_spread_mask), p(self.d_far_spread_records),
-                                                                   self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_far_spread_goals), p(self.d_far_spread_mask),
-                                                           self.n)),
-        ]
+        skip = self._far_skip(ch, after)
+        work_bytes = self._far_work_bytes(ch, block, views[3], abi.FH_FAR_MAX_WORDS)
+        return self._chooser_stages(ch, par, views, work_bytes, block, skip, groups)
 
     def far_spread_records(self):
         """(records [n] abi.far_spread_record_dtype, goals [n][3], mask [n] int32) of the last explore_far_spread() (synchronises)."""
-        if self.d_far_spread_goals is None:
-            raise capi.FasterHipError("Fleet.far_spread_records: explore_far_spread first")
-        self.sync()
-        return (self.d_far_spread_records.cpu().numpy().view(abi.far_spread_record_dtype).copy(), self.d_far_spread_goals.cpu().numpy().copy(),
-                self.d_far_spread_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["far_spread"])
 
     def explore_far_team(self, block=8, r_spread=2.0, gain_blocks=2, hop_cost=None, min_gain=0, claim_blocks=None, r_avoid=None, z=None,
                          want="reached", max_hops=0, passes=None, groups="link", after=None):
@@ -963,37 +903,24 @@ class Fleet:
         anyway.  gain_blocks, hop_cost and min_gain are explore_far_gain()'s, r_spread, passes, groups and after
         explore_far_spread()'s, whose errors are raised before anything is launched; the buffers and the workspace are its own
         (far_team_records())."""
-        stages = self.explore_far_team_stages(block, r_spread, gain_blocks, hop_cost, min_gain, claim_blocks, r_avoid, z, want, max_hops, passes,
-                                              groups, after)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_far_team_stages(block, r_spread, gain_blocks, hop_cost, min_gain, claim_blocks, r_avoid, z, want, max_hops, passes,
+                                               groups, after))   # (raises before anything is launched)
 
     def explore_far_team_stages(self, block=8, r_spread=2.0, gain_blocks=2, hop_cost=None, min_gain=0, claim_blocks=None, r_avoid=None, z=None,
                                 want="reached", max_hops=0, passes=None, groups="link", after=None):
         """The launches of explore_far_team(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them)."""
-        if groups not in ("link", "view"):
-            raise capi.FasterHipError("Fleet.explore_far_team: groups is \"link\" or \"view\", got %r" % (groups,))
+        ch = self.CHOOSERS["far_team"]
+        self._check_groups(ch, groups)
         par = abi.default_far_team_params(block, r_spread, gain_blocks)
-        flags, stride, vo, n_views = self._reach_inputs("explore_far_team", par, r_avoid, z, want, max_hops)
+        views = self._chooser_inputs(ch, par, r_avoid, z, want, max_hops)
         if not (np.isfinite(float(r_spread)) and float(r_spread) > 0.0):
             raise capi.FasterHipError("Fleet.explore_far_team: r_spread must be finite and > 0, got %r" % (r_spread,))
         if passes is not None:
             if not 1 <= int(passes) <= abi.FH_STAKE_MAX_PASSES:
                 raise capi.FasterHipError("Fleet.explore_far_team: passes must be None or 1 .. %d, got %r" % (abi.FH_STAKE_MAX_PASSES, passes))
             par["passes"] = int(passes)
-        skip = None
-        if after is not None:
-            if after not in self._FAR_AFTER:
-                raise capi.FasterHipError("Fleet.explore_far_team: after is None or one of %s, got %r" % (", ".join(sorted(self._FAR_AFTER)), after))
-            skip = getattr(self, self._FAR_AFTER[after])
-            if skip is None:
-                raise capi.FasterHipError("Fleet.explore_far_team: after=%r, but that chooser has not run" % (after,))
-        g = capi._grid_record(self.grid)
-        work_bytes = int(capi.lib().fh_stake_work_bytes(abi.ptr(g), int(block), int(n_views), int(self.n)))
-        if work_bytes == 0:
-            raise capi.FasterHipError("Fleet.explore_far_team: block must be 1 .. 16 and the blocks of the lattice must fit %d words of 64 "
-                                      "(got block %r on a lattice of %s)" % (abi.FH_STAKE_MAX_WORDS, block, tuple(int(d) for d in self.grid[2])))
+        skip = self._far_skip(ch, after)
+        work_bytes = self._far_work_bytes(ch, block, views[3], abi.FH_STAKE_MAX_WORDS)
         if not 0 <= int(gain_blocks) <= abi.FH_STAKE_MAX_BLOCKS:
             raise capi.FasterHipError("Fleet.explore_far_team: gain_blocks must be 0 .. %d, got %r" % (abi.FH_STAKE_MAX_BLOCKS, gain_blocks))
         if hop_cost is not None:
@@ -1008,42 +935,11 @@ class Fleet:
                 raise capi.FasterHipError("Fleet.explore_far_team: claim_blocks must be None or 0 .. %d, got %r"
                                           % (abi.FH_STAKE_MAX_CLAIM_BLOCKS, claim_blocks))
             par["claim_blocks"] = int(claim_blocks)
-        t = self.torch
-        if self.d_far_team_goals is None:
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_far_team_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_far_team_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_far_team_records = t.zeros(self.n * abi.far_team_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-            for d in (self.d_far_team_goals, self.d_far_team_mask, self.d_far_team_records):
-                d.record_stream(self.stream)
-        key = (tuple(int(d) for d in self.grid[2]), int(block), int(n_views), int(self.n))
-        if self._far_team_work_key != key:   # (one workspace per lattice, block, number of views and vehicles)
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_far_team_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
-            self.d_far_team_work.record_stream(self.stream)
-            self._far_team_work_key = key
-        # the labels are per view: with set_unknown's single view there is nothing to label
-        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
-            and self.d_link_labels.numel() == n_views else None
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("far_team_goals", lambda: m.far_team_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if skip is None else p(skip),
-                                                               None if labels is None else p(labels), p(self.d_vehicles), self.n,
-                                                               p(self.d_far_team_work), work_bytes, p(self.d_far_team_goals),
-                                                               p(self.d_far_team_mask), p(self.d_far_team_records), self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_far_team_goals), p(self.d_far_team_mask),
-                                                           self.n)),
-        ]
+        return self._chooser_stages(ch, par, views, work_bytes, block, skip, groups)
 
     def far_team_records(self):
         """(records [n] abi.far_team_record_dtype, goals [n][3], mask [n] int32) of the last explore_far_team() (synchronises)."""
-        if self.d_far_team_goals is None:
-            raise capi.FasterHipError("Fleet.far_team_records: explore_far_team first")
-        self.sync()
-        return (self.d_far_team_records.cpu().numpy().view(abi.far_team_record_dtype).copy(), self.d_far_team_goals.cpu().numpy().copy(),
-                self.d_far_team_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["far_team"])
 
     def explore_spread(self, r_max, r_spread, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link"):
         """explore_reachable() for a team (include/fasterhip_spread.h): a frontier voxel nearer than r_spread to the goal that a peer is
@@ -1053,48 +949,21 @@ class Fleet:
         vehicles that wait for each other may be (None: abi.FH_SPREAD_DEFAULT_PASSES); a vehicle behind that gets no goal this period
         (FH_SPREAD_UNSETTLED) and is wanted again in the next.  The other arguments, the preconditions and the errors are those of
         explore_reachable(); the buffers and the workspace are its own (spread_records())."""
-        stages = self.explore_spread_stages(r_max, r_spread, r_avoid, z, want, max_hops, passes, groups)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_spread_stages(r_max, r_spread, r_avoid, z, want, max_hops, passes, groups))   # (raises before anything is launched)
 
     def explore_spread_stages(self, r_max, r_spread, r_avoid=None, z=None, want="reached", max_hops=0, passes=None, groups="link"):
         """The launches of explore_spread(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them one by one)."""
-        if groups not in ("link", "view"):
-            raise capi.FasterHipError("Fleet.explore_spread: groups is \"link\" or \"view\", got %r" % (groups,))
+        ch = self.CHOOSERS["spread"]
+        self._check_groups(ch, groups)
         par = abi.default_spread_params(r_max, r_spread)
-        flags, stride, vo, n_views = self._reach_inputs("explore_spread", par, r_avoid, z, want, max_hops)   # (set_unknown's one grid: one team)
+        views = self._chooser_inputs(ch, par, r_avoid, z, want, max_hops)   # (set_unknown's one grid: one team)
         if passes is not None:
             par["passes"] = passes
-        work_bytes = int(capi.lib().fh_spread_work_bytes(self.n))
-        if self.d_spread_goals is None:
-            t = self.torch
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_spread_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_spread_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_spread_records = t.zeros(self.n * abi.spread_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-                self.d_spread_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
-            for d in (self.d_spread_goals, self.d_spread_mask, self.d_spread_records, self.d_spread_work):
-                d.record_stream(self.stream)
-        # the labels are per view: with set_unknown's single view there is nothing to label
-        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
-            and self.d_link_labels.numel() == n_views else None
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("spread_goals", lambda: m.spread_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if labels is None else p(labels),
-                                                           p(self.d_vehicles), self.n, p(self.d_spread_work), work_bytes, p(self.d_spread_goals),
-                                                           p(self.d_spread_mask), p(self.d_spread_records), self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_spread_goals), p(self.d_spread_mask), self.n)),
-        ]
+        return self._chooser_stages(ch, par, views, groups=groups)
 
     def spread_records(self):
         """(records [n] abi.spread_record_dtype, goals [n][3], mask [n] int32) of the last explore_spread() (synchronises)."""
-        if self.d_spread_goals is None:
-            raise capi.FasterHipError("Fleet.spread_records: explore_spread first")
-        self.sync()
-        return (self.d_spread_records.cpu().numpy().view(abi.spread_record_dtype).copy(), self.d_spread_goals.cpu().numpy().copy(),
-                self.d_spread_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["spread"])
 
     def explore_gain(self, r_max, gain_radius, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0):
         """explore_reachable() with the choice of include/fasterhip_gain.h: of the frontier voxels that the flood reaches the one with the
@@ -1104,40 +973,18 @@ class Fleet:
         that one step is worth (0 .. 16384); min_gain: a voxel with a smaller gain is never chosen (gain_records() counts them as poor).
         With gain_radius 0, hop_cost 1 and min_gain 0 it is explore_reachable().  The other arguments, the preconditions and the errors
         are those of explore_reachable(); the buffers are its own (gain_records())."""
-        stages = self.explore_gain_stages(r_max, gain_radius, hop_cost, min_gain, r_avoid, z, want, max_hops)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_gain_stages(r_max, gain_radius, hop_cost, min_gain, r_avoid, z, want, max_hops))   # (raises before anything is launched)
 
     def explore_gain_stages(self, r_max, gain_radius, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0):
         """The two launches of explore_gain(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        ch = self.CHOOSERS["gain"]
         par = abi.default_gain_params(r_max, gain_radius)
         par["hop_cost"], par["min_gain"] = hop_cost, min_gain
-        flags, stride, vo, n_views = self._reach_inputs("explore_gain", par, r_avoid, z, want, max_hops)
-        if self.d_gain_goals is None:
-            t = self.torch
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_gain_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_gain_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_gain_records = t.zeros(self.n * abi.gain_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-            for d in (self.d_gain_goals, self.d_gain_mask, self.d_gain_records):
-                d.record_stream(self.stream)
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("gain_goals", lambda: m.gain_goals_device(par, self.grid, p(flags), stride, vo, n_views, p(self.d_vehicles), self.n,
-                                                       p(self.d_gain_goals), p(self.d_gain_mask), p(self.d_gain_records),
-                                                       self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_gain_goals), p(self.d_gain_mask), self.n)),
-        ]
+        return self._chooser_stages(ch, par, self._chooser_inputs(ch, par, r_avoid, z, want, max_hops))
 
     def gain_records(self):
         """(records [n] abi.gain_record_dtype, goals [n][3], mask [n] int32) of the last explore_gain() (synchronises)."""
-        if self.d_gain_goals is None:
-            raise capi.FasterHipError("Fleet.gain_records: explore_gain first")
-        self.sync()
-        return (self.d_gain_records.cpu().numpy().view(abi.gain_record_dtype).copy(), self.d_gain_goals.cpu().numpy().copy(),
-                self.d_gain_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["gain"])
 
     def explore_sight(self, r_max, gain_radius, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0):
         """explore_gain() with a gain that the vehicle's sensor can deliver (include/fasterhip_sight.h): an unknown voxel of the ball
@@ -1146,40 +993,18 @@ class Fleet:
         the hall behind it.  gain_radius is in voxels: sensor radius / res, rounded down, at most 31.  The arguments, the preconditions
         and the errors are those of explore_gain(); the buffers are its own (sight_records()).  Where a vehicle's box holds no such
         voxel the choice is explore_gain()'s."""
-        stages = self.explore_sight_stages(r_max, gain_radius, hop_cost, min_gain, r_avoid, z, want, max_hops)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_sight_stages(r_max, gain_radius, hop_cost, min_gain, r_avoid, z, want, max_hops))   # (raises before anything is launched)
 
     def explore_sight_stages(self, r_max, gain_radius, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached", max_hops=0):
         """The two launches of explore_sight(), in order: [(name, callable)] (scripts/fleet_cycle.py times them one by one)."""
+        ch = self.CHOOSERS["sight"]
         par = abi.default_sight_params(r_max, gain_radius)
         par["hop_cost"], par["min_gain"] = hop_cost, min_gain
-        flags, stride, vo, n_views = self._reach_inputs("explore_sight", par, r_avoid, z, want, max_hops)
-        if self.d_sight_goals is None:
-            t = self.torch
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_sight_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_sight_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_sight_records = t.zeros(self.n * abi.sight_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-            for d in (self.d_sight_goals, self.d_sight_mask, self.d_sight_records):
-                d.record_stream(self.stream)
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("sight_goals", lambda: m.sight_goals_device(par, self.grid, p(flags), stride, vo, n_views, p(self.d_vehicles), self.n,
-                                                         p(self.d_sight_goals), p(self.d_sight_mask), p(self.d_sight_records),
-                                                         self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_sight_goals), p(self.d_sight_mask), self.n)),
-        ]
+        return self._chooser_stages(ch, par, self._chooser_inputs(ch, par, r_avoid, z, want, max_hops))
 
     def sight_records(self):
         """(records [n] abi.sight_record_dtype, goals [n][3], mask [n] int32) of the last explore_sight() (synchronises)."""
-        if self.d_sight_goals is None:
-            raise capi.FasterHipError("Fleet.sight_records: explore_sight first")
-        self.sync()
-        return (self.d_sight_records.cpu().numpy().view(abi.sight_record_dtype).copy(), self.d_sight_goals.cpu().numpy().copy(),
-                self.d_sight_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["sight"])
 
     def explore_team(self, r_max, r_spread, gain_radius, claim_radius=None, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached",
                      max_hops=0, passes=None, groups="link"):
@@ -1190,51 +1015,24 @@ class Fleet:
         whose balls do not count the same voxels twice.  gain_radius, hop_cost and min_gain are explore_gain()'s, passes and groups
         explore_spread()'s; the other arguments, the preconditions and the errors are those of explore_reachable(); the buffers and
         the workspace are its own (team_records())."""
-        stages = self.explore_team_stages(r_max, r_spread, gain_radius, claim_radius, hop_cost, min_gain, r_avoid, z, want, max_hops, passes,
-                                          groups)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_team_stages(r_max, r_spread, gain_radius, claim_radius, hop_cost, min_gain, r_avoid, z, want, max_hops, passes,
+                                           groups))   # (raises before anything is launched)
 
     def explore_team_stages(self, r_max, r_spread, gain_radius, claim_radius=None, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached",
                             max_hops=0, passes=None, groups="link"):
         """The launches of explore_team(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them one by one)."""
-        if groups not in ("link", "view"):
-            raise capi.FasterHipError("Fleet.explore_team: groups is \"link\" or \"view\", got %r" % (groups,))
+        ch = self.CHOOSERS["team"]
+        self._check_groups(ch, groups)
         par = abi.default_team_params(r_max, r_spread, gain_radius, claim_radius)
         par["hop_cost"], par["min_gain"] = hop_cost, min_gain
-        flags, stride, vo, n_views = self._reach_inputs("explore_team", par, r_avoid, z, want, max_hops)   # (set_unknown's one grid: one team)
+        views = self._chooser_inputs(ch, par, r_avoid, z, want, max_hops)   # (set_unknown's one grid: one team)
         if passes is not None:
             par["passes"] = passes
-        work_bytes = int(capi.lib().fh_spread_work_bytes(self.n))
-        if self.d_team_goals is None:
-            t = self.torch
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_team_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_team_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_team_records = t.zeros(self.n * abi.team_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-                self.d_team_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
-            for d in (self.d_team_goals, self.d_team_mask, self.d_team_records, self.d_team_work):
-                d.record_stream(self.stream)
-        # the labels are per view: with set_unknown's single view there is nothing to label
-        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
-            and self.d_link_labels.numel() == n_views else None
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("team_goals", lambda: m.team_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if labels is None else p(labels),
-                                                       p(self.d_vehicles), self.n, p(self.d_team_work), work_bytes, p(self.d_team_goals),
-                                                       p(self.d_team_mask), p(self.d_team_records), self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_team_goals), p(self.d_team_mask), self.n)),
-        ]
+        return self._chooser_stages(ch, par, views, groups=groups)
 
     def team_records(self):
         """(records [n] abi.team_record_dtype, goals [n][3], mask [n] int32) of the last explore_team() (synchronises)."""
-        if self.d_team_goals is None:
-            raise capi.FasterHipError("Fleet.team_records: explore_team first")
-        self.sync()
-        return (self.d_team_records.cpu().numpy().view(abi.team_record_dtype).copy(), self.d_team_goals.cpu().numpy().copy(),
-                self.d_team_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["team"])
 
     def explore_bid(self, r_max, r_spread, gain_radius, claim_radius=None, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached",
                     max_hops=0, passes=None, groups="link"):
@@ -1244,51 +1042,24 @@ class Fleet:
         under the new claims.  Two teammates before one hall: the one beside it gets it, whatever its index.  The arguments (claim_radius
         None: gain_radius; -1: claims cover nothing; at most 31), the preconditions and the errors are those of explore_team(); passes
         counts the rounds; the buffers and the workspace are its own (bid_records())."""
-        stages = self.explore_bid_stages(r_max, r_spread, gain_radius, claim_radius, hop_cost, min_gain, r_avoid, z, want, max_hops, passes,
-                                         groups)   # (raises before anything is launched)
-        self._follow_current()
-        for _, launch in stages:
-            launch()
+        self._run(self.explore_bid_stages(r_max, r_spread, gain_radius, claim_radius, hop_cost, min_gain, r_avoid, z, want, max_hops, passes,
+                                          groups))   # (raises before anything is launched)
 
     def explore_bid_stages(self, r_max, r_spread, gain_radius, claim_radius=None, hop_cost=1, min_gain=0, r_avoid=None, z=None, want="reached",
                            max_hops=0, passes=None, groups="link"):
         """The launches of explore_bid(), in order: [(name, callable)], set_goals last (scripts/fleet_cycle.py times them one by one)."""
-        if groups not in ("link", "view"):
-            raise capi.FasterHipError("Fleet.explore_bid: groups is \"link\" or \"view\", got %r" % (groups,))
+        ch = self.CHOOSERS["bid"]
+        self._check_groups(ch, groups)
         par = abi.default_bid_params(r_max, r_spread, gain_radius, claim_radius)
         par["hop_cost"], par["min_gain"] = hop_cost, min_gain
-        flags, stride, vo, n_views = self._reach_inputs("explore_bid", par, r_avoid, z, want, max_hops)   # (set_unknown's one grid: one team)
+        views = self._chooser_inputs(ch, par, r_avoid, z, want, max_hops)   # (set_unknown's one grid: one team)
         if passes is not None:
             par["passes"] = passes
-        work_bytes = int(capi.lib().fh_bid_work_bytes(self.n))
-        if self.d_bid_goals is None:
-            t = self.torch
-            self._follow_current()
-            with t.cuda.stream(self.stream):
-                self.d_bid_goals = t.zeros((self.n, 3), dtype=t.float64, device=self.dev)
-                self.d_bid_mask = t.zeros(self.n, dtype=t.int32, device=self.dev)
-                self.d_bid_records = t.zeros(self.n * abi.bid_record_dtype.itemsize, dtype=t.uint8, device=self.dev)
-                self.d_bid_work = t.zeros(work_bytes, dtype=t.uint8, device=self.dev)
-            for d in (self.d_bid_goals, self.d_bid_mask, self.d_bid_records, self.d_bid_work):
-                d.record_stream(self.stream)
-        # the labels are per view: with set_unknown's single view there is nothing to label
-        labels = self.d_link_labels if groups == "link" and self.view_flags is not None and self.d_link_labels is not None \
-            and self.d_link_labels.numel() == n_views else None
-        c, m, p = self.ctx, self.map, (lambda x: x.data_ptr())
-        return [
-            ("bid_goals", lambda: m.bid_goals_device(par, self.grid, p(flags), stride, vo, n_views, None if labels is None else p(labels),
-                                                     p(self.d_vehicles), self.n, p(self.d_bid_work), work_bytes, p(self.d_bid_goals),
-                                                     p(self.d_bid_mask), p(self.d_bid_records), self.stream.cuda_stream)),
-            ("set_goals", lambda: c.fleet_set_goals_device(self.params, p(self.d_vehicles), p(self.d_bid_goals), p(self.d_bid_mask), self.n)),
-        ]
+        return self._chooser_stages(ch, par, views, groups=groups)
 
     def bid_records(self):
         """(records [n] abi.bid_record_dtype, goals [n][3], mask [n] int32) of the last explore_bid() (synchronises)."""
-        if self.d_bid_goals is None:
-            raise capi.FasterHipError("Fleet.bid_records: explore_bid first")
-        self.sync()
-        return (self.d_bid_records.cpu().numpy().view(abi.bid_record_dtype).copy(), self.d_bid_goals.cpu().numpy().copy(),
-                self.d_bid_mask.cpu().numpy().copy())
+        return self._chooser_records(self.CHOOSERS["bid"])
 
     def coverage_stages(self):
         """The one launch of coverage(): [(name, callable)]."""

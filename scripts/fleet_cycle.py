@@ -402,62 +402,35 @@ def explore_loop(fl, views, cycles, states, goals, r_sense, r_max):
     fl.enable_heading(yaw0=np.arctan2(u[:, 1], u[:, 0]))
     fl.sense(r_sense)
     first = fl.coverage()
-    goal_stage = "bid_goals" if BID else "team_goals" if TEAM else "spread_goals" if SPREAD is not None else "sight_goals" if SIGHT else "gain_goals" if GAIN is not None else "reach_goals" if REACH \
-        else "frontier_goals"
-    explore_stages, explore_records = (fl.explore_reachable_stages, fl.reach_records) if REACH else (fl.explore_stages, fl.explore_records)
-    if BID:
-        if LINK:   # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
-            fl.link(LINK[0])
-        explore_stages = lambda r, **kw: fl.explore_bid_stages(r, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN, **kw)   # noqa: E731
-        explore_records = fl.bid_records
-        fl.explore_bid(r_max, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN)
-    elif TEAM:
-        if LINK:   # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
-            fl.link(LINK[0])
-        explore_stages = lambda r, **kw: fl.explore_team_stages(r, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN, **kw)   # noqa: E731
-        explore_records = fl.team_records
-        fl.explore_team(r_max, SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN)
-    elif SPREAD is not None:
-        if LINK:   # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
-            fl.link(LINK[0])
-        explore_stages, explore_records = (lambda r, **kw: fl.explore_spread_stages(r, SPREAD, **kw)), fl.spread_records
-        fl.explore_spread(r_max, SPREAD)
-    elif SIGHT:
-        explore_stages, explore_records = (lambda r, **kw: fl.explore_sight_stages(r, GAIN, HOP_COST, MIN_GAIN, **kw)), fl.sight_records
-        fl.explore_sight(r_max, GAIN, HOP_COST, MIN_GAIN)
-    elif GAIN is not None:
-        explore_stages, explore_records = (lambda r, **kw: fl.explore_gain_stages(r, GAIN, HOP_COST, MIN_GAIN, **kw)), fl.gain_records
-        fl.explore_gain(r_max, GAIN, HOP_COST, MIN_GAIN)
-    else:
-        (fl.explore_reachable if REACH else fl.explore)(r_max)
-    far_after = "bid" if BID else "team" if TEAM else "spread" if SPREAD is not None else "sight" if SIGHT else "gain" if GAIN is not None else "reachable" if REACH \
-        else "explore"
-    if FAR_SPREAD is not None and LINK and SPREAD is None:   # teams: the groups of one link() after the first look (the choosers for a team above have linked)
+    # the chooser in use and the fallback behind it, as Fleet.CHOOSERS names them, with what the flags give their methods
+    team_args = (SPREAD, GAIN, CLAIM_RADIUS, HOP_COST, MIN_GAIN)
+    near, near_args = ("bid", team_args) if BID else ("team", team_args) if TEAM else ("spread", (SPREAD,)) if SPREAD is not None \
+        else ("sight", (GAIN, HOP_COST, MIN_GAIN)) if SIGHT else ("gain", (GAIN, HOP_COST, MIN_GAIN)) if GAIN is not None \
+        else ("reach", ()) if REACH else ("explore", ())
+    far, far_args, far_kw = ("far_team", (FAR, FAR_SPREAD, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, FAR_CLAIM_BLOCKS), {"passes": PASSES}) if FAR_TEAM \
+        else ("far_spread", (FAR, FAR_SPREAD), {"passes": PASSES}) if FAR_SPREAD is not None \
+        else ("far_gain", (FAR, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN), {}) if FAR_GAIN is not None else ("far", (FAR,), {}) if FAR is not None \
+        else (None, (), {})
+    ch = Fleet.CHOOSERS[near]
+    goal_stage, explore_records = ch.stage, getattr(fl, near + "_records")
+    explore_stages = lambda r, **kw: getattr(fl, ch.method + "_stages")(r, *near_args, **kw)   # noqa: E731
+    far_after = "reachable" if near == "reach" else near
+    far_kw["after"] = far_after
+    # teams: the groups of one link() after the first look (without it every vehicle is a group of its own)
+    if LINK and ch.labels:
         fl.link(LINK[0])
-    if FAR_TEAM:
-        fl.explore_far_team(FAR, FAR_SPREAD, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, FAR_CLAIM_BLOCKS, passes=PASSES, after=far_after)
-    elif FAR_SPREAD is not None:
-        fl.explore_far_spread(FAR, FAR_SPREAD, passes=PASSES, after=far_after)
-    elif FAR_GAIN is not None:
-        fl.explore_far_gain(FAR, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, after=far_after)
-    elif FAR is not None:
-        fl.explore_far(FAR, after=far_after)
+    getattr(fl, ch.method)(r_max, *near_args)
+    if LINK and FAR_SPREAD is not None and SPREAD is None:   # (the choosers for a team above have linked)
+        fl.link(LINK[0])
+    if far:
+        getattr(fl, Fleet.CHOOSERS[far].method)(*far_args, **far_kw)
     fl.replan()
     fl.next_goals(5)
     fl.sync()
     explore = explore_stages(r_max)
-    if FAR_TEAM:   # the fallback by gain for a team after the chooser in use
-        explore = explore + [(n if n == "far_team_goals" else "far_team_set_goals", f)
-                             for n, f in fl.explore_far_team_stages(FAR, FAR_SPREAD, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, FAR_CLAIM_BLOCKS,
-                                                                    passes=PASSES, after=far_after)]
-    elif FAR_SPREAD is not None:   # the fallback for a team after the chooser in use
-        explore = explore + [(n if n == "far_spread_goals" else "far_spread_set_goals", f)
-                             for n, f in fl.explore_far_spread_stages(FAR, FAR_SPREAD, passes=PASSES, after=far_after)]
-    elif FAR_GAIN is not None:   # the fallback with a gain after the chooser in use
-        explore = explore + [(n if n == "far_gain_goals" else "far_gain_set_goals", f)
-                             for n, f in fl.explore_far_gain_stages(FAR, FAR_GAIN, FAR_HOP_COST, FAR_MIN_GAIN, after=far_after)]
-    elif FAR is not None:   # the fallback after the chooser in use, for the vehicles it left without a goal
-        explore = explore + [(n if n == "far_goals" else "far_set_goals", f) for n, f in fl.explore_far_stages(FAR, after=far_after)]
+    if far:   # the fallback after the chooser in use, for the vehicles it left without a goal
+        explore = explore + [(n if n == far + "_goals" else far + "_set_goals", f)
+                             for n, f in getattr(fl, Fleet.CHOOSERS[far].method + "_stages")(*far_args, **far_kw)]
     names = ["sense"] + [n for n, _ in explore] + [n for n, _ in fl.stages()] + ["next_goals"]
     per, wanted, found = {n: [] for n in names}, [], []
     for _ in range(cycles):
