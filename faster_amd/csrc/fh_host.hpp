@@ -1,5 +1,5 @@
-// fh_host.hpp — what the host sides of the C ABI (fh_capi.hip, fh_map.hip, fh_pool.hip) share: the device-scope guard, the owned
-// device buffer, the HIP check, and the argument rules that more than one entry point applies.  Host code only.
+// fh_host.hpp — what the host sides of the C ABI (fh_capi.hip, fh_map.hip, fh_pool.hip, fh_reach.hip) share: the device-scope guard,
+// the owned device buffer, the HIP check, and the argument rules that more than one entry point applies.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -95,6 +95,19 @@ inline bool voxel_grid_ok(const fh_voxel_grid* g, bool with_res = true) {
   return g && (!with_res || g->res > 0) && g->dims[0] >= 1 && g->dims[1] >= 1 && g->dims[2] >= 1;
 }
 inline long long voxel_grid_cells(const fh_voxel_grid& g) { return (long long)g.dims[0] * g.dims[1] * g.dims[2]; }
+// The cells of a lattice that passed voxel_grid_ok and whose kernels number a cell with an int; 0: more than 2^31 - 1.
+// (Each factor is below 2^31; the product of two fits 62 bits, and what is above the limit after two never comes back under it.)
+inline long long voxel_grid_cells31(const fh_voxel_grid& g) {
+  const long long xy = (long long)g.dims[0] * g.dims[1];
+  return xy > 0x7fffffffll || xy * g.dims[2] > 0x7fffffffll ? 0 : xy * g.dims[2];
+}
+// The lattice of the views of include/fasterhip_frontier.h and of every chooser behind it: a lattice whose cell count fits 31 bits,
+// views at least that many bytes apart, at least one view.  true: fine, `cells` filled in.
+inline bool view_lattice_ok(const fh_voxel_grid* grid, bool with_res, size_t view_stride, int n_views, long long* cells) {
+  if (!voxel_grid_ok(grid, with_res)) return false;
+  *cells = voxel_grid_cells31(*grid);
+  return *cells != 0 && view_stride >= (size_t)*cells && n_views >= 1;
+}
 
 // origin, cell size and dimensions into any of the kernels' argument structs that carry a lattice as ox, oy, oz, res, nx, ny, nz
 template <class To>

@@ -650,18 +650,6 @@ int fh_map_read_views_listed_device(fh_map* m, const double* d_cloud_xyz, int n_
   return FH_OK;
 }
 
-// include/fasterhip_frontier.h: the lattice of the views, judged the same way by both entry points (0: fine, cells filled in)
-static int frontier_lattice(const fh_voxel_grid* grid, bool with_res, size_t view_stride, int n_views, long long* cells) {
-  if (!grid || (with_res && !(grid->res > 0.0)) || grid->dims[0] < 1 || grid->dims[1] < 1 || grid->dims[2] < 1) return FH_ERR_ARG;
-  // (each factor is below 2^31; the product of two fits 62 bits, and what is above the limit after two never comes back under it)
-  const long long xy = (long long)grid->dims[0] * grid->dims[1];
-  if (xy > 0x7fffffffll || xy * grid->dims[2] > 0x7fffffffll) return FH_ERR_ARG;
-  *cells = xy * grid->dims[2];
-  if (view_stride < (size_t)*cells) return FH_ERR_ARG;
-  if (n_views < 1) return FH_ERR_ARG;
-  return FH_OK;
-}
-
 // the nearest frontier voxel of its view for every vehicle that wants a goal, in the shape fh_fleet_set_goals_device takes
 int fh_map_frontier_goals_device(fh_map* m, const fh_frontier_params* par, const fh_voxel_grid* grid, const unsigned char* d_flags,
                                  size_t view_stride, const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles, int n,
@@ -673,7 +661,7 @@ int fh_map_frontier_goals_device(fh_map* m, const fh_frontier_params* par, const
   const int all_wants = FH_FRONTIER_WANT_REACHED | FH_FRONTIER_WANT_NO_PATH | FH_FRONTIER_WANT_ALL;
   if (par->want == 0 || (par->want & ~all_wants) != 0) return FH_ERR_ARG;
   long long cells = 0;
-  if (frontier_lattice(grid, true, view_stride, n_views, &cells) != FH_OK) return FH_ERR_ARG;
+  if (!fhh::view_lattice_ok(grid, true, view_stride, n_views, &cells)) return FH_ERR_ARG;
   if (n < 0) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
   if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
@@ -702,7 +690,7 @@ int fh_map_view_coverage_device(fh_map* m, const fh_voxel_grid* grid, const unsi
                                 fh_view_coverage* d_out) {
   if (!m) return FH_ERR_ARG;
   long long cells = 0;
-  if (frontier_lattice(grid, false, view_stride, n_views, &cells) != FH_OK) return FH_ERR_ARG;
+  if (!fhh::view_lattice_ok(grid, false, view_stride, n_views, &cells)) return FH_ERR_ARG;
   if (!d_flags || !d_out) return FH_ERR_ARG;
   fhh::DeviceScope scope(m->device);
   FM_HIP(hipMemsetAsync(d_out, 0, sizeof(fh_view_coverage) * (size_t)n_views, m->stream));

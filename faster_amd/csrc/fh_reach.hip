@@ -1,18 +1,8 @@
-// fh_reach.hip — host side of include/fasterhip_reach.h (fh_reach_goals_device): the frontier voxel that a flood of the space a vehicle
-// knows to be free reaches in the fewest steps (kernel: fh_reach.hip.hpp), and of include/fasterhip_spread.h (fh_spread_goals_device):
-// that chooser for a team, goals claimed by peers avoided (kernels: fh_spread.hip.hpp), and of include/fasterhip_gain.h
-// (fh_gain_goals_device): the reachable frontier voxel with the most unknown space around it for its steps (kernel: fh_gain.hip.hpp),
-// and of include/fasterhip_team.h (fh_team_goals_device): that utility inside the passes of the chooser for a team, the space a peer's
-// claim covers not counted twice (kernels: fh_team.hip.hpp), and of include/fasterhip_sight.h (fh_sight_goals_device): the gain chooser
-// with a gain that counts only the unknown voxels a candidate has a line of sight to (kernel: fh_sight.hip.hpp), and of
-// include/fasterhip_bid.h (fh_bid_goals_device): the search of the gain-aware chooser for a team inside rounds ordered by bids, the best
-// offer wins a contested frontier (kernels: fh_bid.hip.hpp), and of include/fasterhip_far.h (fh_far_goals_device): the fallback for the
-// vehicles those choosers left without a goal, a flood of the whole view over blocks of voxels (kernels: fh_far.hip.hpp), and of
-// include/fasterhip_apart.h (fh_apart_goals_device): that fallback for a team, the target blocks that a peer's claim covers
-// taken out before the flood (kernels: fh_apart.hpp), and of include/fasterhip_prospect.h (fh_prospect_goals_device): that fallback
-// with a gain, the unknown voxels of the blocks around a target block, chosen by utility over all levels (kernels: fh_prospect.hpp), and
-// of include/fasterhip_stake.h (fh_stake_goals_device): that gain inside the passes of the fallback for a team, a peer's claim covering
-// a cube of blocks whose unknown voxels no gain of the vehicle counts (kernels: fh_stake.hpp).
+// fh_reach.hip — host side of the ten frontier choosers behind fh_map_frontier_goals_device, K15 … K24: one entry point for each of
+// include/fasterhip_{reach,spread,gain,team,sight,bid,far,apart,prospect,stake}.h, its kernels in the device header of the same
+// chooser.  What two entry points share is written once above `extern "C"`: the clause groups, the argument fills, the device of
+// d_records and the one layout of each workspace; the lattice rule and the device scope are fh_host.hpp's.  An entry point keeps
+// its own clauses in its header's order, its static_asserts and its launches.
 // A translation unit of its own: fh_map.hip and fh_capi.hip, their kernels and their code objects are what they were.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
@@ -42,69 +32,223 @@
 #include "fh_stake.hpp"
 #include "fh_apart.hpp"
 
-// the lattice of the views, judged as fh_map_frontier_goals_device judges it (0: fine, cells filled in)
-static int reach_lattice(const fh_voxel_grid* grid, size_t view_stride, int n_views, long long* cells) {
-  if (!fhh::voxel_grid_ok(grid)) return FH_ERR_ARG;
-  // (each factor is below 2^31; the product of two fits 62 bits, and what is above the limit after two never comes back under it)
-  const long long xy = (long long)grid->dims[0] * grid->dims[1];
-  if (xy > 0x7fffffffll || xy * grid->dims[2] > 0x7fffffffll) return FH_ERR_ARG;
-  *cells = xy * grid->dims[2];
-  if (view_stride < (size_t)*cells) return FH_ERR_ARG;
-  if (n_views < 1) return FH_ERR_ARG;
-  return FH_OK;
-}
+// ---- clauses: what more than one entry point tests, each group once; an entry point calls them in its header's order ----
 
-// the clauses of fh_reach_goals_device from r_max to max_hops < 0, in the header's order (the fields that all three params share)
-static int reach_field_clauses(double r_max, double r_avoid, double z_lo, double z_hi, int want, int max_hops) {
+// the clauses of fh_reach_goals_device from r_max to max_hops < 0, in the header's order (the fields that every params struct has;
+// fh_far_params and the three behind it have no r_max: any r_max that passes stands in for it)
+template <class P>
+static int reach_field_clauses(double r_max, const P& par) {
   if (!std::isfinite(r_max) || !(r_max > 0.0)) return FH_ERR_ARG;
-  if (!std::isfinite(r_avoid) || !(r_avoid >= 0.0)) return FH_ERR_ARG;
-  if (std::isnan(z_lo) || std::isnan(z_hi) || z_lo > z_hi) return FH_ERR_ARG;
+  if (!std::isfinite(par.r_avoid) || !(par.r_avoid >= 0.0)) return FH_ERR_ARG;
+  if (std::isnan(par.z_lo) || std::isnan(par.z_hi) || par.z_lo > par.z_hi) return FH_ERR_ARG;
   const int all_wants = FH_FRONTIER_WANT_REACHED | FH_FRONTIER_WANT_NO_PATH | FH_FRONTIER_WANT_ALL;
-  if (want == 0 || (want & ~all_wants) != 0) return FH_ERR_ARG;
-  if (max_hops < 0) return FH_ERR_ARG;
+  if (par.want == 0 || (par.want & ~all_wants) != 0) return FH_ERR_ARG;
+  if (par.max_hops < 0) return FH_ERR_ARG;
   return FH_OK;
 }
 
-// and its clauses from map_grid to n < 0 (fh_gain_goals_device has clauses of its own between the two)
+// and its clauses from map_grid to n < 0 (fh_gain_goals_device and the far choosers have clauses of their own between the two)
 static int reach_table_clauses(const fh_voxel_grid* map_grid, const unsigned* d_map_bits, const fh_voxel_grid* grid, size_t view_stride, int n_views,
                                int n) {
-  if (!fhh::voxel_grid_ok(map_grid)) return FH_ERR_ARG;
-  const long long map_xy = (long long)map_grid->dims[0] * map_grid->dims[1];
-  if (map_xy > 0x7fffffffll || map_xy * map_grid->dims[2] > 0x7fffffffll) return FH_ERR_ARG;
+  if (!fhh::voxel_grid_ok(map_grid) || fhh::voxel_grid_cells31(*map_grid) == 0) return FH_ERR_ARG;
   if (!d_map_bits) return FH_ERR_ARG;
   long long cells = 0;
-  if (reach_lattice(grid, view_stride, n_views, &cells) != FH_OK) return FH_ERR_ARG;
+  if (!fhh::view_lattice_ok(grid, true, view_stride, n_views, &cells)) return FH_ERR_ARG;
   if (n < 0) return FH_ERR_ARG;
   return FH_OK;
 }
 
-// the clauses of fh_reach_goals_device from r_max to n < 0, in the header's order (it and fh_spread_goals_device)
-static int reach_clauses(double r_max, double r_avoid, double z_lo, double z_hi, int want, int max_hops, const fh_voxel_grid* map_grid,
-                         const unsigned* d_map_bits, const fh_voxel_grid* grid, size_t view_stride, int n_views, int n) {
-  if (reach_field_clauses(r_max, r_avoid, z_lo, z_hi, want, max_hops) != FH_OK) return FH_ERR_ARG;
+// both, with nothing between them (K15, K16, K18, K20)
+template <class P>
+static int reach_clauses(const P& par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits, const fh_voxel_grid* grid, size_t view_stride,
+                         int n_views, int n) {
+  if (reach_field_clauses(par.r_max, par) != FH_OK) return FH_ERR_ARG;
   return reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n);
 }
 
-// the kernel's arguments from checked values (the outputs are the caller's to set)
-static void reach_args(fhp::ReachArgs& a, double r_max, double r_avoid, double z_lo, double z_hi, int want, int max_hops,
-                       const fh_voxel_grid* map_grid, const unsigned* d_map_bits, const fh_voxel_grid* grid, const unsigned char* d_flags,
-                       size_t view_stride, const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles) {
+// r_spread and passes against the chooser's cap (K16, K18, K20, K22, K24)
+static bool spread_pair_ok(double r_spread, int passes, int max_passes) {
+  return std::isfinite(r_spread) && r_spread > 0.0 && passes >= 1 && passes <= max_passes;
+}
+
+// gain_radius (the far choosers: gain_blocks), hop_cost and min_gain against the chooser's two caps (K17 … K20, K23, K24)
+static bool gain_triple_ok(int radius, int hop_cost, int min_gain, int max_radius, int max_hop_cost) {
+  return radius >= 0 && radius <= max_radius && hop_cost >= 0 && hop_cost <= max_hop_cost && min_gain >= 0;
+}
+
+// the edge of a block of the far choosers, in voxels
+static bool block_ok(int block) { return block >= 1 && block <= 16; }
+
+// the pointers every chooser reads or writes once n > 0 (a workspace is the entry point's own clause: its place differs)
+static bool pointers_ok(const void* d_flags, const void* d_vehicles, const void* d_goals, const void* d_mask, const void* d_records) {
+  return d_flags && d_vehicles && d_goals && d_mask && d_records;
+}
+
+// The device that `p` lies on, -1: the runtime does not know it as device memory (HIP's error is cleared).  An entry point opens
+// its fhh::DeviceScope on the answer for d_records, which refuses -1: the scope is the entry's own object and lives until it returns.
+static int device_of(const void* p) {
+  hipPointerAttribute_t where;
+  if (hipPointerGetAttributes(&where, p) == hipSuccess && where.type == hipMemoryTypeDevice) return where.device;
+  (void)hipGetLastError();
+  return -1;
+}
+
+// ---- workspaces: one layout each, read by the size function and by the carve ----
+
+// K16's, K18's and K20's: the class bytes, rounded up to a multiple of 64, before the rows (K20's offers: bid_offers_offset below)
+static size_t spread_rows_offset(int n) { return ((size_t)n + 63) & ~(size_t)63; }
+
+// the words of a bitmap of blocks of edge `block` over the lattice; 0: a null grid, a dimension < 1 or a block outside 1..16;
+// FH_FAR_MAX_WORDS + 1: more than FH_FAR_MAX_WORDS (each partial product is tested, so nothing overflows)
+static int far_words(const fh_voxel_grid* grid, int block) {
+  if (!fhh::voxel_grid_ok(grid, false) || !block_ok(block)) return 0;
+  long long w = (((long long)grid->dims[0] + block - 1) / block + 63) / 64;
+  for (int k = 1; k < 3; k++) {
+    if (w > FH_FAR_MAX_WORDS) return FH_FAR_MAX_WORDS + 1;
+    w *= ((long long)grid->dims[k] + block - 1) / block;
+  }
+  return w > FH_FAR_MAX_WORDS ? FH_FAR_MAX_WORDS + 1 : (int)w;
+}
+
+// The far choosers' (K21 … K24), in bytes from d_work: K21's sums [n_views][4][W] at 0, its need bytes (n_views, rounded up to a
+// multiple of 64: `counts - need` is what the memset clears), K23's counts [n_views][64 W] of 16 bits where the chooser has a gain
+// (K23, K24), and for a team (K22, K24; n = 0 for the other two) the class bytes (n, rounded up to a multiple of 64), the groups and
+// `lower`, n int32 each.  A part that a chooser does not have is empty, so `end` is what its header's formula states.  (The
+// offsets through `grp` are multiples of 32, `lower` is one of 4.)
+struct FarLayout {
+  size_t need, counts, cls, grp, lower, end;
+};
+static FarLayout far_layout(int W, int n_views, bool with_counts, int n) {
+  FarLayout at;
+  at.need = (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long);
+  at.counts = at.need + (((size_t)n_views + 63) & ~(size_t)63);
+  at.cls = at.counts + (with_counts ? (size_t)n_views * 64u * (size_t)W * sizeof(uint16_t) : 0);
+  at.grp = at.cls + spread_rows_offset(n);
+  at.lower = at.grp + (size_t)n * sizeof(int32_t);
+  at.end = at.lower + (size_t)n * sizeof(int32_t);
+  return at;
+}
+// what the four size functions answer: `end`, or 0 for a null grid, a dimension < 1, a block outside 1..16, too many words,
+// n_views < 1 or n < 0
+static size_t far_bytes(const fh_voxel_grid* grid, int block, int n_views, bool with_counts, int n) {
+  const int W = far_words(grid, block);
+  if (W < 1 || W > FH_FAR_MAX_WORDS || n_views < 1 || n < 0) return 0;
+  return far_layout(W, n_views, with_counts, n).end;
+}
+
+// ---- argument fills from checked values; what a fill leaves out (a record pointer of the chooser's own type, a pass counter that
+// the launch loop advances) is the entry point's to set ----
+
+// K15's kernel arguments, the head of every chooser's (r_max: see reach_field_clauses; d_records: null wherever the chooser has
+// a longer record of its own)
+template <class P>
+static void reach_args(fhp::ReachArgs& a, double r_max, const P& par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
+                       const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
+                       const fh_vehicle* d_vehicles, double* d_goals, int32_t* d_mask, fh_reach_record* d_records) {
   a.r_max = r_max;
   a.r2 = r_max * r_max;
-  a.a2 = r_avoid * r_avoid;
-  a.z_lo = z_lo; a.z_hi = z_hi;
-  a.want = want;
-  a.max_hops = max_hops;
+  a.a2 = par.r_avoid * par.r_avoid;
+  a.z_lo = par.z_lo; a.z_hi = par.z_hi;
+  a.want = par.want;
+  a.max_hops = par.max_hops;
   fhh::set_lattice(a, *grid);
   a.flags = d_flags; a.view_stride = view_stride; a.view_of = d_view_of; a.n_views = n_views;
   a.vehicles = d_vehicles;
   a.mx = map_grid->dims[0]; a.my = map_grid->dims[1]; a.mz = map_grid->dims[2];
   a.mres = map_grid->res; a.mox = map_grid->origin[0]; a.moy = map_grid->origin[1]; a.moz = map_grid->origin[2];
   a.bits = d_map_bits;
+  a.goals = d_goals; a.mask = d_mask; a.records = d_records;
 }
 
-// the class bytes, rounded up to a multiple of 64, before the rows
-static size_t spread_rows_offset(int n) { return ((size_t)n + 63) & ~(size_t)63; }
+// K17's on top of them (K17 … K20): the gain radius and its square, hop_cost, min_gain
+template <class P>
+static void gain_args(fhp::GainArgs& s, const P& par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits, const fh_voxel_grid* grid,
+                      const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views, const fh_vehicle* d_vehicles,
+                      double* d_goals, int32_t* d_mask) {
+  reach_args(s.r, par.r_max, par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, d_goals, d_mask, nullptr);
+  s.g = par.gain_radius;
+  s.g2 = par.gain_radius * par.gain_radius;
+  s.hop_cost = par.hop_cost;
+  s.min_gain = par.min_gain;
+  s.records = nullptr;
+}
+
+// K18's on top of those, for fhp::TeamArgs and fhp::BidArgs alike (K20's params and arguments are K18's under its own names, as
+// its static_asserts state): the radii, the claim radius, the labels, and the class bytes and rows of the workspace
+template <class A, class P>
+static void team_args(A& s, const P& par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits, const fh_voxel_grid* grid,
+                      const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views, const int32_t* d_group,
+                      const fh_vehicle* d_vehicles, int n, void* d_work, double* d_goals, int32_t* d_mask) {
+  gain_args(s.gn, par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, d_goals, d_mask);
+  // the interaction radius: a peer beyond it cannot touch the ball of a candidate
+  const double r_int = par.claim_radius < 0 ? par.r_spread : std::fmax(par.r_spread, (double)(par.gain_radius + par.claim_radius + 1) * grid->res);
+  const double reach = (par.r_max + par.r_max) + r_int, near = par.r_max + r_int;
+  s.s2 = par.r_spread * par.r_spread;
+  s.reach2 = reach * reach;
+  s.near2 = near * near;
+  s.n = n; s.pass = 0;
+  s.cr = par.claim_radius;
+  s.cr2 = par.claim_radius * par.claim_radius;
+  s.group = d_group;
+  s.cls = static_cast<unsigned char*>(d_work);
+  s.rows = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(d_work) + spread_rows_offset(n));
+}
+
+// what the class kernel of fh_spread.hip.hpp gets from K18 and K20 as it is: it reads the vehicles and writes the class bytes
+template <class A>
+static void spread_class_args(fhp::SpreadArgs& c, const A& s, void* d_work) {
+  c.r = s.gn.r;
+  c.s2 = s.s2; c.reach2 = s.reach2; c.near2 = s.near2;
+  c.n = s.n; c.pass = 0;
+  c.group = s.group;
+  c.cls = static_cast<unsigned char*>(d_work);
+  c.rows = s.rows;
+  c.records = nullptr;
+}
+
+// K21's, the head of every far chooser's: reach_args without an r_max, the blocks, the skip list, the sums and the need bytes
+template <class P>
+static void far_args(fhp::FarArgs& s, const P& par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits, const fh_voxel_grid* grid,
+                     const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views, const int32_t* d_skip,
+                     const fh_vehicle* d_vehicles, int n, void* d_work, int W, const FarLayout& at, double* d_goals, int32_t* d_mask) {
+  reach_args(s.r, 1.0, par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, d_goals, d_mask, nullptr);
+  s.B = par.block;
+  s.cx = (grid->dims[0] + s.B - 1) / s.B;  // (W <= FH_FAR_MAX_WORDS: the dims are far below 2^31 - 16)
+  s.cy = (grid->dims[1] + s.B - 1) / s.B;
+  s.cz = (grid->dims[2] + s.B - 1) / s.B;
+  s.wx = (s.cx + 63) / 64;
+  s.W = W;
+  s.n = n;
+  s.skip = d_skip;
+  s.sums = static_cast<unsigned long long*>(d_work);
+  s.need = static_cast<unsigned char*>(d_work) + at.need;
+  s.records = nullptr;
+}
+
+// K23's on top of them (K23, K24): the gain in blocks, hop_cost, min_gain and the counts
+template <class P>
+static void prospect_args(fhp::ProspectArgs& x, const P& par, void* d_work, const FarLayout& at, fh_prospect_record* d_records) {
+  x.g = par.gain_blocks;
+  x.hop_cost = par.hop_cost;
+  x.min_gain = par.min_gain;
+  x.counts = reinterpret_cast<uint16_t*>(static_cast<unsigned char*>(d_work) + at.counts);
+  x.records = d_records;
+}
+
+// K22's on top of K21's (K22's own arguments, and what its class kernel reads and writes for K24): r_spread squared, the passes,
+// the labels and the three tables of a team
+template <class P>
+static void far_spread_args(fhp::FarSpreadArgs& x, const P& par, const int32_t* d_group, void* d_work, const FarLayout& at,
+                            fh_apart_record* d_records) {
+  unsigned char* const work = static_cast<unsigned char*>(d_work);
+  x.s2 = par.r_spread * par.r_spread;
+  x.pass = 0; x.passes = par.passes;
+  x.group = d_group;
+  x.cls = work + at.cls;
+  x.grp = reinterpret_cast<int32_t*>(work + at.grp);
+  x.lower = reinterpret_cast<int32_t*>(work + at.lower);
+  x.records = d_records;
+}
 
 extern "C" {
 
@@ -112,22 +256,13 @@ int fh_reach_goals_device(void* stream, const fh_reach_params* par, const fh_vox
                           const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
                           const fh_vehicle* d_vehicles, int n, double* d_goals, int32_t* d_mask, fh_reach_record* d_records) {
   if (!par) return FH_ERR_ARG;
-  if (reach_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, view_stride, n_views,
-                    n) != FH_OK)
-    return FH_ERR_ARG;
+  if (reach_clauses(*par, map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  if (!pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::ReachArgs a;
-  reach_args(a, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
-             d_view_of, n_views, d_vehicles);
-  a.goals = d_goals; a.mask = d_mask; a.records = d_records;
+  reach_args(a, par->r_max, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, d_goals, d_mask, d_records);
   hipLaunchKernelGGL(fhp::reach_goals_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
 }
@@ -139,26 +274,16 @@ int fh_spread_goals_device(void* stream, const fh_spread_params* par, const fh_v
                            const int32_t* d_group, const fh_vehicle* d_vehicles, int n, void* d_work, size_t work_bytes, double* d_goals,
                            int32_t* d_mask, fh_spread_record* d_records) {
   if (!par) return FH_ERR_ARG;
-  if (reach_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, view_stride, n_views,
-                    n) != FH_OK)
-    return FH_ERR_ARG;
-  if (!std::isfinite(par->r_spread) || !(par->r_spread > 0.0)) return FH_ERR_ARG;
-  if (par->passes < 1 || par->passes > FH_SPREAD_MAX_PASSES) return FH_ERR_ARG;
+  if (reach_clauses(*par, map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
+  if (!spread_pair_ok(par->r_spread, par->passes, FH_SPREAD_MAX_PASSES)) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  if (!pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
   if (!d_work) return FH_ERR_ARG;
   if (work_bytes < fh_spread_work_bytes(n)) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::SpreadArgs s;
-  reach_args(s.r, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
-             d_view_of, n_views, d_vehicles);
-  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
+  reach_args(s.r, par->r_max, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, d_goals, d_mask, nullptr);
   const double reach = (par->r_max + par->r_max) + par->r_spread, near = par->r_max + par->r_spread;
   s.s2 = par->r_spread * par->r_spread;
   s.reach2 = reach * reach;
@@ -182,50 +307,21 @@ int fh_gain_goals_device(void* stream, const fh_gain_params* par, const fh_voxel
                          const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
                          const fh_vehicle* d_vehicles, int n, double* d_goals, int32_t* d_mask, fh_gain_record* d_records) {
   if (!par) return FH_ERR_ARG;
-  if (reach_field_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
-  if (par->gain_radius < 0 || par->gain_radius > FH_GAIN_MAX_RADIUS) return FH_ERR_ARG;
-  if (par->hop_cost < 0 || par->hop_cost > FH_GAIN_MAX_HOP_COST) return FH_ERR_ARG;
-  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_field_clauses(par->r_max, *par) != FH_OK) return FH_ERR_ARG;
+  if (!gain_triple_ok(par->gain_radius, par->hop_cost, par->min_gain, FH_GAIN_MAX_RADIUS, FH_GAIN_MAX_HOP_COST)) return FH_ERR_ARG;
   if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  if (!pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::GainArgs s;
-  reach_args(s.r, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
-             d_view_of, n_views, d_vehicles);
-  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
-  s.g = par->gain_radius;
-  s.g2 = par->gain_radius * par->gain_radius;
-  s.hop_cost = par->hop_cost;
-  s.min_gain = par->min_gain;
+  gain_args(s, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, d_goals, d_mask);
   s.records = d_records;
   hipLaunchKernelGGL(fhp::gain_goals_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, s);
   return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
 }
 
-// the words of a bitmap of blocks of edge `block` over the lattice; 0: a null grid, a dimension < 1 or a block outside 1..16;
-// FH_FAR_MAX_WORDS + 1: more than FH_FAR_MAX_WORDS (each partial product is tested, so nothing overflows)
-static int far_words(const fh_voxel_grid* grid, int block) {
-  if (!fhh::voxel_grid_ok(grid, false) || block < 1 || block > 16) return 0;
-  long long w = (((long long)grid->dims[0] + block - 1) / block + 63) / 64;
-  for (int k = 1; k < 3; k++) {
-    if (w > FH_FAR_MAX_WORDS) return FH_FAR_MAX_WORDS + 1;
-    w *= ((long long)grid->dims[k] + block - 1) / block;
-  }
-  return w > FH_FAR_MAX_WORDS ? FH_FAR_MAX_WORDS + 1 : (int)w;
-}
-
-size_t fh_far_work_bytes(const fh_voxel_grid* grid, int block, int n_views) {
-  const int W = far_words(grid, block);
-  if (W < 1 || W > FH_FAR_MAX_WORDS || n_views < 1) return 0;
-  return (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long) + (((size_t)n_views + 63) & ~(size_t)63);
-}
+size_t fh_far_work_bytes(const fh_voxel_grid* grid, int block, int n_views) { return far_bytes(grid, block, n_views, false, 0); }
 
 int fh_far_goals_device(void* stream, const fh_far_params* par, const fh_voxel_grid* map_grid, const unsigned* d_map_bits,
                         const fh_voxel_grid* grid, const unsigned char* d_flags, size_t view_stride, const int32_t* d_view_of, int n_views,
@@ -233,40 +329,22 @@ int fh_far_goals_device(void* stream, const fh_far_params* par, const fh_voxel_g
                         int32_t* d_mask, fh_far_record* d_records) {
   static_assert(sizeof(fh_far_params) == 64 && sizeof(fh_far_record) == 64 && FH_FAR_MAX_WORDS % 256 == 0, "include/fasterhip_far.h");
   if (!par) return FH_ERR_ARG;
-  // (K15's field clauses without r_max, which this chooser does not have: any r_max that passes stands in for it)
-  if (reach_field_clauses(1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
-  if (par->block < 1 || par->block > 16) return FH_ERR_ARG;
+  if (reach_field_clauses(1.0, *par) != FH_OK) return FH_ERR_ARG;
+  if (!block_ok(par->block)) return FH_ERR_ARG;
   if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
-  const int W = far_words(grid, par->block);
+  const int W = far_words(grid, par->block);  // (>= 1 after the clauses above, so `at.end` below is what the size function answers)
   if (W > FH_FAR_MAX_WORDS) return FH_ERR_ARG;
-  if (work_bytes < fh_far_work_bytes(grid, par->block, n_views)) return FH_ERR_ARG;
+  const FarLayout at = far_layout(W, n_views, false, 0);
+  if (work_bytes < at.end) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_work || !d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  if (!d_work || !pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::FarArgs s;
-  reach_args(s.r, 1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of,
-             n_views, d_vehicles);
-  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
-  s.B = par->block;
-  s.cx = (grid->dims[0] + s.B - 1) / s.B;  // (W <= FH_FAR_MAX_WORDS: the dims are far below 2^31 - 16)
-  s.cy = (grid->dims[1] + s.B - 1) / s.B;
-  s.cz = (grid->dims[2] + s.B - 1) / s.B;
-  s.wx = (s.cx + 63) / 64;
-  s.W = W;
-  s.n = n;
-  s.skip = d_skip;
-  s.sums = static_cast<unsigned long long*>(d_work);
-  const size_t need_bytes = ((size_t)n_views + 63) & ~(size_t)63;
-  s.need = static_cast<unsigned char*>(d_work) + (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long);
+  far_args(s, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_vehicles, n, d_work, W, at, d_goals, d_mask);
   s.records = d_records;
   const hipStream_t q = (hipStream_t)stream;
-  if (hipMemsetAsync(s.need, 0, need_bytes, q) != hipSuccess) {
+  if (hipMemsetAsync(s.need, 0, at.counts - at.need, q) != hipSuccess) {
     (void)hipGetLastError();
     return FH_ERR_DEVICE;
   }
@@ -281,23 +359,11 @@ static size_t bid_offers_offset(int n) { return spread_rows_offset(n) + (size_t)
 
 size_t fh_bid_work_bytes(int n) { return n <= 0 ? 0 : bid_offers_offset(n) + (size_t)n * 2 * sizeof(int32_t) + (size_t)n * 2 * sizeof(int32_t); }
 
-size_t fh_apart_work_bytes(const fh_voxel_grid* grid, int block, int n_views, int n) {
-  const size_t far = fh_far_work_bytes(grid, block, n_views);
-  if (far == 0 || n < 0) return 0;
-  return far + spread_rows_offset(n) + (size_t)n * sizeof(int32_t) + (size_t)n * sizeof(int32_t);
-}
+size_t fh_apart_work_bytes(const fh_voxel_grid* grid, int block, int n_views, int n) { return far_bytes(grid, block, n_views, false, n); }
 
-size_t fh_prospect_work_bytes(const fh_voxel_grid* grid, int block, int n_views) {
-  const size_t far = fh_far_work_bytes(grid, block, n_views);  // (0: a null grid, a dimension < 1, a block outside 1..16, too many words, n_views < 1)
-  if (far == 0) return 0;
-  return far + (size_t)n_views * 64u * (size_t)far_words(grid, block) * sizeof(uint16_t);
-}
+size_t fh_prospect_work_bytes(const fh_voxel_grid* grid, int block, int n_views) { return far_bytes(grid, block, n_views, true, 0); }
 
-size_t fh_stake_work_bytes(const fh_voxel_grid* grid, int block, int n_views, int n) {
-  const size_t pro = fh_prospect_work_bytes(grid, block, n_views);
-  if (pro == 0 || n < 0) return 0;
-  return pro + spread_rows_offset(n) + (size_t)n * sizeof(int32_t) + (size_t)n * sizeof(int32_t);
-}
+size_t fh_stake_work_bytes(const fh_voxel_grid* grid, int block, int n_views, int n) { return far_bytes(grid, block, n_views, true, n); }
 
 // (K23's clauses through min_gain, K21's tables, then K22's two and claim_blocks; K21's memset and need kernel, K23's one pass for the
 // bitmaps and the counts and K22's class kernel as they stand, then this chooser's count kernel and its pass kernel once per pass)
@@ -348,67 +414,35 @@ int fh_stake_goals_device(void* stream, const fh_stake_params* par, const fh_vox
                     fhp::STAKE_STANDING == fhp::FAR_SPREAD_STANDING,
                 "include/fasterhip_stake.h: K21's, K22's and K23's params, records, flags, limits and class bytes under its own names");
   if (!par) return FH_ERR_ARG;
-  if (reach_field_clauses(1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
-  if (par->block < 1 || par->block > 16) return FH_ERR_ARG;
-  if (par->gain_blocks < 0 || par->gain_blocks > FH_STAKE_MAX_BLOCKS) return FH_ERR_ARG;
-  if (par->hop_cost < 0 || par->hop_cost > FH_STAKE_MAX_HOP_COST) return FH_ERR_ARG;
-  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_field_clauses(1.0, *par) != FH_OK) return FH_ERR_ARG;
+  if (!block_ok(par->block)) return FH_ERR_ARG;
+  if (!gain_triple_ok(par->gain_blocks, par->hop_cost, par->min_gain, FH_STAKE_MAX_BLOCKS, FH_STAKE_MAX_HOP_COST)) return FH_ERR_ARG;
   if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
   const int W = far_words(grid, par->block);
   if (W > FH_STAKE_MAX_WORDS) return FH_ERR_ARG;
-  if (!std::isfinite(par->r_spread) || !(par->r_spread > 0.0)) return FH_ERR_ARG;
-  if (par->passes < 1 || par->passes > FH_STAKE_MAX_PASSES) return FH_ERR_ARG;
+  if (!spread_pair_ok(par->r_spread, par->passes, FH_STAKE_MAX_PASSES)) return FH_ERR_ARG;
   if (par->claim_blocks < 0 || par->claim_blocks > FH_STAKE_MAX_CLAIM_BLOCKS) return FH_ERR_ARG;
-  if (work_bytes < fh_stake_work_bytes(grid, par->block, n_views, n)) return FH_ERR_ARG;
+  const FarLayout at = far_layout(W, n_views, true, n);
+  if (work_bytes < at.end) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_work || !d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  if (!d_work || !pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::StakeArgs k;
   fhp::ProspectArgs& x = k.p;
   fhp::FarArgs& s = x.f;
-  reach_args(s.r, 1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of,
-             n_views, d_vehicles);
-  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
-  s.B = par->block;
-  s.cx = (grid->dims[0] + s.B - 1) / s.B;
-  s.cy = (grid->dims[1] + s.B - 1) / s.B;
-  s.cz = (grid->dims[2] + s.B - 1) / s.B;
-  s.wx = (s.cx + 63) / 64;
-  s.W = W;
-  s.n = n;
-  s.skip = d_skip;
-  unsigned char* const work = static_cast<unsigned char*>(d_work);
-  s.sums = static_cast<unsigned long long*>(d_work);
-  const size_t need_bytes = ((size_t)n_views + 63) & ~(size_t)63;
-  s.need = work + (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long);
-  s.records = nullptr;
-  x.g = par->gain_blocks;
-  x.hop_cost = par->hop_cost;
-  x.min_gain = par->min_gain;
-  x.counts = reinterpret_cast<uint16_t*>(s.need + need_bytes);  // (= work + K21's bytes: a multiple of 8)
-  x.records = nullptr;
+  far_args(s, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_vehicles, n, d_work, W, at, d_goals, d_mask);
+  prospect_args(x, *par, d_work, at, nullptr);
   fhp::FarSpreadArgs c;  // what K22's class kernel reads: the judge's values, the labels and the two tables it writes
   c.f = s;
-  c.s2 = par->r_spread * par->r_spread;
-  c.pass = 0; c.passes = par->passes;
-  c.group = d_group;
-  c.cls = work + fh_prospect_work_bytes(grid, par->block, n_views);  // (K23's bytes: a multiple of 8)
-  c.grp = reinterpret_cast<int32_t*>(c.cls + spread_rows_offset(n));
-  c.lower = c.grp + n;
-  c.records = nullptr;
+  far_spread_args(c, *par, d_group, d_work, at, nullptr);
   k.s2 = c.s2;
   k.pass = 0; k.passes = par->passes;
   k.k = par->claim_blocks;
   k.cls = c.cls; k.grp = c.grp; k.lower = c.lower;
   k.records = d_records;
   const hipStream_t q = (hipStream_t)stream;
-  if (hipMemsetAsync(s.need, 0, need_bytes, q) != hipSuccess) {
+  if (hipMemsetAsync(s.need, 0, at.counts - at.need, q) != hipSuccess) {
     (void)hipGetLastError();
     return FH_ERR_DEVICE;
   }
@@ -450,49 +484,24 @@ int fh_prospect_goals_device(void* stream, const fh_prospect_params* par, const 
                     (FH_PROSPECT_ALL_POOR & (FH_APART_UNSETTLED | FH_APART_CLAIMED | FH_FAR_SKIPPED)) == 0,
                 "include/fasterhip_prospect.h: K21's params, record, skip flag and word cap under its own names");
   if (!par) return FH_ERR_ARG;
-  if (reach_field_clauses(1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
-  if (par->block < 1 || par->block > 16) return FH_ERR_ARG;
-  if (par->gain_blocks < 0 || par->gain_blocks > FH_PROSPECT_MAX_BLOCKS) return FH_ERR_ARG;
-  if (par->hop_cost < 0 || par->hop_cost > FH_PROSPECT_MAX_HOP_COST) return FH_ERR_ARG;
-  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_field_clauses(1.0, *par) != FH_OK) return FH_ERR_ARG;
+  if (!block_ok(par->block)) return FH_ERR_ARG;
+  if (!gain_triple_ok(par->gain_blocks, par->hop_cost, par->min_gain, FH_PROSPECT_MAX_BLOCKS, FH_PROSPECT_MAX_HOP_COST)) return FH_ERR_ARG;
   if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
   const int W = far_words(grid, par->block);
   if (W > FH_PROSPECT_MAX_WORDS) return FH_ERR_ARG;
-  if (work_bytes < fh_prospect_work_bytes(grid, par->block, n_views)) return FH_ERR_ARG;
+  const FarLayout at = far_layout(W, n_views, true, 0);
+  if (work_bytes < at.end) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_work || !d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  if (!d_work || !pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::ProspectArgs x;
   fhp::FarArgs& s = x.f;
-  reach_args(s.r, 1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of,
-             n_views, d_vehicles);
-  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
-  s.B = par->block;
-  s.cx = (grid->dims[0] + s.B - 1) / s.B;
-  s.cy = (grid->dims[1] + s.B - 1) / s.B;
-  s.cz = (grid->dims[2] + s.B - 1) / s.B;
-  s.wx = (s.cx + 63) / 64;
-  s.W = W;
-  s.n = n;
-  s.skip = d_skip;
-  unsigned char* const work = static_cast<unsigned char*>(d_work);
-  s.sums = static_cast<unsigned long long*>(d_work);
-  const size_t need_bytes = ((size_t)n_views + 63) & ~(size_t)63;
-  s.need = work + (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long);
-  s.records = nullptr;
-  x.g = par->gain_blocks;
-  x.hop_cost = par->hop_cost;
-  x.min_gain = par->min_gain;
-  x.counts = reinterpret_cast<uint16_t*>(s.need + need_bytes);  // (= work + K21's bytes: a multiple of 8)
-  x.records = d_records;
+  far_args(s, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_vehicles, n, d_work, W, at, d_goals, d_mask);
+  prospect_args(x, *par, d_work, at, d_records);
   const hipStream_t q = (hipStream_t)stream;
-  if (hipMemsetAsync(s.need, 0, need_bytes, q) != hipSuccess) {
+  if (hipMemsetAsync(s.need, 0, at.counts - at.need, q) != hipSuccess) {
     (void)hipGetLastError();
     return FH_ERR_DEVICE;
   }
@@ -519,50 +528,24 @@ int fh_apart_goals_device(void* stream, const fh_apart_params* par, const fh_vox
                     offsetof(fh_apart_record, members) == offsetof(fh_far_record, members) && offsetof(fh_apart_record, hops) == offsetof(fh_far_record, hops),
                 "include/fasterhip_apart.h: K21's params and record, K16's flags and pass limits under its own names");
   if (!par) return FH_ERR_ARG;
-  if (reach_field_clauses(1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
-  if (par->block < 1 || par->block > 16) return FH_ERR_ARG;
+  if (reach_field_clauses(1.0, *par) != FH_OK) return FH_ERR_ARG;
+  if (!block_ok(par->block)) return FH_ERR_ARG;
   if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
   const int W = far_words(grid, par->block);
   if (W > FH_FAR_MAX_WORDS) return FH_ERR_ARG;
-  if (!std::isfinite(par->r_spread) || !(par->r_spread > 0.0)) return FH_ERR_ARG;
-  if (par->passes < 1 || par->passes > FH_APART_MAX_PASSES) return FH_ERR_ARG;
-  if (work_bytes < fh_apart_work_bytes(grid, par->block, n_views, n)) return FH_ERR_ARG;
+  if (!spread_pair_ok(par->r_spread, par->passes, FH_APART_MAX_PASSES)) return FH_ERR_ARG;
+  const FarLayout at = far_layout(W, n_views, false, n);
+  if (work_bytes < at.end) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_work || !d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  if (!d_work || !pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::FarSpreadArgs x;
   fhp::FarArgs& s = x.f;
-  reach_args(s.r, 1.0, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of,
-             n_views, d_vehicles);
-  s.r.goals = d_goals; s.r.mask = d_mask; s.r.records = nullptr;
-  s.B = par->block;
-  s.cx = (grid->dims[0] + s.B - 1) / s.B;
-  s.cy = (grid->dims[1] + s.B - 1) / s.B;
-  s.cz = (grid->dims[2] + s.B - 1) / s.B;
-  s.wx = (s.cx + 63) / 64;
-  s.W = W;
-  s.n = n;
-  s.skip = d_skip;
-  unsigned char* const work = static_cast<unsigned char*>(d_work);
-  s.sums = static_cast<unsigned long long*>(d_work);
-  const size_t need_bytes = ((size_t)n_views + 63) & ~(size_t)63;
-  s.need = work + (size_t)n_views * 4u * (size_t)W * sizeof(unsigned long long);
-  s.records = nullptr;
-  x.s2 = par->r_spread * par->r_spread;
-  x.pass = 0; x.passes = par->passes;
-  x.group = d_group;
-  x.cls = s.need + need_bytes;  // (= work + fh_far_work_bytes: a multiple of 8)
-  x.grp = reinterpret_cast<int32_t*>(x.cls + spread_rows_offset(n));
-  x.lower = x.grp + n;
-  x.records = d_records;
+  far_args(s, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_skip, d_vehicles, n, d_work, W, at, d_goals, d_mask);
+  far_spread_args(x, *par, d_group, d_work, at, d_records);
   const hipStream_t q = (hipStream_t)stream;
-  if (hipMemsetAsync(s.need, 0, need_bytes, q) != hipSuccess) {
+  if (hipMemsetAsync(s.need, 0, at.counts - at.need, q) != hipSuccess) {
     (void)hipGetLastError();
     return FH_ERR_DEVICE;
   }
@@ -600,59 +583,24 @@ int fh_bid_goals_device(void* stream, const fh_bid_params* par, const fh_voxel_g
                     offsetof(fh_bid_record, covered) == offsetof(fh_team_record, covered),
                 "include/fasterhip_bid.h: K18's record, `lower` read as `rivals` and `reserved0` as `searches`");
   if (!par) return FH_ERR_ARG;
-  if (reach_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, view_stride, n_views,
-                    n) != FH_OK)
-    return FH_ERR_ARG;
-  if (!std::isfinite(par->r_spread) || !(par->r_spread > 0.0)) return FH_ERR_ARG;
-  if (par->passes < 1 || par->passes > FH_BID_MAX_PASSES) return FH_ERR_ARG;
-  if (par->gain_radius < 0 || par->gain_radius > FH_BID_MAX_RADIUS) return FH_ERR_ARG;
-  if (par->hop_cost < 0 || par->hop_cost > FH_BID_MAX_HOP_COST) return FH_ERR_ARG;
-  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_clauses(*par, map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
+  if (!spread_pair_ok(par->r_spread, par->passes, FH_BID_MAX_PASSES)) return FH_ERR_ARG;
+  if (!gain_triple_ok(par->gain_radius, par->hop_cost, par->min_gain, FH_BID_MAX_RADIUS, FH_BID_MAX_HOP_COST)) return FH_ERR_ARG;
   if (par->claim_radius < -1 || par->claim_radius > FH_BID_MAX_RADIUS) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  if (!pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
   if (!d_work) return FH_ERR_ARG;
   if (work_bytes < fh_bid_work_bytes(n)) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::BidArgs s;
-  reach_args(s.gn.r, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
-             d_view_of, n_views, d_vehicles);
-  s.gn.r.goals = d_goals; s.gn.r.mask = d_mask; s.gn.r.records = nullptr;
-  s.gn.g = par->gain_radius;
-  s.gn.g2 = par->gain_radius * par->gain_radius;
-  s.gn.hop_cost = par->hop_cost;
-  s.gn.min_gain = par->min_gain;
-  s.gn.records = nullptr;
-  // the interaction radius: a peer beyond it cannot touch the ball of a candidate
-  const double r_int = par->claim_radius < 0 ? par->r_spread : std::fmax(par->r_spread, (double)(par->gain_radius + par->claim_radius + 1) * grid->res);
-  const double reach = (par->r_max + par->r_max) + r_int, near = par->r_max + r_int;
-  s.s2 = par->r_spread * par->r_spread;
-  s.reach2 = reach * reach;
-  s.near2 = near * near;
-  s.n = n; s.pass = 0; s.last = 0;
-  s.cr = par->claim_radius;
-  s.cr2 = par->claim_radius * par->claim_radius;
-  s.group = d_group;
-  unsigned char* const work = static_cast<unsigned char*>(d_work);
-  s.cls = work;
-  s.rows = reinterpret_cast<int32_t*>(work + spread_rows_offset(n));
-  s.offers = reinterpret_cast<int32_t*>(work + bid_offers_offset(n));
+  team_args(s, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_group, d_vehicles, n, d_work, d_goals, d_mask);
+  s.last = 0;
+  s.offers = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(d_work) + bid_offers_offset(n));
   s.decided = s.offers + 2 * (size_t)n;
   s.records = d_records;
-  fhp::SpreadArgs c;  // the class kernel of fh_spread.hip.hpp as it is: it reads the vehicles and writes the class bytes
-  c.r = s.gn.r;
-  c.s2 = s.s2; c.reach2 = s.reach2; c.near2 = s.near2;
-  c.n = n; c.pass = 0;
-  c.group = d_group;
-  c.cls = work;
-  c.rows = s.rows;
-  c.records = nullptr;
+  fhp::SpreadArgs c;
+  spread_class_args(c, s, d_work);
   const hipStream_t q = (hipStream_t)stream;
   hipLaunchKernelGGL(fhp::spread_class_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, c);
   hipLaunchKernelGGL(fhp::bid_peers_kernel, dim3((unsigned)n), dim3(64), 0, q, s);
@@ -676,29 +624,15 @@ int fh_sight_goals_device(void* stream, const fh_sight_params* par, const fh_vox
                     offsetof(fh_sight_record, ball_gain) == 56 && offsetof(fh_sight_record, walls) == 60,
                 "include/fasterhip_sight.h: K17's params, and K17's record through best_gain");
   if (!par) return FH_ERR_ARG;
-  if (reach_field_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops) != FH_OK) return FH_ERR_ARG;
-  if (par->gain_radius < 0 || par->gain_radius > FH_SIGHT_MAX_RADIUS) return FH_ERR_ARG;
-  if (par->hop_cost < 0 || par->hop_cost > FH_SIGHT_MAX_HOP_COST) return FH_ERR_ARG;
-  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_field_clauses(par->r_max, *par) != FH_OK) return FH_ERR_ARG;
+  if (!gain_triple_ok(par->gain_radius, par->hop_cost, par->min_gain, FH_SIGHT_MAX_RADIUS, FH_SIGHT_MAX_HOP_COST)) return FH_ERR_ARG;
   if (reach_table_clauses(map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  if (!pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::SightArgs s;
-  reach_args(s.gn.r, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
-             d_view_of, n_views, d_vehicles);
-  s.gn.r.goals = d_goals; s.gn.r.mask = d_mask; s.gn.r.records = nullptr;
-  s.gn.g = par->gain_radius;
-  s.gn.g2 = par->gain_radius * par->gain_radius;
-  s.gn.hop_cost = par->hop_cost;
-  s.gn.min_gain = par->min_gain;
-  s.gn.records = nullptr;
+  gain_args(s.gn, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_vehicles, d_goals, d_mask);
   s.records = d_records;
   hipLaunchKernelGGL(fhp::sight_goals_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, s);
   return hipGetLastError() == hipSuccess ? FH_OK : FH_ERR_DEVICE;
@@ -710,56 +644,21 @@ int fh_team_goals_device(void* stream, const fh_team_params* par, const fh_voxel
                          int32_t* d_mask, fh_team_record* d_records) {
   static_assert(FH_TEAM_MAX_RADIUS == FH_GAIN_MAX_RADIUS && FH_TEAM_MAX_HOP_COST == FH_GAIN_MAX_HOP_COST, "include/fasterhip_team.h");
   if (!par) return FH_ERR_ARG;
-  if (reach_clauses(par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, view_stride, n_views,
-                    n) != FH_OK)
-    return FH_ERR_ARG;
-  if (!std::isfinite(par->r_spread) || !(par->r_spread > 0.0)) return FH_ERR_ARG;
-  if (par->passes < 1 || par->passes > FH_TEAM_MAX_PASSES) return FH_ERR_ARG;
-  if (par->gain_radius < 0 || par->gain_radius > FH_TEAM_MAX_RADIUS) return FH_ERR_ARG;
-  if (par->hop_cost < 0 || par->hop_cost > FH_TEAM_MAX_HOP_COST) return FH_ERR_ARG;
-  if (par->min_gain < 0) return FH_ERR_ARG;
+  if (reach_clauses(*par, map_grid, d_map_bits, grid, view_stride, n_views, n) != FH_OK) return FH_ERR_ARG;
+  if (!spread_pair_ok(par->r_spread, par->passes, FH_TEAM_MAX_PASSES)) return FH_ERR_ARG;
+  if (!gain_triple_ok(par->gain_radius, par->hop_cost, par->min_gain, FH_TEAM_MAX_RADIUS, FH_TEAM_MAX_HOP_COST)) return FH_ERR_ARG;
   if (par->claim_radius < -1 || par->claim_radius > FH_TEAM_MAX_RADIUS) return FH_ERR_ARG;
   if (n == 0) return FH_OK;
-  if (!d_flags || !d_vehicles || !d_goals || !d_mask || !d_records) return FH_ERR_ARG;
+  if (!pointers_ok(d_flags, d_vehicles, d_goals, d_mask, d_records)) return FH_ERR_ARG;
   if (!d_work) return FH_ERR_ARG;
   if (work_bytes < fh_spread_work_bytes(n)) return FH_ERR_ARG;
-  hipPointerAttribute_t where;
-  if (hipPointerGetAttributes(&where, d_records) != hipSuccess || where.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return FH_ERR_DEVICE;
-  }
-  fhh::DeviceScope scope(where.device);
+  fhh::DeviceScope scope(device_of(d_records));
   if (!scope.ok) return FH_ERR_DEVICE;
   fhp::TeamArgs s;
-  reach_args(s.gn.r, par->r_max, par->r_avoid, par->z_lo, par->z_hi, par->want, par->max_hops, map_grid, d_map_bits, grid, d_flags, view_stride,
-             d_view_of, n_views, d_vehicles);
-  s.gn.r.goals = d_goals; s.gn.r.mask = d_mask; s.gn.r.records = nullptr;
-  s.gn.g = par->gain_radius;
-  s.gn.g2 = par->gain_radius * par->gain_radius;
-  s.gn.hop_cost = par->hop_cost;
-  s.gn.min_gain = par->min_gain;
-  s.gn.records = nullptr;
-  // the interaction radius: a peer beyond it cannot touch the ball of a candidate
-  const double r_int = par->claim_radius < 0 ? par->r_spread : std::fmax(par->r_spread, (double)(par->gain_radius + par->claim_radius + 1) * grid->res);
-  const double reach = (par->r_max + par->r_max) + r_int, near = par->r_max + r_int;
-  s.s2 = par->r_spread * par->r_spread;
-  s.reach2 = reach * reach;
-  s.near2 = near * near;
-  s.n = n; s.pass = 0;
-  s.cr = par->claim_radius;
-  s.cr2 = par->claim_radius * par->claim_radius;
-  s.group = d_group;
-  s.cls = static_cast<unsigned char*>(d_work);
-  s.rows = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(d_work) + spread_rows_offset(n));
+  team_args(s, *par, map_grid, d_map_bits, grid, d_flags, view_stride, d_view_of, n_views, d_group, d_vehicles, n, d_work, d_goals, d_mask);
   s.records = d_records;
-  fhp::SpreadArgs c;  // the class kernel of fh_spread.hip.hpp as it is: it reads the vehicles and writes the class bytes
-  c.r = s.gn.r;
-  c.s2 = s.s2; c.reach2 = s.reach2; c.near2 = s.near2;
-  c.n = n; c.pass = 0;
-  c.group = d_group;
-  c.cls = static_cast<unsigned char*>(d_work);
-  c.rows = s.rows;
-  c.records = nullptr;
+  fhp::SpreadArgs c;
+  spread_class_args(c, s, d_work);
   const hipStream_t q = (hipStream_t)stream;
   hipLaunchKernelGGL(fhp::spread_class_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, q, c);
   hipLaunchKernelGGL(fhp::team_peers_kernel, dim3((unsigned)n), dim3(64), 0, q, s);
