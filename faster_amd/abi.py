@@ -522,6 +522,49 @@ def traffic_points_per_sample(hull):
     return 7 if float(hull) > 0 else 1
 
 
+# fh_obstacle, fh_obstacle_params, fh_obstacle_audit_params, fh_plan_obstacle_audit: things that move and are no fleet member, as points
+# and bits, and the audit against them (include/fasterhip_obstacles.h)
+FH_OBSTACLE_ON = 1
+FH_OBSTACLE_MAX_SAMPLES, FH_OBSTACLE_MAX_TICK, FH_OBSTACLE_AUDIT_CHUNK = 512, 1 << 62, 64
+FH_OBSTACLE_BAD_PLAN, FH_OBSTACLE_NOT_FINITE, FH_OBSTACLE_HIT = 1, 4, 8
+obstacle_dtype = np.dtype([("p0", "<f8", (3,)), ("v", "<f8", (3,)), ("radius", "<f8"), ("flags", "<i4"), ("reserved", "<i4")], align=True)
+obstacle_params_dtype = np.dtype([("range", "<f8"), ("r_detect", "<f8"), ("dc", "<f8"), ("samples", "<i4"), ("stride", "<i4"), ("points", "<i4"),
+                                  ("first_point", "<i4"), ("first_instant", "<i4"), ("window", "<i4"), ("reserved", "<i4", (4,))], align=True)
+obstacle_audit_params_dtype = np.dtype([("r", "<f8"), ("dc", "<f8"), ("stride", "<i4"), ("count", "<i4"), ("reserved", "<i4", (2,))], align=True)
+plan_obstacle_audit_dtype = np.dtype([("flags", "<i4"), ("n_tested", "<i4"), ("first", "<i4"), ("first_obstacle", "<i4"), ("worst", "<i4"),
+                                      ("worst_obstacle", "<i4"), ("n_hit", "<i4"), ("reserved", "<i4"), ("min_d2", "<f8"),
+                                      ("reserved_d", "<f8", (3,))], align=True)
+assert (obstacle_dtype.itemsize, obstacle_params_dtype.itemsize, obstacle_audit_params_dtype.itemsize, plan_obstacle_audit_dtype.itemsize) == (64, 64, 32, 64)
+
+
+def make_obstacles(p0, v=None, radius=0.0, on=True):
+    """[m] fh_obstacle from [m][3] positions at clock 0, [m][3] velocities (None: at rest) and radii (a number or [m])."""
+    p0 = np.asarray(p0, dtype=np.float64).reshape(-1, 3)
+    o = np.zeros(len(p0), dtype=obstacle_dtype)
+    o["p0"], o["radius"], o["flags"] = p0, radius, FH_OBSTACLE_ON if on else 0
+    if v is not None:
+        o["v"] = np.asarray(v, dtype=np.float64).reshape(-1, 3)
+    return o
+
+
+def default_obstacle_params(samples, stride, range, dc, r_detect=0.0, points=7, first_point=0, first_instant=0, window=0):  # noqa: A002
+    """fh_obstacle_params: `samples` instants of every obstacle's straight flight, `stride` states of `dc` apart from first_instant on,
+    shown to vehicle i when a shown sample of i's own plan within `window` samples of the same instant lies nearer than range + the
+    obstacle's radius, once i stands nearer than r_detect to where the obstacle is now (0: no detection, everything is known)."""
+    p = np.zeros((), dtype=obstacle_params_dtype)
+    p["range"], p["r_detect"], p["dc"], p["samples"], p["stride"], p["points"] = range, r_detect, dc, samples, stride, points
+    p["first_point"], p["first_instant"], p["window"] = first_point, first_instant, window
+    return p
+
+
+def default_obstacle_audit_params(r, dc, stride=1, count=0):
+    """fh_obstacle_audit_params: an obstacle hits a vehicle of radius r at a tested instant when their centres are nearer than
+    r + the obstacle's radius; every state of the plan is tested (stride 1, count 0: all)."""
+    p = np.zeros((), dtype=obstacle_audit_params_dtype)
+    p["r"], p["dc"], p["stride"], p["count"] = r, dc, stride, count
+    return p
+
+
 def certify_tol(corridor, state=None, box=None, cost_rel=None):
     """fh_certify_tol; one number stands for all four (the project's own number for "violated" is fh_params.feas_tol)."""
     t = np.zeros((), dtype=certify_tol_dtype)

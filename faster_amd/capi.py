@@ -74,6 +74,8 @@ FAR_SPREAD_SYMBOLS = ["fh_apart_work_bytes", "fh_apart_goals_device"]
 FAR_GAIN_SYMBOLS = ["fh_prospect_work_bytes", "fh_prospect_goals_device"]
 # include/fasterhip_stake.h
 FAR_TEAM_SYMBOLS = ["fh_stake_work_bytes", "fh_stake_goals_device"]
+# include/fasterhip_obstacles.h
+OBSTACLE_SYMBOLS = ["fh_fleet_obstacles_device", "fh_fleet_obstacle_audit_device"]
 
 _LIB = None
 
@@ -339,6 +341,10 @@ def lib():
         L.fh_fleet_link_groups_device.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp]
         L.fh_fleet_link_groups_los_device.restype = i32
         L.fh_fleet_link_groups_los_device.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp]
+        L.fh_fleet_obstacles_device.restype = i32
+        L.fh_fleet_obstacles_device.argtypes = [vp, vp, vp, i32, ctypes.c_int64, vp, vp, i32, i32, vp, i32, vp, i32]
+        L.fh_fleet_obstacle_audit_device.restype = i32
+        L.fh_fleet_obstacle_audit_device.argtypes = [vp, vp, vp, i32, ctypes.c_int64, vp, vp, i32, i32, vp]
         L.fh_fleet_link_merge_device.restype = i32
         L.fh_fleet_link_merge_device.argtypes = [vp, vp, i32, vp, ctypes.c_size_t, ctypes.c_size_t, vp, i32, i32]
         L.fh_map_view_list_device.restype = i32
@@ -1041,6 +1047,24 @@ class Context:
         p = _one_record(par, "traffic", "fleet_traffic_device")
         self._check(lib().fh_fleet_traffic_device(self._h, abi.ptr(p), d_vehicles, d_plans, int(n), int(max_states), d_cloud, int(n_cloud),
                                                   d_point_mask, int(mask_words)), "fh_fleet_traffic_device")
+
+    def fleet_obstacles_device(self, par, d_obstacles, m, tick0, d_vehicles, d_plans, n, max_states, d_cloud, n_cloud, d_point_mask, mask_words):
+        """fh_fleet_obstacles_device: the predicted positions of m moving obstacles ([m] abi.obstacle_dtype on the device, the clock at
+        tick0) as cloud points from par["first_point"] on and, in row i, the bits of the samples that vehicle i's own plan comes near
+        at the same sampled instant once i has detected the obstacle; par: one abi.obstacle_params_dtype record.  Asynchronous on the
+        context's stream (include/fasterhip_obstacles.h)."""
+        p = _one_record(par, "obstacle", "fleet_obstacles_device")
+        self._check(lib().fh_fleet_obstacles_device(self._h, abi.ptr(p), d_obstacles, int(m), int(tick0), d_vehicles, d_plans, int(n),
+                                                    int(max_states), d_cloud, int(n_cloud), d_point_mask, int(mask_words)),
+                    "fh_fleet_obstacles_device")
+
+    def fleet_obstacle_audit_device(self, par, d_obstacles, m, tick0, d_vehicles, d_plans, n, max_states, d_out):
+        """fh_fleet_obstacle_audit_device: d_out[i] = the abi.plan_obstacle_audit_dtype record of vehicle i's committed plan against
+        where the m obstacles are at the same instants; par: one abi.obstacle_audit_params_dtype record.  A measurement, asynchronous
+        on the context's stream (include/fasterhip_obstacles.h)."""
+        p = _one_record(par, "obstacle_audit", "fleet_obstacle_audit_device")
+        self._check(lib().fh_fleet_obstacle_audit_device(self._h, abi.ptr(p), d_obstacles, int(m), int(tick0), d_vehicles, d_plans, int(n),
+                                                         int(max_states), d_out), "fh_fleet_obstacle_audit_device")
 
     def fleet_traffic_timed_device(self, par, d_vehicles, d_plans, n, max_states, d_cloud, n_cloud, d_point_mask, mask_words):
         """fh_fleet_traffic_timed_device: fleet_traffic_device's points, and in row i the bits of the samples that vehicle i's own plan comes

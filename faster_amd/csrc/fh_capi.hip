@@ -28,6 +28,7 @@
 #include "../../include/fasterhip_rounds.h"
 #include "../../include/fasterhip_link.h"
 #include "../../include/fasterhip_link_los.h"
+#include "../../include/fasterhip_obstacles.h"
 #include "fh_policy.hpp"  // (host only; before fh_solve: the look periods are named there)
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
@@ -40,6 +41,7 @@
 #include "fh_traffic.hip.hpp"
 #include "fh_check.hip.hpp"
 #include "fh_traffic_timed.hip.hpp"  // (after fh_check: where its mask kernels have lain in the code object since they came)
+#include "fh_obstacles.hip.hpp"      // (behind the traffic headers it builds on; fh_rounds and fh_link stay the last two: tests/test_link_abi.py)
 #include "fh_rounds.hip.hpp"         // (after every other device header: the functions of before keep their place and their bytes)
 #include "fh_link.hip.hpp"           // (and this one after that one, for the same reason)
 #include "fh_host.hpp"
@@ -97,6 +99,14 @@ enum Buf {
   LINK_LABELS,      // the two copies of the labels ([2][n_views]) that link_hook_kernel lowers and link_jump_kernel reads and writes in turn
   LINK_LOS_KEPT,    // link_los_narrow_kernel writes, per vehicle and turn of its walk, the ballot of the candidates in line of sight
                     // (rows of fh::LINK_LOS_TURNS words); link_los_hook_kernel reads them where a vehicle has more than a row of LINK_LISTS
+  // fh_fleet_obstacles_device (obstacle_stage below): its own four, so that calls of it and of the traffic entry points may alternate on
+  // one context; each call writes all it reads.  fh_fleet_obstacle_audit_device has no working buffer.
+  OBSTACLE_SAMPLES,    // obstacle_points{1,7}_kernel write centre, show word and obstacle of every sample (whole chunks of 64);
+                       // obstacle_mask{1,7}_kernel read them
+  OBSTACLE_MORE,       // obstacle_points{1,7}_kernel write now[o] and the squared reach of every sample; obstacle_mask{1,7}_kernel read them
+  OBSTACLE_BOXES,      // obstacle_points{1,7}_kernel write the grown box of the shown centres of every chunk; obstacle_mask{1,7}_kernel read them
+  OBSTACLE_OBSERVERS,  // obstacle_observers_kernel writes centre and show word of every sample of every vehicle's own plan (whole chunks
+                       // of 64); obstacle_mask{1,7}_kernel stage a row's samples from them
   N_BUFS
 };
 
@@ -1187,6 +1197,90 @@ int fh_fleet_traffic_timed_device(fh_ctx* ctx, const fh_traffic_timed_params* pa
   return traffic_stage(ctx, par->range, par->hull, par->samples, par->stride, par->rule, par->first_point, par->first_instant, window,
                        fh::traffic_timed_mask1_kernel, fh::traffic_timed_mask7_kernel, d_vehicles, d_plans, n, max_states, d_cloud_xyz,
                        n_cloud, d_point_mask, mask_words);
+}
+
+// ---- moving obstacles (include/fasterhip_obstacles.h): their predicted positions as cloud points and mask bits; the audit against them ----
+static bool obstacle_tick_ok(int64_t tick0) { return tick0 >= 0 && tick0 <= FH_OBSTACLE_MAX_TICK; }
+
+int fh_fleet_obstacles_device(fh_ctx* ctx, const fh_obstacle_params* par, const fh_obstacle* d_obstacles, int m, int64_t tick0,
+                              const fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states, double* d_cloud_xyz,
+                              int n_cloud, uint32_t* d_point_mask, int mask_words) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->range) || !(par->range > 0)) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->r_detect)) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->dc) || !(par->dc > 0)) return FH_ERR_ARG;
+  if (par->samples < 1 || par->samples > FH_OBSTACLE_MAX_SAMPLES) return FH_ERR_ARG;
+  if (par->stride < 1) return FH_ERR_ARG;
+  if (par->points != 1 && par->points != 7) return FH_ERR_ARG;
+  if (par->first_point < 0 || par->first_point % 32 != 0) return FH_ERR_ARG;
+  if (par->first_instant < 0) return FH_ERR_ARG;
+  if (par->window < 0) return FH_ERR_ARG;
+  const long long n_own = (long long)n * (long long)par->samples;  // (below 2^41)
+  if (n < 0 || m < 0 || max_states < 1 || n_own > (long long)INT32_MAX) return FH_ERR_ARG;
+  if (!obstacle_tick_ok(tick0)) return FH_ERR_ARG;
+  const int pps = par->points;
+  const long long n_samples = (long long)m * (long long)par->samples;  // (below 2^41: n_samples * pps is safe in 64 bits)
+  const long long end_point = (long long)par->first_point + n_samples * pps;
+  if (end_point > (long long)n_cloud || end_point > (long long)mask_words * 32) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0 || m == 0) return FH_OK;
+  if (!d_obstacles || !d_vehicles || !d_plans || !d_cloud_xyz || !d_point_mask) return FH_ERR_ARG;
+  const int window = std::min(par->window, par->samples - 1);  // (any window >= S - 1 is every sampled instant)
+  fh::ObstacleArgs A;
+  fh::TrafficArgs& a = A.t;
+  a.range = par->range; a.range2 = par->range * par->range; a.hull = 0.0;
+  a.samples = par->samples; a.stride = par->stride; a.rule = FH_TRAFFIC_ALL; a.first_point = par->first_point;
+  a.n = n; a.max_states = max_states; a.n_samples = (int)n_samples; a.n_chunks = (int)((n_samples + 63) / 64);
+  a.mask_words = mask_words; a.first_word = par->first_point / 32; a.n_words = (int)((end_point + 31) / 32) - a.first_word;
+  a.first_instant = par->first_instant; a.window = window; a.span = std::min(2 * window + 1, par->samples);
+  a.vehicles = d_vehicles; a.plans = d_plans; a.cloud = d_cloud_xyz; a.mask = d_point_mask;
+  A.dc = par->dc; A.detect2 = par->r_detect * par->r_detect; A.tick0 = (long long)tick0;
+  A.m = m; A.detect = par->r_detect != 0.0 ? 1 : 0;
+  A.n_own = (int)n_own; A.n_own_chunks = (int)((n_own + 63) / 64);
+  A.obstacles = d_obstacles;
+  int rc;
+  if ((rc = ensure(ctx, OBSTACLE_SAMPLES, sizeof(fh::TrafficRec) * 64 * (size_t)a.n_chunks)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, OBSTACLE_MORE, sizeof(fh::ObstacleMore) * 64 * (size_t)a.n_chunks)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, OBSTACLE_BOXES, sizeof(fh::TrafficBox) * (size_t)a.n_chunks)) != FH_OK) return rc;
+  if ((rc = ensure(ctx, OBSTACLE_OBSERVERS, sizeof(fh::TrafficRec) * 64 * (size_t)A.n_own_chunks)) != FH_OK) return rc;
+  a.recs = ctx->buf[OBSTACLE_SAMPLES].as<fh::TrafficRec>();
+  a.boxes = ctx->buf[OBSTACLE_BOXES].as<fh::TrafficBox>();
+  A.more = ctx->buf[OBSTACLE_MORE].as<fh::ObstacleMore>();
+  A.own = ctx->buf[OBSTACLE_OBSERVERS].as<fh::TrafficRec>();
+  const dim3 chunks((unsigned)a.n_chunks), own_chunks((unsigned)A.n_own_chunks);
+  const dim3 rows((unsigned)((a.n_chunks + 63) / 64), (unsigned)std::min(n, fh::TRAFFIC_GRID_ROWS));
+  hipLaunchKernelGGL(pps == 7 ? fh::obstacle_points7_kernel : fh::obstacle_points1_kernel, chunks, dim3(64), 0, ctx->stream, A);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(fh::obstacle_observers_kernel, own_chunks, dim3(64), 0, ctx->stream, A);
+  FH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pps == 7 ? fh::obstacle_mask7_kernel : fh::obstacle_mask1_kernel, rows, dim3(64), 0, ctx->stream, A);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
+}
+
+int fh_fleet_obstacle_audit_device(fh_ctx* ctx, const fh_obstacle_audit_params* par, const fh_obstacle* d_obstacles, int m, int64_t tick0,
+                                   const fh_vehicle* d_vehicles, const fh_state* d_plans, int n, int max_states,
+                                   fh_plan_obstacle_audit* d_out) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->r)) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->dc) || !(par->dc > 0)) return FH_ERR_ARG;
+  if (par->stride < 1) return FH_ERR_ARG;
+  if (par->count < 0) return FH_ERR_ARG;
+  if (n < 0 || m < 0 || max_states < 1) return FH_ERR_ARG;
+  if (!obstacle_tick_ok(tick0)) return FH_ERR_ARG;
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (n == 0) return FH_OK;
+  if (!d_vehicles || !d_plans || !d_out || (m > 0 && !d_obstacles)) return FH_ERR_ARG;
+  fh::ObstacleAuditArgs a;
+  a.r = par->r; a.dc = par->dc; a.tick0 = (long long)tick0;
+  a.stride = par->stride; a.count = par->count; a.n = n; a.m = m; a.max_states = max_states;
+  a.obstacles = d_obstacles; a.vehicles = d_vehicles; a.plans = d_plans;
+  a.out = d_out;
+  hipLaunchKernelGGL(fh::obstacle_audit_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
 }
 
 // ---- the commit check (include/fasterhip_check.h): backup before the commit; the cell grid around check_boxes_kernel and

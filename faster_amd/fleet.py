@@ -23,6 +23,12 @@ near where vehicle i stands; with timed=True include/fasterhip_traffic_timed.h: 
 
     sense -> observe -> traffic -> replan -> next_goals
 
+enable_obstacles() does the same for things that move and are no fleet member (include/fasterhip_obstacles.h): obstacles() writes the
+predicted positions of balls that fly a straight line behind the traffic's points and shows vehicle i the samples its own plan comes
+near at the same instant; obstacle_audit() measures what the fleet flies against where they are at the same instant:
+
+    sense -> observe -> traffic -> obstacles -> replan -> next_goals
+
 enable_check() lets the fleet refuse: every commit is compared, instant by instant, with the other vehicles' plans and taken back when it
 conflicts (include/fasterhip_check.h); the chain ends ... -> safe solve -> backup -> commit -> check -> revert.
 
@@ -166,6 +172,8 @@ class Fleet:
         self.d_headings = self.d_goal_yaw = self.yaw_params = None  # enable_heading
         self.point_mask, self.map_args = None, None                 # set_point_views; what set_map built the map with
         self.traffic_par, self.n_cloud_all = None, 0                # enable_traffic: the cloud holds n_cloud static points, then the traffic
+        self.obstacle_par = self.d_obstacles = None                 # enable_obstacles: then the obstacles' points; n_cloud_all is the end
+        self.n_obstacles, self.obstacle_tick = 0, 0                 # the obstacle clock: ticks since set_obstacles (next_goals advances it)
         self.check_par = self.check_cells = self.d_backup_vehicles = self.d_backup_plans = self.d_check = None   # enable_check
         self.round_par = self.round_cells = self.d_rounds = self.d_active_begin = self.d_check_rounds = None      # enable_rounds
         self.round_retries, self.round_fixed = 0, False
@@ -215,12 +223,12 @@ class Fleet:
         which stay, and must end in the same word of the masks as the cloud they replace."""
         static =self._host_to_device(np.asarray(cloud, dtype=np.float64).reshape(-1, 3) if not isinstance(cloud, self.torch.Tensor) else cloud,
                                       self.torch.float64)
-        if self.traffic_par is not None:
+        if self._tail_first() is not None:
             # the tail stays: the new static points are copied in front of it, on the fleet's stream (launches in flight read the cloud)
-            if abi.point_mask_words(static.shape[0]) * 32 != int(self.traffic_par["first_point"]):
+            if abi.point_mask_words(static.shape[0]) * 32 != self._tail_first():
                 raise capi.FasterHipError("Fleet.set_map: with traffic enabled the new cloud must end in the same word of the masks (%d points, "
                                           "the traffic begins at %d): set_point_views and enable_traffic again"
-                                          % (static.shape[0], int(self.traffic_par["first_point"])))
+                                          % (static.shape[0], self._tail_first()))
             self._follow_current()
             with self.torch.cuda.stream(self.stream):
                 self._write_static(self.cloud, static)
@@ -300,8 +308,9 @@ class Fleet:
         the grid of its view and cuts both corridors around the points its view knows.  mask = False detaches: replan() is what it was.
         Memory per view: a grid of ceil(cells / 32) words and a mask row; the jump point search adds 64 bytes per cell and view."""
         t = self.torch
-        if self.traffic_par is not None:   # (the traffic lives in masks that are replaced: enable_traffic again)
+        if self._tail_first() is not None:   # (traffic and obstacles live in masks that are replaced: enable_traffic, enable_obstacles again)
             self.traffic_par, self.n_cloud_all = None, 0
+            self.obstacle_par = self.d_obstacles = None
             self.cloud = self.cloud[:self.n_cloud]
         if mask is False:
             self.point_mask = None
@@ -358,6 +367,8 @@ class Fleet:
         vehicle i only when i's own committed plan is nearer than `range` to it within `window` samples of the same instant; at most
         abi.FH_TRAFFIC_TIMED_MAX_SAMPLES samples.  With timed=False window and first_instant are ignored."""
         t = self.torch
+        if self.obstacle_par is not None:
+            raise capi.FasterHipError("Fleet.enable_traffic: traffic first, the obstacles behind it (set_point_views, enable_traffic, enable_obstacles)")
         if self.cloud is None or self.view_flags is None or self.point_mask is None:
             raise capi.FasterHipError("Fleet.enable_traffic: set_map, set_unknown_views and set_point_views first")
         if self.view_of is not None or self.n_views != self.n:
@@ -410,6 +421,123 @@ class Fleet:
         (self.ctx.fleet_traffic_timed_device if timed else self.ctx.fleet_traffic_device)(
             self.traffic_par, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.n, self.max_states, self.cloud.data_ptr(),
             self.n_cloud_all, self.point_mask.data_ptr(), self.point_mask.shape[1])
+
+    def _tail_first(self):
+        """The cloud index at which what traffic() and obstacles() write begins, None without either."""
+        if self.traffic_par is not None:
+            return int(self.traffic_par["first_point"])
+        return None if self.obstacle_par is None else int(self.obstacle_par["first_point"])
+
+    def enable_obstacles(self, obstacles, samples, stride, range, r_detect=0.0, points=7, window=0, first_instant=None):  # noqa: A002  (the header's word)
+        """The vehicles avoid things that move and are no fleet member (include/fasterhip_obstacles.h): obstacles is [m]
+        abi.obstacle_dtype (abi.make_obstacles), each a ball that flies p0 + v t from now on.  From now on obstacles() writes `samples`
+        instants of every obstacle's flight, `stride` states apart from first_instant on (None: max(params["delta_t"] - 1, 0), the start
+        state of the replan), as points behind whatever the cloud holds, static points or static points and traffic, and shows a sample
+        to vehicle i when i's own committed plan is nearer than range + the obstacle's radius to it within `window` samples of the same
+        instant, once i stands nearer than r_detect to where the obstacle is now (0: everything is known).  points: 1, or 7 for a hull
+        at the obstacle's radius.  After set_map, set_unknown_views with a view per vehicle, set_point_views and, if wanted,
+        enable_traffic.  The cloud tensor and every mask row grow and keep their words; replan() reads the whole cloud.  The obstacle
+        clock starts at 0 and next_goals advances it.  Memory: n rows of ceil(m samples points / 32) words more."""
+        t = self.torch
+        if self.cloud is None or self.view_flags is None or self.point_mask is None:
+            raise capi.FasterHipError("Fleet.enable_obstacles: set_map, set_unknown_views and set_point_views first")
+        if self.view_of is not None or self.n_views != self.n:
+            raise capi.FasterHipError("Fleet.enable_obstacles: needs a view per vehicle (set_unknown_views without view_of, n_views = n)")
+        obs = np.ascontiguousarray(obstacles)
+        if obs.dtype != abi.obstacle_dtype:
+            raise capi.FasterHipError("Fleet.enable_obstacles: obstacles must be abi.obstacle_dtype records (abi.make_obstacles)")
+        m = int(obs.size)
+        held = self.n_cloud   # the points in front, which stay: the static ones, or those and the traffic's (obstacles of before go)
+        if self.traffic_par is not None:
+            tp = self.traffic_par
+            held = int(tp["first_point"]) + self.n * int(tp["samples"]) * abi.traffic_points_per_sample(tp["hull"])
+        first = abi.point_mask_words(held) * 32
+        if not 1 <= int(samples) <= abi.FH_OBSTACLE_MAX_SAMPLES or int(points) not in (1, 7):
+            raise capi.FasterHipError("Fleet.enable_obstacles: 1 .. %d samples and 1 or 7 points, got %d and %d"
+                                      % (abi.FH_OBSTACLE_MAX_SAMPLES, int(samples), int(points)))
+        first_instant = max(int(self.params["delta_t"]) - 1, 0) if first_instant is None else int(first_instant)
+        par = abi.default_obstacle_params(samples, stride, range, self.dc, r_detect, points, first, first_instant, window)
+        total = first + m * int(samples) * int(points)
+        if total >= 1 << 31:
+            raise capi.FasterHipError("Fleet.enable_obstacles: %d samples of %d obstacles do not fit a cloud" % (int(samples), m))
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            cloud = t.zeros((total, 3), dtype=t.float64, device=self.dev)
+            cloud[:held] = self.cloud[:held]
+            if self.traffic_par is None:
+                self._write_static(cloud, self.cloud[:held])
+            words = max(abi.point_mask_words(total), int(self.point_mask.shape[1]))
+            mask = t.zeros((self.n_views, words), dtype=t.int32, device=self.dev)
+            mask[:, :self.point_mask.shape[1]] = self.point_mask
+            if first > held:   # the bits of the padding points stay clear
+                mask[:, first // 32 - 1] &= (1 << (held & 31)) - 1
+            mask[:, first // 32:] = 0
+            d_obs = t.from_numpy(obs.view(np.uint8).reshape(-1).copy()).to(self.dev)
+        self.cloud, self.point_mask, self.d_obstacles = cloud, mask, d_obs
+        for d in (self.cloud, self.point_mask, self.d_obstacles):
+            d.record_stream(self.stream)
+        self.ctx.set_point_views_device(self.point_mask.data_ptr(), self.point_mask.shape[1], None, self.n_views)
+        self.obstacle_par, self.n_cloud_all, self.n_obstacles, self.obstacle_tick = par, total, m, 0
+        self._views_changed()
+
+    def set_obstacles(self, obstacles):
+        """New records for the same number of obstacles ([m] abi.obstacle_dtype): what a tracker knows now.  The clock starts again at
+        0: p0 is where an obstacle is at this call."""
+        if self.obstacle_par is None:
+            raise capi.FasterHipError("Fleet.set_obstacles: enable_obstacles first")
+        obs = np.ascontiguousarray(obstacles)
+        if obs.dtype != abi.obstacle_dtype or int(obs.size) != self.n_obstacles:
+            raise capi.FasterHipError("Fleet.set_obstacles: %d abi.obstacle_dtype records, as in enable_obstacles" % self.n_obstacles)
+        src = self.torch.from_numpy(obs.view(np.uint8).reshape(-1).copy()).to(self.dev)
+        self._follow_current()
+        with self.torch.cuda.stream(self.stream):
+            self.d_obstacles.copy_(src)
+            src.record_stream(self.stream)
+        self.obstacle_tick = 0
+
+    def obstacles(self):
+        """The predicted positions of the obstacles into their part of the cloud and into every vehicle's mask row
+        (fh_fleet_obstacles_device): after observe() and traffic(), before replan(), once a cycle, with rounds too.  Three launches on
+        the fleet's stream; the words are written whole, so what a vehicle saw of the obstacles last cycle goes."""
+        if self.obstacle_par is None:
+            raise capi.FasterHipError("Fleet.obstacles: enable_obstacles first")
+        self._follow_current()
+        self._obstacles_launch()
+
+    def _obstacles_launch(self):
+        self.ctx.fleet_obstacles_device(self.obstacle_par, self.d_obstacles.data_ptr(), self.n_obstacles, self.obstacle_tick,
+                                        self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.n, self.max_states, self.cloud.data_ptr(),
+                                        self.n_cloud_all, self.point_mask.data_ptr(), self.point_mask.shape[1])
+
+    def obstacle_audit_device(self, r=None, stride=1, count=0, obstacles=None, tick0=None):
+        """obstacle_audit() without the copy to the host: one launch on the fleet's stream; returns the device tensor of [n]
+        fh_plan_obstacle_audit records as bytes (asynchronous)."""
+        t, B = self.torch, self.n
+        par = abi.default_obstacle_audit_params(float(self.params["rule"]["drone_radius"]) if r is None else r, self.dc, stride, count)
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            if obstacles is None:
+                if self.d_obstacles is None:
+                    raise capi.FasterHipError("Fleet.obstacle_audit: enable_obstacles first, or pass obstacles")
+                d_obs, m = self.d_obstacles, self.n_obstacles
+            else:
+                obs = np.ascontiguousarray(obstacles)
+                if obs.dtype != abi.obstacle_dtype:
+                    raise capi.FasterHipError("Fleet.obstacle_audit: obstacles must be abi.obstacle_dtype records (abi.make_obstacles)")
+                d_obs, m = t.from_numpy(obs.view(np.uint8).reshape(-1).copy()).to(self.dev), int(obs.size)
+                d_obs.record_stream(self.stream)
+            d_out = t.empty(B * abi.plan_obstacle_audit_dtype.itemsize, dtype=t.uint8, device=self.dev)  # (the kernel writes every byte of every record)
+            self.ctx.fleet_obstacle_audit_device(par, d_obs.data_ptr() if m else None, m, self.obstacle_tick if tick0 is None else int(tick0),
+                                                 self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), B, self.max_states, d_out.data_ptr())
+        return d_out
+
+    def obstacle_audit(self, r=None, stride=1, count=0, obstacles=None, tick0=None):
+        """The committed plans, the states the vehicles fly, against where the obstacles are at the same instants
+        (include/fasterhip_obstacles.h): [n] abi.plan_obstacle_audit_dtype with squared distances.  An obstacle hits when the centres
+        are nearer than r (None: params["rule"]["drone_radius"]) + its radius.  obstacles, tick0: other records and another clock than
+        the fleet's own, for a fleet that was never told of them (the control of an experiment).  count=params["delta_t"] audits the
+        states the next replan cannot change.  A measurement: nothing of the fleet is written (synchronises)."""
+        return self._host(self.obstacle_audit_device(r, stride, count, obstacles, tick0), abi.plan_obstacle_audit_dtype)
 
     def enable_check(self, r=None, stride=1, count=0, cells=None):
         """Every commit is checked against the other plans and withheld when it conflicts (include/fasterhip_check.h): from now on
@@ -608,7 +736,7 @@ class Fleet:
         vo = None if self.view_of is None else p(self.view_of)
         mask = None if self.point_mask is None else p(self.point_mask)
         words = 0 if self.point_mask is None else int(self.point_mask.shape[1])
-        shared = words if self.traffic_par is None else int(self.traffic_par["first_point"]) // 32   # (below the traffic)
+        shared = words if self._tail_first() is None else self._tail_first() // 32   # (below the traffic and the obstacles)
         groups = ("link_groups", lambda: c.fleet_link_groups_device(par, p(self.d_vehicles), self.n, vo, self.n_views, cells,
                                                                     p(self.d_link_labels), p(self.d_link_info)))
         if los:
@@ -1179,7 +1307,8 @@ class Fleet:
         B, P, c, m = self.n, self.params, self.ctx, self.map
         p = lambda t: t.data_ptr()  # noqa: E731
         origin, res, dims = self.grid
-        n_cloud = self.n_cloud if self.traffic_par is None else self.n_cloud_all   # (with traffic: the static points and the others' plans)
+        # (with traffic or obstacles: the static points, the others' plans and the obstacles' points)
+        n_cloud = self.n_cloud if self._tail_first() is None else self.n_cloud_all
         chain = self._shared_map_stages(B, P, c, m, p, origin, res, dims, n_cloud, d_active_begin)
         if self.check_par is not None:   # backup -> commit -> check -> revert (include/fasterhip_check.h)
             chain = chain[:-1] + [
@@ -1249,6 +1378,7 @@ class Fleet:
         """getNextGoal `ticks` times for every vehicle; returns the device buffer of the last goals ([n] fh_state as bytes).  follow: the
         current state becomes that goal (updateState of a vehicle that tracks its plan perfectly).  With enable_heading the yaw entry
         runs instead (1 <= ticks <= 65536): the same goals, and (yaw, dyaw) of the last one in self.d_goal_yaw ([n][2], goal_yaw())."""
+        self.obstacle_tick += int(ticks)   # (the obstacle clock runs with the plans' cursor)
         if self.d_headings is not None:
             self.ctx.fleet_next_goals_yaw_device(self.yaw_params, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.d_headings.data_ptr(),
                                                  self.n, self.max_states, int(ticks), follow, self.d_next.data_ptr(), self.d_goal_yaw.data_ptr())

@@ -105,9 +105,13 @@ Fleet.explore_far_team(BLOCK, R_SPREAD, G, H, M, C, passes=P, after=...) in thei
 "far_team_goals" and "far_team_set_goals", and under "far_team" the launch with every vehicle wanted and nobody skipped as
 "far_team_goals_all_ms" beside "far_spread_goals_all_beside_ms" and "far_gain_goals_all_beside_ms" of the same call (medians of five), the
 same launch with 1, 8 and 64 passes, the cost of an idle pass from the last two, and what the claims covered and removed.
+--obstacles M [--obstacle-samples S] adds "obstacles" (include/fasterhip_obstacles.h): the fleet of --traffic-timed after two cycles
+with time-aware traffic of S samples (default 64, stride 5, 6 m, window 2) and, behind it, Fleet.enable_obstacles with M obstacles
+scattered over the map that fly up to 1 m/s; Fleet.traffic, Fleet.obstacles and Fleet.obstacle_audit_device fenced one by one in the same
+run ("traffic_timed_ms", "obstacles_ms", "obstacle_audit_ms", medians with their spread), the bits set per vehicle and the vehicles hit.
     usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..] [--link-los]] [--explore R_MAX [--far BLOCK [--far-gain G [--far-hop-cost H] [--far-min-gain M]] [--far-spread R_SPREAD [--passes P]] [--far-claim-blocks C]] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
-                                         [--rounds R [--round-reach M] [--retries T]] [--listed-views]"""
+                                         [--rounds R [--round-reach M] [--retries T]] [--listed-views] [--obstacles M [--obstacle-samples S]]"""
 import json
 import os
 import sys
@@ -872,6 +876,52 @@ def traffic_cycles(B, cycles, p, world, samples, stride, reach, window=None):
     return {"traffic" if window is None else "traffic_timed": out}
 
 
+def obstacle_cycles(B, cycles, p, world, m, samples, rng):
+    """--obstacles M: the fleet of --traffic-timed after two cycles, then time-aware traffic (samples, stride 5, 6 m, window 2) timed as a
+    stage of its own, then Fleet.enable_obstacles with M obstacles scattered over the map that fly up to 1 m/s (the same samples,
+    stride, range and window, seven points, no detection radius) and Fleet.obstacles and Fleet.obstacle_audit_device timed one by one,
+    each fenced by events, max(cycles, 5) times: the medians and the spread in ms, and what each found."""
+    cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims = world
+    out = {"obstacles": m, "samples": samples, "stride": 5, "range": 6.0, "window": 2, "points": 7}
+    fl = Fleet(B, p, max_states=1024)
+    try:
+        fl.set_map(cloud, cells, res, center, zmax, infl)
+        fl.set_unknown_views(torch.from_numpy(flags.reshape(1, -1)).to(fl.dev).repeat(B, 1), origin=origin, res=res, dims=dims)
+        fl.set_point_views(torch.full((B, abi.point_mask_words(len(cloud))), -1, dtype=torch.int32, device=fl.dev))
+        fl.init(states, goals)
+        for _ in range(2):
+            fl.replan()
+            fl.next_goals(5)
+        fl.enable_traffic(samples, 5, 6.0, timed=True, window=2)
+        lo, hi = cloud.min(axis=0), cloud.max(axis=0)
+        obs = abi.make_obstacles(rng.uniform(lo, hi, size=(m, 3)), rng.uniform(-1.0, 1.0, size=(m, 3)) / np.sqrt(3.0), 0.3)
+        fl.enable_obstacles(obs, samples, 5, 6.0, window=2)
+        out.update({"cloud_points": fl.n_cloud_all, "mask_bytes": int(fl.point_mask.numel()) * 4})
+        stages = [("traffic_timed", fl.traffic), ("obstacles", fl.obstacles), ("obstacle_audit", fl.obstacle_audit_device)]
+        ms = {n: [] for n, _ in stages}
+        for name, launch in stages:
+            launch()   # (warm-up: the working buffers of the context grow)
+        fl.sync()
+        for _ in range(max(cycles, 5)):
+            for name, launch in stages:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(fl.stream)
+                launch()
+                e1.record(fl.stream)
+                fl.sync()
+                ms[name].append(e0.elapsed_time(e1))
+        for name, v in ms.items():
+            out[name + "_ms"] = float(np.median(v))
+            out[name + "_ms_min_max"] = [float(min(v)), float(max(v))]
+        bits = fl.point_mask[:, int(fl.obstacle_par["first_point"]) // 32:]
+        rec = fl.obstacle_audit()
+        out.update({"obstacle_bits_set_per_vehicle": sum(int(((bits >> b) & 1).sum().item()) for b in range(32)) / B,
+                    "audit_hit": int(((rec["flags"] & abi.FH_OBSTACLE_HIT) != 0).sum()), "audit_n_tested_mean": float(rec["n_tested"].mean())})
+    finally:
+        fl.close()
+    return {"obstacles": out}
+
+
 def rounds_cycles(B, cycles, p, world, rounds, reach, retries, traffic, window, check):
     """The cycle before and after Fleet.enable_rounds: see the module docstring."""
     cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims = world
@@ -984,6 +1034,15 @@ def main():
     for opt in ("--gain", "--hop-cost", "--min-gain", "--claim-radius"):   # (read into GAIN, HOP_COST, MIN_GAIN, CLAIM_RADIUS above)
         if opt in argv:
             k = argv.index(opt)
+            del argv[k:k + 2]
+    n_obstacles, obstacle_samples = 0, 64
+    for opt in ("--obstacles", "--obstacle-samples"):
+        if opt in argv:
+            k = argv.index(opt)
+            if opt == "--obstacles":
+                n_obstacles = int(argv[k + 1])
+            else:
+                obstacle_samples = int(argv[k + 1])
             del argv[k:k + 2]
     if "--traffic-timed" in argv:
         k = argv.index("--traffic-timed")
@@ -1122,6 +1181,9 @@ def main():
     if window is not None:
         world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
         out.update(traffic_cycles(B, cycles, p, world, *(traffic or (8, 25, 6.0)), window=window))
+    if n_obstacles:
+        world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
+        out.update(obstacle_cycles(B, cycles, p, world, n_obstacles, obstacle_samples, rng))
     if rounds:
         world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
         out.update(rounds_cycles(B, cycles, p, world, rounds, round_reach, retries, traffic, window, "--check" in sys.argv))
