@@ -20,10 +20,19 @@
 //                       smallest (D2, b) by wave_min / wave_min_i32 and across the wavefronts through LDS; then the workgroup scans the
 //                       at most 16^3 voxels of that block for the smallest (d2, c) and counts them.  The flood runs on for the counts.
 //                       Its body is far_body<false>; the chooser for a team instantiates far_body<true>.
+// The pieces that the three later far choosers (by gain, for a team, both) share with this one stand here, once, and their kernels
+// call them: far_start (the vehicle's values, judged, and its start block), far_summary (the view's bitmaps into LDS, r_avoid out of T),
+// far_expand and far_level_any (one level of the flood for an owned word; its barrier), far_scan_block (the voxels of the chosen
+// block), far_put_goal and far_head (goal, mask, the 64 bytes every record begins with), and for the teams the class bytes,
+// far_count_body (lower and standing, the outputs no pass decides) and far_claim_scan<COVER> (peers' claims out of T; with COVER
+// also the blocks they cover, into a seventh bitmap).
 // LDS of far_goals_kernel: 6 bitmaps of FH_FAR_MAX_WORDS words = 24 KB static, and the slots of the reductions.
 // Every address comes from a checked number: view in [0, n_views), the start cell tested against the dims before it is used, block
 // extents clipped to the lattice, neighbour bytes tested against the dims and neighbour words against the rows before they are loaded,
-// the map cell tested against the map's dims before its word is loaded.
+// the map cell tested against the map's dims before its word is loaded; in the claim scan k < n before a class byte is read, a class
+// other than none says that the view is in [0, n_views), d_goals of a lower peer is read only under its mask, which an earlier launch
+// wrote, a claim's voxel is tested against the dims as a double before it is a block, and the bits of C are clipped to the word and to
+// [0, Cx).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -168,10 +177,9 @@ struct FarCounts {
   int block, hops, targets, reachable, reached, levels, members;
 };
 
-// the three outputs of vehicle i, by one thread
-__device__ __forceinline__ void far_store(const FarArgs& a, int i, int flags, int view, int cell, double d2, double block_d2, const FarCounts& n) {
+// goal and mask of vehicle i, by one thread: the centre of voxel `cell`, or with cell < 0 the bits of g_term; -> FOUND or 0
+__device__ __forceinline__ int far_put_goal(const ReachArgs& r, int i, int cell) {
 #pragma clang fp contract(off)
-  const ReachArgs& r = a.r;
   const unsigned long long* g = (const unsigned long long*)r.vehicles[i].g_term;
   unsigned long long* out = (unsigned long long*)(r.goals + 3 * (size_t)i);
   if (cell >= 0) {
@@ -179,16 +187,27 @@ __device__ __forceinline__ void far_store(const FarArgs& a, int i, int flags, in
     r.goals[3 * (size_t)i] = (ix + 0.5) * r.res + r.ox;
     r.goals[3 * (size_t)i + 1] = (iy + 0.5) * r.res + r.oy;
     r.goals[3 * (size_t)i + 2] = (iz + 0.5) * r.res + r.oz;
-    flags |= FH_FRONTIER_FOUND;
   } else {
     out[0] = g[0]; out[1] = g[1]; out[2] = g[2];  // the bits of g_term, whatever they are
   }
   r.mask[i] = cell >= 0 ? 1 : 0;
-  fh_far_record q;
+  return cell >= 0 ? FH_FRONTIER_FOUND : 0;
+}
+
+// the 64 bytes that the records of all four far choosers begin with (the host file asserts the offsets)
+template <class R>
+__device__ __forceinline__ void far_head(R& q, int flags, int view, int cell, double d2, double block_d2, const FarCounts& n) {
   q.flags = flags; q.view = view; q.cell = cell; q.block_cell = n.block; q.hops = n.hops;
   q.targets = n.targets; q.reachable = n.reachable; q.reached = n.reached; q.levels = n.levels; q.members = n.members;
   q.reserved[0] = 0; q.reserved[1] = 0;
   q.d2 = d2; q.block_d2 = block_d2;
+}
+
+// the three outputs of vehicle i, by one thread
+__device__ __forceinline__ void far_store(const FarArgs& a, int i, int flags, int view, int cell, double d2, double block_d2, const FarCounts& n) {
+  flags |= far_put_goal(a.r, i, cell);
+  fh_far_record q;
+  far_head(q, flags, view, cell, d2, block_d2, n);
   a.records[i] = q;
 }
 
@@ -210,55 +229,58 @@ __device__ __forceinline__ double far_block_d2(const FarArgs& a, int bx, int by,
   return gx2 + gy2 + gz2;
 }
 
-struct FarNoClaims {};
+// what a workgroup of a goals kernel knows of its vehicle i before it searches (every member uniform over the workgroup)
+struct FarStart {
+  int view;
+  FarWho who;
+  double px, py, pz, gx, gy, gz;  // position and g_term
+  int sw;                         // the word of the start block (< W) and its bit; of a searched vehicle only
+  unsigned long long sbit;
+};
 
-// The body of far_goals_kernel, and with CLAIMS that of far_spread_goals_kernel (fh_apart.hpp): x.clear() takes the blocks that
-// the claims of peers cover out of T in LDS before the flood, x.store() writes the longer record.  With CLAIMS false every
-// `if constexpr` below is gone and the code is what the kernel held before it was a template.
-template <bool CLAIMS, class X>
-__device__ __forceinline__ void far_body(const FarArgs& a, const X& x) {
+__device__ __forceinline__ FarStart far_start(const FarArgs& a, int i) {
 #pragma clang fp contract(off)
-  __shared__ unsigned long long s_t[FAR_WORDS], s_lx[FAR_WORDS], s_ly[FAR_WORDS], s_lz[FAR_WORDS], s_a[FAR_WORDS], s_b[FAR_WORDS];
-  __shared__ double s_bd2[4], s_vd2[4];
-  __shared__ int s_bc[4], s_vc[4], s_vm[4], s_n[4], s_m[4], s_k[4];
-  __shared__ unsigned s_or[2][4];
   const ReachArgs& r = a.r;
-  const int i = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, w = t >> 6;
   const fh_vehicle& V = r.vehicles[i];
-  const int view = fhw::uniform_i32(r.view_of ? r.view_of[i] : i);
+  FarStart s;
+  s.view = fhw::uniform_i32(r.view_of ? r.view_of[i] : i);
   const int status = fhw::uniform_i32(V.status), stage = fhw::uniform_i32(V.stage);
   const int skip = fhw::uniform_i32(a.skip ? a.skip[i] : 0);
-  const double px = fhw::uniform_f64(V.state.pos[0]), py = fhw::uniform_f64(V.state.pos[1]), pz = fhw::uniform_f64(V.state.pos[2]);
-  const double gx = fhw::uniform_f64(V.g_term[0]), gy = fhw::uniform_f64(V.g_term[1]), gz = fhw::uniform_f64(V.g_term[2]);
-  const FarWho who = far_judge(a, view, status, stage, skip, px, py, pz, gx, gy, gz);
-  int flags = who.flags;
-  const FarCounts none = {-1, -1, 0, 0, 0, 0, 0};
-  if (!who.searched) {  // (uniform over the workgroup)
-    if constexpr (!CLAIMS) {  // (with CLAIMS the count kernel has written the outputs of a vehicle that is not searched)
-      if (t == 0) far_store(a, i, flags, view, -1, INFINITY, INFINITY, none);
-    }
-    return;
-  }
-  const int W = a.W, wx = a.wx, slab = a.wx * a.cy;
-  const unsigned char* F = r.flags + (size_t)view * r.view_stride;
-  const unsigned long long* S = a.sums + (size_t)view * 4u * (size_t)W;
-  const int sbx = who.sx / a.B, sby = who.sy / a.B, sbz = who.sz / a.B;  // (< cx, cy, cz: s is inside the lattice)
-  const int sw = (sbz * a.cy + sby) * wx + (sbx >> 6);                   // (< W)
-  const unsigned long long sbit = 1ull << (sbx & 63);
+  s.px = fhw::uniform_f64(V.state.pos[0]); s.py = fhw::uniform_f64(V.state.pos[1]); s.pz = fhw::uniform_f64(V.state.pos[2]);
+  s.gx = fhw::uniform_f64(V.g_term[0]); s.gy = fhw::uniform_f64(V.g_term[1]); s.gz = fhw::uniform_f64(V.g_term[2]);
+  s.who = far_judge(a, s.view, status, stage, skip, s.px, s.py, s.pz, s.gx, s.gy, s.gz);
+  const int sbx = s.who.sx / a.B, sby = s.who.sy / a.B, sbz = s.who.sz / a.B;  // (< cx, cy, cz: s is inside the lattice)
+  s.sw = (sbz * a.cy + sby) * a.wx + (sbx >> 6);
+  s.sbit = 1ull << (sbx & 63);
+  return s;
+}
 
-  // ---- the view's summary into LDS, T without the blocks within r_avoid of g_term ----
-  unsigned long long own_seen[FAR_OWN];
-  unsigned own_nb[FAR_OWN];  // bit 0: owned (u < W); 1, 2: a word before / after in the same row; 4, 8: a row before / after in the slab; 16, 32: a slab below / above
+// the six bitmaps of a flood in LDS, FAR_WORDS words each: T, the links, and the two levels
+struct FarMaps {
+  unsigned long long *t, *lx, *ly, *lz, *a, *b;
+};
+
+// The view's summary into LDS, by the thread that owns the words u = t + 256 j: T without the blocks within r_avoid of g_term, the
+// links, the start bit in m.a, and with COVER an empty word of the seventh bitmap c.  -> the set bits of T in this thread's words; in
+// seen the start bit; in nb, per word: 1: owned (u < W); 2, 4: a word before / after in the same row; 8, 16: a row before / after in
+// the slab; 32, 64: a slab below / above.
+template <bool COVER>
+__device__ __forceinline__ int far_summary(const FarArgs& a, const FarStart& s, int t, const FarMaps& m, unsigned long long* c,
+                                           unsigned long long (&seen)[FAR_OWN], unsigned (&nb)[FAR_OWN]) {
+#pragma clang fp contract(off)
+  const ReachArgs& r = a.r;
+  const int W = a.W, wx = a.wx;
+  const unsigned long long* S = a.sums + (size_t)s.view * 4u * (size_t)W;
   int n_targets = 0;
 #pragma unroll
   for (int j = 0; j < FAR_OWN; j++) {
     const int u = t + 256 * j;
     const bool own = u < W;
     const int k = own ? u % wx : 0, row = own ? u / wx : 0, by = row % a.cy, bz = row / a.cy;
-    own_nb[j] = own ? (1u | (k > 0 ? 2u : 0u) | (k < wx - 1 ? 4u : 0u) | (by > 0 ? 8u : 0u) | (by < a.cy - 1 ? 16u : 0u) | (bz > 0 ? 32u : 0u) |
-                       (bz < a.cz - 1 ? 64u : 0u))
-                    : 0u;
-    own_seen[j] = own && u == sw ? sbit : 0ull;
+    nb[j] = own ? (1u | (k > 0 ? 2u : 0u) | (k < wx - 1 ? 4u : 0u) | (by > 0 ? 8u : 0u) | (by < a.cy - 1 ? 16u : 0u) | (bz > 0 ? 32u : 0u) |
+                   (bz < a.cz - 1 ? 64u : 0u))
+                : 0u;
+    seen[j] = own && u == s.sw ? s.sbit : 0ull;
     if (own) {
       unsigned long long tw = S[u];
       if (r.a2 > 0.0) {  // (with a2 == 0 no E2 is below it)
@@ -266,23 +288,285 @@ __device__ __forceinline__ void far_body(const FarArgs& a, const X& x) {
         while (h) {
           const int bit = (int)__builtin_ctzll(h);
           h &= h - 1ull;
-          const double e2 = far_block_d2(a, 64 * k + bit, by, bz, gx, gy, gz);
+          const double e2 = far_block_d2(a, 64 * k + bit, by, bz, s.gx, s.gy, s.gz);
           if (e2 < r.a2) tw &= ~(1ull << bit);
         }
       }
       n_targets += __popcll(tw);
-      s_t[u] = tw;
-      s_lx[u] = S[(size_t)W + u];
-      s_ly[u] = S[2 * (size_t)W + u];
-      s_lz[u] = S[3 * (size_t)W + u];
-      s_a[u] = u == sw ? sbit : 0ull;
-      s_b[u] = 0ull;
+      m.t[u] = tw;
+      m.lx[u] = S[(size_t)W + u];
+      m.ly[u] = S[2 * (size_t)W + u];
+      m.lz[u] = S[3 * (size_t)W + u];
+      m.a[u] = u == s.sw ? s.sbit : 0ull;
+      m.b[u] = 0ull;
+      if constexpr (COVER) c[u] = 0ull;
     }
   }
+  return n_targets;
+}
+
+// One level of the flood for the owned word u with neighbour bits nb: nxt[u] and -> the new bits, which join seen
+__device__ __forceinline__ unsigned long long far_expand(const FarMaps& m, const unsigned long long* cur, unsigned long long* nxt, int u, unsigned nb,
+                                                         int wx, int slab, unsigned long long& seen) {
+  const unsigned long long c = cur[u], lx = m.lx[u];
+  unsigned long long v = (c & lx) << 1;                  // +x inside the word
+  unsigned long long down = c >> 1;                      // -x: block b from block b + 1, the link at b
+  if (nb & 2u) v |= (cur[u - 1] & m.lx[u - 1]) >> 63;
+  if (nb & 4u) down |= cur[u + 1] << 63;
+  v |= down & lx;
+  if (nb & 8u) v |= cur[u - wx] & m.ly[u - wx];
+  if (nb & 16u) v |= cur[u + wx] & m.ly[u];
+  if (nb & 32u) v |= cur[u - slab] & m.lz[u - slab];
+  if (nb & 64u) v |= cur[u + slab] & m.lz[u];
+  v &= ~seen;
+  nxt[u] = v;
+  seen |= v;
+  return v;
+}
+
+// the level's barrier: -> the or of `any` over the workgroup.  The slots s_or[2][4] are chosen by the level's parity, so that one
+// barrier per level suffices.
+__device__ __forceinline__ unsigned far_level_any(unsigned any, unsigned (*s_or)[4], int level, int lane, int w) {
+  const unsigned wave_any = fhw::wave_or(any);
+  if (lane == 0) s_or[level & 1][w] = wave_any;
+  __syncthreads();
+  return s_or[level & 1][0] | s_or[level & 1][1] | s_or[level & 1][2] | s_or[level & 1][3];
+}
+
+struct FarVoxel {
+  double d2;
+  int cell, members;
+};
+
+// the voxels of block b, a set bit of T (so a block of the lattice), by the workgroup: the smallest (d2, c) of its target voxels from
+// the point p, and their number.  One barrier; the slots are this scan's own.
+__device__ __forceinline__ FarVoxel far_scan_block(const FarArgs& a, const unsigned char* F, int b, double px, double py, double pz, int t) {
+#pragma clang fp contract(off)
+  __shared__ double s_vd2[4];
+  __shared__ int s_vc[4], s_vm[4];
+  const ReachArgs& r = a.r;
+  const int lane = t & 63, w = t >> 6;
+  const int bx = b % a.cx, by = (b / a.cx) % a.cy, bz = b / (a.cx * a.cy);
+  const int x0 = bx * a.B, y0 = by * a.B, z0 = bz * a.B;
+  const int bw = min(x0 + a.B, r.nx) - x0, bh = min(y0 + a.B, r.ny) - y0, vol = bw * bh * (min(z0 + a.B, r.nz) - z0);
+  double v_d2 = INFINITY;
+  int v_c = 0x7fffffff, v_n = 0;
+  for (int l = t; l < vol; l += 256) {
+    const int ix = x0 + l % bw, iy = y0 + (l / bw) % bh, iz = z0 + l / (bw * bh);
+    if (far_passable(r, F, ix, iy, iz) && far_target(r, F, ix, iy, iz)) {
+      const double qx = (ix + 0.5) * r.res + r.ox, qy = (iy + 0.5) * r.res + r.oy, qz = (iz + 0.5) * r.res + r.oz;
+      const double dx = qx - px, dy = qy - py, dz = qz - pz;
+      const double d2 = dx * dx + dy * dy + dz * dz;
+      const int c = (iz * r.ny + iy) * r.nx + ix;
+      v_n++;
+      if (reach_before(d2, c, v_d2, v_c)) { v_d2 = d2; v_c = c; }
+    }
+  }
+  const double wave_v = fhw::wave_min(v_d2);
+  const int wave_vc = fhw::wave_min_i32(v_d2 == wave_v ? v_c : 0x7fffffff);
+  const int wave_vn = fhw::wave_sum_i32(v_n);
+  if (lane == 0) { s_vd2[w] = wave_v; s_vc[w] = wave_vc; s_vm[w] = wave_vn; }
+  __syncthreads();
+  FarVoxel best = {s_vd2[0], s_vc[0], s_vm[0] + s_vm[1] + s_vm[2] + s_vm[3]};
+  for (int k = 1; k < 4; k++)
+    if (reach_before(s_vd2[k], s_vc[k], best.d2, best.cell)) { best.d2 = s_vd2[k]; best.cell = s_vc[k]; }
+  return best;
+}
+
+// ---- the teams: vehicles of a group decided in passes, the goals of standing and lower peers are claims ----
+
+constexpr int FAR_CLASS_NONE = 0, FAR_CLASS_SEARCHER = 1, FAR_CLASS_STANDING = 2;  // the class byte of a vehicle
+constexpr int FAR_CHUNK = 256;                                                     // claims held in LDS at a time: one per thread
+
+// the team's words of a record, which follow the 64 bytes of far_head
+struct FarTeamCounts {
+  int group, decided_pass, lower, standing, claims, claimed;
+};
+
+template <class R>
+__device__ __forceinline__ void far_team_words(R& q, const FarTeamCounts& m) {
+  q.group = m.group; q.decided_pass = m.decided_pass; q.lower = m.lower; q.standing = m.standing; q.claims = m.claims; q.claimed = m.claimed;
+  q.reserved_tail[0] = 0; q.reserved_tail[1] = 0;
+}
+
+// what a claim scan reads
+struct FarTeam {
+  const unsigned char* cls;  // [n]
+  const int32_t* grp;        // [n]
+  int group;                 // the vehicle's own
+  double s2;                 // r_spread^2
+  int k;                     // claim_blocks (COVER only)
+};
+
+// The body of a count kernel, a wavefront per vehicle: lower -> lower_out[i]; a vehicle that is no searcher, or one with
+// lower >= passes, has its final outputs written by lane 0 through store(flags, view, counts).
+template <class STORE>
+__device__ __forceinline__ void far_count_body(const FarArgs& a, const unsigned char* cls, const int32_t* grp, int32_t* lower_out, int passes,
+                                               int unsettled, const STORE& store) {
+#pragma clang fp contract(off)
+  const ReachArgs& r = a.r;
+  const int i = (int)blockIdx.x, lane = (int)threadIdx.x, n = a.n;
+  const fh_vehicle& V = r.vehicles[i];
+  const int view = fhw::uniform_i32(r.view_of ? r.view_of[i] : i);
+  const int mine = fhw::uniform_i32((int)cls[i]), group = fhw::uniform_i32(grp[i]);
+  if (mine != FAR_CLASS_SEARCHER) {  // (uniform)
+    if (lane == 0) {
+      const FarWho w = far_judge(a, view, V.status, V.stage, a.skip ? a.skip[i] : 0, V.state.pos[0], V.state.pos[1], V.state.pos[2], V.g_term[0],
+                                 V.g_term[1], V.g_term[2]);
+      const FarTeamCounts m = {group, 0, 0, 0, 0, 0};
+      store(w.flags, view, m);
+      lower_out[i] = 0;
+    }
+    return;
+  }
+  int lower = 0, standing = 0;  // (uniform: sums of popcounts of ballots)
+  for (int base = 0; base < n; base += 64) {
+    const int k = base + lane;
+    const bool in = k < n && k != i;
+    const int ck = in ? (int)cls[k] : FAR_CLASS_NONE;
+    const bool peer = ck != FAR_CLASS_NONE && grp[k] == group;  // (a class other than none: a view in range)
+    lower += __popcll(__ballot(peer && ck == FAR_CLASS_SEARCHER && k < i));
+    standing += __popcll(__ballot(peer && ck == FAR_CLASS_STANDING));
+  }
+  if (lane == 0) {
+    lower_out[i] = lower;
+    if (lower >= passes) {  // (a searcher: its flags are WANTED alone)
+      const FarTeamCounts m = {group, -1, lower, standing, standing, 0};
+      store(FH_FRONTIER_WANTED | unsettled, view, m);
+    }
+  }
+}
+
+// The claim scan of a pass kernel, called by all 256 threads.  The n vehicles in chunks of 256, thread = k; the claim points of a chunk
+// are compacted into LDS in ascending k by ballot and rank.  Every thread then takes the blocks with G2 < r_spread^2 of a claim out of
+// the words u = t, t + 256, .. < W of T that it OWNS (and alone has written).  With COVER the block of each claim's voxel stands
+// beside the point (3 x 16 bits, 0xffff: the voxel lies outside the lattice) and the thread sets in its words of C the blocks within
+// k - 1 of it per axis.  A word of either bitmap has one writer, so the bytes do not depend on scheduling.  The barriers inside are
+// uniform.  -> how many bits of T this thread cleared, and in n_claims and n_standing the number of claims and of the standing peers
+// among them (uniform).
+template <bool COVER>
+__device__ __forceinline__ int far_claim_scan(const FarArgs& a, const FarTeam& m, int i, int t, unsigned long long* s_t, unsigned long long* s_c,
+                                              int& n_claims, int& n_standing) {
+#pragma clang fp contract(off)
+  __shared__ double s_pts[3 * FAR_CHUNK];
+  __shared__ int s_cnt[8];  // [2][4]: the claims of a chunk per wavefront (the standing ones among them << 16), by the chunk's parity
+  __shared__ unsigned short s_cb[COVER ? 3 * FAR_CHUNK : 1];  // (without COVER nothing refers to it, and it takes no LDS)
+  const ReachArgs& r = a.r;
+  const int lane = t & 63, w = t >> 6, n = a.n;
+  int cleared = 0, total = 0, standing = 0, parity = 0;
+  for (int base = 0; base < n; base += FAR_CHUNK, parity ^= 1) {
+    const int k = base + t;
+    const bool in = k < n && k != i;
+    const int ck = in ? (int)m.cls[k] : FAR_CLASS_NONE;
+    const bool low = ck == FAR_CLASS_SEARCHER && k < i;
+    bool has = (low || ck == FAR_CLASS_STANDING) && m.grp[k] == m.group;
+    if (has && low) has = r.mask[k] == 1;  // (a lower peer of this chain: a launch before this one wrote its mask and goal)
+    const unsigned long long bh = __ballot(has);
+    const unsigned long long bs = __ballot(has && !low);
+    if (lane == 0) s_cnt[4 * parity + w] = __popcll(bh) | (__popcll(bs) << 16);  // (each <= 64)
+    __syncthreads();
+    const int c0 = s_cnt[4 * parity], c1 = s_cnt[4 * parity + 1], c2 = s_cnt[4 * parity + 2], c3 = s_cnt[4 * parity + 3];
+    const int both = c0 + c1 + c2 + c3, cm = both & 0xffff;  // (<= 256 each: no carry between the halves)
+    if (cm == 0) continue;  // (uniform over the workgroup; the next chunk writes the other half of s_cnt)
+    if (has) {
+      const double* c = low ? r.goals + 3 * (size_t)k : r.vehicles[k].g_term;
+      const int j = (((w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0)) & 0xffff) + fhw::rank_in(bh);  // (< 256)
+      const double c_x = c[0], c_y = c[1], c_z = c[2];
+      s_pts[3 * j] = c_x; s_pts[3 * j + 1] = c_y; s_pts[3 * j + 2] = c_z;
+      if constexpr (COVER) {
+        // the voxel of the claim, tested as a double before it is an index (the expression of the start cell)
+        const double vfx = floor((c_x - r.ox) / r.res), vfy = floor((c_y - r.oy) / r.res), vfz = floor((c_z - r.oz) / r.res);
+        const bool inside = vfx >= 0.0 && vfx < (double)r.nx && vfy >= 0.0 && vfy < (double)r.ny && vfz >= 0.0 && vfz < (double)r.nz;
+        s_cb[3 * j] = inside ? (unsigned short)((int)vfx / a.B) : (unsigned short)0xffffu;  // (a block per axis: < 64 * 512)
+        s_cb[3 * j + 1] = inside ? (unsigned short)((int)vfy / a.B) : (unsigned short)0xffffu;
+        s_cb[3 * j + 2] = inside ? (unsigned short)((int)vfz / a.B) : (unsigned short)0xffffu;
+      }
+    }
+    __syncthreads();
+    total += cm;
+    standing += both >> 16;
+    for (int u = t; u < a.W; u += 256) {
+      const int kx = u % a.wx, row = u / a.wx, by = row % a.cy, bz = row / a.cy;
+      if constexpr (COVER) {
+        if (m.k > 0) {  // the covered blocks of this word
+          const int first = 64 * kx, last = min(first + 63, a.cx - 1);
+          unsigned long long cw = 0ull;
+          for (int j = 0; j < cm; j++) {
+            const int cbx = (int)s_cb[3 * j], cby = (int)s_cb[3 * j + 1], cbz = (int)s_cb[3 * j + 2];
+            if (cbx == 0xffff) continue;
+            if (abs(by - cby) >= m.k || abs(bz - cbz) >= m.k) continue;
+            const int lo = max(cbx - m.k + 1, first), hi = min(cbx + m.k - 1, last);
+            if (lo <= hi) cw |= ((1ull << (hi - lo + 1)) - 1ull) << (lo - first);  // (hi - lo <= 8, lo - first <= 63 - (hi - lo))
+          }
+          if (cw) s_c[u] |= cw;
+        }
+      }
+      unsigned long long tw = s_t[u];
+      if (tw == 0ull) continue;
+      const unsigned long long before = tw;
+      const int y0 = by * a.B, y1 = min(y0 + a.B, r.ny) - 1, z0 = bz * a.B, z1 = min(z0 + a.B, r.nz) - 1;
+      for (int j = 0; j < cm && tw != 0ull; j++) {
+        const double cx = s_pts[3 * j], cy = s_pts[3 * j + 1], cz = s_pts[3 * j + 2];
+        const double gy2 = far_gap2(cy, y0, y1, r.res, r.oy), gz2 = far_gap2(cz, z0, z1, r.res, r.oz);
+        if (!(gy2 + gz2 < m.s2)) continue;  // (x2 + y2) + z2 >= y2 + z2 in rounded sums of non-negative terms: no block of this word
+        unsigned long long h = tw;
+        while (h) {
+          const int bit = (int)__builtin_ctzll(h);
+          h &= h - 1ull;
+          const int x0 = (64 * kx + bit) * a.B;
+          const double gx2 = far_gap2(cx, x0, min(x0 + a.B, r.nx) - 1, r.res, r.ox);
+          if ((gx2 + gy2) + gz2 < m.s2) tw &= ~(1ull << bit);
+        }
+      }
+      if (tw != before) {
+        s_t[u] = tw;
+        cleared += __popcll(before ^ tw);
+      }
+    }
+    // (the next chunk's first barrier stands between these reads of s_pts / s_cb and the next writes)
+  }
+  n_claims = total;
+  n_standing = standing;
+  return cleared;
+}
+
+struct FarNoClaims {};
+
+// The body of far_goals_kernel, and with CLAIMS that of far_spread_goals_kernel (fh_apart.hpp): far_claim_scan takes the blocks that
+// the claims of x.team cover out of T in LDS before the flood, x.store() writes the longer record.  With CLAIMS false every
+// `if constexpr` below is gone.
+template <bool CLAIMS, class X>
+__device__ __forceinline__ void far_body(const FarArgs& a, const X& x) {
+#pragma clang fp contract(off)
+  __shared__ unsigned long long s_t[FAR_WORDS], s_lx[FAR_WORDS], s_ly[FAR_WORDS], s_lz[FAR_WORDS], s_a[FAR_WORDS], s_b[FAR_WORDS];
+  __shared__ double s_bd2[4];
+  __shared__ int s_bc[4], s_n[4], s_m[4], s_k[4];
+  __shared__ unsigned s_or[2][4];
+  const ReachArgs& r = a.r;
+  const int i = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, w = t >> 6;
+  const FarStart st = far_start(a, i);
+  const int view = st.view;
+  int flags = st.who.flags;
+  const FarCounts none = {-1, -1, 0, 0, 0, 0, 0};
+  if (!st.who.searched) {  // (uniform over the workgroup)
+    if constexpr (!CLAIMS) {  // (with CLAIMS the count kernel has written the outputs of a vehicle that is not searched)
+      if (t == 0) far_store(a, i, flags, view, -1, INFINITY, INFINITY, none);
+    }
+    return;
+  }
+  const int wx = a.wx, slab = a.wx * a.cy, sw = st.sw;
+  const unsigned long long sbit = st.sbit;
+  const double px = st.px, py = st.py, pz = st.pz;
+  const unsigned char* F = r.flags + (size_t)view * r.view_stride;
+  const FarMaps maps = {s_t, s_lx, s_ly, s_lz, s_a, s_b};
+
+  // ---- the view's summary into LDS, T without the blocks within r_avoid of g_term ----
+  unsigned long long own_seen[FAR_OWN];
+  unsigned own_nb[FAR_OWN];
+  const int n_targets = far_summary<false>(a, st, t, maps, nullptr, own_seen, own_nb);
   int n_claims = 0, n_standing = 0;  // (uniform)
   if constexpr (CLAIMS) {
-    // every thread takes the claimed blocks out of the words of T it owns (and alone has written); the barriers inside are uniform
-    const int n_claimed = x.clear(a, i, t, s_t, n_claims, n_standing);
+    const int n_claimed = far_claim_scan<false>(a, x.team, i, t, s_t, nullptr, n_claims, n_standing);
     const int wave_claimed = fhw::wave_sum_i32(n_claimed);
     if (lane == 0) x.sum[w] = wave_claimed;
   }
@@ -295,8 +579,9 @@ __device__ __forceinline__ void far_body(const FarArgs& a, const X& x) {
   unsigned long long* cur = s_a;
   unsigned long long* nxt = s_b;
   int n_reached = t == 0 ? 1 : 0, n_reachable = 0;  // sums over this thread's words (the start: thread 0's)
-  int level = 0, hops = -1, best_block = -1, best_cell = -1, members = 0;
-  double best_bd2 = INFINITY, best = INFINITY;
+  int level = 0, hops = -1, best_block = -1;
+  double best_bd2 = INFINITY;
+  FarVoxel voxel = {INFINITY, -1, 0};
   bool cut = false;
   bool hit = (s_t[sw] & sbit) != 0ull;  // a target block in the level that cur holds (uniform)
   if (hit && t == 0) n_reachable = 1;
@@ -329,33 +614,7 @@ __device__ __forceinline__ void far_body(const FarArgs& a, const X& x) {
       for (int k = 1; k < 4; k++)
         if (reach_before(s_bd2[k], s_bc[k], best_bd2, best_block)) { best_bd2 = s_bd2[k]; best_block = s_bc[k]; }
       hops = level;
-      // the voxels of that block: the smallest (d2, c) of its target voxels, and their number
-      const int bx = best_block % a.cx, by = (best_block / a.cx) % a.cy, bz = best_block / (a.cx * a.cy);  // (a set bit of T: a block of the lattice)
-      const int x0 = bx * a.B, y0 = by * a.B, z0 = bz * a.B;
-      const int bw = min(x0 + a.B, r.nx) - x0, bh = min(y0 + a.B, r.ny) - y0, vol = bw * bh * (min(z0 + a.B, r.nz) - z0);
-      double v_d2 = INFINITY;
-      int v_c = 0x7fffffff, v_n = 0;
-      for (int l = t; l < vol; l += 256) {
-        const int ix = x0 + l % bw, iy = y0 + (l / bw) % bh, iz = z0 + l / (bw * bh);
-        if (far_passable(r, F, ix, iy, iz) && far_target(r, F, ix, iy, iz)) {
-          const double qx = (ix + 0.5) * r.res + r.ox, qy = (iy + 0.5) * r.res + r.oy, qz = (iz + 0.5) * r.res + r.oz;
-          const double dx = qx - px, dy = qy - py, dz = qz - pz;
-          const double d2 = dx * dx + dy * dy + dz * dz;
-          const int c = (iz * r.ny + iy) * r.nx + ix;
-          v_n++;
-          if (reach_before(d2, c, v_d2, v_c)) { v_d2 = d2; v_c = c; }
-        }
-      }
-      const double wave_v = fhw::wave_min(v_d2);
-      const int wave_vc = fhw::wave_min_i32(v_d2 == wave_v ? v_c : 0x7fffffff);
-      const int wave_vn = fhw::wave_sum_i32(v_n);
-      if (lane == 0) { s_vd2[w] = wave_v; s_vc[w] = wave_vc; s_vm[w] = wave_vn; }
-      __syncthreads();
-      best = s_vd2[0];
-      best_cell = s_vc[0];
-      for (int k = 1; k < 4; k++)
-        if (reach_before(s_vd2[k], s_vc[k], best, best_cell)) { best = s_vd2[k]; best_cell = s_vc[k]; }
-      members = s_vm[0] + s_vm[1] + s_vm[2] + s_vm[3];
+      voxel = far_scan_block(a, F, best_block, px, py, pz, t);
     }
     if (r.max_hops > 0 && level >= r.max_hops) {  // (cur is never empty)
       cut = true;
@@ -366,29 +625,13 @@ __device__ __forceinline__ void far_body(const FarArgs& a, const X& x) {
     for (int j = 0; j < FAR_OWN; j++) {
       if (!(own_nb[j] & 1u)) continue;
       const int u = t + 256 * j;
-      const unsigned nb = own_nb[j];
-      const unsigned long long c = cur[u], lx = s_lx[u];
-      unsigned long long v = (c & lx) << 1;                  // +x inside the word
-      unsigned long long down = c >> 1;                      // -x: block b from block b + 1, the link at b
-      if (nb & 2u) v |= (cur[u - 1] & s_lx[u - 1]) >> 63;
-      if (nb & 4u) down |= cur[u + 1] << 63;
-      v |= down & lx;
-      if (nb & 8u) v |= cur[u - wx] & s_ly[u - wx];
-      if (nb & 16u) v |= cur[u + wx] & s_ly[u];
-      if (nb & 32u) v |= cur[u - slab] & s_lz[u - slab];
-      if (nb & 64u) v |= cur[u + slab] & s_lz[u];
-      v &= ~own_seen[j];
-      nxt[u] = v;
-      own_seen[j] |= v;
+      const unsigned long long v = far_expand(maps, cur, nxt, u, own_nb[j], wx, slab, own_seen[j]);
       const unsigned long long h = v & s_t[u];
       n_reached += __popcll(v);
       n_reachable += __popcll(h);
       any |= (v ? 1u : 0u) | (h ? 2u : 0u);
     }
-    const unsigned wave_any = fhw::wave_or(any);
-    if (lane == 0) s_or[level & 1][w] = wave_any;
-    __syncthreads();
-    const unsigned all = s_or[level & 1][0] | s_or[level & 1][1] | s_or[level & 1][2] | s_or[level & 1][3];
+    const unsigned all = far_level_any(any, s_or, level, lane, w);
     if (!(all & 1u)) break;
     level++;
     hit = (all & 2u) != 0u;
@@ -406,13 +649,13 @@ __device__ __forceinline__ void far_body(const FarArgs& a, const X& x) {
     n.reachable = s_m[0] + s_m[1] + s_m[2] + s_m[3];
     n.reached = s_n[0] + s_n[1] + s_n[2] + s_n[3];
     n.levels = level;
-    n.members = hops >= 0 ? members : 0;
+    n.members = hops >= 0 ? voxel.members : 0;
     if (cut) flags |= FH_REACH_CUT;
     if constexpr (CLAIMS)
-      x.store(a, i, flags, view, hops >= 0 ? best_cell : -1, hops >= 0 ? best : INFINITY, hops >= 0 ? best_bd2 : INFINITY, n, n_claims, n_standing,
+      x.store(i, flags, view, hops >= 0 ? voxel.cell : -1, hops >= 0 ? voxel.d2 : INFINITY, hops >= 0 ? best_bd2 : INFINITY, n, n_claims, n_standing,
               x.sum[0] + x.sum[1] + x.sum[2] + x.sum[3]);
     else
-      far_store(a, i, flags, view, hops >= 0 ? best_cell : -1, hops >= 0 ? best : INFINITY, hops >= 0 ? best_bd2 : INFINITY, n);
+      far_store(a, i, flags, view, hops >= 0 ? voxel.cell : -1, hops >= 0 ? voxel.d2 : INFINITY, hops >= 0 ? best_bd2 : INFINITY, n);
   }
 }
 

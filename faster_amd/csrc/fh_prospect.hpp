@@ -17,15 +17,21 @@
 //                            counts in global memory (a row of the cube is at most 2 g - 1 consecutive uint16_t: the words of a row of
 //                            x follow each other, so entry 64 (row wx) + bx' is block bx' of that row), the utility, poor or not, and
 //                            a running best under the total order (-utility, hops, D2, b).  One reduction after the last level (wave,
-//                            then LDS), then the voxel scan of the chosen block, once.
+//                            then LDS), then the voxel scan of the chosen block, once.  Its body is prospect_body<false>.
+// prospect_body<true> is the pass kernel of the chooser by gain for a team (K24, the device header after this one): between the
+// summary and the flood K21's claim scan takes the claimed blocks out of T and sets the covered ones in a SEVENTH bitmap C; each
+// thread sums popcount(C[u]) and the U of the set bits of its words, covered and removed; and the weighing skips covered counts — a
+// row of the cube is at most 9 consecutive counts, and the 9-bit piece of C that belongs to it is taken from one or two words.  A
+// workgroup that covered nothing (a uniform flag) weighs as K23 does: prospect_weigh<false>.
 // LDS of prospect_goals_kernel: 6 bitmaps of FAR_WORDS words = 24 KB static, and the slots of the reductions.
 // Every address comes from a checked number: what K21's header lists, and the cube of a gain is clipped to [0, C_a) per axis before an
-// entry of the counts is loaded.  Integer work and minima of total orders; nothing depends on scheduling.
+// entry of C or of the counts is loaded.  Integer work and minima of total orders; nothing depends on scheduling.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/fasterhip_prospect.h"
-// (FarArgs, FarWho, far_judge, far_passable, far_target, far_block_d2, reach_before and fhw:: come from K21's device header, which
+// (FarArgs, FarStart, FarMaps, FarCounts, far_judge by far_start, far_summary, far_claim_scan, far_expand, far_level_any, far_scan_block,
+// far_put_goal, far_head, far_passable, far_target, far_block_d2, reach_before and fhw:: come from K21's device header, which
 // fh_reach.hip includes before this)
 
 namespace fhp {
@@ -100,29 +106,23 @@ __global__ void __launch_bounds__(256) prospect_blocks_kernel(ProspectArgs p) {
   }
 }
 
+// the gain's words of a record
+struct ProspectGain {
+  int gain, utility, poor, best_gain;
+};
+
+template <class R>
+__device__ __forceinline__ void prospect_words(R& q, const ProspectGain& e) {
+  q.gain = e.gain; q.utility = e.utility; q.poor = e.poor; q.best_gain = e.best_gain;
+}
+
 // the three outputs of vehicle i, by one thread
 __device__ __forceinline__ void prospect_store(const ProspectArgs& p, int i, int flags, int view, int cell, double d2, double block_d2,
-                                               const FarCounts& n, int gain, int utility, int poor, int best_gain) {
-#pragma clang fp contract(off)
-  const ReachArgs& r = p.f.r;
-  const unsigned long long* g = (const unsigned long long*)r.vehicles[i].g_term;
-  unsigned long long* out = (unsigned long long*)(r.goals + 3 * (size_t)i);
-  if (cell >= 0) {
-    const int ix = cell % r.nx, iy = (cell / r.nx) % r.ny, iz = cell / (r.nx * r.ny);
-    r.goals[3 * (size_t)i] = (ix + 0.5) * r.res + r.ox;
-    r.goals[3 * (size_t)i + 1] = (iy + 0.5) * r.res + r.oy;
-    r.goals[3 * (size_t)i + 2] = (iz + 0.5) * r.res + r.oz;
-    flags |= FH_FRONTIER_FOUND;
-  } else {
-    out[0] = g[0]; out[1] = g[1]; out[2] = g[2];  // the bits of g_term, whatever they are
-  }
-  r.mask[i] = cell >= 0 ? 1 : 0;
+                                               const FarCounts& n, const ProspectGain& e) {
+  flags |= far_put_goal(p.f.r, i, cell);
   fh_prospect_record q;
-  q.flags = flags; q.view = view; q.cell = cell; q.block_cell = n.block; q.hops = n.hops;
-  q.targets = n.targets; q.reachable = n.reachable; q.reached = n.reached; q.levels = n.levels; q.members = n.members;
-  q.reserved[0] = 0; q.reserved[1] = 0;
-  q.d2 = d2; q.block_d2 = block_d2;
-  q.gain = gain; q.utility = utility; q.poor = poor; q.best_gain = best_gain;
+  far_head(q, flags, view, cell, d2, block_d2, n);
+  prospect_words(q, e);
   p.records[i] = q;
 }
 
@@ -139,10 +139,11 @@ __device__ __forceinline__ bool prospect_before(int utility, int hops, double d2
   return reach_before(d2, b, o.d2, o.b);
 }
 
-// Weighs the target blocks `h` (bits of word u) of level `hops`: the gain of each from the counts U of the view, poor or not, the
-// running best; -> in poor and best_gain this thread's sums.
-__device__ __forceinline__ void prospect_weigh(const ProspectArgs& p, const uint16_t* U, unsigned long long h, int u, int hops, double px, double py,
-                                               double pz, ProspectBest& best, int& poor, int& best_gain) {
+// Weighs the target blocks `h` (bits of word u) of level `hops`: the gain of each from the counts U of the view, with COVERED without
+// the blocks whose bit of C (LDS, [W]) is set, poor or not, the running best; -> in poor and best_gain this thread's sums.
+template <bool COVERED>
+__device__ __forceinline__ void prospect_weigh(const ProspectArgs& p, const uint16_t* U, const unsigned long long* C, unsigned long long h, int u,
+                                               int hops, double px, double py, double pz, ProspectBest& best, int& poor, int& best_gain) {
 #pragma clang fp contract(off)
   const FarArgs& a = p.f;
   if (h == 0ull) return;
@@ -152,13 +153,28 @@ __device__ __forceinline__ void prospect_weigh(const ProspectArgs& p, const uint
   while (h) {
     const int bx = 64 * k + (int)__builtin_ctzll(h);  // (a set bit of T: bx < cx)
     h &= h - 1ull;
-    const int xlo = max(bx - g + 1, 0), xhi = min(bx + g - 1, a.cx - 1);
+    const int xlo = max(bx - g + 1, 0), xhi = min(bx + g - 1, a.cx - 1);  // (g >= 1: 0 <= xlo <= bx <= xhi < cx, xhi - xlo <= 8)
     int gain = 0;
-    for (int z = zlo; z <= zhi; z++)      // (g == 0: lo > hi on every axis, nothing is loaded)
-      for (int y = ylo; y <= yhi; y++) {
-        const uint16_t* line = U + (size_t)(z * a.cy + y) * (size_t)(64 * a.wx);
-        for (int x = xlo; x <= xhi; x++) gain += (int)line[x];
+    if constexpr (COVERED) {
+      if (g > 0) {
+        const int w0 = xlo >> 6, w1 = xhi >> 6, sh = xlo & 63;  // (w0 <= w1 < wx; w1 > w0: sh >= 56)
+        for (int z = zlo; z <= zhi; z++)
+          for (int y = ylo; y <= yhi; y++) {
+            const int rw = (z * a.cy + y) * a.wx;  // the first word of the row (< W)
+            unsigned long long piece = C[rw + w0] >> sh;
+            if (w1 != w0) piece |= C[rw + w1] << (64 - sh);
+            const uint16_t* line = U + (size_t)rw * 64u;
+            for (int x = xlo; x <= xhi; x++)
+              if (!((piece >> (x - xlo)) & 1ull)) gain += (int)line[x];
+          }
       }
+    } else {
+      for (int z = zlo; z <= zhi; z++)      // (g == 0: lo > hi on every axis, nothing is loaded)
+        for (int y = ylo; y <= yhi; y++) {
+          const uint16_t* line = U + (size_t)(z * a.cy + y) * (size_t)(64 * a.wx);
+          for (int x = xlo; x <= xhi; x++) gain += (int)line[x];
+        }
+    }
     if (gain > best_gain) best_gain = gain;
     if (gain < p.min_gain) {
       poor++;
@@ -171,68 +187,64 @@ __device__ __forceinline__ void prospect_weigh(const ProspectArgs& p, const uint
   }
 }
 
-__global__ void __launch_bounds__(256) prospect_goals_kernel(ProspectArgs p) {
+struct ProspectNoClaims {};
+
+// The body of prospect_goals_kernel, and with CLAIMS that of the pass kernel of the chooser by gain for a team: K21's claim scan
+// with the covered set x.c between the summary and the flood, covered and removed summed into x.sum, the weighing without the
+// covered counts unless nothing is covered, and x.store() for the longer record.  With CLAIMS false every `if constexpr` below is gone.
+template <bool CLAIMS, class X>
+__device__ __forceinline__ void prospect_body(const ProspectArgs& p, const X& x) {
 #pragma clang fp contract(off)
   __shared__ unsigned long long s_t[FAR_WORDS], s_lx[FAR_WORDS], s_ly[FAR_WORDS], s_lz[FAR_WORDS], s_a[FAR_WORDS], s_b[FAR_WORDS];
-  __shared__ double s_bd2[4], s_vd2[4];
-  __shared__ int s_bu[4], s_bh[4], s_bc[4], s_bg[4], s_vc[4], s_vm[4], s_n[4], s_m[4], s_k[4], s_p[4], s_g[4];
+  __shared__ double s_bd2[4];
+  __shared__ int s_bu[4], s_bh[4], s_bc[4], s_bg[4], s_n[4], s_m[4], s_k[4], s_p[4], s_g[4];
   __shared__ unsigned s_or[2][4];
   const FarArgs& a = p.f;
   const ReachArgs& r = a.r;
   const int i = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, w = t >> 6;
-  const fh_vehicle& V = r.vehicles[i];
-  const int view = fhw::uniform_i32(r.view_of ? r.view_of[i] : i);
-  const int status = fhw::uniform_i32(V.status), stage = fhw::uniform_i32(V.stage);
-  const int skip = fhw::uniform_i32(a.skip ? a.skip[i] : 0);
-  const double px = fhw::uniform_f64(V.state.pos[0]), py = fhw::uniform_f64(V.state.pos[1]), pz = fhw::uniform_f64(V.state.pos[2]);
-  const double gx = fhw::uniform_f64(V.g_term[0]), gy = fhw::uniform_f64(V.g_term[1]), gz = fhw::uniform_f64(V.g_term[2]);
-  const FarWho who = far_judge(a, view, status, stage, skip, px, py, pz, gx, gy, gz);
-  int flags = who.flags;
-  if (!who.searched) {  // (uniform over the workgroup)
-    const FarCounts none = {-1, -1, 0, 0, 0, 0, 0};
-    if (t == 0) prospect_store(p, i, flags, view, -1, INFINITY, INFINITY, none, -1, 0, 0, -1);
+  const FarStart st = far_start(a, i);
+  const int view = st.view;
+  int flags = st.who.flags;
+  if (!st.who.searched) {  // (uniform over the workgroup)
+    if constexpr (!CLAIMS) {  // (with CLAIMS the count kernel has written the outputs of a vehicle that is not searched)
+      const FarCounts none = {-1, -1, 0, 0, 0, 0, 0};
+      const ProspectGain no_gain = {-1, 0, 0, -1};
+      if (t == 0) prospect_store(p, i, flags, view, -1, INFINITY, INFINITY, none, no_gain);
+    }
     return;
   }
-  const int W = a.W, wx = a.wx, slab = a.wx * a.cy;
+  const int W = a.W, wx = a.wx, slab = a.wx * a.cy, sw = st.sw;
+  const unsigned long long sbit = st.sbit;
+  const double px = st.px, py = st.py, pz = st.pz;
   const unsigned char* F = r.flags + (size_t)view * r.view_stride;
-  const unsigned long long* S = a.sums + (size_t)view * 4u * (size_t)W;
   const uint16_t* U = p.counts + (size_t)view * (size_t)W * 64u;
-  const int sbx = who.sx / a.B, sby = who.sy / a.B, sbz = who.sz / a.B;  // (< cx, cy, cz: s is inside the lattice)
-  const int sw = (sbz * a.cy + sby) * wx + (sbx >> 6);                   // (< W)
-  const unsigned long long sbit = 1ull << (sbx & 63);
+  const FarMaps maps = {s_t, s_lx, s_ly, s_lz, s_a, s_b};
 
-  // ---- the view's summary into LDS, T without the blocks within r_avoid of g_term (K21's) ----
+  // ---- the view's summary into LDS, T without the blocks within r_avoid of g_term (K21's); with CLAIMS C starts empty ----
   unsigned long long own_seen[FAR_OWN];
-  unsigned own_nb[FAR_OWN];  // bit 0: owned (u < W); 1, 2: a word before / after in the same row; 4, 8: a row before / after in the slab; 16, 32: a slab below / above
-  int n_targets = 0;
-#pragma unroll
-  for (int j = 0; j < FAR_OWN; j++) {
-    const int u = t + 256 * j;
-    const bool own = u < W;
-    const int k = own ? u % wx : 0, row = own ? u / wx : 0, by = row % a.cy, bz = row / a.cy;
-    own_nb[j] = own ? (1u | (k > 0 ? 2u : 0u) | (k < wx - 1 ? 4u : 0u) | (by > 0 ? 8u : 0u) | (by < a.cy - 1 ? 16u : 0u) | (bz > 0 ? 32u : 0u) |
-                       (bz < a.cz - 1 ? 64u : 0u))
-                    : 0u;
-    own_seen[j] = own && u == sw ? sbit : 0ull;
-    if (own) {
-      unsigned long long tw = S[u];
-      if (r.a2 > 0.0) {  // (with a2 == 0 no E2 is below it)
-        unsigned long long h = tw;
-        while (h) {
-          const int bit = (int)__builtin_ctzll(h);
-          h &= h - 1ull;
-          const double e2 = far_block_d2(a, 64 * k + bit, by, bz, gx, gy, gz);
-          if (e2 < r.a2) tw &= ~(1ull << bit);
+  unsigned own_nb[FAR_OWN];
+  const unsigned long long* C = nullptr;
+  int n_targets, n_claims = 0, n_standing = 0;  // (the last two are uniform)
+  if constexpr (CLAIMS) {
+    n_targets = far_summary<true>(a, st, t, maps, x.c, own_seen, own_nb);
+    // every thread takes the claimed blocks out of the words of T it owns and sets the covered blocks in the words of C it owns
+    const int n_claimed = far_claim_scan<true>(a, x.team, i, t, s_t, x.c, n_claims, n_standing);
+    // covered and removed: the set bits of the words of C this thread owns, and their counts
+    int n_covered = 0, n_removed = 0;
+    if (x.team.k > 0)
+      for (int u = t; u < W; u += 256) {
+        unsigned long long cw = x.c[u];
+        n_covered += __popcll(cw);
+        while (cw) {
+          n_removed += (int)U[(size_t)u * 64u + (size_t)__builtin_ctzll(cw)];  // (<= 64 * 512 blocks of <= 4096 voxels: < 2^31)
+          cw &= cw - 1ull;
         }
       }
-      n_targets += __popcll(tw);
-      s_t[u] = tw;
-      s_lx[u] = S[(size_t)W + u];
-      s_ly[u] = S[2 * (size_t)W + u];
-      s_lz[u] = S[3 * (size_t)W + u];
-      s_a[u] = u == sw ? sbit : 0ull;
-      s_b[u] = 0ull;
-    }
+    const int wave_claimed = fhw::wave_sum_i32(n_claimed), wave_covered = fhw::wave_sum_i32(n_covered), wave_removed = fhw::wave_sum_i32(n_removed);
+    if (lane == 0) { x.sum[w] = wave_claimed; x.sum[4 + w] = wave_covered; x.sum[8 + w] = wave_removed; }
+    C = x.c;
+  } else {
+    n_targets = far_summary<false>(a, st, t, maps, nullptr, own_seen, own_nb);
   }
   const int wave_targets = fhw::wave_sum_i32(n_targets);
   if (lane == 0) s_k[w] = wave_targets;
@@ -240,15 +252,26 @@ __global__ void __launch_bounds__(256) prospect_goals_kernel(ProspectArgs p) {
 
   // ---- flood: every target block of every level is weighed by the thread that owns its word ----
   const int targets = s_k[0] + s_k[1] + s_k[2] + s_k[3];
+  int covered = 0;  // (uniform) nothing is covered: the weighing without C
+  if constexpr (CLAIMS) covered = x.sum[4] + x.sum[5] + x.sum[6] + x.sum[7];
   unsigned long long* cur = s_a;
   unsigned long long* nxt = s_b;
   int n_reached = t == 0 ? 1 : 0, n_reachable = 0;  // sums over this thread's words (the start: thread 0's)
   int n_poor = 0, top_gain = -1;
   ProspectBest mine = {0, 0, -1, 0, INFINITY};
+  const auto weigh = [&](unsigned long long h, int u, int hops) {
+    if constexpr (CLAIMS) {
+      if (covered != 0) {
+        prospect_weigh<true>(p, U, C, h, u, hops, px, py, pz, mine, n_poor, top_gain);
+        return;
+      }
+    }
+    prospect_weigh<false>(p, U, C, h, u, hops, px, py, pz, mine, n_poor, top_gain);
+  };
   int level = 0;
   bool cut = false;
   if ((s_t[sw] & sbit) != 0ull && t == 0) n_reachable = 1;  // (uniform read) the start's block is a target block of level 0
-  if (t == (sw & 255)) prospect_weigh(p, U, s_t[sw] & sbit, sw, 0, px, py, pz, mine, n_poor, top_gain);  // (the owner of word sw)
+  if (t == (sw & 255)) weigh(s_t[sw] & sbit, sw, 0);        // (the owner of word sw)
   for (;;) {
     if (r.max_hops > 0 && level >= r.max_hops) {  // (cur is never empty)
       cut = true;
@@ -259,30 +282,14 @@ __global__ void __launch_bounds__(256) prospect_goals_kernel(ProspectArgs p) {
     for (int j = 0; j < FAR_OWN; j++) {
       if (!(own_nb[j] & 1u)) continue;
       const int u = t + 256 * j;
-      const unsigned nb = own_nb[j];
-      const unsigned long long c = cur[u], lx = s_lx[u];
-      unsigned long long v = (c & lx) << 1;                  // +x inside the word
-      unsigned long long down = c >> 1;                      // -x: block b from block b + 1, the link at b
-      if (nb & 2u) v |= (cur[u - 1] & s_lx[u - 1]) >> 63;
-      if (nb & 4u) down |= cur[u + 1] << 63;
-      v |= down & lx;
-      if (nb & 8u) v |= cur[u - wx] & s_ly[u - wx];
-      if (nb & 16u) v |= cur[u + wx] & s_ly[u];
-      if (nb & 32u) v |= cur[u - slab] & s_lz[u - slab];
-      if (nb & 64u) v |= cur[u + slab] & s_lz[u];
-      v &= ~own_seen[j];
-      nxt[u] = v;
-      own_seen[j] |= v;
+      const unsigned long long v = far_expand(maps, cur, nxt, u, own_nb[j], wx, slab, own_seen[j]);
       const unsigned long long h = v & s_t[u];
       n_reached += __popcll(v);
       n_reachable += __popcll(h);
       any |= v ? 1u : 0u;
-      prospect_weigh(p, U, h, u, level + 1, px, py, pz, mine, n_poor, top_gain);
+      weigh(h, u, level + 1);
     }
-    const unsigned wave_any = fhw::wave_or(any);
-    if (lane == 0) s_or[level & 1][w] = wave_any;
-    __syncthreads();
-    const unsigned all = s_or[level & 1][0] | s_or[level & 1][1] | s_or[level & 1][2] | s_or[level & 1][3];
+    const unsigned all = far_level_any(any, s_or, level, lane, w);
     if (!(all & 1u)) break;
     level++;
     unsigned long long* const swap = cur;
@@ -313,38 +320,10 @@ __global__ void __launch_bounds__(256) prospect_goals_kernel(ProspectArgs p) {
       best.utility = -s_bu[k]; best.hops = s_bh[k]; best.d2 = s_bd2[k]; best.b = s_bc[k]; best.gain = s_bg[k];
     }
   // ---- the voxels of the chosen block: the smallest (d2, c) of its target voxels, and their number (K21's scan, once) ----
-  double v_best = INFINITY;
-  int best_cell = -1, members = 0;
-  if (best.b >= 0) {  // (uniform over the workgroup)
-    const int bx = best.b % a.cx, by = (best.b / a.cx) % a.cy, bz = best.b / (a.cx * a.cy);  // (a set bit of T: a block of the lattice)
-    const int x0 = bx * a.B, y0 = by * a.B, z0 = bz * a.B;
-    const int bw = min(x0 + a.B, r.nx) - x0, bh = min(y0 + a.B, r.ny) - y0, vol = bw * bh * (min(z0 + a.B, r.nz) - z0);
-    double v_d2 = INFINITY;
-    int v_c = 0x7fffffff, v_n = 0;
-    for (int l = t; l < vol; l += 256) {
-      const int ix = x0 + l % bw, iy = y0 + (l / bw) % bh, iz = z0 + l / (bw * bh);
-      if (far_passable(r, F, ix, iy, iz) && far_target(r, F, ix, iy, iz)) {
-        const double qx = (ix + 0.5) * r.res + r.ox, qy = (iy + 0.5) * r.res + r.oy, qz = (iz + 0.5) * r.res + r.oz;
-        const double dx = qx - px, dy = qy - py, dz = qz - pz;
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        const int c = (iz * r.ny + iy) * r.nx + ix;
-        v_n++;
-        if (reach_before(d2, c, v_d2, v_c)) { v_d2 = d2; v_c = c; }
-      }
-    }
-    const double wave_v = fhw::wave_min(v_d2);
-    const int wave_vc = fhw::wave_min_i32(v_d2 == wave_v ? v_c : 0x7fffffff);
-    const int wave_vn = fhw::wave_sum_i32(v_n);
-    if (lane == 0) { s_vd2[w] = wave_v; s_vc[w] = wave_vc; s_vm[w] = wave_vn; }
-    __syncthreads();
-    v_best = s_vd2[0];
-    best_cell = s_vc[0];
-    for (int k = 1; k < 4; k++)
-      if (reach_before(s_vd2[k], s_vc[k], v_best, best_cell)) { v_best = s_vd2[k]; best_cell = s_vc[k]; }
-    members = s_vm[0] + s_vm[1] + s_vm[2] + s_vm[3];
-  }
+  const bool found = best.b >= 0;  // (uniform over the workgroup)
+  FarVoxel voxel = {INFINITY, -1, 0};
+  if (found) voxel = far_scan_block(a, F, best.b, px, py, pz, t);
   if (t == 0) {
-    const bool found = best.b >= 0;
     FarCounts n;
     n.block = found ? best.b : -1;
     n.hops = found ? best.hops : -1;
@@ -352,14 +331,20 @@ __global__ void __launch_bounds__(256) prospect_goals_kernel(ProspectArgs p) {
     n.reachable = s_m[0] + s_m[1] + s_m[2] + s_m[3];
     n.reached = s_n[0] + s_n[1] + s_n[2] + s_n[3];
     n.levels = level;
-    n.members = found ? members : 0;
+    n.members = voxel.members;
     const int poor = s_p[0] + s_p[1] + s_p[2] + s_p[3];
     const int top = max(max(s_g[0], s_g[1]), max(s_g[2], s_g[3]));
     if (cut) flags |= FH_REACH_CUT;
     if (n.reachable > 0 && poor == n.reachable) flags |= FH_PROSPECT_ALL_POOR;
-    prospect_store(p, i, flags, view, found ? best_cell : -1, found ? v_best : INFINITY, found ? best.d2 : INFINITY, n, found ? best.gain : -1,
-                   found ? best.utility : 0, poor, top);
+    const ProspectGain e = {found ? best.gain : -1, found ? best.utility : 0, poor, top};
+    if constexpr (CLAIMS)
+      x.store(i, flags, view, voxel.cell, voxel.d2, found ? best.d2 : INFINITY, n, e, n_claims, n_standing, x.sum[0] + x.sum[1] + x.sum[2] + x.sum[3],
+              covered, x.sum[8] + x.sum[9] + x.sum[10] + x.sum[11]);
+    else
+      prospect_store(p, i, flags, view, voxel.cell, voxel.d2, found ? best.d2 : INFINITY, n, e);
   }
 }
+
+__global__ void __launch_bounds__(256) prospect_goals_kernel(ProspectArgs p) { prospect_body<false>(p, ProspectNoClaims()); }
 
 }  // namespace fhp

@@ -148,9 +148,12 @@ def test_the_symbols_are_exported_and_bound_and_the_device_code_is_included_by_f
     assert "#pragma clang fp contract(off)" in body and "atomic" not in raw.lower()
     assert re.findall(r'#include "([^"]+)"', body) == ["../../include/fasterhip_prospect.h"]
     assert "fh_far.hip.hpp" not in body and "fh_apart.hpp" not in body and not re.search(OTHERS, raw)
-    for called in ("far_judge(", "far_passable(", "far_target(", "far_block_d2(", "reach_before(", "FAR_WORDS", "FarArgs"):   # the far chooser's own, called
+    for called in ("far_start(", "far_summary<false>(", "far_expand(", "far_level_any(", "far_scan_block(", "far_put_goal(", "far_head(",
+                   "far_passable(", "far_target(", "far_block_d2(", "reach_before(", "FAR_WORDS", "FarArgs"):   # the far chooser's own, called
         assert called in body, called
-    assert not re.search(r"__device__[^\n;{]*\b(far_judge|far_gap2|far_body|far_block_d2|far_passable|far_target|reach_before)\s*\(", body)   # not copied
+    assert not re.search(r"__device__[^\n;{]*\b(far_judge|far_gap2|far_body|far_block_d2|far_passable|far_target|reach_before|far_start|far_summary|"
+                         r"far_expand|far_level_any|far_scan_block|far_put_goal|far_head|far_claim_scan)\s*\(", body)   # not copied
+    assert "prospect_goals_kernel(ProspectArgs p) { prospect_body<false>(p, ProspectNoClaims()); }" in body
     far = strip(os.path.join(CSRC, "fh_far.hip.hpp"))
     assert "far_goals_kernel(FarArgs a) { far_body<false>(a, FarNoClaims()); }" in far and "far_body<true>(" in strip(os.path.join(CSRC, "fh_apart.hpp"))
     assert sorted(set(re.findall(r"\b(\w+_kernel)\s*\(", far))) == ["far_blocks_kernel", "far_goals_kernel", "far_need_kernel"]

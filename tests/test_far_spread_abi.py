@@ -140,8 +140,12 @@ def test_the_symbols_are_exported_and_bound_and_the_device_code_is_included_by_f
     assert sorted(set(re.findall(r"\b(\w+_kernel)\s*\(", body))) == ["far_spread_class_kernel", "far_spread_count_kernel", "far_spread_goals_kernel"]
     assert "#pragma clang fp contract(off)" in body and "atomic" not in body.lower()
     assert re.findall(r'#include "([^"]+)"', body) == ["../../include/fasterhip_apart.h"]
-    assert "far_body<true>(" in body and "far_judge(" in body and "far_gap2(" in body    # the chooser's own, called
-    assert not re.search(r"__device__[^\n;{]*\b(far_judge|far_gap2|far_body|far_block_d2)\s*\(", body)   # not copied
+    for called in ("far_body<true>(", "far_judge(", "far_count_body(", "far_put_goal(", "far_head(", "far_team_words("):   # the chooser's own, called
+        assert called in body, called
+    assert not re.search(r"__device__[^\n;{]*\b(far_judge|far_gap2|far_body|far_block_d2|far_count_body|far_claim_scan|far_put_goal|far_head|"
+                         r"far_team_words)\s*\(", body)   # not copied
+    assert not re.search(r"far_gap2|__ballot|rank_in|s_pts|s_cnt", body)   # the claim scan stands in the chooser's device header, behind far_body<true>
+    assert "far_claim_scan<false>(" in strip(os.path.join(CSRC, "fh_far.hip.hpp"))
     far = strip(os.path.join(CSRC, "fh_far.hip.hpp"))
     assert "far_goals_kernel(FarArgs a) { far_body<false>(a, FarNoClaims()); }" in far
     # the entry points stand behind fh_far_goals_device; the summary stage is that chooser's: its memset and its two launches

@@ -161,12 +161,26 @@ def test_the_symbols_are_exported_and_bound_and_the_device_code_is_included_by_f
     assert sorted(set(re.findall(r"\b(\w+_kernel)\s*\(", body))) == ["stake_count_kernel", "stake_goals_kernel"]
     assert "#pragma clang fp contract(off)" in body and "atomic" not in raw.lower()
     assert re.findall(r'#include "([^"]+)"', body) == ["../../include/fasterhip_stake.h"]
-    for called in ("far_judge(", "far_passable(", "far_target(", "far_block_d2(", "far_gap2(", "reach_before(", "prospect_weigh(", "prospect_before(",
+    for called in ("far_count_body(", "far_put_goal(", "far_head(", "far_team_words(", "prospect_words(", "prospect_body<true>(",
                    "FAR_WORDS", "ProspectArgs"):   # the far choosers' own, called
         assert called in body, called
     assert not re.search(r"__device__[^\n;{]*\b(far_judge|far_gap2|far_body|far_block_d2|far_passable|far_target|reach_before|prospect_weigh|"
                          r"prospect_before|prospect_store)\s*\(", body)   # not copied
-    assert "FarClaims" not in body and "s_c[FAR_WORDS]" in body   # the claim scan is its own, the covered set a seventh bitmap
+    # the claim scan is the far chooser's, called by the gain chooser's body, and no loop of it stands here; the covered set is a seventh
+    # bitmap, which this file holds
+    shared = [strip(os.path.join(CSRC, f)) for f in ("fh_far.hip.hpp", "fh_prospect.hpp")]
+    assert len(re.findall(r"\bfar_claim_scan\s*\(", shared[0])) == 1 and "far_claim_scan<true>(" in shared[1] and "far_claim_scan<false>(" in shared[0]
+    assert not re.search(r"far_claim_scan|FarClaims|__ballot|rank_in|s_pts|s_cnt|s_cb|far_expand|far_summary|far_scan_block", body)
+    assert "s_c[FAR_WORDS]" in body
+    # what the far chooser's and the gain chooser's device headers define, no other file of the device code defines
+    defined = lambda text: set(re.findall(r"__device__ __forceinline__ [^\n;{(]*?(\w+)\s*\(", text))   # noqa: E731
+    helpers = defined(shared[0]) | defined(shared[1])
+    assert {"far_start", "far_summary", "far_expand", "far_level_any", "far_scan_block", "far_put_goal", "far_head", "far_team_words",
+            "far_count_body", "far_claim_scan", "far_body", "prospect_words", "prospect_weigh", "prospect_body"} <= helpers
+    assert not defined(shared[0]) & defined(shared[1])
+    for other in glob.glob(os.path.join(CSRC, "*")):
+        if os.path.basename(other) not in ("fh_far.hip.hpp", "fh_prospect.hpp"):
+            assert not helpers & defined(strip(other)), other
     # the entry points stand outside the spans the other choosers' tests cut out
     at = [host.index("static size_t bid_offers_offset"), host.index("size_t fh_prospect_work_bytes"), host.index("size_t fh_stake_work_bytes"),
           host.index("int fh_stake_goals_device"), host.index("int fh_prospect_goals_device"), host.index("int fh_apart_goals_device")]
