@@ -565,6 +565,26 @@ def default_obstacle_audit_params(r, dc, stride=1, count=0):
     return p
 
 
+# fh_track_params, fh_obstacle_track: the obstacles some vehicle sees, a ring of sightings each, a constant velocity fitted to it
+# (include/fasterhip_track.h)
+FH_TRACK_HISTORY = 8
+FH_TRACK_SEEN, FH_TRACK_LOST, FH_TRACK_RESET, FH_TRACK_STALE, FH_TRACK_BAD_FIT = 1, 2, 4, 8, 16
+track_params_dtype = np.dtype([("r_detect", "<f8"), ("dc", "<f8"), ("gate", "<f8"), ("grow", "<f8"), ("max_age", "<i8"), ("fit", "<i4"),
+                               ("min_obs", "<i4"), ("reserved", "<i4", (4,))], align=True)
+obstacle_track_dtype = np.dtype([("tick", "<i8", (FH_TRACK_HISTORY,)), ("pos", "<f8", (FH_TRACK_HISTORY, 3)), ("radius", "<f8"), ("count", "<i4"),
+                                 ("head", "<i4"), ("flags", "<i4"), ("reserved", "<i4", (11,))], align=True)
+assert (track_params_dtype.itemsize, obstacle_track_dtype.itemsize) == (64, 320)
+
+
+def default_track_params(r_detect, dc, fit=4, min_obs=2, max_age=0, gate=0.0, grow=0.0):
+    """fh_track_params: a vehicle sees an obstacle nearer than r_detect; the newest `fit` sightings are fitted, a record is on from
+    min_obs sightings; a track not seen for more than max_age ticks of dc is forgotten (0: never), a sighting farther than `gate` from
+    the prediction starts it anew (0: no gate), and the radius grows by `grow` per unit of time unseen."""
+    p = np.zeros((), dtype=track_params_dtype)
+    p["r_detect"], p["dc"], p["gate"], p["grow"], p["max_age"], p["fit"], p["min_obs"] = r_detect, dc, gate, grow, max_age, fit, min_obs
+    return p
+
+
 def certify_tol(corridor, state=None, box=None, cost_rel=None):
     """fh_certify_tol; one number stands for all four (the project's own number for "violated" is fh_params.feas_tol)."""
     t = np.zeros((), dtype=certify_tol_dtype)

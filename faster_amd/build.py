@@ -33,7 +33,8 @@ DEPS = SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + [os.pa
                                                                                     os.path.join(ROOT, "include", "fasterhip_prospect.h"),
                                                                                     os.path.join(ROOT, "include", "fasterhip_stake.h"),
                                                                                     os.path.join(ROOT, "include", "fasterhip_link_los.h"),
-                                                                                    os.path.join(ROOT, "include", "fasterhip_obstacles.h")]
+                                                                                    os.path.join(ROOT, "include", "fasterhip_obstacles.h"),
+                                                                                    os.path.join(ROOT, "include", "fasterhip_track.h")]
 HOST_SO = os.path.join(HERE, "libsolverhip.so")
 HOST_SOURCES = [os.path.join(HERE, "host", "solver_hip.cpp"), os.path.join(HERE, "host", "decomp_hip.cpp"),
                 os.path.join(HERE, "host", "jps_hip.cpp"), os.path.join(HERE, "host", "corridor_frontend.cpp")]  # (JpsHip searches ONE query on the host)

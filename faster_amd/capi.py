@@ -76,6 +76,8 @@ FAR_GAIN_SYMBOLS = ["fh_prospect_work_bytes", "fh_prospect_goals_device"]
 FAR_TEAM_SYMBOLS = ["fh_stake_work_bytes", "fh_stake_goals_device"]
 # include/fasterhip_obstacles.h
 OBSTACLE_SYMBOLS = ["fh_fleet_obstacles_device", "fh_fleet_obstacle_audit_device"]
+# include/fasterhip_track.h
+TRACK_SYMBOLS = ["fh_fleet_obstacle_track_device"]
 
 _LIB = None
 
@@ -345,6 +347,8 @@ def lib():
         L.fh_fleet_obstacles_device.argtypes = [vp, vp, vp, i32, ctypes.c_int64, vp, vp, i32, i32, vp, i32, vp, i32]
         L.fh_fleet_obstacle_audit_device.restype = i32
         L.fh_fleet_obstacle_audit_device.argtypes = [vp, vp, vp, i32, ctypes.c_int64, vp, vp, i32, i32, vp]
+        L.fh_fleet_obstacle_track_device.restype = i32
+        L.fh_fleet_obstacle_track_device.argtypes = [vp, vp, vp, vp, i32, ctypes.c_int64, ctypes.c_int64, vp, i32, vp, vp, vp, vp]
         L.fh_fleet_link_merge_device.restype = i32
         L.fh_fleet_link_merge_device.argtypes = [vp, vp, i32, vp, ctypes.c_size_t, ctypes.c_size_t, vp, i32, i32]
         L.fh_map_view_list_device.restype = i32
@@ -1065,6 +1069,17 @@ class Context:
         p = _one_record(par, "obstacle_audit", "fleet_obstacle_audit_device")
         self._check(lib().fh_fleet_obstacle_audit_device(self._h, abi.ptr(p), d_obstacles, int(m), int(tick0), d_vehicles, d_plans, int(n),
                                                          int(max_states), d_out), "fh_fleet_obstacle_audit_device")
+
+    def fleet_obstacle_track_device(self, vmap, par, d_truth, m, truth_tick0, tick, d_vehicles, n, d_tracks, d_est, d_seer, d_info):
+        """fh_fleet_obstacle_track_device: which of the m obstacles of d_truth ([m] abi.obstacle_dtype, their clock at truth_tick0) some
+        vehicle sees at `tick` (nearer than par["r_detect"], and no occupied cell of vmap between: a Map, or None for no walls), the
+        sighting into d_tracks ([m] abi.obstacle_track_dtype, read and rewritten), the fitted records into d_est ([m]
+        abi.obstacle_dtype, p0 = now), the seeing vehicle or -1 into d_seer ([m] int32) and four counts into d_info ([4] int64); par:
+        one abi.track_params_dtype record.  Asynchronous on the context's stream (include/fasterhip_track.h)."""
+        p = _one_record(par, "track", "fleet_obstacle_track_device")
+        self._check(lib().fh_fleet_obstacle_track_device(self._h, None if vmap is None else vmap._h, abi.ptr(p), d_truth, int(m), int(truth_tick0),
+                                                         int(tick), d_vehicles, int(n), d_tracks, d_est, d_seer, d_info),
+                    "fh_fleet_obstacle_track_device")
 
     def fleet_traffic_timed_device(self, par, d_vehicles, d_plans, n, max_states, d_cloud, n_cloud, d_point_mask, mask_words):
         """fh_fleet_traffic_timed_device: fleet_traffic_device's points, and in row i the bits of the samples that vehicle i's own plan comes

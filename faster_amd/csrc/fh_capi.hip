@@ -29,6 +29,7 @@
 #include "../../include/fasterhip_link.h"
 #include "../../include/fasterhip_link_los.h"
 #include "../../include/fasterhip_obstacles.h"
+#include "../../include/fasterhip_track.h"
 #include "fh_policy.hpp"  // (host only; before fh_solve: the look periods are named there)
 #include "fh_sample.hip.hpp"
 #include "fh_solve.hip.hpp"
@@ -1475,6 +1476,63 @@ int fh_fleet_link_groups_los_device(fh_ctx* ctx, fh_map* map, const fh_link_para
   los.ox = morigin[0]; los.oy = morigin[1]; los.oz = morigin[2]; los.res = mres;
   los.mx = mdims[0]; los.my = mdims[1]; los.mz = mdims[2]; los.pad = 0;
   return link_groups_launch(ctx, par, d_vehicles, n, d_view_of, n_views, cells, d_labels, d_info, &los);
+}
+
+// ---- tracking moving obstacles (include/fasterhip_track.h): who sees which obstacle, the ring of sightings, the fit, the records ----
+static_assert(sizeof(fh::TrackRec) == sizeof(fh_obstacle_track) && offsetof(fh::TrackRec, tick) == offsetof(fh_obstacle_track, tick) &&
+                  offsetof(fh::TrackRec, pos) == offsetof(fh_obstacle_track, pos) && offsetof(fh::TrackRec, radius) == offsetof(fh_obstacle_track, radius) &&
+                  offsetof(fh::TrackRec, count) == offsetof(fh_obstacle_track, count) && offsetof(fh::TrackRec, head) == offsetof(fh_obstacle_track, head) &&
+                  offsetof(fh::TrackRec, flags) == offsetof(fh_obstacle_track, flags) && offsetof(fh::TrackRec, reserved) == offsetof(fh_obstacle_track, reserved),
+              "fh::TrackRec is fh_obstacle_track field for field");
+static_assert(fh::TRACK_TRUTH_ON == FH_OBSTACLE_ON && fh::TRACK_MAX_TICK == FH_OBSTACLE_MAX_TICK, "the tracker reads and writes fh_obstacle records");
+
+int fh_fleet_obstacle_track_device(fh_ctx* ctx, fh_map* map, const fh_track_params* par, const fh_obstacle* d_truth, int m, int64_t truth_tick0,
+                                   int64_t tick, const fh_vehicle* d_vehicles, int n, fh_obstacle_track* d_tracks, fh_obstacle* d_est,
+                                   int32_t* d_seer, int64_t* d_info) {
+  if (!ctx || !par) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->r_detect) || !(par->r_detect > 0)) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->dc) || !(par->dc > 0)) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->gate)) return FH_ERR_ARG;
+  if (!audit_radius_ok(par->grow)) return FH_ERR_ARG;
+  if (par->max_age < 0) return FH_ERR_ARG;
+  if (par->fit < 1 || par->fit > FH_TRACK_HISTORY) return FH_ERR_ARG;
+  if (par->min_obs < 1 || par->min_obs > FH_TRACK_HISTORY) return FH_ERR_ARG;
+  if (n < 0 || m < 0) return FH_ERR_ARG;
+  if (!obstacle_tick_ok(truth_tick0)) return FH_ERR_ARG;
+  if (!obstacle_tick_ok(tick)) return FH_ERR_ARG;
+  fh::TrackArgs a;
+  a.map.occ = nullptr; a.map.ox = a.map.oy = a.map.oz = 0.0; a.map.res = 1.0;
+  a.map.mx = a.map.my = a.map.mz = 0; a.map.pad = 0;
+  if (map) {
+    int32_t mdims[3];
+    double morigin[3], mres = 0;
+    if (fh_map_dims(map, mdims, morigin) != FH_OK || fh_map_occupancy_bits_device(map, &a.map.occ, &mres) != FH_OK || !a.map.occ) {
+      ctx->err = "fh_fleet_obstacle_track_device: the map holds no grid (fh_map_read_device first)";
+      return FH_ERR_ARG;
+    }
+    if (!(par->r_detect / mres <= 4096.0)) {  // (a ray has ceil(|z - pos| / (0.5 res_map)) - 1 sample points)
+      ctx->err = "fh_fleet_obstacle_track_device: r_detect is more than 4096 cells of the map";
+      return FH_ERR_ARG;
+    }
+    a.map.ox = morigin[0]; a.map.oy = morigin[1]; a.map.oz = morigin[2]; a.map.res = mres;
+    a.map.mx = mdims[0]; a.map.my = mdims[1]; a.map.mz = mdims[2];
+  }
+  if (ctx->device < 0) return FH_ERR_DEVICE;
+  DeviceScope device_scope(ctx->device);
+  if (m == 0) return FH_OK;
+  if (!d_truth || !d_tracks || !d_est || !d_seer || !d_info || (n > 0 && !d_vehicles)) return FH_ERR_ARG;
+  a.detect2 = par->r_detect * par->r_detect; a.gate2 = par->gate * par->gate;
+  a.dc = par->dc; a.grow = par->grow;
+  a.max_age = (long long)par->max_age; a.truth_tick0 = (long long)truth_tick0; a.tick = (long long)tick;
+  a.fit = par->fit; a.min_obs = par->min_obs; a.gate = par->gate > 0 ? 1 : 0; a.n = n; a.m = m; a.pad = 0;
+  a.truth = d_truth; a.vehicles = d_vehicles;
+  a.tracks = reinterpret_cast<fh::TrackRec*>(d_tracks);
+  a.est = d_est; a.seer = d_seer;
+  a.info = reinterpret_cast<unsigned long long*>(d_info);
+  FH_HIP(hipMemsetAsync(d_info, 0, sizeof(int64_t) * 4, ctx->stream));
+  hipLaunchKernelGGL(fh::track_kernel, dim3((unsigned)m), dim3(64), 0, ctx->stream, a);
+  FH_HIP(hipGetLastError());
+  return FH_OK;
 }
 
 int fh_fleet_link_merge_device(fh_ctx* ctx, const int32_t* d_labels, int n_views, unsigned char* d_flags, size_t view_stride, size_t view_bytes,

@@ -169,4 +169,14 @@ __global__ void __launch_bounds__(64) link_los_hook_kernel(LinkLosArgs a, const 
   if (lane == 0 && m < L[view]) atomicMin(H + view, m);
 }
 
+// The ray test above for the device header that comes in below: the prefix of this file's names stays in this file
+// (tests/test_link_los_abi.py), so the tracker calls the same function, unchanged, by this name.
+__device__ __forceinline__ bool ray_blocked(const LinkLosMap& m, int lane, double px, double py, double pz, double qx, double qy, double qz) {
+  return link_los_blocked(m, lane, px, py, pz, qx, qy, qz);
+}
+
 }  // namespace fh
+
+// The tracker of moving obstacles (include/fasterhip_track.h) comes in here, behind the last kernel of the link headers: its kernel lies
+// after every kernel of before in the code object of fh_capi.hip, and fh_capi.hip names no device header more.
+#include "fh_track.hip.hpp"

@@ -29,6 +29,12 @@ near at the same instant; obstacle_audit() measures what the fleet flies against
 
     sense -> observe -> traffic -> obstacles -> replan -> next_goals
 
+enable_tracking() takes the host out of that loop (include/fasterhip_track.h): track() decides on the device which obstacles some vehicle
+sees now (in range, no wall of the map between), keeps a ring of sightings per obstacle, fits a constant velocity to it and writes the
+records that obstacles() reads:
+
+    sense -> observe -> traffic -> track -> obstacles -> replan -> next_goals
+
 enable_check() lets the fleet refuse: every commit is compared, instant by instant, with the other vehicles' plans and taken back when it
 conflicts (include/fasterhip_check.h); the chain ends ... -> safe solve -> backup -> commit -> check -> revert.
 
@@ -174,6 +180,8 @@ class Fleet:
         self.traffic_par, self.n_cloud_all = None, 0                # enable_traffic: the cloud holds n_cloud static points, then the traffic
         self.obstacle_par = self.d_obstacles = None                 # enable_obstacles: then the obstacles' points; n_cloud_all is the end
         self.n_obstacles, self.obstacle_tick = 0, 0                 # the obstacle clock: ticks since set_obstacles (next_goals advances it)
+        self.track_par = self.d_truth = self.d_tracks = self.d_track_seer = self.d_track_info = None   # enable_tracking
+        self.track_los, self.track_tick, self.truth_tick = False, 0, 0   # the sightings' clock; ticks since set_truth (next_goals advances both)
         self.check_par = self.check_cells = self.d_backup_vehicles = self.d_backup_plans = self.d_check = None   # enable_check
         self.round_par = self.round_cells = self.d_rounds = self.d_active_begin = self.d_check_rounds = None      # enable_rounds
         self.round_retries, self.round_fixed = 0, False
@@ -311,6 +319,7 @@ class Fleet:
         if self._tail_first() is not None:   # (traffic and obstacles live in masks that are replaced: enable_traffic, enable_obstacles again)
             self.traffic_par, self.n_cloud_all = None, 0
             self.obstacle_par = self.d_obstacles = None
+            self.track_par = self.d_truth = self.d_tracks = self.d_track_seer = self.d_track_info = None
             self.cloud = self.cloud[:self.n_cloud]
         if mask is False:
             self.point_mask = None
@@ -478,6 +487,7 @@ class Fleet:
             d.record_stream(self.stream)
         self.ctx.set_point_views_device(self.point_mask.data_ptr(), self.point_mask.shape[1], None, self.n_views)
         self.obstacle_par, self.n_cloud_all, self.n_obstacles, self.obstacle_tick = par, total, m, 0
+        self.track_par = self.d_truth = self.d_tracks = self.d_track_seer = self.d_track_info = None   # (another m: enable_tracking again)
         self._views_changed()
 
     def set_obstacles(self, obstacles):
@@ -538,6 +548,77 @@ class Fleet:
         the fleet's own, for a fleet that was never told of them (the control of an experiment).  count=params["delta_t"] audits the
         states the next replan cannot change.  A measurement: nothing of the fleet is written (synchronises)."""
         return self._host(self.obstacle_audit_device(r, stride, count, obstacles, tick0), abi.plan_obstacle_audit_dtype)
+
+    def _truth_bytes(self, obstacles, where):
+        obs = np.ascontiguousarray(obstacles)
+        if obs.dtype != abi.obstacle_dtype or int(obs.size) != self.n_obstacles:
+            raise capi.FasterHipError("Fleet.%s: %d abi.obstacle_dtype records, as in enable_obstacles" % (where, self.n_obstacles))
+        return self.torch.from_numpy(obs.view(np.uint8).reshape(-1).copy()).to(self.dev)
+
+    def enable_tracking(self, truth, r_detect, los=True, fit=4, min_obs=2, max_age=0, gate=0.0, grow=0.0):
+        """The fleet estimates the obstacles it avoids from what its vehicles see (include/fasterhip_track.h).  After enable_obstacles,
+        with as many records: truth is [m] abi.obstacle_dtype, where the obstacles really are (p0 + v t from now on: a simulation's
+        ground truth, or v = 0 and this cycle's detections through set_truth every cycle).  From now on track() writes the records
+        obstacles() reads: an obstacle is seen when a vehicle stands nearer than r_detect to it and, with los, no occupied cell of the
+        fleet's map lies between (needs set_map); the newest `fit` sightings are fitted, a record is on from min_obs sightings; a track
+        unseen for more than max_age ticks is forgotten (0: never), a sighting farther than `gate` from the prediction starts it anew
+        (0: no gate), the radius grows by `grow` per second unseen.  The tracks start empty and the records off; the clock of the
+        sightings and the truth's clock start at 0 and next_goals advances both.  Memory: 320 bytes per obstacle."""
+        t = self.torch
+        if self.obstacle_par is None:
+            raise capi.FasterHipError("Fleet.enable_tracking: enable_obstacles first")
+        src = self._truth_bytes(truth, "enable_tracking")
+        par = abi.default_track_params(r_detect, self.dc, fit, min_obs, max_age, gate, grow)
+        m = self.n_obstacles
+        self._follow_current()
+        with t.cuda.stream(self.stream):
+            self.d_truth = src.clone()
+            self.d_tracks = t.zeros(m * abi.obstacle_track_dtype.itemsize, dtype=t.uint8, device=self.dev)
+            self.d_track_seer = t.full((m,), -1, dtype=t.int32, device=self.dev)
+            self.d_track_info = t.zeros(4, dtype=t.int64, device=self.dev)
+            self.d_obstacles.zero_()   # (nothing is known yet: every record off)
+        for d in (src, self.d_truth, self.d_tracks, self.d_track_seer, self.d_track_info):
+            d.record_stream(self.stream)
+        self.track_par, self.track_los, self.track_tick, self.truth_tick, self.obstacle_tick = par, bool(los), 0, 0, 0
+
+    def set_truth(self, obstacles):
+        """New truth for the same number of obstacles ([m] abi.obstacle_dtype), its clock at 0: p0 is where an obstacle is at this
+        call.  The tracks and their clock stay."""
+        if self.track_par is None:
+            raise capi.FasterHipError("Fleet.set_truth: enable_tracking first")
+        src = self._truth_bytes(obstacles, "set_truth")
+        self._follow_current()
+        with self.torch.cuda.stream(self.stream):
+            self.d_truth.copy_(src)
+            src.record_stream(self.stream)
+        self.truth_tick = 0
+
+    def track(self):
+        """What the vehicles see of the truth now, into the tracks and from them into the records of obstacles(), in place on the device
+        (fh_fleet_obstacle_track_device): after observe() and traffic(), before obstacles(), once a cycle.  A clear and one launch on the
+        fleet's stream.  The records say where an obstacle is NOW, so the obstacle clock starts again at 0."""
+        if self.track_par is None:
+            raise capi.FasterHipError("Fleet.track: enable_tracking first")
+        self._follow_current()
+        self._track_launch()
+
+    def _track_launch(self):
+        p = lambda t: t.data_ptr()  # noqa: E731
+        self.ctx.fleet_obstacle_track_device(self.map if self.track_los else None, self.track_par, p(self.d_truth), self.n_obstacles, self.truth_tick,
+                                             self.track_tick, p(self.d_vehicles), self.n, p(self.d_tracks), p(self.d_obstacles), p(self.d_track_seer),
+                                             p(self.d_track_info))
+        self.obstacle_tick = 0
+
+    def track_records(self):
+        """(tracks [m] abi.obstacle_track_dtype, estimates [m] abi.obstacle_dtype, seers [m] int32, info [4] int64) of the last track():
+        the ring of sightings and this call's flags per obstacle, the records obstacles() reads, the smallest vehicle that saw each or
+        -1, and (seen, records on, resets, lost).  Against the truth: obstacle_audit(obstacles=truth, tick0=fleet.truth_tick)
+        (synchronises)."""
+        if self.track_par is None:
+            raise capi.FasterHipError("Fleet.track_records: enable_tracking first")
+        self.sync()
+        return (self.d_tracks.cpu().numpy().view(abi.obstacle_track_dtype).copy(), self.d_obstacles.cpu().numpy().view(abi.obstacle_dtype).copy(),
+                self.d_track_seer.cpu().numpy().copy(), self.d_track_info.cpu().numpy().copy())
 
     def enable_check(self, r=None, stride=1, count=0, cells=None):
         """Every commit is checked against the other plans and withheld when it conflicts (include/fasterhip_check.h): from now on
@@ -1379,6 +1460,8 @@ class Fleet:
         current state becomes that goal (updateState of a vehicle that tracks its plan perfectly).  With enable_heading the yaw entry
         runs instead (1 <= ticks <= 65536): the same goals, and (yaw, dyaw) of the last one in self.d_goal_yaw ([n][2], goal_yaw())."""
         self.obstacle_tick += int(ticks)   # (the obstacle clock runs with the plans' cursor)
+        self.track_tick += int(ticks)      # (and so do the clock of the sightings and the truth's)
+        self.truth_tick += int(ticks)
         if self.d_headings is not None:
             self.ctx.fleet_next_goals_yaw_device(self.yaw_params, self.d_vehicles.data_ptr(), self.d_plans.data_ptr(), self.d_headings.data_ptr(),
                                                  self.n, self.max_states, int(ticks), follow, self.d_next.data_ptr(), self.d_goal_yaw.data_ptr())

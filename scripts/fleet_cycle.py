@@ -109,9 +109,14 @@ same launch with 1, 8 and 64 passes, the cost of an idle pass from the last two,
 with time-aware traffic of S samples (default 64, stride 5, 6 m, window 2) and, behind it, Fleet.enable_obstacles with M obstacles
 scattered over the map that fly up to 1 m/s; Fleet.traffic, Fleet.obstacles and Fleet.obstacle_audit_device fenced one by one in the same
 run ("traffic_timed_ms", "obstacles_ms", "obstacle_audit_ms", medians with their spread), the bits set per vehicle and the vehicles hit.
+--obstacles M --track R_DETECT [--track-los] adds Fleet.enable_tracking on those obstacles as the truth (include/fasterhip_track.h; fit 4,
+min_obs 2; --track-los: the walls of the fleet's map hide an obstacle) and Fleet.track as "track_ms", fenced like the others between
+traffic and obstacles, each timed call one tick later than the one before so that every sighting is appended and fitted; and what the last
+call saw ("track_seen", "track_records_on").
     usage: python scripts/fleet_cycle.py [vehicles] [cycles] [--views [--link RANGE[,RANGE..] [--link-los]] [--explore R_MAX [--far BLOCK [--far-gain G [--far-hop-cost H] [--far-min-gain M]] [--far-spread R_SPREAD [--passes P]] [--far-claim-blocks C]] [--reach [--spread R_SPREAD] [--gain G [--hop-cost K] [--min-gain M] [--claim-radius R] [--bid] [--sight]]]]] [--walls] [--fov TAN_H TAN_V] [--occupancy [TEAMS]] [--r-sense R] [--no-staging]
                                          [--audit] [--separation] [--traffic [SAMPLES STRIDE RANGE]] [--traffic-timed WINDOW] [--check]
-                                         [--rounds R [--round-reach M] [--retries T]] [--listed-views] [--obstacles M [--obstacle-samples S]]"""
+                                         [--rounds R [--round-reach M] [--retries T]] [--listed-views]
+                                         [--obstacles M [--obstacle-samples S] [--track R_DETECT [--track-los]]]"""
 import json
 import os
 import sys
@@ -876,7 +881,7 @@ def traffic_cycles(B, cycles, p, world, samples, stride, reach, window=None):
     return {"traffic" if window is None else "traffic_timed": out}
 
 
-def obstacle_cycles(B, cycles, p, world, m, samples, rng):
+def obstacle_cycles(B, cycles, p, world, m, samples, rng, track=None, track_los=False):
     """--obstacles M: the fleet of --traffic-timed after two cycles, then time-aware traffic (samples, stride 5, 6 m, window 2) timed as a
     stage of its own, then Fleet.enable_obstacles with M obstacles scattered over the map that fly up to 1 m/s (the same samples,
     stride, range and window, seven points, no detection radius) and Fleet.obstacles and Fleet.obstacle_audit_device timed one by one,
@@ -898,6 +903,15 @@ def obstacle_cycles(B, cycles, p, world, m, samples, rng):
         fl.enable_obstacles(obs, samples, 5, 6.0, window=2)
         out.update({"cloud_points": fl.n_cloud_all, "mask_bytes": int(fl.point_mask.numel()) * 4})
         stages = [("traffic_timed", fl.traffic), ("obstacles", fl.obstacles), ("obstacle_audit", fl.obstacle_audit_device)]
+        if track is not None:   # --track: the obstacles as the truth; the records obstacles() reads are the tracker's from here on
+            fl.enable_tracking(obs, track, los=track_los)
+            out.update({"track_r_detect": track, "track_los": track_los})
+
+            def track_next():   # (one tick later each time: a sighting at the tick of the last one would be stale and not appended)
+                fl.track_tick += 1
+                fl.truth_tick += 1
+                fl.track()
+            stages.insert(1, ("track", track_next))
         ms = {n: [] for n, _ in stages}
         for name, launch in stages:
             launch()   # (warm-up: the working buffers of the context grow)
@@ -915,6 +929,9 @@ def obstacle_cycles(B, cycles, p, world, m, samples, rng):
             out[name + "_ms_min_max"] = [float(min(v)), float(max(v))]
         bits = fl.point_mask[:, int(fl.obstacle_par["first_point"]) // 32:]
         rec = fl.obstacle_audit()
+        if track is not None:
+            info = fl.track_records()[3]
+            out.update({"track_seen": int(info[0]), "track_records_on": int(info[1])})
         out.update({"obstacle_bits_set_per_vehicle": sum(int(((bits >> b) & 1).sum().item()) for b in range(32)) / B,
                     "audit_hit": int(((rec["flags"] & abi.FH_OBSTACLE_HIT) != 0).sum()), "audit_n_tested_mean": float(rec["n_tested"].mean())})
     finally:
@@ -1035,6 +1052,13 @@ def main():
         if opt in argv:
             k = argv.index(opt)
             del argv[k:k + 2]
+    track, track_los = None, "--track-los" in argv
+    if track_los:
+        argv.remove("--track-los")
+    if "--track" in argv:
+        k = argv.index("--track")
+        track = float(argv[k + 1])
+        del argv[k:k + 2]
     n_obstacles, obstacle_samples = 0, 64
     for opt in ("--obstacles", "--obstacle-samples"):
         if opt in argv:
@@ -1183,7 +1207,7 @@ def main():
         out.update(traffic_cycles(B, cycles, p, world, *(traffic or (8, 25, 6.0)), window=window))
     if n_obstacles:
         world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
-        out.update(obstacle_cycles(B, cycles, p, world, n_obstacles, obstacle_samples, rng))
+        out.update(obstacle_cycles(B, cycles, p, world, n_obstacles, obstacle_samples, rng, track, track_los))
     if rounds:
         world = (cloud, cells, res, center, zmax, infl, states, goals, flags, origin, dims)
         out.update(rounds_cycles(B, cycles, p, world, rounds, round_reach, retries, traffic, window, "--check" in sys.argv))
